@@ -2,6 +2,7 @@
 """Headline benchmark: queries/sec of exact top-10 over a 10M x 256-d fp32 corpus (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: starts N rank processes itself)
+    python bench.py ... --dump-outputs DIR              (also writes the last timed step's top-k to DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch of B=1024 synthetic queries: every rank scores
@@ -901,6 +902,20 @@ def serve_b1_leg(dev, index, n_queries=200, warm=20):
             "reference_published_note": "README.md:9 screenshot: author's machine, corpus size unknown, Chroma HNSW top-50 (approximate)"}
 
 
+def dump_outputs(out_dir, vals: torch.Tensor, idx: torch.Tensor) -> list:
+    """What the timed path's caller receives from its last step, as DIR/<name>.npy: the top-k scores (float32 [B,k]) and
+    the document indices (int64 on the device, written as float64: every index below 2^53 is exact).  The inputs are
+    seeded (gen_rows / gen_queries), so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"topk_scores": vals.detach().cpu().numpy().astype(np.float32),
+              "topk_indices": idx.detach().cpu().numpy().astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(out_dir / f"{name}.npy", arr)
+    return sorted(arrays)
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` from a bare shell: this parent makes NO GPU call; it starts N fresh rank processes
     (never an exec of itself), relays rank 0's JSON line and fails if any rank fails."""
@@ -941,7 +956,11 @@ def main():
     ap.add_argument("--no-streamed", action="store_true", help="skip the configs[4] leg (6.4 GB of pinned host memory per rank)")
     ap.add_argument("--stream-docs", type=int, default=STREAM_DOCS_PER_GPU, help="rows per GPU of the configs[4] leg (rehearsals)")
     ap.add_argument("--graph-legs-child", action="store_true", help="internal: graph_legs() on cuda:0, one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k scores and indices to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.graph_legs_child:
         torch.cuda.set_device(0)
@@ -1018,6 +1037,8 @@ def main():
         dt = float(t.item())
     vals, idx = out
     assert vals.shape == (BATCH, TOPK) and bool((vals[:, 1:] <= vals[:, :-1]).all()) and int(idx.min()) >= 0
+    if a.dump_outputs and rank == 0:  # every rank holds the same merged top-k; the legs below do not touch it
+        dump_outputs(a.dump_outputs, vals, idx)
 
     flags = int(local_index.fallback_flags.ne(0).sum().item())
     # the legs that are collectives (configs[4] streamed shards, configs[2] data-parallel training): all ranks, same order
