@@ -54,17 +54,6 @@ __global__ __launch_bounds__(256) void prep_len_kernel(const int64_t *__restrict
 
 constexpr int SORT_BINS = 256; // length classes of the row sort (8 ballots per row; [16][256] per-wave counts in LDS)
 
-int enc_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    return cus;
-}
-
 // Single block of 1024 threads: tok_off = exclusive scan of len; perm = rows sorted by length, longest first (a counting
 // sort over SORT_BINS length classes), rows of one class in ASCENDING ROW ORDER.  The order inside a class matters: perm
 // decides which rows share a 16-row recurrence workgroup, and the backward kernels sum the bias gradients per workgroup, so
@@ -779,7 +768,7 @@ static int encoder_forward(const char *who, const int64_t *ids, int B, int T, co
         gp.B = B;
         gp.H = H;
         gp.out_ld = ndir * H;
-        gp.slots = 2 * enc_cus();
+        gp.slots = 2 * tt_device_cus();
         const bool last = l == num_layers - 1;
         float *xout = (last && !train) ? nullptr : (float *)(ws + lo.x[l + 1]);
         if (train && l > 0) // the all-zero row that stands for "h before the first step" in the backward GEMMs (layer 0: above)

@@ -313,14 +313,7 @@ int launch_rows16(const SgemmParams &p, hipStream_t st)
         attr_done = true;
     }
     // resident workgroups (the kernel's rounds): two per CU for the narrow form, one for the wide one; the comparison build's TT_ROWS_SPLIT=0: no tail split
-    static const int resident = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-            (void)hipGetLastError();
-            cus = 256;
-        }
-        return (WIDE ? 1 : 2) * cus;
-    }();
+    static const int resident = (WIDE ? 1 : 2) * tt_device_cus();
     const int slots = TT_AB_SWITCH(TT_ROWS_SPLIT, 1) ? resident : 0; // (tt_common.h: a constant in the product build)
     // (a split tail has at most slots / RS_SPLIT token blocks, each RS_SPLIT workgroups: (RS_SPLIT - 1) slots / RS_SPLIT extra)
     const unsigned blocks = (unsigned)((p.M + RS_ROWS - 1) / RS_ROWS) + (unsigned)(slots - slots / RS_SPLIT);

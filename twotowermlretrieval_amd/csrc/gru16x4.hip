@@ -1493,17 +1493,6 @@ __global__ __launch_bounds__(512, 1) void gru_bwd16x4p_kernel(GruSplitBwdParams 
     }
 }
 
-int device_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    return cus;
-}
-
 } // namespace
 
 // The caller chooses between these kernels and the one-workgroup recurrences per call (TT_ENC_ONE_WORKGROUP, include/tt.h); the
@@ -1530,9 +1519,9 @@ int gru16x4_launches(int B, int H, int ndir)
     if (!split_enabled() || H != X4_H || B <= 0)
         return 0;
     const int per_dir = ((B + ENC_RB - 1) / ENC_RB + 7) / 8 * 32;
-    if (per_dir * ndir <= device_cus())
+    if (per_dir * ndir <= tt_device_cus())
         return 1;
-    return ndir == 2 && per_dir <= device_cus() ? 2 : 0;
+    return ndir == 2 && per_dir <= tt_device_cus() ? 2 : 0;
 }
 
 bool gru16x4_usable(int B, int H, int ndir) { return gru16x4_launches(B, H, ndir) > 0; }

@@ -1112,17 +1112,6 @@ struct Plan {
     size_t redo_off; // one int per query tile: a wave of the tile gave up a pool draw -> the static-split pass redoes the tile
 };
 
-int device_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256; // MI355X; keeps the workspace query usable without a device
-    }
-    return cus;
-}
-
 bool tt_score_pacing() // TT_SCORE_PACE=0: every wave for itself (measurement)
 {
     return TT_AB_SWITCH(TT_SCORE_PACE, 1) != 0;
@@ -1134,32 +1123,18 @@ Pass make_pass(int B, int64_t N, int slots, int qt, bool tail = false)
     ps.N = N;
     ps.n_qtiles = (B + qt - 1) / qt; // qt queries per task: 32, or 16 for wide embeddings (d > 256)
     ps.n_tiles = (int)((N + TILE_DOCS - 1) / TILE_DOCS);
-    int want = (slots + ps.n_qtiles - 1) / ps.n_qtiles;
-    want = want < 1 ? 1 : want;
-    want = want > ps.n_tiles ? ps.n_tiles : want;
-    want = want < 1 ? 1 : want;
-    ps.tiles_per_chunk = ps.n_tiles > 0 ? (ps.n_tiles + want - 1) / want : 1;
-    ps.n_chunks = ps.n_tiles > 0 ? (ps.n_tiles + ps.tiles_per_chunk - 1) / ps.tiles_per_chunk : 1;
+    const TTChunks c = tt_chunks(ps.n_tiles, (slots + ps.n_qtiles - 1) / ps.n_qtiles, INT_MAX);
+    ps.tiles_per_chunk = c.tiles_per_chunk;
+    ps.n_chunks = c.n_chunks;
     ps.n_tasks = ps.n_qtiles * ps.n_chunks;
-    ps.tail_own = ps.tiles_per_chunk;
-    ps.static_tiles = ps.n_tiles;
-    ps.tail_g = 1;
-    ps.tail_blocks = 0;
-    if (tail) {
-        // pool = the last 1/TT_SCORE_TAIL_DIV of every chunk's share (0: everything static) in blocks of a quarter of it,
-        // 4..64 tiles (a block costs one refill of the wave's ring, ~2 us)
-        const int tail_div = TT_AB_SWITCH(TT_SCORE_TAIL_DIV, 8);
-        const int share = tail_div > 0 ? ps.tiles_per_chunk / tail_div : 0;
-        if (share >= 8) {
-            const int own = ps.tiles_per_chunk - share;
-            int g = share / 4;
-            g = g < 4 ? 4 : (g > 64 ? 64 : g);
-            ps.tail_own = own;
-            ps.static_tiles = (int64_t)own * ps.n_chunks < ps.n_tiles ? own * ps.n_chunks : ps.n_tiles;
-            ps.tail_g = g;
-            ps.tail_blocks = (ps.n_tiles - ps.static_tiles + g - 1) / g;
-        }
-    }
+    // pool = the last 1/TT_SCORE_TAIL_DIV of every chunk's share (0: everything static) in blocks of a quarter of it,
+    // 4..64 tiles (a block costs one refill of the wave's ring, ~2 us)
+    const TTTailSplit t = tt_tail_split(ps.tiles_per_chunk, ps.n_chunks, ps.n_tiles, tail ? TT_AB_SWITCH(TT_SCORE_TAIL_DIV, 8) : 0,
+                                        8, 4, 64);
+    ps.tail_own = t.own;
+    ps.static_tiles = t.static_tiles;
+    ps.tail_g = t.tail_g;
+    ps.tail_blocks = t.tail_blocks;
     return ps;
 }
 
@@ -1178,7 +1153,7 @@ Plan make_plan(int B, int64_t N, int k, int d)
     const int qt = (d > 256 || B <= 16) ? 16 : 32; // 16-query tiles: wide embeddings, and batches that fit one such tile
     pl.cap = k <= 16 ? 64 : 128;
     pl.smem = (size_t)WPB * NSTAGE * SLAB_BYTES;
-    const int slots = device_cus() * 8;
+    const int slots = tt_device_cus() * 8;
     pl.main = make_pass(B, N, slots, qt, true);
     pl.prepass = N >= PREPASS_MIN_N && (int64_t)pl.main.tiles_per_chunk * TILE_DOCS < PREPASS_MAX_CHUNK_DOCS;
     int max_tasks = pl.main.n_tasks;
@@ -1195,19 +1170,14 @@ Plan make_plan(int B, int64_t N, int k, int d)
     size_t max_chunks = pl.main.n_chunks;
     if (pl.prepass && (size_t)pl.pre.n_chunks > max_chunks)
         max_chunks = pl.pre.n_chunks;
-    size_t off = 0;
-    pl.cand_off = off;
-    off = tt_align_up(off + (size_t)max_tasks * qt * pl.cap * 8, 256);
-    pl.pval_off = off;
-    off = tt_align_up(off + rows * max_chunks * k * sizeof(float), 256);
-    pl.pidx_off = off;
-    off = tt_align_up(off + rows * max_chunks * k * sizeof(int64_t), 256);
-    pl.pre_val_off = off;
-    off = tt_align_up(off + rows * k * sizeof(float), 256);
-    pl.pre_idx_off = off;
-    off = tt_align_up(off + rows * k * sizeof(int64_t), 256);
-    pl.tailctr_off = off;
-    off = tt_align_up(off + (size_t)pl.main.n_qtiles * sizeof(int), 256);
+    TTWorkspace ws;
+    pl.cand_off = ws.take((size_t)max_tasks * qt * pl.cap * 8);
+    pl.pval_off = ws.take(rows * max_chunks * k * sizeof(float));
+    pl.pidx_off = ws.take(rows * max_chunks * k * sizeof(int64_t));
+    pl.pre_val_off = ws.take(rows * k * sizeof(float));
+    pl.pre_idx_off = ws.take(rows * k * sizeof(int64_t));
+    pl.tailctr_off = ws.take((size_t)pl.main.n_qtiles * sizeof(int));
+    // (32-query tiles only: the redo pass in tt_score_topk_f32_pred keeps one flag per 32 queries)
     pl.paced = qt == 32 && pl.main.n_qtiles >= 3; // (two query tiles: +0.7 % with it, 1.7x fetched either way)
     {
         // the chunks of one XCD (an eighth of them) share its 4 MiB L2: a chunk's waves must stay within its part of
@@ -1223,46 +1193,22 @@ Plan make_plan(int B, int64_t N, int k, int d)
             pl.pace_lag = PACE_R - 2;
     }
     pl.grp_maxseg = 0;
-    pl.pace_off = pl.grp_off = off;
+    pl.pace_off = pl.grp_off = ws.off;
     if (pl.paced) {
-        off = tt_align_up(off + ((size_t)pl.main.n_chunks * PACE_R + 1) * sizeof(int), 256); // + the time-out count
-        pl.grp_off = off;
+        ws.take(((size_t)pl.main.n_chunks * PACE_R + 1) * sizeof(int)); // + the time-out count
+        pl.grp_off = ws.off;
         if (pl.main.tail_blocks > 0) {
             // a chunk's waves may take up to 4x their even share of the pool (>= 16 blocks); n_chunks * grp_maxseg >=
             // tail_blocks, so every block is drawn by a chunk that still may
             const int even = (pl.main.tail_blocks + pl.main.n_chunks - 1) / pl.main.n_chunks;
             pl.grp_maxseg = 4 * even > 16 ? 4 * even : 16;
-            off = tt_align_up(off + (size_t)pl.main.n_chunks * pl.grp_maxseg * sizeof(int), 256);
+            ws.take((size_t)pl.main.n_chunks * pl.grp_maxseg * sizeof(int));
         }
     }
-    pl.ctr_bytes = off - pl.tailctr_off;
-    pl.redo_off = off;
-    off = tt_align_up(off + (size_t)pl.main.n_qtiles * sizeof(int), 256);
-    pl.ws_bytes = off;
+    pl.ctr_bytes = ws.off - pl.tailctr_off;
+    pl.redo_off = ws.take((size_t)pl.main.n_qtiles * sizeof(int));
+    pl.ws_bytes = ws.off;
     return pl;
-}
-
-template <int NS, int CAP, bool MAXONLY, bool NT = false>
-int launch_score_t(const ScoreParams &sp, const Plan &pl, hipStream_t st)
-{
-    auto kern = score_topk_kernel<NS, CAP, MAXONLY, NT>;
-    const size_t smem = NT ? (size_t)WPB * NSTAGE_NT * SLAB_BYTES : pl.smem;
-    TT_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int grid = (sp.n_tasks + WPB - 1) / WPB;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WPB * 64), smem, st, sp);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-
-template <int NS>
-int launch_score_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
-{
-    if (maxonly)
-        return launch_score_t<NS, 64, true>(sp, pl, st);
-    if constexpr (NS == 8) // (d = 256 only: the instantiations are not free)
-        if (sp.n_qtiles == 1)
-            return pl.cap == 64 ? launch_score_t<NS, 64, false, true>(sp, pl, st) : launch_score_t<NS, 128, false, true>(sp, pl, st);
-    return pl.cap == 64 ? launch_score_t<NS, 64, false>(sp, pl, st) : launch_score_t<NS, 128, false>(sp, pl, st);
 }
 
 constexpr bool score_dim_ok(int d)
@@ -1270,51 +1216,61 @@ constexpr bool score_dim_ok(int d)
     return d == 32 || d == 64 || d == 96 || d == 128 || d == 192 || d == 256 || d == 320 || d == 384 || d == 448 || d == 512;
 }
 
-template <int NS, int CAP, bool MAXONLY, bool NT = false>
-int launch_score16_t(const ScoreParams &sp, const Plan &pl, hipStream_t st)
-{
-    auto kern = score_topk16_kernel<NS, CAP, MAXONLY, NT>;
-    TT_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem));
-    const int grid = (sp.n_tasks + WPB - 1) / WPB;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WPB * 64), pl.smem, st, sp);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
+// The two kernel families, for launch_ns: score_topk_kernel (32-query tiles) and score_topk16_kernel (16-query tiles).
+struct Score32 {
+    template <int NS, int CAP, bool MAXONLY, bool NT>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT>; }
+    static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
+};
+struct Score16 {
+    template <int NS, int CAP, bool MAXONLY, bool NT>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT>; }
+    static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
+};
 
-template <int NS>
-int launch_score16_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+template <class K, int NS>
+int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
 {
-    if (maxonly)
-        return launch_score16_t<NS, 64, true>(sp, pl, st);
-    if constexpr (NS == 8)
-        if (sp.n_qtiles == 1)
-            return pl.cap == 64 ? launch_score16_t<NS, 64, false, true>(sp, pl, st) : launch_score16_t<NS, 128, false, true>(sp, pl, st);
-    return pl.cap == 64 ? launch_score16_t<NS, 64, false>(sp, pl, st) : launch_score16_t<NS, 128, false>(sp, pl, st);
+    const void *fn;
+    size_t smem = pl.smem;
+    if (maxonly) {
+        fn = K::template fn<NS, 64, true, false>();
+    } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
+        fn = pl.cap == 64 ? K::template fn<8, 64, false, true>() : K::template fn<8, 128, false, true>();
+        smem = K::smem_nt;
+    } else {
+        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false>() : K::template fn<NS, 128, false, false>();
+    }
+    TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    ScoreParams args = sp;
+    void *argv[] = {&args};
+    TT_HIP_CHECK(hipLaunchKernel(fn, dim3((sp.n_tasks + WPB - 1) / WPB), dim3(WPB * 64), argv, smem, st));
+    return TT_OK;
 }
 
 int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
 {
     if (d <= 256 && sp.B <= 16) { // half the MFMA work of a 32-query tile: the launch stays on the HBM roofline
         switch (d) {
-        case 32: return launch_score16_ns<1>(sp, pl, st, maxonly);
-        case 64: return launch_score16_ns<2>(sp, pl, st, maxonly);
-        case 96: return launch_score16_ns<3>(sp, pl, st, maxonly);
-        case 128: return launch_score16_ns<4>(sp, pl, st, maxonly);
-        case 192: return launch_score16_ns<6>(sp, pl, st, maxonly);
-        default: return launch_score16_ns<8>(sp, pl, st, maxonly);
+        case 32: return launch_ns<Score16, 1>(sp, pl, st, maxonly);
+        case 64: return launch_ns<Score16, 2>(sp, pl, st, maxonly);
+        case 96: return launch_ns<Score16, 3>(sp, pl, st, maxonly);
+        case 128: return launch_ns<Score16, 4>(sp, pl, st, maxonly);
+        case 192: return launch_ns<Score16, 6>(sp, pl, st, maxonly);
+        default: return launch_ns<Score16, 8>(sp, pl, st, maxonly);
         }
     }
     switch (d) {
-    case 320: return launch_score16_ns<10>(sp, pl, st, maxonly);
-    case 384: return launch_score16_ns<12>(sp, pl, st, maxonly);
-    case 448: return launch_score16_ns<14>(sp, pl, st, maxonly);
-    case 512: return launch_score16_ns<16>(sp, pl, st, maxonly);
-    case 32: return launch_score_ns<1>(sp, pl, st, maxonly);
-    case 64: return launch_score_ns<2>(sp, pl, st, maxonly);
-    case 96: return launch_score_ns<3>(sp, pl, st, maxonly);
-    case 128: return launch_score_ns<4>(sp, pl, st, maxonly);
-    case 192: return launch_score_ns<6>(sp, pl, st, maxonly);
-    default: return launch_score_ns<8>(sp, pl, st, maxonly);
+    case 320: return launch_ns<Score16, 10>(sp, pl, st, maxonly);
+    case 384: return launch_ns<Score16, 12>(sp, pl, st, maxonly);
+    case 448: return launch_ns<Score16, 14>(sp, pl, st, maxonly);
+    case 512: return launch_ns<Score16, 16>(sp, pl, st, maxonly);
+    case 32: return launch_ns<Score32, 1>(sp, pl, st, maxonly);
+    case 64: return launch_ns<Score32, 2>(sp, pl, st, maxonly);
+    case 96: return launch_ns<Score32, 3>(sp, pl, st, maxonly);
+    case 128: return launch_ns<Score32, 4>(sp, pl, st, maxonly);
+    case 192: return launch_ns<Score32, 6>(sp, pl, st, maxonly);
+    default: return launch_ns<Score32, 8>(sp, pl, st, maxonly);
     }
 }
 
@@ -1474,13 +1430,13 @@ TT_EXPORT int tt_score_topk_partials_f32(const float *Q, int B, int d, const flo
 
 namespace {
 // flags[t] = 1 when a query of 32-query tile t came out of the merge with the give-up marker in its first place
-__global__ __launch_bounds__(64) void redo_flag_kernel(const int64_t *__restrict__ out_idx, int B, int k, int qt, int *__restrict__ flags)
+__global__ __launch_bounds__(64) void redo_flag_kernel(const int64_t *__restrict__ out_idx, int B, int k, int *__restrict__ flags)
 {
-    const int t = blockIdx.x, q = t * qt + threadIdx.x;
-    const bool bad = threadIdx.x < qt && q < B && out_idx[(size_t)q * k] >= (int64_t)TT_TOPK_INVALID_INDEX;
+    const int q = blockIdx.x * 32 + threadIdx.x;
+    const bool bad = threadIdx.x < 32 && q < B && out_idx[(size_t)q * k] >= (int64_t)TT_TOPK_INVALID_INDEX;
     const unsigned long long any = __ballot(bad);
     if (threadIdx.x == 0)
-        flags[t] = any != 0ull;
+        flags[blockIdx.x] = any != 0ull;
 }
 } // namespace
 
@@ -1532,9 +1488,9 @@ int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t
         // marker, so it is dealt with HERE, on the device: the query tiles whose merged list starts with it are done again on
         // the static split (the predicated form: no pool, no pacing, nobody to wait for) -- three small launches that find
         // nothing to do in every run observed so far (~10 us behind a search of >= 4 ms).
+        // (only paced plans get here, and make_plan paces 32-query tiles only: one flag per 32 queries)
         int *redo = (int *)((char *)workspace + pl.redo_off);
-        const int qt = d > 256 ? 16 : 32;
-        hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, st, (const int64_t *)out_idx, B, k, qt, redo);
+        hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, st, (const int64_t *)out_idx, B, k, redo);
         TT_LAUNCH_CHECK();
         return tt_score_topk_f32_pred(Q, B, d, D, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, redo, st);
     }

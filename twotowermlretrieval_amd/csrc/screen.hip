@@ -1141,17 +1141,17 @@ __global__ __launch_bounds__(256) void build_from_bf16_kernel(const unsigned sho
 
 struct SPlan {
     bool stream;      // B <= STREAM_MAX_B: one independent streaming wave per (32-query tile, document chunk)
-    int nset;         // shared-tile form: 16-query sets per wave (4, 2 or 1)
+    int nset;         // shared-tile form: 16-query sets per wave (4, 3, 2 or 1)
     int n_qgroups;    // query groups of q_per_block rows (workgroup rows of 128 nset queries, or 32-query tiles when streaming)
     int q_per_block;
-    int n_tiles, n_chunks, tiles_per_chunk, n_blocks;
+    int n_tiles, n_chunks, tiles_per_chunk;
     int static_tiles, tail_g, tail_blocks; // shared-tile main pass: see ScreenParams
     size_t tailctr_off;
     // sample pass
     bool sample;
-    int s_tiles, s_chunks, s_tiles_per_chunk, s_blocks;
+    int s_tiles, s_chunks, s_tiles_per_chunk;
     int64_t s_docs;
-    size_t cand_off, pcnt_off, smax_val_off, sthr_val_off, qimg_off, qnorm_off, stats_off, ws_bytes, lds;
+    size_t cand_off, pcnt_off, smax_val_off, sthr_val_off, qimg_off, qnorm_off, stats_off, ws_bytes;
     int rows_pad; // n_qgroups * q_per_block
 };
 
@@ -1159,15 +1159,12 @@ constexpr int64_t SAMPLE_MIN_N = 65536;
 constexpr int STREAM_MAX_B = 64; // one streaming pass: 32 queries per wave (2 sets) up to B = 32, 64 (4 sets) up to B = 64;
                                  // beyond that the shared-tile kernel wins (B = 65 .. 128: 1.20 ms against two passes)
 
-int screen_cus()
+// Document chunks per query group for one round of resident work: streaming, 8 resident waves per CU (2 workgroups of 4);
+// shared-tile, one workgroup per CU (8 waves x 256 VGPRs) -- the per-workgroup set-up (query load + conversion, final
+// compaction) is ~0.1 ms and would be paid once per round.
+int one_round(bool stream, int n_qgroups)
 {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    return cus;
+    return stream ? (tt_device_cus() * 2 * TW + n_qgroups - 1) / n_qgroups : (tt_device_cus() + n_qgroups - 1) / n_qgroups;
 }
 
 SPlan make_splan(int B, int64_t N, int k)
@@ -1183,52 +1180,24 @@ SPlan make_splan(int B, int64_t N, int k)
     pl.q_per_block = pl.stream ? (B <= 32 ? 32 : 64) : SW * 16 * pl.nset;
     pl.n_qgroups = (B + pl.q_per_block - 1) / pl.q_per_block;
     pl.n_tiles = (int)((N + 31) / 32);
-    int want, max_chunks;
-    if (pl.stream) {
-        // 8 resident waves per CU (2 workgroups of 4), one round
-        want = (screen_cus() * 2 * TW + pl.n_qgroups - 1) / pl.n_qgroups;
-        // with seeded thresholds a chunk rarely keeps anything; without them every chunk ends with >= k entries
-        // and the finish kernel's pool bounds the number of chunks
-        max_chunks = N >= SAMPLE_MIN_N ? FIN_MAX_CHUNKS : POOL_MAX / (k + 16);
-    } else {
-        // one workgroup per CU is resident (8 waves x 256 VGPRs): aim at exactly one round, the per-workgroup
-        // set-up (query load + conversion, final compaction) is ~0.1 ms and would be paid once per round
-        want = (screen_cus() + pl.n_qgroups - 1) / pl.n_qgroups;
-        // room in the finish kernel's pool for k + slack entries per chunk
-        max_chunks = POOL_MAX / (k + 16);
+    // streaming: with seeded thresholds a chunk rarely keeps anything; without them every chunk ends with >= k entries and
+    // the finish kernel's pool bounds the number of chunks.  Shared-tile: room in that pool for k + slack entries per chunk.
+    int max_chunks = pl.stream && N >= SAMPLE_MIN_N ? FIN_MAX_CHUNKS : POOL_MAX / (k + 16);
+    if (!pl.stream)
         max_chunks = max_chunks > 255 ? 255 : max_chunks;
-    }
-    want = want > max_chunks ? max_chunks : want;
-    want = want > pl.n_tiles ? pl.n_tiles : want;
-    want = want < 1 ? 1 : want;
-    pl.tiles_per_chunk = (pl.n_tiles + want - 1) / want;
-    pl.n_chunks = (pl.n_tiles + pl.tiles_per_chunk - 1) / pl.tiles_per_chunk;
-    pl.static_tiles = pl.n_tiles;
-    pl.tail_g = 1;
-    pl.tail_blocks = 0;
-    {
-        // pool = the last 1/TT_SCREEN_TAIL_DIV of every chunk's share (0: everything static), in blocks of a quarter of
-        // that share, 8..32 tiles; only worth it when a share is long enough for several blocks
-        const int tail_div = TT_AB_SWITCH(TT_SCREEN_TAIL_DIV, 8);
-        const int share = tail_div > 0 ? pl.tiles_per_chunk / tail_div : 0;
-        if (!pl.stream && share >= 16) {
-            const int own = pl.tiles_per_chunk - share;
-            int g = share / 4;
-            g = g < 8 ? 8 : (g > 32 ? 32 : g);
-            pl.tiles_per_chunk = own;
-            pl.static_tiles = own * pl.n_chunks < pl.n_tiles ? own * pl.n_chunks : pl.n_tiles;
-            pl.tail_g = g;
-            pl.tail_blocks = (pl.n_tiles - pl.static_tiles + g - 1) / g;
-        }
-    }
+    const TTChunks c = tt_chunks(pl.n_tiles, one_round(pl.stream, pl.n_qgroups), max_chunks);
+    pl.n_chunks = c.n_chunks;
+    // pool = the last 1/TT_SCREEN_TAIL_DIV of every chunk's share (0: everything static), in blocks of a quarter of
+    // that share, 8..32 tiles; only worth it when a share is long enough for several blocks
+    const TTTailSplit t = tt_tail_split(c.tiles_per_chunk, c.n_chunks, pl.n_tiles,
+                                        pl.stream ? 0 : TT_AB_SWITCH(TT_SCREEN_TAIL_DIV, 8), 16, 8, 32);
+    pl.tiles_per_chunk = t.own;
+    pl.static_tiles = t.static_tiles;
+    pl.tail_g = t.tail_g;
+    pl.tail_blocks = t.tail_blocks;
     const int n_tasks = pl.n_qgroups * pl.n_chunks;
-    pl.n_blocks = pl.stream ? (n_tasks + TW - 1) / TW : n_tasks;
     const size_t rows = (size_t)pl.n_qgroups * pl.q_per_block;
-    size_t off = 0;
-    pl.cand_off = off;
-    off = tt_align_up(off + (size_t)n_tasks * pl.q_per_block * SCAP * sizeof(SCand), 256);
-    pl.pcnt_off = off;
-    off = tt_align_up(off + rows * pl.n_chunks * sizeof(int), 256);
+    pl.rows_pad = (int)rows;
     // sample pass: one maximum per 32-document tile of the sample; the k-th largest seeds the thresholds
     pl.sample = N >= SAMPLE_MIN_N;
     // Sample size: 1/64 of the corpus, or enough documents that the k-th sample maximum lets through about
@@ -1242,29 +1211,47 @@ SPlan make_splan(int B, int64_t N, int k)
     s_docs = s_docs < 32 ? 32 : s_docs;
     pl.s_docs = (s_docs + 31) / 32 * 32;
     pl.s_tiles = (int)(pl.s_docs / 32);
-    int s_want = pl.stream ? (screen_cus() * 2 * TW + pl.n_qgroups - 1) / pl.n_qgroups
-                           : (screen_cus() + pl.n_qgroups - 1) / pl.n_qgroups; // one round, one maximum per TILE
-    s_want = s_want > pl.s_tiles ? pl.s_tiles : s_want;
-    s_want = s_want < 1 ? 1 : s_want;
-    pl.s_tiles_per_chunk = (pl.s_tiles + s_want - 1) / s_want;
-    pl.s_chunks = pl.sample ? (pl.s_tiles + pl.s_tiles_per_chunk - 1) / pl.s_tiles_per_chunk : 0;
-    pl.s_blocks = pl.stream ? (pl.n_qgroups * pl.s_chunks + TW - 1) / TW : pl.n_qgroups * pl.s_chunks;
-    pl.smax_val_off = off;
-    off = tt_align_up(off + rows * (size_t)(pl.sample ? pl.s_tiles : 1) * sizeof(float), 256);
-    pl.sthr_val_off = off;
-    off = tt_align_up(off + rows * sizeof(float), 256);
-    pl.rows_pad = (int)rows;
-    pl.qimg_off = off;
-    off = tt_align_up(off + rows * 256 * sizeof(_Float16), 256);
-    pl.qnorm_off = off;
-    off = tt_align_up(off + rows * sizeof(float), 256);
-    pl.tailctr_off = off;
-    off = tt_align_up(off + (size_t)pl.n_qgroups * sizeof(int), 256);
-    pl.stats_off = off;
-    off = tt_align_up(off + rows * 2 * sizeof(int), 256);
-    pl.ws_bytes = off;
-    pl.lds = pl.stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
+    const TTChunks sc = tt_chunks(pl.s_tiles, one_round(pl.stream, pl.n_qgroups), INT_MAX); // one maximum per TILE
+    pl.s_tiles_per_chunk = sc.tiles_per_chunk;
+    pl.s_chunks = pl.sample ? sc.n_chunks : 0;
+    TTWorkspace ws;
+    pl.cand_off = ws.take((size_t)n_tasks * pl.q_per_block * SCAP * sizeof(SCand));
+    pl.pcnt_off = ws.take(rows * pl.n_chunks * sizeof(int));
+    pl.smax_val_off = ws.take(rows * (size_t)(pl.sample ? pl.s_tiles : 1) * sizeof(float));
+    pl.sthr_val_off = ws.take(rows * sizeof(float));
+    pl.qimg_off = ws.take(rows * 256 * sizeof(_Float16));
+    pl.qnorm_off = ws.take(rows * sizeof(float));
+    pl.tailctr_off = ws.take((size_t)pl.n_qgroups * sizeof(int));
+    pl.stats_off = ws.take(rows * 2 * sizeof(int));
+    pl.ws_bytes = ws.off;
     return pl;
+}
+
+// The screen kernel of one form: streaming (q_per_block 32 or 64: 2 or 4 query sets per wave) or shared-tile (nset 16-query
+// sets per wave, 1..4).  MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).
+template <bool MAXONLY>
+const void *screen_fn(bool stream, int q_per_block, int nset)
+{
+    if (stream)
+        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4> : (const void *)screen_stream_kernel<MAXONLY, 2>;
+    switch (nset) {
+    case 4: return (const void *)screen_kernel<MAXONLY, 4>;
+    case 3: return (const void *)screen_kernel<MAXONLY, 3>;
+    case 2: return (const void *)screen_kernel<MAXONLY, 2>;
+    default: return (const void *)screen_kernel<MAXONLY, 1>;
+    }
+}
+
+// One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
+int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st)
+{
+    const void *fn = maxonly ? screen_fn<true>(stream, q_per_block, nset) : screen_fn<false>(stream, q_per_block, nset);
+    const size_t lds = stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
+    const int blocks = stream ? (n_tasks + TW - 1) / TW : n_tasks;
+    TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void *args[] = {&p};
+    TT_HIP_CHECK(hipLaunchKernel(fn, dim3(blocks), dim3((stream ? TW : SW) * 64), args, lds, st));
+    return TT_OK;
 }
 
 } // namespace
@@ -1331,11 +1318,17 @@ __global__ void seed_fill_kernel(float *seed, int n)
         seed[i] = -3.0e38f; // no sample pass for this corpus size: no information (the floor threshold applies)
 }
 
-// phase 0: the whole search.  phase 1: query image + sample pass; seed[q] <- the k_seed-th largest sample maximum (nothing
-// else); phase 3: the same, but seed[q][0..k_seed) <- the k_seed LARGEST sample maxima, unordered (a shard's share of the
-// union seed: tt_seed_union_f32).  phase 2: the screen with the caller's seed[] as thresholds (the workspace still holds phase 1's query image and
-// flags), finish, predicated exact kernels.
-int screened_impl(const char *who, int phase, const float *Q, int B, int d, const float *D32, const void *D16, int64_t N, int k,
+// What one call of screened_impl does: one per TT_EXPORT entry point below.
+enum class Phase {
+    Whole,         // the whole search
+    SeedThreshold, // query image + sample pass; seed[q] <- the k_seed-th largest sample maximum (nothing else)
+    SeedList,      // the same, but seed[q][0..k_seed) <- the k_seed LARGEST sample maxima, unordered (a shard's share of the
+                   // union seed: tt_seed_union_f32)
+    Seeded,        // the screen with the caller's seed[] as thresholds (the workspace still holds the seed phase's query
+                   // image and flags), finish, predicated exact kernels
+};
+
+int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, const float *D32, const void *D16, int64_t N, int k,
                   int k_seed, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
                   float *seed, void *workspace, size_t workspace_bytes, void *const *prof_events, hipStream_t st)
 {
@@ -1349,8 +1342,9 @@ int screened_impl(const char *who, int phase, const float *Q, int B, int d, cons
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: N too large; shard the corpus", who);
     if (!(dmax_norm >= 0.0f) || !(dmax_norm < 60000.0f))
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: corpus norm %g outside the fp16 range", who, dmax_norm);
-    const bool seed_only = phase == 1 || phase == 3;
-    if (!Q || !D16 || !fallback_flag || (!seed_only && (!D32 || !out_val || !out_idx)) || (phase != 0 && !seed))
+    const bool seed_only = phase == Phase::SeedThreshold || phase == Phase::SeedList; // stop after the sample pass
+    const bool caller_seed = phase == Phase::Seeded; // thresholds from seed[]: no query image, no sample pass
+    if (!Q || !D16 || !fallback_flag || (!seed_only && (!D32 || !out_val || !out_idx)) || (phase != Phase::Whole && !seed))
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
     if (seed_only && (k_seed < 1 || k_seed > k))
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: k_seed=%d outside [1, k=%d]", who, k_seed, k);
@@ -1359,6 +1353,9 @@ int screened_impl(const char *who, int phase, const float *Q, int B, int d, cons
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
         return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     char *ws = (char *)workspace;
+    // the sample maximum that becomes a threshold, and where it goes
+    const int k_thr = phase == Phase::SeedThreshold ? k_seed : k;
+    float *thr_out = phase == Phase::SeedThreshold ? seed : (float *)(ws + pl.sthr_val_off);
     // (the fallback flags are initialised by q_image_kernel below -- a kernel, not hipMemsetAsync: a 16-byte-multiple
     //  memset node captured in a HIP graph came back with garbage from the second replay on; ROCm 7.2, found with
     //  GraphedSearch at B=128)
@@ -1386,99 +1383,41 @@ int screened_impl(const char *who, int phase, const float *Q, int B, int d, cons
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
     sp.qnorm = (const float *)(ws + pl.qnorm_off);
     sp.dbg_thr = nullptr;
-    if (phase != 2) {
+    if (caller_seed) {
+        sp.thr0 = seed;
+        sp.thr0_stride = 1;
+    } else {
         hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
                            (float *)(ws + pl.qnorm_off), fallback_flag, (B + 31) / 32, (int *)(ws + pl.tailctr_off),
                            pl.n_qgroups);
         TT_LAUNCH_CHECK();
-    }
-    auto launch = [&](const ScreenParams &a, int blocks, bool maxonly) -> int {
-        if (pl.stream && pl.q_per_block == 64) {
-            if (maxonly)
-                hipLaunchKernelGGL((screen_stream_kernel<true, 4>), dim3(blocks), dim3(TW * 64), pl.lds, st, a);
+        if (pl.sample) {
+            ScreenParams ss = sp;
+            ss.N = (int)pl.s_docs;
+            ss.n_tiles = pl.s_tiles;
+            ss.n_chunks = pl.s_chunks;
+            ss.tiles_per_chunk = pl.s_tiles_per_chunk;
+            ss.static_tiles = pl.s_tiles;
+            ss.tail_blocks = 0;
+            ss.max_val = (float *)(ws + pl.smax_val_off);
+            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st));
+            if (phase == Phase::SeedList)
+                TT_RC_CHECK(tt_k_largest_list(ss.max_val, B, pl.s_tiles, k_seed, seed, st));
             else
-                hipLaunchKernelGGL((screen_stream_kernel<false, 4>), dim3(blocks), dim3(TW * 64), pl.lds, st, a);
-        } else if (pl.stream) {
-            if (maxonly)
-                hipLaunchKernelGGL(screen_stream_kernel<true>, dim3(blocks), dim3(TW * 64), pl.lds, st, a);
-            else
-                hipLaunchKernelGGL(screen_stream_kernel<false>, dim3(blocks), dim3(TW * 64), pl.lds, st, a);
-        } else if (pl.nset == 4) {
-            if (maxonly)
-                hipLaunchKernelGGL((screen_kernel<true, 4>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-            else
-                hipLaunchKernelGGL((screen_kernel<false, 4>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-        } else if (pl.nset == 3) {
-            if (maxonly)
-                hipLaunchKernelGGL((screen_kernel<true, 3>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-            else
-                hipLaunchKernelGGL((screen_kernel<false, 3>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-        } else if (pl.nset == 2) {
-            if (maxonly)
-                hipLaunchKernelGGL((screen_kernel<true, 2>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-            else
-                hipLaunchKernelGGL((screen_kernel<false, 2>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-        } else {
-            if (maxonly)
-                hipLaunchKernelGGL((screen_kernel<true, 1>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
-            else
-                hipLaunchKernelGGL((screen_kernel<false, 1>), dim3(blocks), dim3(SW * 64), pl.lds, st, a);
+                TT_RC_CHECK(tt_kth_largest(ss.max_val, B, pl.s_tiles, k_thr, thr_out, st));
+            sp.thr0 = (const float *)(ws + pl.sthr_val_off);
+            sp.thr0_stride = 1;
+        } else if (seed_only) {
+            const int n = phase == Phase::SeedList ? B * k_seed : B;
+            hipLaunchKernelGGL(seed_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seed, n);
+            TT_LAUNCH_CHECK();
         }
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-    };
-    if (pl.stream && pl.q_per_block == 64) {
-        TT_HIP_CHECK(hipFuncSetAttribute((const void *)screen_stream_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-        TT_HIP_CHECK(hipFuncSetAttribute((const void *)screen_stream_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-    } else if (pl.stream) {
-        TT_HIP_CHECK(hipFuncSetAttribute((const void *)screen_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-        TT_HIP_CHECK(hipFuncSetAttribute((const void *)screen_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-    } else {
-        const void *fns[8] = {(const void *)screen_kernel<false, 4>, (const void *)screen_kernel<true, 4>,
-                              (const void *)screen_kernel<false, 2>, (const void *)screen_kernel<true, 2>,
-                              (const void *)screen_kernel<false, 1>, (const void *)screen_kernel<true, 1>,
-                              (const void *)screen_kernel<false, 3>, (const void *)screen_kernel<true, 3>};
-        const int f0 = pl.nset == 4 ? 0 : (pl.nset == 2 ? 2 : (pl.nset == 3 ? 6 : 4));
-        TT_HIP_CHECK(hipFuncSetAttribute(fns[f0], hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-        TT_HIP_CHECK(hipFuncSetAttribute(fns[f0 + 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
-    }
-    if (phase == 2) {
-        sp.thr0 = seed;
-        sp.thr0_stride = 1;
-    } else if (!pl.sample && seed_only) {
-        const int n = phase == 3 ? B * k_seed : B;
-        hipLaunchKernelGGL(seed_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seed, n);
-        TT_LAUNCH_CHECK();
-    } else if (pl.sample) {
-        ScreenParams ss = sp;
-        ss.N = (int)pl.s_docs;
-        ss.n_tiles = pl.s_tiles;
-        ss.n_chunks = pl.s_chunks;
-        ss.tiles_per_chunk = pl.s_tiles_per_chunk;
-        ss.static_tiles = pl.s_tiles;
-        ss.tail_blocks = 0;
-        ss.max_val = (float *)(ws + pl.smax_val_off);
-        int rc = launch(ss, pl.s_blocks, true);
-        if (rc != TT_OK)
-            return rc;
-        if (phase == 3)
-            rc = tt_k_largest_list(ss.max_val, B, pl.s_tiles, k_seed, seed, st);
-        else
-            rc = tt_kth_largest(ss.max_val, B, pl.s_tiles, phase == 1 ? k_seed : k, phase == 1 ? seed : (float *)(ws + pl.sthr_val_off), st);
-        if (rc != TT_OK)
-            return rc;
-        sp.thr0 = (const float *)(ws + pl.sthr_val_off);
-        sp.thr0_stride = 1;
     }
     if (seed_only)
         return TT_OK;
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    {
-        const int rc = launch(sp, pl.n_blocks, false);
-        if (rc != TT_OK)
-            return rc;
-    }
+    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st));
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
 
@@ -1511,7 +1450,7 @@ TT_EXPORT int tt_score_topk_screened_f32(const float *Q, int B, int d, const flo
                                          int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
                                          void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_f32", 0, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val, out_idx,
+    return screened_impl("tt_score_topk_screened_f32", Phase::Whole, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val, out_idx,
                          fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream);
 }
 
@@ -1519,7 +1458,7 @@ TT_EXPORT int tt_score_topk_screened_seed_f32(const float *Q, int B, int d, cons
                                               float dmax_norm, int32_t *fallback_flag, float *seed, void *workspace,
                                               size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_f32", 1, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr, nullptr,
+    return screened_impl("tt_score_topk_screened_seed_f32", Phase::SeedThreshold, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr, nullptr,
                          fallback_flag, seed, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
@@ -1527,7 +1466,7 @@ TT_EXPORT int tt_score_topk_screened_seed_list_f32(const float *Q, int B, int d,
                                                    float dmax_norm, int32_t *fallback_flag, float *seed_list, void *workspace,
                                                    size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_list_f32", 3, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr,
+    return screened_impl("tt_score_topk_screened_seed_list_f32", Phase::SeedList, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr,
                          nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
@@ -1536,7 +1475,7 @@ TT_EXPORT int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, co
                                                 int32_t *fallback_flag, const float *seed, void *workspace,
                                                 size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seeded_f32", 2, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val,
+    return screened_impl("tt_score_topk_screened_seeded_f32", Phase::Seeded, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val,
                          out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events, (hipStream_t)stream);
 }
 
@@ -1549,9 +1488,11 @@ TT_EXPORT int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, co
 // with 32 copies of one document reads that document's value.  Not bound by the Python package.
 namespace {
 struct DbgPlan {
-    int q_per_block, n_qgroups, rows_pad, n_tiles, n_chunks, tiles_per_chunk, n_blocks;
+    int q_per_block, n_qgroups, rows_pad, n_tiles, n_chunks, tiles_per_chunk;
     size_t qimg_off, qnorm_off, flag_off, total;
 };
+// form 0: streaming, 32 queries per wave; form 1, 2, 4: shared-tile with that many query sets per wave.  The chunks are
+// make_splan's without its finish-pool bound (there is no finish kernel here) and without the tail pool.
 bool make_dbg_plan(int B, int64_t N, int form, DbgPlan &pl)
 {
     if (form != 0 && form != 1 && form != 2 && form != 4)
@@ -1560,22 +1501,14 @@ bool make_dbg_plan(int B, int64_t N, int form, DbgPlan &pl)
     pl.n_qgroups = (B + pl.q_per_block - 1) / pl.q_per_block;
     pl.rows_pad = pl.n_qgroups * pl.q_per_block;
     pl.n_tiles = (int)((N + 31) / 32);
-    int want = form == 0 ? (screen_cus() * 2 * TW + pl.n_qgroups - 1) / pl.n_qgroups
-                         : (screen_cus() + pl.n_qgroups - 1) / pl.n_qgroups;
-    want = want > pl.n_tiles ? pl.n_tiles : want;
-    want = want < 1 ? 1 : want;
-    pl.tiles_per_chunk = (pl.n_tiles + want - 1) / want;
-    pl.n_chunks = (pl.n_tiles + pl.tiles_per_chunk - 1) / pl.tiles_per_chunk;
-    const int n_tasks = pl.n_qgroups * pl.n_chunks;
-    pl.n_blocks = form == 0 ? (n_tasks + TW - 1) / TW : n_tasks;
-    size_t off = 0;
-    pl.qimg_off = off;
-    off = tt_align_up(off + (size_t)pl.rows_pad * 256 * sizeof(_Float16), 256);
-    pl.qnorm_off = off;
-    off = tt_align_up(off + (size_t)pl.rows_pad * sizeof(float), 256);
-    pl.flag_off = off;
-    off = tt_align_up(off + (size_t)(pl.rows_pad / 32 + 1) * sizeof(int), 256);
-    pl.total = off;
+    const TTChunks c = tt_chunks(pl.n_tiles, one_round(form == 0, pl.n_qgroups), INT_MAX);
+    pl.tiles_per_chunk = c.tiles_per_chunk;
+    pl.n_chunks = c.n_chunks;
+    TTWorkspace ws;
+    pl.qimg_off = ws.take((size_t)pl.rows_pad * 256 * sizeof(_Float16));
+    pl.qnorm_off = ws.take((size_t)pl.rows_pad * sizeof(float));
+    pl.flag_off = ws.take((size_t)(pl.rows_pad / 32 + 1) * sizeof(int));
+    pl.total = ws.off;
     return true;
 }
 } // namespace
@@ -1626,22 +1559,5 @@ TT_EXPORT int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_
     hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
                        (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0);
     TT_LAUNCH_CHECK();
-    if (form == 0) {
-        const size_t lds = (size_t)TW * TSTAGE * TSLAB_BYTES;
-        TT_HIP_CHECK(hipFuncSetAttribute((const void *)screen_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(screen_stream_kernel<true>, dim3(pl.n_blocks), dim3(TW * 64), lds, st, sp);
-    } else {
-        const size_t lds = (size_t)SRING * STILE_BYTES;
-        const void *fn = form == 4 ? (const void *)screen_kernel<true, 4>
-                                   : (form == 2 ? (const void *)screen_kernel<true, 2> : (const void *)screen_kernel<true, 1>);
-        TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (form == 4)
-            hipLaunchKernelGGL((screen_kernel<true, 4>), dim3(pl.n_blocks), dim3(SW * 64), lds, st, sp);
-        else if (form == 2)
-            hipLaunchKernelGGL((screen_kernel<true, 2>), dim3(pl.n_blocks), dim3(SW * 64), lds, st, sp);
-        else
-            hipLaunchKernelGGL((screen_kernel<true, 1>), dim3(pl.n_blocks), dim3(SW * 64), lds, st, sp);
-    }
-    TT_LAUNCH_CHECK();
-    return TT_OK;
+    return launch_screen(form == 0, pl.q_per_block, form, true, sp, pl.n_qgroups * pl.n_chunks, st);
 }

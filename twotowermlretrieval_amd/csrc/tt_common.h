@@ -33,6 +33,55 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline size_t tt_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Compute units of the current device; 256 (MI355X) when the query fails, so that workspace-size queries work without a device.
+int tt_device_cus();
+
+// Host-side planning pieces shared by the search planners (score_topk.hip, screen.hip); each planner keeps its own policy.
+// n_tiles tiles in chunks of whole tiles: about `want` chunks, at most max_chunks, at least one (one empty chunk for no tiles).
+struct TTChunks {
+    int tiles_per_chunk, n_chunks;
+};
+static inline TTChunks tt_chunks(int n_tiles, int want, int max_chunks)
+{
+    if (n_tiles <= 0)
+        return {1, 1};
+    want = want > max_chunks ? max_chunks : want;
+    want = want > n_tiles ? n_tiles : want;
+    want = want < 1 ? 1 : want;
+    const int per = (n_tiles + want - 1) / want;
+    return {per, (n_tiles + per - 1) / per};
+}
+
+// Tail pool of a chunked pass: the last 1/div of every chunk's share (div <= 0: none) is drawn from a shared pool in blocks of
+// a quarter of that share, clamped to [g_lo, g_hi] tiles; only when the share is at least min_share tiles.  A chunk keeps
+// `own` tiles; tiles [0, static_tiles) are cut statically, the rest are tail_blocks blocks of tail_g tiles.
+struct TTTailSplit {
+    int own, static_tiles, tail_g, tail_blocks;
+};
+static inline TTTailSplit tt_tail_split(int tiles_per_chunk, int n_chunks, int n_tiles, int div, int min_share, int g_lo,
+                                        int g_hi)
+{
+    const int share = div > 0 ? tiles_per_chunk / div : 0;
+    if (share < min_share)
+        return {tiles_per_chunk, n_tiles, 1, 0};
+    const int own = tiles_per_chunk - share;
+    int g = share / 4;
+    g = g < g_lo ? g_lo : (g > g_hi ? g_hi : g);
+    const int static_tiles = (int64_t)own * n_chunks < n_tiles ? own * n_chunks : n_tiles;
+    return {own, static_tiles, g, (n_tiles - static_tiles + g - 1) / g};
+}
+
+// Workspace layout: take(bytes) returns the next buffer's offset and moves on by bytes rounded up to 256.
+struct TTWorkspace {
+    size_t off = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t at = off;
+        off = tt_align_up(off + bytes, 256);
+        return at;
+    }
+};
+
 // Zero `bytes` bytes (multiple of 4, 4-byte aligned) at p with a KERNEL.  Never hipMemsetAsync on a path a caller may
 // capture into a HIP graph: on ROCm 7.2 a captured memset node of a larger graph fills with garbage from the second
 // replay on (a repeating 16-byte pattern that looks like two kernel-argument pointers: the node's pattern staging is

@@ -11,6 +11,17 @@ int tt_fail(int code, const char *fmt, ...)
     return code;
 }
 
+int tt_device_cus()
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+        (void)hipGetLastError();
+        cus = 256;
+    }
+    return cus;
+}
+
 TT_EXPORT const char *tt_version(void) { return "tt 0.2.0 (gfx950)"; }
 TT_EXPORT const char *tt_last_error(void) { return g_err; }
 

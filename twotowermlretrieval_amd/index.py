@@ -196,59 +196,18 @@ class BruteForceIndex:
         then runs with that global seed and `out` holds this shard's documents above it."""
         B = 1 if q.dim() == 1 else q.shape[0]
         N, d = self.docs.shape
-        L = _lib.lib()
         _need_cuda(q)
         if q.device != self.docs.device:
             raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
         if q.shape[-1] != d:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        if (self.docs16 is not None and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
-                and N >= SCREEN_MIN_DOCS and k <= 64):
-            _need_cuda(q)
+        if self._screens(B, k):
             if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank): same path, squeezed result
-                vals, idx = self.search(q.unsqueeze(0), k, _prof_events)
+                vals, idx = self._search_screened(q.unsqueeze(0), k, _prof_events)
                 return vals[0], idx[0]
-            q = _f32c(q)
-            if d < 256:
-                qp = torch.zeros((B, 256), dtype=torch.float32, device=q.device)
-                qp[:, :d] = q
-                q, d = qp, 256
-            if out is not None:
-                vals, idx = out
-            else:
-                vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
-                idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
-            with torch.cuda.device(self.docs.device):  # workspace sizing depends on the device's CU count
-                # per-call workspace and flags (cached allocator blocks): safe for concurrent callers and streams
-                need = L.tt_score_topk_screened_workspace_bytes(B, N, d, k)
-                ws_s = torch.empty(need, dtype=torch.uint8, device=self.docs.device)
-                flags = torch.empty((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
-                if self.keep_stats:
-                    self._last_ws = (ws_s, B, k)
-                if _seed_union is not None:
-                    ks = min(_k_list or _k_seed or k, k)  # entries per seed list (the caller ranks the union)
-                    lst = torch.empty((B, ks), dtype=torch.float32, device=self.docs.device)
-                    _lib.check(L.tt_score_topk_screened_seed_list_f32(q.data_ptr(), B, d, self.docs16.data_ptr(), N, k, ks,
-                                                                      self.dmax_norm, flags.data_ptr(), lst.data_ptr(),
-                                                                      ws_s.data_ptr(), ws_s.numel(), _stream(q)))
-                    seed = _seed_union(lst)
-                    if seed.shape != (B,) or seed.dtype != torch.float32 or not seed.is_contiguous():
-                        raise ValueError("_seed_union must return a contiguous float32 [B] tensor")
-                    _lib.check(L.tt_score_topk_screened_seeded_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(),
-                                                                   self.docs16.data_ptr(), N, k, self.dmax_norm,
-                                                                   self.idx_offset, vals.data_ptr(), idx.data_ptr(),
-                                                                   flags.data_ptr(), seed.data_ptr(), ws_s.data_ptr(),
-                                                                   ws_s.numel(), _prof_events, _stream(q)))
-                    self.fallback_flags = flags
-                    return vals, idx
-                _lib.check(L.tt_score_topk_screened_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(), self.docs16.data_ptr(),
-                                                        N, k, self.dmax_norm, self.idx_offset, vals.data_ptr(),
-                                                        idx.data_ptr(), flags.data_ptr(), ws_s.data_ptr(), ws_s.numel(),
-                                                        _prof_events, _stream(q)))
-            self.fallback_flags = flags  # of the most recent search (per 32-query tile; non-zero = exact kernel took over)
-            return vals, idx
+            return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list)
         with torch.cuda.device(self.docs.device):
-            need = L.tt_score_topk_workspace_bytes(B, N, d, k)
+            need = _lib.lib().tt_score_topk_workspace_bytes(B, N, d, k)
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.docs.device)
         v, i = score_topk(q, self.docs, k, self.idx_offset, ws)
         if out is not None:
@@ -256,6 +215,58 @@ class BruteForceIndex:
             out[1].copy_(i)
             return out
         return v, i
+
+    def _screens(self, B: int, k: int) -> bool:
+        """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
+        whether they enter the seed exchange; the thresholds are the module's at the time of the call."""
+        N, d = self.docs.shape
+        return (self.docs16 is not None and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
+                and N >= SCREEN_MIN_DOCS and k <= 64)
+
+    def _search_screened(self, q: torch.Tensor, k: int, _prof_events=None, out=None, _seed_union=None,
+                         _k_seed: int = 0, _k_list: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search()'s screened path for a 2-D q; the arguments are search()'s."""
+        B, d = q.shape
+        N = self.docs.shape[0]
+        L = _lib.lib()
+        q = _f32c(q)
+        if d < 256:
+            qp = torch.zeros((B, 256), dtype=torch.float32, device=q.device)
+            qp[:, :d] = q
+            q, d = qp, 256
+        if out is not None:
+            vals, idx = out
+        else:
+            vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
+            idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+        with torch.cuda.device(self.docs.device):  # workspace sizing depends on the device's CU count
+            # per-call workspace and flags (cached allocator blocks): safe for concurrent callers and streams
+            need = L.tt_score_topk_screened_workspace_bytes(B, N, d, k)
+            ws_s = torch.empty(need, dtype=torch.uint8, device=self.docs.device)
+            flags = torch.empty((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+            if self.keep_stats:
+                self._last_ws = (ws_s, B, k)
+            if _seed_union is not None:
+                ks = min(_k_list or _k_seed or k, k)  # entries per seed list (the caller ranks the union)
+                lst = torch.empty((B, ks), dtype=torch.float32, device=self.docs.device)
+                _lib.check(L.tt_score_topk_screened_seed_list_f32(q.data_ptr(), B, d, self.docs16.data_ptr(), N, k, ks,
+                                                                  self.dmax_norm, flags.data_ptr(), lst.data_ptr(),
+                                                                  ws_s.data_ptr(), ws_s.numel(), _stream(q)))
+                seed = _seed_union(lst)
+                if seed.shape != (B,) or seed.dtype != torch.float32 or not seed.is_contiguous():
+                    raise ValueError("_seed_union must return a contiguous float32 [B] tensor")
+                _lib.check(L.tt_score_topk_screened_seeded_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(),
+                                                               self.docs16.data_ptr(), N, k, self.dmax_norm,
+                                                               self.idx_offset, vals.data_ptr(), idx.data_ptr(),
+                                                               flags.data_ptr(), seed.data_ptr(), ws_s.data_ptr(),
+                                                               ws_s.numel(), _prof_events, _stream(q)))
+            else:
+                _lib.check(L.tt_score_topk_screened_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(), self.docs16.data_ptr(),
+                                                        N, k, self.dmax_norm, self.idx_offset, vals.data_ptr(),
+                                                        idx.data_ptr(), flags.data_ptr(), ws_s.data_ptr(), ws_s.numel(),
+                                                        _prof_events, _stream(q)))
+        self.fallback_flags = flags  # of the most recent search (per 32-query tile; non-zero = exact kernel took over)
+        return vals, idx
 
 
 class GraphedSearch:
@@ -452,8 +463,8 @@ class ShardedIndex:
         if self.streamed:
             mine = 0
         else:
-            N, d = self._index.docs.shape
-            mine = int(self._index.docs16 is not None and d == 256 and N >= SCREEN_MIN_DOCS)
+            # the smallest batch that screens at d = 256
+            mine = int(self._index.docs.shape[1] == 256 and self._index._screens(SCREEN_MIN_BATCH, 1))
         if self._coll.world > 1:
             dev = self._dev
             send = torch.tensor([mine], dtype=torch.int64, device=dev)
@@ -480,9 +491,8 @@ class ShardedIndex:
         coll, world = self._coll, self._coll.world
         plan = self._seed_plan(k)
         B = q.shape[0]
-        padded = (not self.streamed) and self._index.docs.shape[1] != 256
-        screens = plan is not None and B >= (SCREEN_MIN_BATCH if not padded else SCREEN_PADDED_MIN_BATCH)  # (BruteForceIndex.search's rule)
-        if not screens or (world == 1 and kp == k):
+        # (a seed plan implies a resident shard: no rank exchanges seeds when any shard is streamed)
+        if plan is None or not self._index._screens(B, k) or (world == 1 and kp == k):
             # no seed exchange on any rank (agreed in the constructor; B and k are the same everywhere): the shard's own search
             if comm_stream is not None:
                 self._flush()
