@@ -173,6 +173,17 @@ def score_rank(Q, D, target):
     return rank
 
 
+def score_all(Q, D):
+    """[B,N] fp32 scores, the ascending-index fmaf chain of score_topk."""
+    Q = _f32(Q)
+    D = _f32(D)
+    B, d = Q.shape
+    N = D.shape[0]
+    S = np.zeros((B, N), dtype=np.float32)
+    _check(lib().o_score_all(_p(Q), B, d, _p(D), C.c_int64(N), _p(S)), "o_score_all")
+    return S
+
+
 def triplet_loss(q, p, n, margin=0.2, with_grads=True):
     q, p, n = _f32(q), _f32(p), _f32(n)
     B, H = q.shape

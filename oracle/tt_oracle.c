@@ -531,6 +531,28 @@ int o_score_rank(const float *Q, int B, int d, const float *D, int64_t N,
     return O_OK;
 }
 
+/*
+ * Every score of every query, S [B,N] = the same fp32 FMA chain o_score_topk
+ * selects from (features ascending, acc0 = 0): the dense scores the hybrid
+ * retriever blends.  backend/simple_hybrid.py:53-54
+ */
+int o_score_all(const float *Q, int B, int d, const float *D, int64_t N, float *S)
+{
+    if (B < 0 || d <= 0 || N < 0)
+        return O_ERR_BAD_SHAPE;
+    for (int b = 0; b < B; ++b) {
+        const float *q = Q + (size_t)b * d;
+        for (int64_t n = 0; n < N; ++n) {
+            const float *row = D + (size_t)n * d;
+            float acc = 0.0f;
+            for (int j = 0; j < d; ++j)
+                acc = fmaf(q[j], row[j], acc);
+            S[(size_t)b * N + n] = acc;
+        }
+    }
+    return O_OK;
+}
+
 /* ------------------------------------------------------------------ */
 /* triplet loss                                                        */
 /* ------------------------------------------------------------------ */

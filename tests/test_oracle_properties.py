@@ -66,3 +66,26 @@ def test_score_rank_is_the_position_in_the_full_ordering(oracle, B, N, seed):
             assert rank[b] == pos[0] + 1
         else:
             assert rank[b] > 64
+
+
+@settings(max_examples=30, deadline=None, derandomize=True)
+@given(st.integers(1, 7), st.integers(1, 300), st.sampled_from([4, 36, 100, 256, 300, 512]), st.floats(1e-3, 1e3),
+       st.integers(0, 2 ** 31 - 1))
+def test_score_all_is_the_fmaf_chain_within_its_error_bound(oracle, B, N, d, scale, seed):
+    """o_score_all (the checker of tt_score_all_f32) against fp64: a chain of d fp32 FMAs errs by at most
+    gamma_d * sum_j |q_j D_j|, gamma_d = d u / (1 - d u), u = 2^-24; and its rows hold exactly the scores o_score_topk ranks."""
+    rs = np.random.RandomState(seed)
+    Q = (rs.standard_normal((B, d)) * scale).astype(np.float32)
+    D = rs.standard_normal((N, d)).astype(np.float32)
+    S = oracle.score_all(Q, D)
+    assert S.shape == (B, N) and S.dtype == np.float32
+    q64, d64 = Q.astype(np.float64), D.astype(np.float64)
+    exact = q64 @ d64.T
+    u = 2.0 ** -24
+    bound = d * u / (1 - d * u) * (np.abs(q64) @ np.abs(d64).T)
+    assert (np.abs(S - exact) <= bound).all()
+    k = min(N, 64)
+    v, i = oracle.score_topk(Q, D, k)
+    for b in range(B):
+        order = sorted(range(N), key=lambda n: (-S[b, n], n))[:k]
+        assert list(i[b]) == order and np.array_equal(v[b], S[b, order])

@@ -478,11 +478,15 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             compact_where(over);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    // 32*k output slots, lanes take them round-robin so the candidate loads overlap
+    // 32*k output slots, lanes take them round-robin so the candidate loads overlap.  The trip count is wave-uniform: the
+    // __shfl reads query q's count from lane q, and a lane that has left the loop would return 0 there (ds_bpermute)
     const int rows_live = min(32, p.B - qtile * 32);
-    for (int it = lane; it < rows_live * k; it += 64) {
-        const int q = it / k, t = it - q * k;
+    for (int it0 = 0; it0 < rows_live * k; it0 += 64) {
+        const int it = it0 + lane;
+        const int q = min(it / k, rows_live - 1), t = it - q * k;
         const int n = __shfl(cnt, q);
+        if (it >= rows_live * k)
+            continue;
         const size_t o = ((size_t)(qtile * 32 + q) * p.n_chunks + chunk) * k + t;
         Cand c;
         c.v = -INFINITY;
@@ -695,9 +699,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     const int rows_live = min(16, p.B - qtile * 16);
-    for (int it = lane; it < rows_live * k; it += 64) {
-        const int q = it / k, t = it - q * k;
+    for (int it0 = 0; it0 < rows_live * k; it0 += 64) { // wave-uniform trip count: see score_topk_kernel's output loop
+        const int it = it0 + lane;
+        const int q = min(it / k, rows_live - 1), t = it - q * k;
         const int nn = __shfl(cnt, q);
+        if (it >= rows_live * k)
+            continue;
         const size_t o = ((size_t)(qtile * 16 + q) * p.n_chunks + chunk) * k + t;
         Cand c;
         c.v = -INFINITY;
