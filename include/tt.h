@@ -88,6 +88,45 @@ int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, i
                       size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The same search over a bf16 corpus kept as it is (BASELINE configs[4]'s passages: 2 bytes per element in HBM, no widened
+ * copy).  Replaces  torch.matmul(q, D.t()) ; torch.topk(scores, k)  (backend/evaluators.py:185-186) for D_bf16 [N,d] bf16
+ * (raw 16-bit words, 16-byte aligned), Q [B,d] f32.  bf16 -> fp32 is exact, and the kernel widens each element in a
+ * register and feeds the fp32 chain in the same ascending order: out_val / out_idx are those of tt_score_topk_f32 over the
+ * widened rows, bit for bit, ties and the N < k tail included.  Supported: d in {64,128,192,256} (32-query tiles at every
+ * B), 1 <= k <= 64, N < 2^31 - 64; another d returns TT_ERR_UNSUPPORTED.  The give-up redo is tt_score_topk_f32's.  Its
+ * workspace is sized by tt_score_topk_bf16_workspace_bytes; for B > 16 the layout is tt_score_topk_f32's, so the two
+ * diagnostic offsets above apply to it as they are.
+ */
+size_t tt_score_topk_bf16_workspace_bytes(int B, int64_t N, int d, int k);
+int tt_score_topk_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                       int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                       size_t workspace_bytes, tt_stream_t stream);
+
+/*
+ * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
+ * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
+ * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it
+ * moved (bf16 -> fp32 -> fp16, round to nearest even: the fp16 shadow's bits, so screen_eps holds unchanged); survivors are
+ * rescored from the bf16 rows widened exactly, and the fallback is tt_score_topk_bf16.  Results, fallback flags and the
+ * statistics equal the f32 calls' over the widened rows and their shadow.  dmax_norm comes from tt_index_stats_bf16:
+ * stats[2] = {largest row L2 norm, largest |element|} of D_bf16 [N,d] (any d, a multiple of 4), the norm summed in
+ * tt_index_build_from_bf16's order, accumulated across calls unless reset_stats != 0; no copy is made.  The screen applies
+ * only when stats[1] < 6e4 and stats[0] < 6e4, as for the shadow.
+ */
+size_t tt_score_topk_screened_bf16_workspace_bytes(int B, int64_t N, int d, int k);
+int tt_index_stats_bf16(const void *D_bf16, int64_t N, int d, float *stats, int reset_stats, tt_stream_t stream);
+int tt_score_topk_screened_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, float dmax_norm,
+                                int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
+                                void *workspace, size_t workspace_bytes, void *const *prof_events, tt_stream_t stream);
+int tt_score_topk_screened_seed_list_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, int k_seed,
+                                          float dmax_norm, int32_t *fallback_flag, float *seed_list, void *workspace,
+                                          size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_screened_seeded_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, float dmax_norm,
+                                       int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
+                                       const float *seed, void *workspace, size_t workspace_bytes,
+                                       void *const *prof_events, tt_stream_t stream);
+
+/*
  * First half of tt_score_topk_f32 alone: the streaming score + per-tile top-k kernel.
  * Leaves [B, *part_m] unordered candidates (idx -1 = empty) in the workspace and returns
  * host pointers-to-device-pointers to them; follow with tt_topk_merge.  Exposed so a

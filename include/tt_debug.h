@@ -29,6 +29,11 @@ size_t tt_debug_screen_s16_workspace_bytes(int B, int64_t N, int form);
 int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr, int form,
                         float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream);
 
+/* The same over a bf16 corpus D_bf16 [N,256] (tt_score_topk_screened_bf16: converted to fp16 in LDS by the screen
+ * kernels); bit-identical to tt_debug_screen_s16 over the fp16 shadow of the widened rows.  Same workspace. */
+int tt_debug_screen_s16_bf16(const float *Q, int B, const void *D_bf16, int64_t N, float dmax_norm, const float *thr, int form,
+                             float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

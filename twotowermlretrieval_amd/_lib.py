@@ -39,6 +39,13 @@ SIGNATURES = {
     "tt_score_topk_pace_timeouts_offset": (_sz, [_i, _i64, _i, _i]),
     "tt_score_topk_redo_flags_offset": (_sz, [_i, _i64, _i, _i]),
     "tt_score_topk_f32": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_bf16_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
+    "tt_score_topk_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_screened_bf16_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
+    "tt_index_stats_bf16": (_i, [_vp, _i64, _i, _vp, _i, _vp]),
+    "tt_score_topk_screened_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tt_score_topk_screened_seed_list_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_screened_seeded_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tt_score_topk_partials_f32": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "tt_index_build_f16": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "tt_index_build_from_bf16": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _vp]),

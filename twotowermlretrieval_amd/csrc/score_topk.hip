@@ -55,7 +55,7 @@ typedef const __attribute__((address_space(1))) void gbl_void;
 struct Cand;
 struct ScoreParams {
     const float *Q;
-    const float *D;
+    const void *D; // [N][d] f32, or bf16 for the BF instantiations
     int B;
     int N;
     int k;
@@ -183,13 +183,19 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // maximum score over its documents (one partial entry, index = chunk id).
 // NT: the document stream with the nt cache policy (aux = 2): for ONE query tile, when every byte is read once by one wave
 // (B = 32 over 10M x 256: 1.884 -> 1.84 ms; with 32 query tiles re-reading each chunk from L2 it costs 20 %: 44.2 -> 52.9 ms)
-template <int NS, int CAP, bool MAXONLY, bool NT = false>
+// BF: the documents are bf16 rows (tt_score_topk_bf16).  A 128-B line of a row then carries 64 features, so a tile is NS/2
+// slabs; the same ring, swizzle and reads bring in the raw words and each A operand is widened in a register (bf16 -> fp32
+// is exact: the high half of the fp32 word), in the same ascending feature order -- the scores are tt_score_topk_f32's over
+// the widened rows, bit for bit.
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!BF || NS % 2 == 0, "bf16 rows: d a multiple of 64");
     constexpr int NST = NT ? NSTAGE_NT : NSTAGE;
     constexpr int WAVE_LDS = NST * SLAB_BYTES;
-    constexpr int ROW_BYTES = NS * 128;
+    constexpr int NSD = BF ? NS / 2 : NS; // 128-B slabs per document row
+    constexpr int ROW_BYTES = NSD * 128;
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     char *ring = smem + wid * WAVE_LDS;
@@ -315,7 +321,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
         for (int jj = 0; jj < DMA_PER_SLAB; ++jj)
             __builtin_amdgcn_global_load_lds((gbl_void *)(rowp[jj] + dma_s * 128),
                                              (lds_void *)(dst + jj * 1024), 16, 0, NT ? 2 : 0);
-        if (++dma_s == NS) {
+        if (++dma_s == NSD) {
             dma_s = 0;
             dma_tile = min(dma_tile + 1, t1 - 1); // past the end: harmless re-read
             set_rows(dma_tile);
@@ -339,7 +345,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 pace_gate(gb - p.pace_lag);
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
+            for (int s = 0; s < NSD; ++s) {
                 // slab (tile,s) has landed once at most (NST-2) younger slabs are pending
                 // (candidate stores also count in vmcnt: they only make this wait stricter)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_SLAB * (NST - 2)) : "memory");
@@ -353,12 +359,27 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
                 dma_issue((stage + NST - 1) % NST);
+                if (BF) {
+                    // chunk c holds features 8c..8c+7 of the slab; word w = features (8c+2w, 8c+2w+1) in its (low, high)
+                    // half = feature pair 4c+w, of which lane half h supplies feature 8c+2w+h
+                    const int sh = h ? 0 : 16;
 #pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    float a0 = h ? frag[c].y : frag[c].x;
-                    float a1 = h ? frag[c].w : frag[c].z;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, qreg[16 * s + 2 * c], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, qreg[16 * s + 2 * c + 1], acc, 0, 0, 0);
+                    for (int c = 0; c < 8; ++c) {
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) {
+                            const unsigned u = __float_as_uint(frag[c][w]);
+                            const float a = __uint_as_float((u << sh) & 0xffff0000u);
+                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, qreg[32 * s + 4 * c + w], acc, 0, 0, 0);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) {
+                        float a0 = h ? frag[c].y : frag[c].x;
+                        float a1 = h ? frag[c].w : frag[c].z;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, qreg[16 * s + 2 * c], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, qreg[16 * s + 2 * c + 1], acc, 0, 0, 0);
+                    }
                 }
                 stage = (stage + 1) % NST;
             }
@@ -1154,10 +1175,12 @@ constexpr int64_t PREPASS_MIN_N = 262144;
 constexpr int PREPASS_MAX_CHUNK_DOCS = 65536;
 constexpr int64_t PREPASS_MIN_SAMPLE = 16384;
 
-Plan make_plan(int B, int64_t N, int k, int d)
+// bf16: bf16 document rows (tt_score_topk_bf16), which run on 32-query tiles at every batch size; for B > 16 the
+// workspace layout is the fp32 one (only the pacing block length, a kernel argument, depends on the row bytes)
+Plan make_plan(int B, int64_t N, int k, int d, bool bf16 = false)
 {
     Plan pl;
-    const int qt = (d > 256 || B <= 16) ? 16 : 32; // 16-query tiles: wide embeddings, and batches that fit one such tile
+    const int qt = (!bf16 && (d > 256 || B <= 16)) ? 16 : 32; // 16-query tiles: wide embeddings, and batches that fit one such tile
     pl.cap = k <= 16 ? 64 : 128;
     pl.smem = (size_t)WPB * NSTAGE * SLAB_BYTES;
     const int slots = tt_device_cus() * 8;
@@ -1192,7 +1215,7 @@ Plan make_plan(int B, int64_t N, int k, int d)
         const int env_g = TT_AB_SWITCH(TT_SCORE_PACE_G, 0);
         const int env_lag = TT_AB_SWITCH(TT_SCORE_PACE_LAG, 0);
         const int64_t per_xcd = (pl.main.n_chunks + 7) / 8;
-        const int64_t window = (3 << 20) / (per_xcd * TILE_DOCS * d * 4); // tiles
+        const int64_t window = (3 << 20) / (per_xcd * TILE_DOCS * d * (bf16 ? 2 : 4)); // tiles
         pl.pace_lag = env_lag > 0 ? env_lag : 2;
         int g = (int)(window / (pl.pace_lag + 1));
         pl.pace_g = env_g > 0 ? env_g : (g < 1 ? 1 : (g > 8 ? 8 : g));
@@ -1218,16 +1241,24 @@ Plan make_plan(int B, int64_t N, int k, int d)
     return pl;
 }
 
-constexpr bool score_dim_ok(int d)
+constexpr bool score_dim_ok(int d, bool bf16 = false)
 {
+    if (bf16)
+        return d == 64 || d == 128 || d == 192 || d == 256;
     return d == 32 || d == 64 || d == 96 || d == 128 || d == 192 || d == 256 || d == 320 || d == 384 || d == 448 || d == 512;
 }
 
-// The two kernel families, for launch_ns: score_topk_kernel (32-query tiles) and score_topk16_kernel (16-query tiles).
+// The kernel families, for launch_ns: score_topk_kernel (32-query tiles) over fp32 and over bf16 rows, and
+// score_topk16_kernel (16-query tiles).
 struct Score32 {
     template <int NS, int CAP, bool MAXONLY, bool NT>
     static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
+};
+struct Score32Bf16 {
+    template <int NS, int CAP, bool MAXONLY, bool NT>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true>; }
+    static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
     template <int NS, int CAP, bool MAXONLY, bool NT>
@@ -1255,8 +1286,16 @@ int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonl
     return TT_OK;
 }
 
-int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly, bool bf16)
 {
+    if (bf16) { // (score_dim_ok: 64 <= d <= 256, 32-query tiles at every B)
+        switch (d) {
+        case 64: return launch_ns<Score32Bf16, 2>(sp, pl, st, maxonly);
+        case 128: return launch_ns<Score32Bf16, 4>(sp, pl, st, maxonly);
+        case 192: return launch_ns<Score32Bf16, 6>(sp, pl, st, maxonly);
+        default: return launch_ns<Score32Bf16, 8>(sp, pl, st, maxonly);
+        }
+    }
     if (d <= 256 && sp.B <= 16) { // half the MFMA work of a 32-query tile: the launch stays on the HBM roofline
         switch (d) {
         case 32: return launch_ns<Score16, 1>(sp, pl, st, maxonly);
@@ -1281,7 +1320,7 @@ int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, b
     }
 }
 
-ScoreParams pass_params(const Pass &ps, const float *Q, int B, const float *D, int k, int64_t idx_offset, char *ws,
+ScoreParams pass_params(const Pass &ps, const float *Q, int B, const void *D, int k, int64_t idx_offset, char *ws,
                         const Plan &pl)
 {
     ScoreParams sp;
@@ -1316,21 +1355,28 @@ ScoreParams pass_params(const Pass &ps, const float *Q, int B, const float *D, i
     return sp;
 }
 
-int score_partials(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
+// The supported widths, for error messages.
+const char *score_dims(bool bf16)
+{
+    return bf16 ? "64, 128, 192, 256" : "32, 64, 96, 128, 192, 256, 320, 384, 448, 512";
+}
+
+// D: fp32 rows, or bf16 rows when bf16 is set.
+int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
                    void *workspace, size_t workspace_bytes, hipStream_t st, Plan *plan_out, const char *who,
                    const int *run_if = nullptr, void *const *prof_events = nullptr)
 {
     if (B <= 0 || N <= 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
-    if (!score_dim_ok(d))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: 32, 64, 96, 128, 192, 256, 320, 384, 448, 512)", who, d);
+    if (!score_dim_ok(d, bf16))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", who, d, score_dims(bf16));
     if (k > 64)
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, k);
     if (N >= (int64_t)INT_MAX - 64)
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; shard the corpus", who, (long long)N);
     if (!Q || !D)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
-    const Plan pl = make_plan(B, N, k, d);
+    const Plan pl = make_plan(B, N, k, d, bf16);
     if (!workspace || workspace_bytes < pl.ws_bytes)
         return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, pl.ws_bytes);
     if (((uintptr_t)D & 15) || ((uintptr_t)Q & 3) || ((uintptr_t)workspace & 255))
@@ -1345,7 +1391,7 @@ int score_partials(const float *Q, int B, int d, const float *D, int64_t N, int 
         // k distinct documents score at least that much, so it bounds the final k-th score from below.
         ScoreParams pp = pass_params(pl.pre, Q, B, D, k, 0, ws, pl);
         pp.run_if = run_if;
-        int rc = launch_score(d, pp, pl, st, true);
+        int rc = launch_score(d, pp, pl, st, true, bf16);
         if (rc != TT_OK)
             return rc;
         hipLaunchKernelGGL(kth_largest_kernel, dim3(B), dim3(256), 0, st, (const float *)pp.pval, pl.pre.n_chunks, k,
@@ -1381,7 +1427,7 @@ int score_partials(const float *Q, int B, int d, const float *D, int64_t N, int 
         TT_RC_CHECK(tt_zero_async(ws + pl.tailctr_off, pl.ctr_bytes, st));
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    const int rc = launch_score(d, sp, pl, st, false);
+    const int rc = launch_score(d, sp, pl, st, false, bf16);
     if (prof_events && rc == TT_OK)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
     return rc;
@@ -1416,13 +1462,20 @@ TT_EXPORT size_t tt_score_topk_workspace_bytes(int B, int64_t N, int d, int k)
     return make_plan(B, N, k, d).ws_bytes;
 }
 
+TT_EXPORT size_t tt_score_topk_bf16_workspace_bytes(int B, int64_t N, int d, int k)
+{
+    if (B <= 0 || N < 0 || k <= 0)
+        return 0;
+    return make_plan(B, N, k, d, true).ws_bytes;
+}
+
 TT_EXPORT int tt_score_topk_partials_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
                                          int64_t idx_offset, void *workspace, size_t workspace_bytes,
                                          const float **part_val, const int64_t **part_idx, int *part_m,
                                          void *const *prof_events, tt_stream_t stream)
 {
     Plan pl;
-    int rc = score_partials(Q, B, d, D, N, k, idx_offset, workspace, workspace_bytes, (hipStream_t)stream, &pl,
+    int rc = score_partials(Q, B, d, D, false, N, k, idx_offset, workspace, workspace_bytes, (hipStream_t)stream, &pl,
                             "tt_score_topk_partials_f32", nullptr, prof_events);
     if (rc != TT_OK)
         return rc;
@@ -1447,33 +1500,22 @@ __global__ __launch_bounds__(64) void redo_flag_kernel(const int64_t *__restrict
 }
 } // namespace
 
-// Exact path, optionally predicated on a device flag (the screened path's fallback).
-int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                           const int *run_if, hipStream_t st);
-
-TT_EXPORT int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
-                                int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
-                                size_t workspace_bytes, tt_stream_t stream)
-{
-    return tt_score_topk_f32_pred(Q, B, d, D, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr,
-                                  (hipStream_t)stream);
-}
-
-int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                           const int *run_if, hipStream_t st)
+// Exact path over fp32 (bf16 = false) or bf16 rows, optionally predicated on a device flag (the screened path's fallback).
+namespace {
+int score_topk_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
+                    float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, const int *run_if,
+                    hipStream_t st, const char *who)
 {
     if (B < 0 || N < 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_score_topk_f32: B=%d N=%lld k=%d", B, (long long)N, k);
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
     if (B == 0)
         return TT_OK;
-    if (!score_dim_ok(d))
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_score_topk_f32: d=%d (supported: 32, 64, 96, 128, 192, 256, 320, 384, 448, 512)", d);
+    if (!score_dim_ok(d, bf16))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", who, d, score_dims(bf16));
     if (k > 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_score_topk_f32: k=%d > 64", k);
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, k);
     if (!out_val || !out_idx)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_score_topk_f32: null output pointer");
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null output pointer", who);
     if (N == 0) { // merge over zero candidates writes the (-inf,-1) tail
         hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(MERGE_THREADS), 0, st, (const float *)nullptr,
                            (const int64_t *)nullptr, 0, k, out_val, out_idx, (const int *)nullptr, 1, (size_t)0);
@@ -1481,7 +1523,7 @@ int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t
         return TT_OK;
     }
     Plan pl;
-    int rc = score_partials(Q, B, d, D, N, k, idx_offset, workspace, workspace_bytes, st, &pl, "tt_score_topk_f32", run_if);
+    int rc = score_partials(Q, B, d, D, bf16, N, k, idx_offset, workspace, workspace_bytes, st, &pl, who, run_if);
     if (rc != TT_OK)
         return rc;
     const char *ws = (const char *)workspace;
@@ -1499,9 +1541,44 @@ int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t
         int *redo = (int *)((char *)workspace + pl.redo_off);
         hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, st, (const int64_t *)out_idx, B, k, redo);
         TT_LAUNCH_CHECK();
-        return tt_score_topk_f32_pred(Q, B, d, D, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, redo, st);
+        return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, redo, st,
+                               who);
     }
     return TT_OK;
+}
+} // namespace
+
+// The predicated forms, for the screened path's fallback (csrc/screen.hip).
+int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
+                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                           const int *run_if, hipStream_t st)
+{
+    return score_topk_pred(Q, B, d, D, false, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, run_if, st,
+                           "tt_score_topk_f32");
+}
+
+int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
+                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                            const int *run_if, hipStream_t st)
+{
+    return score_topk_pred(Q, B, d, D, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, run_if, st,
+                           "tt_score_topk_bf16");
+}
+
+TT_EXPORT int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
+                                int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                size_t workspace_bytes, tt_stream_t stream)
+{
+    return tt_score_topk_f32_pred(Q, B, d, D, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr,
+                                  (hipStream_t)stream);
+}
+
+TT_EXPORT int tt_score_topk_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                                 int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                 size_t workspace_bytes, tt_stream_t stream)
+{
+    return tt_score_topk_bf16_pred(Q, B, d, D_bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
+                                   nullptr, (hipStream_t)stream);
 }
 
 // k-th largest of each row of vals [B][M] -> out [B] (internal: threshold seeding of both search paths)

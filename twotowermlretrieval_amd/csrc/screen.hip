@@ -41,6 +41,9 @@
 int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
                            const int *run_if, hipStream_t st);
+int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
+                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                            const int *run_if, hipStream_t st);
 
 int tt_kth_largest(const float *vals, int B, int M, int k, float *out, hipStream_t st);
 int tt_k_largest_list(const float *vals, int B, int M, int k, float *list, hipStream_t st);
@@ -49,6 +52,7 @@ namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
 
@@ -78,6 +82,30 @@ struct SCand {
 __device__ __forceinline__ float screen_eps(float qnorm, float dmax)
 {
     return 1.10e-3f * qnorm * dmax + 1e-6f * (qnorm + dmax);
+}
+
+// bf16 corpus (BF kernels): the LDS-DMA brings the bf16 rows -- the same 512 B per row, the same source swizzle -- and
+// each wave converts the pieces it DMA'd itself, in place, once: bf16 -> fp32 (exact) -> fp16 with round-to-nearest-even,
+// the cast build_from_bf16_kernel makes the fp16 shadow with, so the LDS image is the shadow's bit for bit.  NCH 16-byte
+// chunks per lane at base + (i * 64 + lane) * 16; the caller waits for the DMA before and for lgkmcnt(0) after.
+template <int NCH>
+__device__ __forceinline__ void bf16_to_f16_lds(char *base, int lane)
+{
+    uint4 v[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+        v[i] = *(const uint4 *)(base + (i * 64 + lane) * 16);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const _Float16 lo = (_Float16)__uint_as_float(w[e] << 16);
+            const _Float16 hi = (_Float16)__uint_as_float(w[e] & 0xffff0000u);
+            w[e] = (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
+        }
+        *(uint4 *)(base + (i * 64 + lane) * 16) = uint4{w[0], w[1], w[2], w[3]};
+    }
 }
 
 __device__ __forceinline__ SCand scand_load_l2(const SCand *p)
@@ -255,7 +283,7 @@ __global__ __launch_bounds__(128) void q_image_kernel(const float *__restrict__ 
 // workgroup, round 4) for the batches a 512-query group would leave a quarter or more empty: B = 257 .. 384 (one group) and
 // 513 .. 768 (two groups of 384 instead of a full one and a nearly empty one -- a group costs a pass whatever it holds: B = 513
 // took 3.6 ms where 512 took 2.1, profiles/r04_p_batch_sweep.log).
-template <bool MAXONLY, int NSET>
+template <bool MAXONLY, int NSET, bool BF = false>
 __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char ring[]; // [SRING][STILE_BYTES]
@@ -475,7 +503,25 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                 // own DMAs of this interval's tiles have landed; the barrier extends that to every wave's
                 // and guarantees every wave is done reading the tiles of the previous interval
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (SRING - 2 * STPB)) : "memory");
+                if (BF && tile == t0) { // bf16 rows, a segment's first interval: this wave's own two pieces of each of its
+                                        // tiles, converted before the barrier publishes them (later intervals: below)
+#pragma unroll
+                    for (int i = 0; i < STPB; ++i)
+                        bf16_to_f16_lds<2>(ring + ((stage + i) % SRING) * STILE_BYTES + (2 * w) * 1024, lane);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
                 __builtin_amdgcn_s_barrier();
+            } else if (BF && (tile - t0) % STPB == STPB - 1) {
+                // bf16 rows: the last tile of an interval converts the NEXT interval's pieces of this wave, off the barrier
+                // path (the waves drift freely inside an interval).  The ring runs SRING - STPB tiles ahead, so those STPB
+                // tiles have landed once at most the (SRING - 3 STPB + 1) younger tiles' pieces are pending; their slots
+                // are read by nobody until the next barrier publishes them.  (Past the segment's end they hold the clamped
+                // re-read of its last tile: converted, never read.)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (SRING - 3 * STPB + 1)) : "memory");
+#pragma unroll
+                for (int i = 1; i <= STPB; ++i)
+                    bf16_to_f16_lds<2>(ring + ((stage + i) % SRING) * STILE_BYTES + (2 * w) * 1024, lane);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
             // Every tile iteration refills the ring slot SRING - STPB tiles ahead (free since the last barrier);
             // the two LDS-DMA pieces go out between k-steps of the MFMA loop rather than in one burst behind
@@ -590,7 +636,7 @@ constexpr int TSTREAM_AUX = 2;
 
 // NQS = 16-query sets per wave: 2 (B <= 32), or 4 (33 <= B <= 64: ONE pass of the stream for 64 queries instead of the
 // shared-tile form's 1.03 ms; twice the MFMAs per tile, still a fifth of what the stream allows)
-template <bool MAXONLY, int NQS = 2>
+template <bool MAXONLY, int NQS = 2, bool BF = false>
 __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams p)
 {
     constexpr int QPT = 16 * NQS; // queries per task
@@ -700,6 +746,10 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
                 // slab (tile,kq) has landed once at most TSTAGE-2 younger slabs are pending (candidate stores
                 // also count in vmcnt: they only make this wait stricter)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TDMA * (TSTAGE - 2)) : "memory");
+                if (BF) { // bf16 rows: the wave's own slab, converted in place before its reads
+                    bf16_to_f16_lds<TSLAB_BYTES / 1024>(ring + stage * TSLAB_BYTES, lane);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
                 const char *buf = rd_row + stage * TSLAB_BYTES;
                 h8 a[2][2];
 #pragma unroll
@@ -807,6 +857,7 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
 struct FinishParams {
     const float *Q;
     const float *D32;
+    const unsigned *Dbf; // bf16 corpus instead of D32 (512-B rows of bf16 pairs), or null
     int B, N, k, n_chunks;
     float dmax;
     const SCand *cand;
@@ -1006,8 +1057,29 @@ __global__ __launch_bounds__(256) void screen_finish_kernel(FinishParams p)
         // definition, but the row's loads are not -- 16 of them (256 B) are issued back to back before the 64 fmaf that
         // consume them, four batches per row (left to hipcc the loop waited for one 16-byte load per iteration: ~30 us of a
         // 46 us kernel at k = 50)
-        const float *drow = p.D32 + (size_t)sv_x[sidx] * 256;
         float acc = 0.0f;
+        if (p.Dbf) { // bf16 rows: widened exactly, the same fmaf chain
+            const unsigned *brow = p.Dbf + (size_t)sv_x[sidx] * 128;
+#pragma unroll 1
+            for (int x0 = 0; x0 < 256; x0 += 64) {
+                u32x4 dv[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    dv[i] = __builtin_nontemporal_load((const u32x4 *)(brow + x0 / 2 + 4 * i));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned wv[4] = {dv[i].x, dv[i].y, dv[i].z, dv[i].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        acc = fmaf(qs[x0 + 8 * i + 2 * e], __uint_as_float(wv[e] << 16), acc);
+                        acc = fmaf(qs[x0 + 8 * i + 2 * e + 1], __uint_as_float(wv[e] & 0xffff0000u), acc);
+                    }
+                }
+            }
+            sv_v[sidx] = acc;
+            continue;
+        }
+        const float *drow = p.D32 + (size_t)sv_x[sidx] * 256;
 #pragma unroll 1
         for (int x0 = 0; x0 < 256; x0 += 64) {
             f32x4 dv[16];
@@ -1116,7 +1188,8 @@ __global__ __launch_bounds__(256) void build_from_bf16_kernel(const unsigned sho
                     amax = INFINITY;
                 hv[e] = (_Float16)v[e];
             }
-            *(f32x4 *)(out32 + row * d + x) = v;
+            if (out32) // (null: tt_index_stats_bf16, the statistics alone)
+                *(f32x4 *)(out32 + row * d + x) = v;
             if (out16)
                 *(h4 *)(out16 + row * d + x) = hv;
         }
@@ -1229,23 +1302,27 @@ SPlan make_splan(int B, int64_t N, int k)
 
 // The screen kernel of one form: streaming (q_per_block 32 or 64: 2 or 4 query sets per wave) or shared-tile (nset 16-query
 // sets per wave, 1..4).  MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).
-template <bool MAXONLY>
+// BF: the corpus is bf16 rows, converted in LDS (bf16_to_f16_lds).
+template <bool MAXONLY, bool BF>
 const void *screen_fn(bool stream, int q_per_block, int nset)
 {
     if (stream)
-        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4> : (const void *)screen_stream_kernel<MAXONLY, 2>;
+        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4, BF>
+                                 : (const void *)screen_stream_kernel<MAXONLY, 2, BF>;
     switch (nset) {
-    case 4: return (const void *)screen_kernel<MAXONLY, 4>;
-    case 3: return (const void *)screen_kernel<MAXONLY, 3>;
-    case 2: return (const void *)screen_kernel<MAXONLY, 2>;
-    default: return (const void *)screen_kernel<MAXONLY, 1>;
+    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF>;
+    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF>;
+    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF>;
+    default: return (const void *)screen_kernel<MAXONLY, 1, BF>;
     }
 }
 
 // One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
-int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st)
+int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st,
+                  bool bf16 = false)
 {
-    const void *fn = maxonly ? screen_fn<true>(stream, q_per_block, nset) : screen_fn<false>(stream, q_per_block, nset);
+    const void *fn = maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset) : screen_fn<true, false>(stream, q_per_block, nset))
+                             : (bf16 ? screen_fn<false, true>(stream, q_per_block, nset) : screen_fn<false, false>(stream, q_per_block, nset));
     const size_t lds = stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
     const int blocks = stream ? (n_tasks + TW - 1) / TW : n_tasks;
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1328,9 +1405,11 @@ enum class Phase {
                    // image and flags), finish, predicated exact kernels
 };
 
-int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, const float *D32, const void *D16, int64_t N, int k,
+// bf16: D32 and D16 are both the bf16 corpus (the screen converts it in LDS, the finish kernel and the fallback widen it).
+int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, const void *D32, const void *D16, int64_t N, int k,
                   int k_seed, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
-                  float *seed, void *workspace, size_t workspace_bytes, void *const *prof_events, hipStream_t st)
+                  float *seed, void *workspace, size_t workspace_bytes, void *const *prof_events, hipStream_t st,
+                  bool bf16 = false)
 {
     if (B <= 0 || N <= 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
@@ -1349,8 +1428,8 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     if (seed_only && (k_seed < 1 || k_seed > k))
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: k_seed=%d outside [1, k=%d]", who, k_seed, k);
     const SPlan pl = make_splan(B, N, k);
-    const size_t need = pl.ws_bytes + tt_score_topk_workspace_bytes(B, N, d, k);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
+    const size_t need = pl.ws_bytes + (bf16 ? tt_score_topk_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_workspace_bytes(B, N, d, k));
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255) || (bf16 && ((uintptr_t)D16 & 15)))
         return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     char *ws = (char *)workspace;
     // the sample maximum that becomes a threshold, and where it goes
@@ -1400,7 +1479,7 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
             ss.static_tiles = pl.s_tiles;
             ss.tail_blocks = 0;
             ss.max_val = (float *)(ws + pl.smax_val_off);
-            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st));
+            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st, bf16));
             if (phase == Phase::SeedList)
                 TT_RC_CHECK(tt_k_largest_list(ss.max_val, B, pl.s_tiles, k_seed, seed, st));
             else
@@ -1417,13 +1496,14 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
         return TT_OK;
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st));
+    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st, bf16));
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
 
     FinishParams fp;
     fp.Q = Q;
-    fp.D32 = D32;
+    fp.D32 = bf16 ? nullptr : (const float *)D32;
+    fp.Dbf = bf16 ? (const unsigned *)D32 : nullptr;
     fp.B = B;
     fp.N = (int)N;
     fp.k = k;
@@ -1440,10 +1520,67 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     hipLaunchKernelGGL(screen_finish_kernel, dim3(B), dim3(256), (size_t)(2 * pl.n_chunks + 1) * sizeof(int), st, fp);
     TT_LAUNCH_CHECK();
     // exact kernel, a no-op unless a workgroup raised the flag; then it rewrites every output row
-    return tt_score_topk_f32_pred(Q, B, d, D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
+    if (bf16)
+        return tt_score_topk_bf16_pred(Q, B, d, D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
+                                       workspace_bytes - pl.ws_bytes, fallback_flag, st);
+    return tt_score_topk_f32_pred(Q, B, d, (const float *)D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
                                   workspace_bytes - pl.ws_bytes, fallback_flag, st);
 }
 } // namespace
+
+// ---- the same over a bf16 corpus kept as bf16: D_bf16 replaces D32 + D16 (include/tt.h)
+TT_EXPORT size_t tt_score_topk_screened_bf16_workspace_bytes(int B, int64_t N, int d, int k)
+{
+    if (B <= 0 || N <= 0)
+        return 0;
+    return make_splan(B, N, k).ws_bytes + tt_score_topk_bf16_workspace_bytes(B, N, d, k);
+}
+
+TT_EXPORT int tt_index_stats_bf16(const void *D_bf16, int64_t N, int d, float *stats, int reset_stats, tt_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (N < 0 || d <= 0 || d % 4 != 0 || d > 4096)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_index_stats_bf16: N=%lld d=%d", (long long)N, d);
+    if (!stats || (N > 0 && !D_bf16))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_index_stats_bf16: null pointer");
+    if (reset_stats)
+        TT_RC_CHECK(tt_zero_async(stats, 2 * sizeof(float), st));
+    if (N == 0)
+        return TT_OK;
+    const int64_t want_blocks = (N + 3) / 4;
+    hipLaunchKernelGGL(build_from_bf16_kernel, dim3((unsigned)(want_blocks > 8192 ? 8192 : want_blocks)), dim3(256), 0,
+                       st, (const unsigned short *)D_bf16, N, d, (float *)nullptr, (_Float16 *)nullptr, (unsigned *)stats);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+TT_EXPORT int tt_score_topk_screened_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, float dmax_norm,
+                                          int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
+                                          void *workspace, size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_bf16", Phase::Whole, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm, idx_offset,
+                         out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream,
+                         true);
+}
+
+TT_EXPORT int tt_score_topk_screened_seed_list_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                                                    int k_seed, float dmax_norm, int32_t *fallback_flag, float *seed_list,
+                                                    void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seed_list_bf16", Phase::SeedList, Q, B, d, nullptr, D_bf16, N, k, k_seed,
+                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
+                         (hipStream_t)stream, true);
+}
+
+TT_EXPORT int tt_score_topk_screened_seeded_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                                                 float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                                 int32_t *fallback_flag, const float *seed, void *workspace,
+                                                 size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seeded_bf16", Phase::Seeded, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
+                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
+                         (hipStream_t)stream, true);
+}
 
 TT_EXPORT int tt_score_topk_screened_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
                                          int k, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
@@ -1521,8 +1658,9 @@ TT_EXPORT size_t tt_debug_screen_s16_workspace_bytes(int B, int64_t N, int form)
     return pl.total;
 }
 
-TT_EXPORT int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr,
-                                  int form, float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+namespace {
+int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr, int form, float *out_t,
+                 void *workspace, size_t workspace_bytes, tt_stream_t stream, bool bf16)
 {
     hipStream_t st = (hipStream_t)stream;
     DbgPlan pl;
@@ -1559,5 +1697,18 @@ TT_EXPORT int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_
     hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
                        (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0);
     TT_LAUNCH_CHECK();
-    return launch_screen(form == 0, pl.q_per_block, form, true, sp, pl.n_qgroups * pl.n_chunks, st);
+    return launch_screen(form == 0, pl.q_per_block, form, true, sp, pl.n_qgroups * pl.n_chunks, st, bf16);
+}
+} // namespace
+
+TT_EXPORT int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr,
+                                  int form, float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return debug_screen(Q, B, D16, N, dmax_norm, thr, form, out_t, workspace, workspace_bytes, stream, false);
+}
+
+TT_EXPORT int tt_debug_screen_s16_bf16(const float *Q, int B, const void *D_bf16, int64_t N, float dmax_norm, const float *thr,
+                                       int form, float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return debug_screen(Q, B, D_bf16, N, dmax_norm, thr, form, out_t, workspace, workspace_bytes, stream, true);
 }

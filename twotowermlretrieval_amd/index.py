@@ -41,14 +41,29 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _docs_c(t: torch.Tensor) -> torch.Tensor:
+    """A document matrix as the exact kernels read it: float32, or bfloat16 kept as it is (tt_score_topk_bf16)."""
+    if t.dtype == torch.bfloat16:
+        return t if t.is_contiguous() else t.contiguous()
+    return _f32c(t)
+
+
+def _topk_workspace_bytes(B: int, N: int, d: int, k: int, dtype: torch.dtype) -> int:
+    L = _lib.lib()
+    if dtype == torch.bfloat16:
+        return L.tt_score_topk_bf16_workspace_bytes(B, N, d, k)
+    return L.tt_score_topk_workspace_bytes(B, N, d, k)
+
+
 def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
                workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """topk(q @ docs.T, k) fused.  q [B,d] or [d]; docs [N,d] (row i <-> document i)."""
+    """topk(q @ docs.T, k) fused.  q [B,d] or [d] float32; docs [N,d] (row i <-> document i), float32 or bfloat16.  A bf16
+    matrix is read as it is (d in {64, 128, 192, 256}); the result is that of its exact fp32 widening, bit for bit."""
     squeeze = q.dim() == 1
     if squeeze:
         q = q.unsqueeze(0)
     _need_cuda(q, docs)
-    q, docs = _f32c(q), _f32c(docs)
+    q, docs = _f32c(q), _docs_c(docs)
     B, d = q.shape
     N = docs.shape[0]
     if docs.dim() != 2 or docs.shape[1] != d:
@@ -56,12 +71,13 @@ def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
     L = _lib.lib()
     vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
-    need = L.tt_score_topk_workspace_bytes(B, N, d, k)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(L.tt_score_topk_f32(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(),
-                                       idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q)))
+    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
+        need = _topk_workspace_bytes(B, N, d, k, docs.dtype)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+        fn = L.tt_score_topk_bf16 if docs.dtype == torch.bfloat16 else L.tt_score_topk_f32
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(), idx.data_ptr(),
+                      workspace.data_ptr(), workspace.numel(), _stream(q)))
     return (vals[0], idx[0]) if squeeze else (vals, idx)
 
 
@@ -126,11 +142,17 @@ class BruteForceIndex:
     screen=True additionally keeps an fp16 shadow copy (N*d*2 bytes) so that large query batches
     run the screened path (fp16 MFMA filter + exact fp32 rescoring, tt_score_topk_screened_f32):
     same bit-exact result, an order of magnitude more queries/s than the fp32-MFMA-bound kernel.
+
+    A bfloat16 [N,d] matrix (d in {64, 128, 192, 256}) is kept as it is: `docs` is the caller's tensor (no copy, N*d*2
+    bytes, no shadow).  screen=True at d = 256 runs one statistics pass (tt_index_stats_bf16) and screens straight from the
+    bf16 rows (tt_score_topk_screened_bf16: converted to fp16 in LDS); otherwise, and outside the fp16 range, searches run
+    the exact kernel over the bf16 rows (tt_score_topk_bf16).  Either way the result is that of the widened fp32 rows, bit
+    for bit.
     """
 
     def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False):
         _need_cuda(doc_embeddings)
-        self.docs = _f32c(doc_embeddings)
+        self.docs = _docs_c(doc_embeddings)
         self.idx_offset = int(idx_offset)
         self.docs16: Optional[torch.Tensor] = None
         self.dmax_norm = float("nan")
@@ -139,7 +161,22 @@ class BruteForceIndex:
         self._last_ws = None
         N, d = self.docs.shape
         self._sdocs = self.docs  # what the screened path scores against: [N,256] fp32
-        if screen and N > 0 and (d == 256 or (d < 256 and d % 4 == 0)):
+        self._screen_bf16 = False  # bf16 rows screened as they are (no docs16)
+        if self.docs.dtype == torch.bfloat16 and screen and N > 0:
+            if d == 256:
+                stats = torch.zeros(2, dtype=torch.float32, device=self.docs.device)
+                with torch.cuda.device(self.docs.device):
+                    _lib.check(_lib.lib().tt_index_stats_bf16(self.docs.data_ptr(), N, d, stats.data_ptr(), 1,
+                                                              _stream(self.docs)))
+                dmax, amax = (float(x) for x in stats.tolist())  # one sync, at index-build time
+                if dmax == dmax and amax < 6.0e4 and dmax < 6.0e4:
+                    self.dmax_norm = dmax
+                    self._screen_bf16 = True
+            if not self._screen_bf16:
+                import warnings
+                warnings.warn(f"BruteForceIndex: a bf16 [{N},{d}] corpus is screened only at d = 256 within the fp16 range; "
+                              "this index runs the exact bf16 kernel", RuntimeWarning, stacklevel=2)
+        if screen and N > 0 and self.docs.dtype == torch.float32 and (d == 256 or (d < 256 and d % 4 == 0)):
             L = _lib.lib()
             if d < 256:
                 # narrower embeddings (HIDDEN_DIM 64, 128, ...): zero-padded to the screen kernels' 256 features.
@@ -165,6 +202,7 @@ class BruteForceIndex:
         self = cls.__new__(cls)
         self.docs, self.docs16, self.dmax_norm, self.idx_offset = docs32, docs16, float(dmax_norm), int(idx_offset)
         self._sdocs = docs32
+        self._screen_bf16 = False
         self.fallback_flags = torch.zeros(1, dtype=torch.int32, device=docs32.device)
         self.keep_stats, self._last_ws = False, None
         return self
@@ -207,7 +245,7 @@ class BruteForceIndex:
                 return vals[0], idx[0]
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list)
         with torch.cuda.device(self.docs.device):
-            need = _lib.lib().tt_score_topk_workspace_bytes(B, N, d, k)
+            need = _topk_workspace_bytes(B, N, d, k, self.docs.dtype)
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.docs.device)
         v, i = score_topk(q, self.docs, k, self.idx_offset, ws)
         if out is not None:
@@ -220,7 +258,7 @@ class BruteForceIndex:
         """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
         whether they enter the seed exchange; the thresholds are the module's at the time of the call."""
         N, d = self.docs.shape
-        return (self.docs16 is not None and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
+        return ((self.docs16 is not None or self._screen_bf16) and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
                 and N >= SCREEN_MIN_DOCS and k <= 64)
 
     def _search_screened(self, q: torch.Tensor, k: int, _prof_events=None, out=None, _seed_union=None,
@@ -241,7 +279,8 @@ class BruteForceIndex:
             idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
         with torch.cuda.device(self.docs.device):  # workspace sizing depends on the device's CU count
             # per-call workspace and flags (cached allocator blocks): safe for concurrent callers and streams
-            need = L.tt_score_topk_screened_workspace_bytes(B, N, d, k)
+            bf = self._screen_bf16
+            need = (L.tt_score_topk_screened_bf16_workspace_bytes if bf else L.tt_score_topk_screened_workspace_bytes)(B, N, d, k)
             ws_s = torch.empty(need, dtype=torch.uint8, device=self.docs.device)
             flags = torch.empty((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
             if self.keep_stats:
@@ -249,17 +288,27 @@ class BruteForceIndex:
             if _seed_union is not None:
                 ks = min(_k_list or _k_seed or k, k)  # entries per seed list (the caller ranks the union)
                 lst = torch.empty((B, ks), dtype=torch.float32, device=self.docs.device)
-                _lib.check(L.tt_score_topk_screened_seed_list_f32(q.data_ptr(), B, d, self.docs16.data_ptr(), N, k, ks,
-                                                                  self.dmax_norm, flags.data_ptr(), lst.data_ptr(),
-                                                                  ws_s.data_ptr(), ws_s.numel(), _stream(q)))
+                fn = L.tt_score_topk_screened_seed_list_bf16 if bf else L.tt_score_topk_screened_seed_list_f32
+                _lib.check(fn(q.data_ptr(), B, d, (self.docs if bf else self.docs16).data_ptr(), N, k, ks, self.dmax_norm,
+                              flags.data_ptr(), lst.data_ptr(), ws_s.data_ptr(), ws_s.numel(), _stream(q)))
                 seed = _seed_union(lst)
                 if seed.shape != (B,) or seed.dtype != torch.float32 or not seed.is_contiguous():
                     raise ValueError("_seed_union must return a contiguous float32 [B] tensor")
-                _lib.check(L.tt_score_topk_screened_seeded_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(),
-                                                               self.docs16.data_ptr(), N, k, self.dmax_norm,
-                                                               self.idx_offset, vals.data_ptr(), idx.data_ptr(),
-                                                               flags.data_ptr(), seed.data_ptr(), ws_s.data_ptr(),
-                                                               ws_s.numel(), _prof_events, _stream(q)))
+                if bf:
+                    _lib.check(L.tt_score_topk_screened_seeded_bf16(q.data_ptr(), B, d, self.docs.data_ptr(), N, k,
+                                                                    self.dmax_norm, self.idx_offset, vals.data_ptr(),
+                                                                    idx.data_ptr(), flags.data_ptr(), seed.data_ptr(),
+                                                                    ws_s.data_ptr(), ws_s.numel(), _prof_events, _stream(q)))
+                else:
+                    _lib.check(L.tt_score_topk_screened_seeded_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(),
+                                                                   self.docs16.data_ptr(), N, k, self.dmax_norm,
+                                                                   self.idx_offset, vals.data_ptr(), idx.data_ptr(),
+                                                                   flags.data_ptr(), seed.data_ptr(), ws_s.data_ptr(),
+                                                                   ws_s.numel(), _prof_events, _stream(q)))
+            elif bf:
+                _lib.check(L.tt_score_topk_screened_bf16(q.data_ptr(), B, d, self.docs.data_ptr(), N, k, self.dmax_norm,
+                                                         self.idx_offset, vals.data_ptr(), idx.data_ptr(), flags.data_ptr(),
+                                                         ws_s.data_ptr(), ws_s.numel(), _prof_events, _stream(q)))
             else:
                 _lib.check(L.tt_score_topk_screened_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(), self.docs16.data_ptr(),
                                                         N, k, self.dmax_norm, self.idx_offset, vals.data_ptr(),
@@ -432,7 +481,9 @@ class ShardedIndex:
     def __init__(self, local_docs, row_offset: int, group=None, shard_k: int = 50, screen: bool = False,
                  comm=None, block_docs: int = 1 << 20, device=None):
         """local_docs: this rank's rows [row_offset, row_offset + n) of the corpus, as
-          * a device fp32 [n,d] tensor: resident shard (BruteForceIndex; BASELINE configs[3]), or
+          * a device fp32 [n,d] tensor: resident shard (BruteForceIndex; BASELINE configs[3]),
+          * a device bf16 [n,d] tensor: resident shard kept as bf16 (BruteForceIndex over it; with screen=True it screens from
+            the bf16 rows and takes part in the seed exchange like an fp32 shard), or
           * a CPU bfloat16 [n,d] tensor / a StreamedIndex: the shard stays in pinned host DRAM and every search streams it
             through the GPU in blocks of block_docs rows (BASELINE configs[4]: 100M x 256 bf16 over 8 GPUs = 12.5M rows,
             6.4 GB per rank, PCIe-bound).  The streamed shard's list is the exact top-k' of its rows (bf16 -> fp32 is exact),
@@ -536,14 +587,19 @@ class ShardedIndex:
         return cls(docs[lo:hi], lo, group=group, **kw)
 
     @classmethod
-    def from_host_bf16(cls, host_docs: torch.Tensor, group=None, **kw) -> "ShardedIndex":
+    def from_host_bf16(cls, host_docs: torch.Tensor, group=None, resident: bool = False, **kw) -> "ShardedIndex":
         """BASELINE configs[4]: `host_docs` is the WHOLE bf16 corpus [N,d] in host memory (an np.memmap-backed tensor will do:
-        only this rank's rows are touched); rank r pins and streams rows [r*N/W, (r+1)*N/W) only."""
+        only this rank's rows are touched); rank r pins and streams rows [r*N/W, (r+1)*N/W) only.  resident=True: rank r
+        copies those rows to its GPU once, as bf16 (n*d*2 bytes of HBM), and searches them there."""
         import torch.distributed as dist
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         lo, hi = shard_bounds(host_docs.shape[0], rank, world)
-        return cls(host_docs[lo:hi], lo, group=group, **kw)
+        rows = host_docs[lo:hi]
+        if resident:
+            dev = kw.pop("device", None)
+            rows = rows.to(torch.device(dev) if dev is not None else torch.device("cuda", torch.cuda.current_device()))
+        return cls(rows, lo, group=group, **kw)
 
     @classmethod
     def from_documents(cls, model, tokenizer, documents, device, group=None, **kw) -> "ShardedIndex":
@@ -695,9 +751,15 @@ class StreamedIndex:
             self._free[s].record(cur)
             visit(s, lo, n)
 
-    def resident(self) -> "BruteForceIndex":
+    def resident(self, dtype: torch.dtype = torch.float32) -> "BruteForceIndex":
         """The same corpus widened once into HBM (N*d*4 bytes fp32 + N*d*2 bytes fp16 shadow): configs[4]'s shard
-        of 12.5M passages is 19.2 GB of a 288 GB GPU, after which it is searched at the resident rates."""
+        of 12.5M passages is 19.2 GB of a 288 GB GPU, after which it is searched at the resident rates.
+        dtype=torch.bfloat16: the rows are copied to HBM as they are (N*d*2 bytes, 6.4 GB for that shard) and searched by
+        the exact bf16 kernel (same results)."""
+        if dtype == torch.bfloat16:
+            return BruteForceIndex(self.host.to(self.device), idx_offset=self.idx_offset)
+        if dtype != torch.float32:
+            raise ValueError(f"resident() keeps float32 or bfloat16 rows, not {dtype}")
         d32 = torch.empty((self.N, self.d), dtype=torch.float32, device=self.device)
         d16 = torch.empty((self.N, self.d), dtype=torch.float16, device=self.device) if self._d16[0] is not None else None
 
