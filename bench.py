@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: starts N rank processes itself)
     python bench.py ... --dump-outputs DIR              (also writes the last timed step's top-k to DIR/*.npy)
+    python bench.py ... --full                          (also runs every leg below: several minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch of B=1024 synthetic queries: every rank scores
@@ -11,7 +12,9 @@ the screened exact search (fp16-MFMA filter over an fp16 shadow copy with a rigo
 exact fp32 rescoring of the survivors: bit-identical to the plain fp32 kernel and to the CPU
 oracle), and for N > 1 the per-shard top-50 lists are all-gathered over RCCL and merged to the
 global top-10 on every rank (strong scaling: the corpus is fixed, the shard shrinks with N).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run stops there: set-up, warm-up, the timed steps, the dump,
+the headline line.  `roofline` and `cpu_baseline` are in the line only with --full, which runs the
+legs below after the timed loop (the headline value is the same either way).
 
 Legs EVERY rank executes after the timed loop (collectives; reported under `roofline.legs`): `streamed_bf16` (BASELINE configs[4]:
 each GPU's 12.5M-row bf16 shard streamed from pinned host DRAM through a ShardedIndex, GB/s per GPU against PCIe, resident variant
@@ -945,22 +948,31 @@ def launch_ranks(n: int) -> int:
     return rc or 1
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the encoder / train / encoder-corpus legs")
-    ap.add_argument("--no-encoder-corpus", action="store_true", help="skip the encoder-produced-corpus leg (~20 s)")
-    ap.add_argument("--no-streamed", action="store_true", help="skip the configs[4] leg (6.4 GB of pinned host memory per rank)")
-    ap.add_argument("--stream-docs", type=int, default=STREAM_DOCS_PER_GPU, help="rows per GPU of the configs[4] leg (rehearsals)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline, collective, encoder / train, serving and CPU baseline legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline legs")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the encoder / train / encoder-corpus legs")
+    ap.add_argument("--no-encoder-corpus", action="store_true", help="(--full) skip the encoder-produced-corpus leg (~20 s)")
+    ap.add_argument("--no-streamed", action="store_true",
+                    help="(--full) skip the configs[4] leg (6.4 GB of pinned host memory per rank)")
+    ap.add_argument("--stream-docs", type=int, default=STREAM_DOCS_PER_GPU,
+                    help="(--full) rows per GPU of the configs[4] leg (rehearsals)")
     ap.add_argument("--graph-legs-child", action="store_true", help="internal: graph_legs() on cuda:0, one JSON line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's top-k scores and indices to DIR/<name>.npy (rank 0)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.graph_legs_child:
         torch.cuda.set_device(0)
@@ -1039,6 +1051,27 @@ def main():
     assert vals.shape == (BATCH, TOPK) and bool((vals[:, 1:] <= vals[:, :-1]).all()) and int(idx.min()) >= 0
     if a.dump_outputs and rank == 0:  # every rank holds the same merged top-k; the legs below do not touch it
         dump_outputs(a.dump_outputs, vals, idx)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "queries/sec top-k over 10M x 256-d docs", "value": round(BATCH * a.steps / dt, 2),
+            "unit": "queries/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32 results (bit-identical to the fp32 FMA chain); f16-MFMA screen + fp32 rescoring",
+            "data": "synthetic",
+            "config": {"workload": f"exact cosine top-{TOPK} of B={BATCH} queries over {N_DOCS} x {DIM} fp32 unit-norm "
+                                   f"passages resident in HBM (BASELINE configs[3]; configs[1] batch), row-sharded "
+                                   f"over {world} GPU(s), screened path (f16-MFMA filter + exact fp32 rescoring, "
+                                   f"bit-identical to the fp32 kernel)"
+                                   + (f", union seed (all-gather of every rank's {TOPK} largest sample maxima per query), "
+                                      f"per-shard lists of up to {SHARD_K} (the shard's documents above the global "
+                                      f"threshold) + RCCL all-gather + merge" if world > 1 else ""),
+                       "n_docs": N_DOCS, "dim": DIM, "batch": BATCH, "k": TOPK, "parallelism": f"rowshard{world}",
+                       "collective": index.collective if world > 1 else None},
+        }
+    if not a.full:  # a plain run: the headline figure only (the legs below take minutes)
+        finish(line, world)
+        return
 
     flags = int(local_index.fallback_flags.ne(0).sum().item())
     # the legs that are collectives (configs[4] streamed shards, configs[2] data-parallel training): all ranks, same order
@@ -1086,23 +1119,7 @@ def main():
                     "traffic": pmc_traffic("stream_b32") if world == 1 else None,
                     "kernel_ms": round(ms32s, 4), "search_ms": round(t32, 4), "batch": 32,
                     "docs_per_gpu": n_shard, "qps": round(32 / t32 * 1e3, 1)}
-        line = {
-            "metric": "queries/sec top-k over 10M x 256-d docs", "value": round(BATCH * a.steps / dt, 2),
-            "unit": "queries/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32 results (bit-identical to the fp32 FMA chain); f16-MFMA screen + fp32 rescoring",
-            "data": "synthetic",
-            "config": {"workload": f"exact cosine top-{TOPK} of B={BATCH} queries over {N_DOCS} x {DIM} fp32 unit-norm "
-                                   f"passages resident in HBM (BASELINE configs[3]; configs[1] batch), row-sharded "
-                                   f"over {world} GPU(s), screened path (f16-MFMA filter + exact fp32 rescoring, "
-                                   f"bit-identical to the fp32 kernel)"
-                                   + (f", union seed (all-gather of every rank's {TOPK} largest sample maxima per query), "
-                                      f"per-shard lists of up to {SHARD_K} (the shard's documents above the global "
-                                      f"threshold) + RCCL all-gather + merge" if world > 1 else ""),
-                       "n_docs": N_DOCS, "dim": DIM, "batch": BATCH, "k": TOPK, "parallelism": f"rowshard{world}",
-                       "collective": index.collective if world > 1 else None},
-            "roofline": roof,
-        }
+        line["roofline"] = roof
         # every other leg rides INSIDE `roofline` (the driver's record keeps `roofline` and `cpu_baseline` whole):
         #   hbm_screen      north_star's ">= 70 % of HBM" regime: the streaming screen at B = 32 over the fp16 shadow corpus
         #   hbm_exact_f32   the plain fp32 kernel at B = 32 (N x 1024 bytes)
@@ -1139,6 +1156,12 @@ def main():
                 roof["legs"]["clustered_corpus"] = clustered_corpus_leg(dev)
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(q, docs, enc_inputs)
+    finish(line, world)
+
+
+def finish(line, world: int):
+    """Rank 0 (line given) prints the result line; then every rank leaves the process group."""
+    if line is not None:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,5 +1,6 @@
 """bench.py's output dump (--dump-outputs DIR) and its argument checks, on the host: the files a comparison of two builds
-reads, their dtypes and their values; a step count below one is refused before any device is touched."""
+reads, their dtypes and their values; a step count below one is refused before any device is touched; the legs beyond the
+headline figure run only when --full asks for them."""
 import subprocess
 import sys
 
@@ -27,3 +28,9 @@ def test_bench_refuses_zero_steps():
     for args in (["--steps", "0"], ["--warmup", "-1"]):
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, (args, r.returncode, r.stderr[-500:])
+
+
+def test_legs_beyond_the_headline_need_full():
+    import bench
+    assert not bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"]).full
+    assert bench.parse_args(["--full", "--no-cpu-baseline"]).full

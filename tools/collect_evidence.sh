@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence of one build (run on the MI355X box from the repo root):  bash tools/collect_evidence.sh TAG
-#   gpurun_out/TAG_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats over `bench.py --steps 5 --warmup 2 --no-cpu-baseline`
+#   $OUT/TAG_bench_kernel_stats.csv         rocprofv3 --kernel-trace --stats over `bench.py --steps 5 --warmup 2 --full --no-cpu-baseline`
 #                                           (tools/rocpd_stats.py: one row per kernel, grid and duration cluster)
 #   gpurun_out/TAG_bench_profiled.json      the bench line of that same run
 #   gpurun_out/TAG_pmc_summary.txt          FETCH_SIZE / WRITE_SIZE per launch (separate --pmc passes, --kernel-trace only) over
@@ -11,7 +11,7 @@ TAG=${1:-evidence}
 OUT=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 rm -rf $OUT/${TAG}_prof $OUT/${TAG}_pmc_*
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_profiled.json 2> $OUT/${TAG}_bench_profiled.err || exit 2
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o bench -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/${TAG}_bench_profiled.json 2> $OUT/${TAG}_bench_profiled.err || exit 2
 DB=$(ls $OUT/${TAG}_prof/*results.db $OUT/${TAG}_prof/*/*results.db 2>/dev/null | head -1)
 python3 tools/rocpd_stats.py "$DB" $OUT/${TAG}_bench_kernel_stats.csv || exit 3
 echo "kernel stats done" 

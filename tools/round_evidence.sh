@@ -1,7 +1,7 @@
 #!/bin/bash
 # The evidence of one build in ONE gpurun call (run on the MI355X box from the repo root):  bash tools/round_evidence.sh TAG
 #   gpurun_out/TAG_tests.log                 pytest -m gpu (all) tail
-#   gpurun_out/TAG_bench_n1.json             python bench.py (defaults: full line with cpu_baseline)
+#   $OUT/TAG_bench_n1.json                   python bench.py --full (full line with cpu_baseline)
 #   gpurun_out/TAG_bench_profiled.json, TAG_bench_kernel_stats.csv, TAG_pmc_summary.txt      tools/collect_evidence.sh TAG
 #   gpurun_out/TAG_train_timeline.txt, TAG_train_step_kernel_stats.csv    rocprofv3 --kernel-trace --stats over tools/train_prof.py 6
 # Steps are joined with && : a step that fails or is killed ends the call.
@@ -12,7 +12,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_tests.log 2
 cp $OUT/tolerance_report.json $OUT/${TAG}_tolerance_report.json 2>/dev/null
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1 || { tail -5 $OUT/${TAG}_smoke.log; exit 6; }
 tail -1 $OUT/${TAG}_smoke.log
-timeout -k 10 900 python3 bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err || exit 3
+timeout -k 10 900 python3 bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err || exit 3
 python3 -c "
 import json; d = json.load(open('$OUT/${TAG}_bench_n1.json')); L = d['roofline']['legs']
 print('value', d['value'], 'ms/step', d['ms_per_step'], 'roofline.frac', d['roofline']['frac'], 'hbm_screen', L['hbm_screen']['frac'], 'hbm_exact', L['hbm_exact_f32']['frac'], 'mfma_exact', L['mfma_exact_f32']['frac'])
