@@ -103,6 +103,33 @@ int tt_score_topk_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t
                        size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * Large k: the same exact search for 1 <= k <= TT_TOPK_LARGE_KMAX.  Replaces
+ *   torch.matmul(q, D.t()) ; torch.topk(scores, k=max(top_k))   backend/evaluators.py:185-186, :269-272 ;
+ *   backend/trainer.py:62-65
+ * where top_k is whatever the caller asks for (Recall@100 / @1000, a candidate set for a reranker).  Arguments, supported d,
+ * N < 2^31 - 64 and the result contract are tt_score_topk_f32's / tt_score_topk_bf16's (bf16 = 0 / 1 in the size queries),
+ * bit for bit, ties and the N < k tail included; k <= 64 runs that call (same bits; one extra launch zeroes the tier
+ * words), k > TT_TOPK_LARGE_KMAX returns TT_ERR_UNSUPPORTED.  Above 64 the k = 64 main pass runs unchanged (seeded with the k-th, not the 64th, sample
+ * maximum); t_q = the k-th best of the union of its per-wave lists bounds the k-th score from below, and a query none of whose
+ * full lists reaches t_q is answered from the union (tier 0).  Otherwise the query is rescanned with the same fp32 chain and
+ * every document >= t_q collected (tier 1), or, when they exceed the per-query buffer (4096), the k-th (score, index) is
+ * narrowed by radix histograms over further scans before the collection (tier 2: huge tie groups, near-duplicate clusters).
+ * All of it is decided on the device (no host synchronisation: capturable), in a workspace of
+ * tt_score_topk_large_workspace_bytes (known before the call, ~40 KB per query beyond the k = 64 search's).
+ * tt_score_topk_large_tier_offset: diagnostic byte offset, in the workspace of a finished call of this shape, of one int32 per
+ * query: 0 = answered from the first pass, 1 = rescanned, 2 = needed the histogram refinement.
+ */
+#define TT_TOPK_LARGE_KMAX 1024
+size_t tt_score_topk_large_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+size_t tt_score_topk_large_tier_offset(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_large_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
+                            int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                            size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_large_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                             int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                             size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
  * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
  * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it
@@ -221,6 +248,18 @@ int tt_topk_merge(const float *in_val, const int64_t *in_idx, int B, int M, int 
  */
 int tt_topk_merge_shards(const void *gathered, int world, size_t rank_stride, size_t idx_byte_offset,
                          int B, int kp, int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
+
+/*
+ * The two merges for 1 <= k <= TT_TOPK_LARGE_KMAX: the merge of per-shard lists after the all-gather, for the
+ * torch.topk(scores, k=max(top_k)) of backend/evaluators.py:185-186, :269-272 at any top_k.  Same arguments and contract
+ * as tt_topk_merge / tt_topk_merge_shards (candidate indices distinct within a row, or identical pairs); k <= 64 is that
+ * call.  Above it one block per row: radix select of the k-th score, of the closing index when the k-th score's tie group
+ * is larger than the places left (exact for any number of ties), compaction and a bitonic sort in LDS.
+ */
+int tt_topk_merge_large(const float *in_val, const int64_t *in_idx, int B, int M, int k,
+                        float *out_val, int64_t *out_idx, tt_stream_t stream);
+int tt_topk_merge_shards_large(const void *gathered, int world, size_t rank_stride, size_t idx_byte_offset,
+                               int B, int kp, int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
 
 /*
  * Rank (1-based) of one designated document per query under (score desc,

@@ -41,6 +41,10 @@ SIGNATURES = {
     "tt_score_topk_f32": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "tt_score_topk_bf16_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
     "tt_score_topk_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_large_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "tt_score_topk_large_tier_offset": (_sz, [_i, _i64, _i, _i, _i]),
+    "tt_score_topk_large_f32": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_large_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "tt_score_topk_screened_bf16_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
     "tt_index_stats_bf16": (_i, [_vp, _i64, _i, _vp, _i, _vp]),
     "tt_score_topk_screened_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
@@ -61,6 +65,8 @@ SIGNATURES = {
     "tt_event_elapsed_ms": (_i, [_vp, _vp, _vp]),
     "tt_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tt_topk_merge_shards": (_i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _vp]),
+    "tt_topk_merge_large": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "tt_topk_merge_shards_large": (_i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _vp]),
     "tt_score_rank_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "tt_score_all_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp]),
     "tt_tok_create": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),

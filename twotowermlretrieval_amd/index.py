@@ -48,8 +48,31 @@ def _docs_c(t: torch.Tensor) -> torch.Tensor:
     return _f32c(t)
 
 
+# Above this k the exact search and the merges take the large-k entry points (tt_score_topk_large_*, tt_topk_merge_large,
+# tt_topk_merge_shards_large: k <= 1024); at or below it, the k <= 64 calls as they always were.
+SMALL_KMAX = 64
+
+
+def _topk_fn(k: int, dtype: torch.dtype) -> str:
+    """The C entry point an exact search for k over a matrix of this dtype calls."""
+    bf = dtype == torch.bfloat16
+    if k > SMALL_KMAX:
+        return "tt_score_topk_large_bf16" if bf else "tt_score_topk_large_f32"
+    return "tt_score_topk_bf16" if bf else "tt_score_topk_f32"
+
+
+def _merge_fn(k: int, kp: int = 0, shards: bool = False) -> str:
+    """The C merge a k-merge (of per-shard lists of kp when `shards`) calls."""
+    large = k > SMALL_KMAX or kp > SMALL_KMAX
+    if shards:
+        return "tt_topk_merge_shards_large" if large else "tt_topk_merge_shards"
+    return "tt_topk_merge_large" if large else "tt_topk_merge"
+
+
 def _topk_workspace_bytes(B: int, N: int, d: int, k: int, dtype: torch.dtype) -> int:
     L = _lib.lib()
+    if k > SMALL_KMAX:
+        return L.tt_score_topk_large_workspace_bytes(B, N, d, k, int(dtype == torch.bfloat16))
     if dtype == torch.bfloat16:
         return L.tt_score_topk_bf16_workspace_bytes(B, N, d, k)
     return L.tt_score_topk_workspace_bytes(B, N, d, k)
@@ -75,7 +98,7 @@ def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
         need = _topk_workspace_bytes(B, N, d, k, docs.dtype)
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        fn = L.tt_score_topk_bf16 if docs.dtype == torch.bfloat16 else L.tt_score_topk_f32
+        fn = getattr(L, _topk_fn(k, docs.dtype))
         _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(), idx.data_ptr(),
                       workspace.data_ptr(), workspace.numel(), _stream(q)))
     return (vals[0], idx[0]) if squeeze else (vals, idx)
@@ -92,8 +115,8 @@ def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Ten
     ov = torch.empty((B, k), dtype=torch.float32, device=vals.device)
     oi = torch.empty((B, k), dtype=torch.int64, device=vals.device)
     with torch.cuda.device(vals.device):
-        _lib.check(_lib.lib().tt_topk_merge(vals.data_ptr(), idx.data_ptr(), B, M, k, ov.data_ptr(), oi.data_ptr(),
-                                            _stream(vals)))
+        _lib.check(getattr(_lib.lib(), _merge_fn(k))(vals.data_ptr(), idx.data_ptr(), B, M, k, ov.data_ptr(),
+                                                     oi.data_ptr(), _stream(vals)))
     return ov, oi
 
 
@@ -651,8 +674,9 @@ class ShardedIndex:
         """all-gather + in-place merge of one slot on the CURRENT stream."""
         self._coll.all_gather_blocks(sl.send, sl.recv)
         with torch.cuda.device(sl.recv.device):
-            _lib.check(_lib.lib().tt_topk_merge_shards(sl.recv.data_ptr(), self._coll.world, sl.stride, sl.nv, B, kp, k,
-                                                       sl.out_v.data_ptr(), sl.out_i.data_ptr(), _stream(sl.recv)))
+            merge = getattr(_lib.lib(), _merge_fn(k, kp, shards=True))
+            _lib.check(merge(sl.recv.data_ptr(), self._coll.world, sl.stride, sl.nv, B, kp, k, sl.out_v.data_ptr(),
+                             sl.out_i.data_ptr(), _stream(sl.recv)))
 
     def search(self, q: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
         """One search, everything on the caller's stream; fresh result tensors."""
