@@ -95,3 +95,28 @@ def test_python_workspace_sizing_by_k(libtt):
             == libtt.tt_score_topk_large_workspace_bytes(8, 100_000, 128, 1000, 1))
     # seed exchange stays off above 64
     assert index.seed_plan(8, 65) is None
+
+
+def test_python_routing_of_the_screened_phases():
+    """_screened_fn is the one place that names the screened entry points: every (phase, dtype) pair gives a bound export,
+    and the six of them are exactly the tt_score_topk_screened_{seed_list_,seeded_,}{f32,bf16} the header declares."""
+    import re
+    from twotowermlretrieval_amd import _lib, index
+    names = {index._screened_fn(phase, bf16) for phase in ("whole", "seed_list", "seeded") for bf16 in (False, True)}
+    assert names <= set(_lib.SIGNATURES)
+    declared = {n for n in _declared() if re.fullmatch(r"tt_score_topk_screened_(seed_list_|seeded_|)(f32|bf16)", n)}
+    assert len(declared) == 6 and names == declared
+    assert index._screened_fn("whole", False) == "tt_score_topk_screened_f32"
+    assert index._screened_fn("seed_list", True) == "tt_score_topk_screened_seed_list_bf16"
+    assert index._screened_fn("seeded", False) == "tt_score_topk_screened_seeded_f32"
+    with pytest.raises(KeyError):
+        index._screened_fn("seed", False)  # (tt_score_topk_screened_seed_f32 exists, with another signature)
+
+
+def test_fp16_range_rule():
+    from twotowermlretrieval_amd.index import _fp16_range_ok
+    nan, below = float("nan"), 59999.996  # the largest float32 below 6.0e4
+    assert _fp16_range_ok(1.0, 0.5) and _fp16_range_ok(below, below)
+    assert not _fp16_range_ok(nan, 0.5) and not _fp16_range_ok(1.0, nan) and not _fp16_range_ok(nan, nan)
+    assert not _fp16_range_ok(6.0e4, 0.5) and not _fp16_range_ok(below, 6.0e4)
+    assert not _fp16_range_ok(float("inf"), 0.5)

@@ -252,3 +252,51 @@ def test_100m_rows_resident_on_one_gpu(tt):
     assert torch.equal(i32, ei[:32]) and torch.equal(v32, ev[:32])
     del ix, D
     torch.cuda.empty_cache()
+
+
+# ---- one screened call site for every corpus layout (index._Screen) ----
+LAYOUT_N, LAYOUT_B, LAYOUT_K, LAYOUT_OFF = 65536, 33, 10, 9
+
+
+@pytest.fixture(scope="module")
+def layouts(oracle):
+    """layout -> (device rows, Q, the oracle's top-k over the fp32-widened rows), computed once for both search forms."""
+    made = {}
+
+    def get(layout):
+        if layout not in made:
+            d = 128 if layout == "f32_d128_padded" else 256
+            D = synth.unit_rows(500 + d, LAYOUT_N, d)
+            rows = dev(D).to(torch.bfloat16) if layout == "bf16_d256" else dev(D)
+            Q = synth.unit_rows(600 + d, LAYOUT_B, d)
+            made[layout] = (rows, Q, oracle.score_topk(Q, rows.float().cpu().numpy(), LAYOUT_K, idx_offset=LAYOUT_OFF))
+        return made[layout]
+
+    yield get
+    made.clear()
+
+
+@pytest.mark.parametrize("form", ["index", "sharded_world1"])
+@pytest.mark.parametrize("layout", ["f32_d256", "f32_d128_padded", "bf16_d256"])
+def test_every_layout_screens_through_the_same_calls(tt, layouts, monkeypatch, layout, form):
+    """The smallest shapes that still screen with the product thresholds: N = SCREEN_MIN_DOCS rows, B = 33 (the smallest
+    batch at which the padded layout screens; two 32-query tiles).  BruteForceIndex.search makes the whole-search call; a
+    world-1 ShardedIndex with shard_k > k makes the seed-list + seeded calls where the seed exchange applies (d = 256) and the
+    whole-search call for the padded layout.  Every result is the oracle's over the fp32-widened rows, bit for bit."""
+    from twotowermlretrieval_amd import index as _index
+    monkeypatch.setattr(_index, "SCREEN_MIN_DOCS", 65536)  # the product values (other tests lower them)
+    monkeypatch.setattr(_index, "SCREEN_MIN_BATCH", 1)
+    monkeypatch.setattr(_index, "SCREEN_PADDED_MIN_BATCH", 33)
+    rows, Q, (ov, oi) = layouts(layout)
+    if form == "index":
+        ix = top = tt.BruteForceIndex(rows, idx_offset=LAYOUT_OFF, screen=True)
+    else:
+        top = tt.ShardedIndex(rows, LAYOUT_OFF, shard_k=50, screen=True)
+        ix = top._index
+        assert top._seed_exchange is (layout != "f32_d128_padded")
+    assert ix._screens(LAYOUT_B, LAYOUT_K) and ix._screens(LAYOUT_B, 50)
+    assert ix._screen_bf16 is (layout == "bf16_d256") and (ix.docs16 is None) is (layout == "bf16_d256")
+    v, i = top.search(dev(Q), LAYOUT_K)
+    torch.cuda.synchronize()
+    assert np.array_equal(i.cpu().numpy(), oi) and np.array_equal(v.cpu().numpy(), ov)
+    assert ix.fallback_flags.shape[0] == 2 and int(ix.fallback_flags.ne(0).sum().item()) == 0

@@ -22,8 +22,6 @@ for r in range(8):
     ix.search(q, 50, _seed_union=lambda l: (got.append(l.clone()), _local_seed(l))[1], _k_seed=10)
     lists.append(got[0])
     idx.append(ix)
-    if r > 0:
-        ix.docs = ix._sdocs = ix.docs  # (kept: the exactness check below searches every shard)
 stack = torch.stack(lists).contiguous()                 # [8, B, 10]: what the all-gather leaves on every rank
 torch.cuda.synchronize()
 own_seed, union_seed = _local_seed(lists[0]), seed_union(stack, 8)

@@ -14,6 +14,7 @@ PyTorch/CPU fallback: inputs must be CUDA(ROCm) tensors.
 """
 from __future__ import annotations
 
+from functools import lru_cache
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -69,6 +70,13 @@ def _merge_fn(k: int, kp: int = 0, shards: bool = False) -> str:
     return "tt_topk_merge_large" if large else "tt_topk_merge"
 
 
+@lru_cache(maxsize=None)  # (six names; composed once each, not per search)
+def _screened_fn(phase: str, bf16: bool) -> str:
+    """The C entry point of one phase of a screened search: "whole", or "seed_list" then "seeded" (ShardedIndex's union seed)."""
+    infix = {"whole": "", "seed_list": "seed_list_", "seeded": "seeded_"}[phase]
+    return f"tt_score_topk_screened_{infix}{'bf16' if bf16 else 'f32'}"
+
+
 def _topk_workspace_bytes(B: int, N: int, d: int, k: int, dtype: torch.dtype) -> int:
     L = _lib.lib()
     if k > SMALL_KMAX:
@@ -78,30 +86,40 @@ def _topk_workspace_bytes(B: int, N: int, d: int, k: int, dtype: torch.dtype) ->
     return L.tt_score_topk_workspace_bytes(B, N, d, k)
 
 
+def _out_pair(B: int, k: int, device, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The (values f32 [B,k], indices int64 [B,k]) a search writes: the caller's `out`, or fresh tensors."""
+    if out is not None:
+        return out
+    return (torch.empty((B, k), dtype=torch.float32, device=device), torch.empty((B, k), dtype=torch.int64, device=device))
+
+
+def _squeezed(search: Callable, q: torch.Tensor, *args) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A single query vector [d]: the same search as the [1,d] batch, squeezed result."""
+    vals, idx = search(q.unsqueeze(0), *args)
+    return vals[0], idx[0]
+
+
 def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
                workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """topk(q @ docs.T, k) fused.  q [B,d] or [d] float32; docs [N,d] (row i <-> document i), float32 or bfloat16.  A bf16
     matrix is read as it is (d in {64, 128, 192, 256}); the result is that of its exact fp32 widening, bit for bit."""
-    squeeze = q.dim() == 1
-    if squeeze:
-        q = q.unsqueeze(0)
+    if q.dim() == 1:
+        return _squeezed(score_topk, q, docs, k, idx_offset, workspace)
     _need_cuda(q, docs)
     q, docs = _f32c(q), _docs_c(docs)
     B, d = q.shape
     N = docs.shape[0]
     if docs.dim() != 2 or docs.shape[1] != d:
         raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
-    L = _lib.lib()
-    vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    vals, idx = _out_pair(B, k, q.device)
     with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
         need = _topk_workspace_bytes(B, N, d, k, docs.dtype)
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        fn = getattr(L, _topk_fn(k, docs.dtype))
+        fn = getattr(_lib.lib(), _topk_fn(k, docs.dtype))
         _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(), idx.data_ptr(),
                       workspace.data_ptr(), workspace.numel(), _stream(q)))
-    return (vals[0], idx[0]) if squeeze else (vals, idx)
+    return vals, idx
 
 
 def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -112,8 +130,7 @@ def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Ten
     if idx.dtype != torch.int64 or vals.shape != idx.shape or vals.dim() != 2:
         raise ValueError("topk_merge wants vals f32 [B,M] and idx int64 [B,M]")
     B, M = vals.shape
-    ov = torch.empty((B, k), dtype=torch.float32, device=vals.device)
-    oi = torch.empty((B, k), dtype=torch.int64, device=vals.device)
+    ov, oi = _out_pair(B, k, vals.device)
     with torch.cuda.device(vals.device):
         _lib.check(getattr(_lib.lib(), _merge_fn(k))(vals.data_ptr(), idx.data_ptr(), B, M, k, ov.data_ptr(),
                                                      oi.data_ptr(), _stream(vals)))
@@ -158,77 +175,119 @@ SCREEN_PADDED_MIN_BATCH = 33  # d < 256 (zero-padded screen copy): only where th
 SCREEN_MIN_DOCS = 65536  # below this there is no sample pass to seed thresholds and the exact kernel is faster
 
 
-class BruteForceIndex:
-    """A [N,d] fp32 document matrix resident in HBM (document_embeddings.npy layout,
-    backend/main.py:125-138: row i <-> documents[i]) with exact top-k search.
+def _fp16_range_ok(dmax: float, amax: float) -> bool:
+    """Whether a corpus with largest row norm dmax and largest |element| amax can be screened in fp16 (NaN: no)."""
+    return dmax == dmax and amax < 6.0e4 and dmax < 6.0e4
 
-    screen=True additionally keeps an fp16 shadow copy (N*d*2 bytes) so that large query batches
-    run the screened path (fp16 MFMA filter + exact fp32 rescoring, tt_score_topk_screened_f32):
-    same bit-exact result, an order of magnitude more queries/s than the fp32-MFMA-bound kernel.
+
+class _Screen:
+    """The screened half of a corpus layout, as the screened entry points (_screened_fn) read it: `rows` [N,256] is what the
+    finish pass rescores, `filt` [N,256] what the screen reads.  fp32: rows are the fp32 matrix (a zero-padded copy when
+    d < 256) and filt its fp16 shadow; bf16: both are the bf16 matrix, screened as it is."""
+
+    def __init__(self, rows: torch.Tensor, filt: torch.Tensor, bf16: bool, dmax_norm: float):
+        self.rows, self.filt, self.bf16, self.dmax_norm = rows, filt, bool(bf16), float(dmax_norm)
+        self.n = rows.shape[0]
+
+    @classmethod
+    def for_f32(cls, docs: torch.Tensor) -> Optional["_Screen"]:
+        """fp32 rows + fp16 shadow (N*512 bytes), or None: d does not qualify, or the corpus is outside the fp16 range."""
+        N, d = docs.shape
+        if not (d == 256 or (d < 256 and d % 4 == 0)):
+            return None
+        rows = docs
+        if d < 256:
+            # narrower embeddings (HIDDEN_DIM 64, 128, ...): zero-padded to the screen kernels' 256 features.  Padding adds
+            # fmaf(0, 0, acc) terms to the fp32 chain, which leave every score bit-identical; the padded copy costs N KiB and is
+            # used for batches above 32 queries (MFMA-bound), smaller batches stream the original rows through the exact
+            # kernel, which already moves only N*d*4 bytes.
+            rows = torch.zeros((N, 256), dtype=torch.float32, device=docs.device)
+            rows[:, :d] = docs
+        filt = torch.empty((N, 256), dtype=torch.float16, device=docs.device)
+        stats = torch.zeros(2, dtype=torch.float32, device=docs.device)
+        with torch.cuda.device(docs.device):
+            _lib.check(_lib.lib().tt_index_build_f16(rows.data_ptr(), N, 256, filt.data_ptr(), stats.data_ptr(), _stream(docs)))
+        dmax, amax = (float(x) for x in stats.tolist())  # one sync, at index-build time
+        return cls(rows, filt, False, dmax) if _fp16_range_ok(dmax, amax) else None
+
+    @classmethod
+    def for_bf16(cls, docs: torch.Tensor) -> Optional["_Screen"]:
+        """bf16 rows screened as they are (one statistics pass, no copy), or None with a warning: d != 256, or out of range."""
+        N, d = docs.shape
+        if d == 256:
+            stats = torch.zeros(2, dtype=torch.float32, device=docs.device)
+            with torch.cuda.device(docs.device):
+                _lib.check(_lib.lib().tt_index_stats_bf16(docs.data_ptr(), N, d, stats.data_ptr(), 1, _stream(docs)))
+            dmax, amax = (float(x) for x in stats.tolist())  # one sync, at index-build time
+            if _fp16_range_ok(dmax, amax):
+                return cls(docs, docs, True, dmax)
+        import warnings
+        warnings.warn(f"BruteForceIndex: a bf16 [{N},{d}] corpus is screened only at d = 256 within the fp16 range; "
+                      "this index runs the exact bf16 kernel", RuntimeWarning, stacklevel=3)  # BruteForceIndex(...)'s caller
+        return None
+
+    def workspace_bytes(self, B: int, k: int) -> int:
+        name = "tt_score_topk_screened_bf16_workspace_bytes" if self.bf16 else "tt_score_topk_screened_workspace_bytes"
+        return getattr(_lib.lib(), name)(B, self.n, 256, k)
+
+    def seed_list(self, q: torch.Tensor, k: int, ks: int, flags: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+        """Query image + sample pass of a search of q [B,256] for k: [B,ks] f32, each query's ks largest sample maxima."""
+        B, d = q.shape
+        lst = torch.empty((B, ks), dtype=torch.float32, device=q.device)
+        fn = getattr(_lib.lib(), _screened_fn("seed_list", self.bf16))
+        _lib.check(fn(q.data_ptr(), B, d, self.filt.data_ptr(), self.n, k, ks, self.dmax_norm, flags.data_ptr(),
+                      lst.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
+        return lst
+
+    def run(self, q: torch.Tensor, k: int, idx_offset: int, vals: torch.Tensor, idx: torch.Tensor, flags: torch.Tensor,
+            ws: torch.Tensor, seed: Optional[torch.Tensor] = None, prof_events=None) -> None:
+        """The screened search of q [B,256] into (vals, idx); with `seed` [B] f32, what follows seed_list() on the same ws."""
+        B, d = q.shape
+        fn = getattr(_lib.lib(), _screened_fn("whole" if seed is None else "seeded", self.bf16))
+        corpus = (self.rows.data_ptr(),) if self.bf16 else (self.rows.data_ptr(), self.filt.data_ptr())
+        thr = () if seed is None else (seed.data_ptr(),)
+        _lib.check(fn(q.data_ptr(), B, d, *corpus, self.n, k, self.dmax_norm, idx_offset, vals.data_ptr(),
+                      idx.data_ptr(), flags.data_ptr(), *thr, ws.data_ptr(), ws.numel(), prof_events, _stream(q)))
+
+
+class BruteForceIndex:
+    """A [N,d] fp32 document matrix resident in HBM (document_embeddings.npy layout, backend/main.py:125-138: row i <->
+    documents[i]) with exact top-k search.
+
+    screen=True additionally keeps an fp16 shadow copy (N*d*2 bytes) so that large query batches run the screened path (fp16
+    MFMA filter + exact fp32 rescoring, tt_score_topk_screened_f32 and its kin: _Screen): same bit-exact result, an order
+    of magnitude more queries/s than the fp32-MFMA-bound kernel.
 
     A bfloat16 [N,d] matrix (d in {64, 128, 192, 256}) is kept as it is: `docs` is the caller's tensor (no copy, N*d*2
     bytes, no shadow).  screen=True at d = 256 runs one statistics pass (tt_index_stats_bf16) and screens straight from the
-    bf16 rows (tt_score_topk_screened_bf16: converted to fp16 in LDS); otherwise, and outside the fp16 range, searches run
-    the exact kernel over the bf16 rows (tt_score_topk_bf16).  Either way the result is that of the widened fp32 rows, bit
-    for bit.
+    bf16 rows (converted to fp16 in LDS); otherwise, and outside the fp16 range, searches run the exact kernel over the bf16
+    rows (tt_score_topk_bf16).  Either way the result is that of the widened fp32 rows, bit for bit.
     """
 
     def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False):
+        # (screen may also be a ready _Screen over doc_embeddings: _from_buffers)
         _need_cuda(doc_embeddings)
         self.docs = _docs_c(doc_embeddings)
         self.idx_offset = int(idx_offset)
-        self.docs16: Optional[torch.Tensor] = None
-        self.dmax_norm = float("nan")
+        if not isinstance(screen, _Screen):
+            build = _Screen.for_bf16 if self.docs.dtype == torch.bfloat16 else _Screen.for_f32
+            screen = build(self.docs) if screen and self.docs.shape[0] > 0 else None
+        self._screen: Optional[_Screen] = screen
+        # for callers to read: the fp16 shadow [N,256] (None for screened bf16 rows) and the largest row norm
+        self.docs16 = screen.filt if screen is not None and not screen.bf16 else None
+        self.dmax_norm = screen.dmax_norm if screen is not None else float("nan")
         self.fallback_flags = torch.zeros(1, dtype=torch.int32, device=self.docs.device)  # per 32-query tile
         self.keep_stats = False   # True: the most recent screened search's workspace is kept for search_stats()
         self._last_ws = None
-        N, d = self.docs.shape
-        self._sdocs = self.docs  # what the screened path scores against: [N,256] fp32
-        self._screen_bf16 = False  # bf16 rows screened as they are (no docs16)
-        if self.docs.dtype == torch.bfloat16 and screen and N > 0:
-            if d == 256:
-                stats = torch.zeros(2, dtype=torch.float32, device=self.docs.device)
-                with torch.cuda.device(self.docs.device):
-                    _lib.check(_lib.lib().tt_index_stats_bf16(self.docs.data_ptr(), N, d, stats.data_ptr(), 1,
-                                                              _stream(self.docs)))
-                dmax, amax = (float(x) for x in stats.tolist())  # one sync, at index-build time
-                if dmax == dmax and amax < 6.0e4 and dmax < 6.0e4:
-                    self.dmax_norm = dmax
-                    self._screen_bf16 = True
-            if not self._screen_bf16:
-                import warnings
-                warnings.warn(f"BruteForceIndex: a bf16 [{N},{d}] corpus is screened only at d = 256 within the fp16 range; "
-                              "this index runs the exact bf16 kernel", RuntimeWarning, stacklevel=2)
-        if screen and N > 0 and self.docs.dtype == torch.float32 and (d == 256 or (d < 256 and d % 4 == 0)):
-            L = _lib.lib()
-            if d < 256:
-                # narrower embeddings (HIDDEN_DIM 64, 128, ...): zero-padded to the screen kernels' 256 features.
-                # Padding adds fmaf(0, 0, acc) terms to the fp32 chain, which leave every score bit-identical; the
-                # padded copy costs N KiB and is used for batches above 32 queries (MFMA-bound), smaller batches
-                # stream the original rows through the exact kernel, which already moves only N*d*4 bytes.
-                self._sdocs = torch.zeros((N, 256), dtype=torch.float32, device=self.docs.device)
-                self._sdocs[:, :d] = self.docs
-            self.docs16 = torch.empty((N, 256), dtype=torch.float16, device=self.docs.device)
-            stats = torch.zeros(2, dtype=torch.float32, device=self.docs.device)
-            with torch.cuda.device(self.docs.device):
-                _lib.check(L.tt_index_build_f16(self._sdocs.data_ptr(), N, 256, self.docs16.data_ptr(), stats.data_ptr(),
-                                                _stream(self.docs)))
-            dmax, amax = (float(x) for x in stats.tolist())  # one sync, at index-build time
-            if dmax == dmax and amax < 6.0e4 and dmax < 6.0e4:
-                self.dmax_norm = dmax
-            else:
-                self.docs16 = None  # outside the fp16 range: exact kernel only
 
     @classmethod
     def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int):
         """An index over caller-managed device buffers (StreamedIndex's per-block view)."""
-        self = cls.__new__(cls)
-        self.docs, self.docs16, self.dmax_norm, self.idx_offset = docs32, docs16, float(dmax_norm), int(idx_offset)
-        self._sdocs = docs32
-        self._screen_bf16 = False
-        self.fallback_flags = torch.zeros(1, dtype=torch.int32, device=docs32.device)
-        self.keep_stats, self._last_ws = False, None
-        return self
+        return cls(docs32, idx_offset, _Screen(docs32, docs16, False, dmax_norm) if docs16 is not None else False)
+
+    @property
+    def _screen_bf16(self) -> bool:  # bf16 rows screened as they are (no docs16)
+        return self._screen is not None and self._screen.bf16
 
     @property
     def ntotal(self) -> int:
@@ -252,25 +311,19 @@ class BruteForceIndex:
                _k_seed: int = 0, _k_list: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) contiguous device tensors to write into (2-D q only).
         _seed_union (ShardedIndex): a callable that turns this shard's seed list [B, _k_seed] f32 (its _k_seed largest
-        sample maxima per query, tt_score_topk_screened_seed_list_f32) into the seed thresholds [B] f32 -- the _k_seed-th
-        largest of the UNION of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen
-        then runs with that global seed and `out` holds this shard's documents above it."""
-        B = 1 if q.dim() == 1 else q.shape[0]
-        N, d = self.docs.shape
+        sample maxima per query, _Screen.seed_list) into the seed thresholds [B] f32 -- the _k_seed-th largest of the UNION
+        of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen then runs with that
+        global seed and `out` holds this shard's documents above it."""
+        if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank)
+            return _squeezed(self.search, q, k, _prof_events)
         _need_cuda(q)
         if q.device != self.docs.device:
             raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != d:
+        if q.shape[-1] != self.docs.shape[1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        if self._screens(B, k):
-            if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank): same path, squeezed result
-                vals, idx = self._search_screened(q.unsqueeze(0), k, _prof_events)
-                return vals[0], idx[0]
+        if self._screens(q.shape[0], k):
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list)
-        with torch.cuda.device(self.docs.device):
-            need = _topk_workspace_bytes(B, N, d, k, self.docs.dtype)
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.docs.device)
-        v, i = score_topk(q, self.docs, k, self.idx_offset, ws)
+        v, i = score_topk(q, self.docs, k, self.idx_offset)
         if out is not None:
             out[0].copy_(v)
             out[1].copy_(i)
@@ -281,70 +334,41 @@ class BruteForceIndex:
         """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
         whether they enter the seed exchange; the thresholds are the module's at the time of the call."""
         N, d = self.docs.shape
-        return ((self.docs16 is not None or self._screen_bf16) and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
-                and N >= SCREEN_MIN_DOCS and k <= 64)
+        return (self._screen is not None and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
+                and N >= SCREEN_MIN_DOCS and k <= SMALL_KMAX)
 
     def _search_screened(self, q: torch.Tensor, k: int, _prof_events=None, out=None, _seed_union=None,
                          _k_seed: int = 0, _k_list: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """search()'s screened path for a 2-D q; the arguments are search()'s."""
         B, d = q.shape
-        N = self.docs.shape[0]
-        L = _lib.lib()
+        sc = self._screen
         q = _f32c(q)
         if d < 256:
             qp = torch.zeros((B, 256), dtype=torch.float32, device=q.device)
             qp[:, :d] = q
-            q, d = qp, 256
-        if out is not None:
-            vals, idx = out
-        else:
-            vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
-            idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+            q = qp
+        vals, idx = _out_pair(B, k, q.device, out)
         with torch.cuda.device(self.docs.device):  # workspace sizing depends on the device's CU count
             # per-call workspace and flags (cached allocator blocks): safe for concurrent callers and streams
-            bf = self._screen_bf16
-            need = (L.tt_score_topk_screened_bf16_workspace_bytes if bf else L.tt_score_topk_screened_workspace_bytes)(B, N, d, k)
-            ws_s = torch.empty(need, dtype=torch.uint8, device=self.docs.device)
+            ws = torch.empty(sc.workspace_bytes(B, k), dtype=torch.uint8, device=self.docs.device)
             flags = torch.empty((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
             if self.keep_stats:
-                self._last_ws = (ws_s, B, k)
+                self._last_ws = (ws, B, k)
+            seed = None
             if _seed_union is not None:
                 ks = min(_k_list or _k_seed or k, k)  # entries per seed list (the caller ranks the union)
-                lst = torch.empty((B, ks), dtype=torch.float32, device=self.docs.device)
-                fn = L.tt_score_topk_screened_seed_list_bf16 if bf else L.tt_score_topk_screened_seed_list_f32
-                _lib.check(fn(q.data_ptr(), B, d, (self.docs if bf else self.docs16).data_ptr(), N, k, ks, self.dmax_norm,
-                              flags.data_ptr(), lst.data_ptr(), ws_s.data_ptr(), ws_s.numel(), _stream(q)))
-                seed = _seed_union(lst)
+                seed = _seed_union(sc.seed_list(q, k, ks, flags, ws))
                 if seed.shape != (B,) or seed.dtype != torch.float32 or not seed.is_contiguous():
                     raise ValueError("_seed_union must return a contiguous float32 [B] tensor")
-                if bf:
-                    _lib.check(L.tt_score_topk_screened_seeded_bf16(q.data_ptr(), B, d, self.docs.data_ptr(), N, k,
-                                                                    self.dmax_norm, self.idx_offset, vals.data_ptr(),
-                                                                    idx.data_ptr(), flags.data_ptr(), seed.data_ptr(),
-                                                                    ws_s.data_ptr(), ws_s.numel(), _prof_events, _stream(q)))
-                else:
-                    _lib.check(L.tt_score_topk_screened_seeded_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(),
-                                                                   self.docs16.data_ptr(), N, k, self.dmax_norm,
-                                                                   self.idx_offset, vals.data_ptr(), idx.data_ptr(),
-                                                                   flags.data_ptr(), seed.data_ptr(), ws_s.data_ptr(),
-                                                                   ws_s.numel(), _prof_events, _stream(q)))
-            elif bf:
-                _lib.check(L.tt_score_topk_screened_bf16(q.data_ptr(), B, d, self.docs.data_ptr(), N, k, self.dmax_norm,
-                                                         self.idx_offset, vals.data_ptr(), idx.data_ptr(), flags.data_ptr(),
-                                                         ws_s.data_ptr(), ws_s.numel(), _prof_events, _stream(q)))
-            else:
-                _lib.check(L.tt_score_topk_screened_f32(q.data_ptr(), B, d, self._sdocs.data_ptr(), self.docs16.data_ptr(),
-                                                        N, k, self.dmax_norm, self.idx_offset, vals.data_ptr(),
-                                                        idx.data_ptr(), flags.data_ptr(), ws_s.data_ptr(), ws_s.numel(),
-                                                        _prof_events, _stream(q)))
+            sc.run(q, k, self.idx_offset, vals, idx, flags, ws, seed, _prof_events)
         self.fallback_flags = flags  # of the most recent search (per 32-query tile; non-zero = exact kernel took over)
         return vals, idx
 
 
 class GraphedSearch:
-    """One search of a fixed shape (B, k) captured in a HIP graph and replayed: the nine launches of a
-    screened search (flag reset, sample pass, threshold select, screen, finish, predicated exact kernels)
-    become one graph launch, which matters at serving sizes where the whole search is < 1 ms.
+    """One search of a fixed shape (B, k) captured in a HIP graph and replayed: the launches of a
+    screened search (query image with the flag reset, sample pass, threshold select, screen, finish, predicated
+    exact kernels) become one graph launch, which matters at serving sizes where the whole search is < 1 ms.
     Everything in the library is asynchronous on the caller's stream with caller-owned memory, so plain
     stream capture works; queries are copied into a static buffer, results are returned in static buffers
     (valid until the next call)."""
@@ -354,8 +378,7 @@ class GraphedSearch:
         dev = index.docs.device
         d = index.docs.shape[1]
         self.q = torch.zeros((self.B, d), dtype=torch.float32, device=dev)
-        self.vals = torch.empty((self.B, self.k), dtype=torch.float32, device=dev)
-        self.idx = torch.empty((self.B, self.k), dtype=torch.int64, device=dev)
+        self.vals, self.idx = _out_pair(self.B, self.k, dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up outside capture: workspaces get allocated, kernels loaded
@@ -381,6 +404,13 @@ def shard_bounds(n_total: int, rank: int, world: int) -> Tuple[int, int]:
     base, rem = divmod(n_total, world)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+def _my_shard(n_total: int, group=None) -> Tuple[int, int]:
+    """shard_bounds of this process in `group` (one shard holding everything without torch.distributed)."""
+    import torch.distributed as dist
+    on = dist.is_initialized()
+    return shard_bounds(n_total, dist.get_rank(group) if on else 0, dist.get_world_size(group) if on else 1)
 
 
 def _exchange_and_merge(vals: torch.Tensor, idx: torch.Tensor, k: int, merge: Callable, group=None):
@@ -422,7 +452,7 @@ def seed_plan(world: int, k: int, exchange: bool = True):
     apply: world * list length is bounded by tt_seed_union_f32's tile (SEED_UNION_MAX values per query); a job too wide for k
     values per rank lists fewer -- the k-th of the union is still reached by k distinct documents -- and one too wide even for
     that (or a k beyond the screen's 64) seeds every shard by itself."""
-    if not exchange or k > 64 or world < 1:
+    if not exchange or k > SMALL_KMAX or world < 1:
         return None
     ks = min(k, SEED_UNION_MAX // world)
     if ks < 1 or world * ks < k:
@@ -447,8 +477,7 @@ class _Slot:
         self.recv = torch.empty(world * self.stride, dtype=torch.uint8, device=dev)
         self.send_v = self.send[:B * kp * 4].view(torch.float32).view(B, kp)
         self.send_i = self.send[self.nv:].view(torch.int64).view(B, kp)
-        self.out_v = torch.empty((B, k), dtype=torch.float32, device=dev)
-        self.out_i = torch.empty((B, k), dtype=torch.int64, device=dev)
+        self.out_v, self.out_i = _out_pair(B, k, dev)
         self.sampled = torch.cuda.Event()   # caller's stream: the seed list is written
         self.seeded = torch.cuda.Event()    # exchange stream: the ranks' seed lists have been gathered
         self.searched = torch.cuda.Event()  # caller's stream: the send block is written
@@ -534,11 +563,8 @@ class ShardedIndex:
         self._n_submitted = 0
         self._xs: Optional[torch.cuda.Stream] = None
         self._deferred = None  # (slot, B, kp, k) of the last submit(): its list exchange goes out behind the next seed gather
-        if self.streamed:
-            mine = 0
-        else:
-            # the smallest batch that screens at d = 256
-            mine = int(self._index.docs.shape[1] == 256 and self._index._screens(SCREEN_MIN_BATCH, 1))
+        # a resident d = 256 shard that screens its smallest screened batch
+        mine = int(not self.streamed and self._index.docs.shape[1] == 256 and self._index._screens(SCREEN_MIN_BATCH, 1))
         if self._coll.world > 1:
             dev = self._dev
             send = torch.tensor([mine], dtype=torch.int64, device=dev)
@@ -603,10 +629,7 @@ class ShardedIndex:
 
     @classmethod
     def from_global(cls, docs: torch.Tensor, group=None, **kw) -> "ShardedIndex":
-        import torch.distributed as dist
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
-        lo, hi = shard_bounds(docs.shape[0], rank, world)
+        lo, hi = _my_shard(docs.shape[0], group)
         return cls(docs[lo:hi], lo, group=group, **kw)
 
     @classmethod
@@ -614,10 +637,7 @@ class ShardedIndex:
         """BASELINE configs[4]: `host_docs` is the WHOLE bf16 corpus [N,d] in host memory (an np.memmap-backed tensor will do:
         only this rank's rows are touched); rank r pins and streams rows [r*N/W, (r+1)*N/W) only.  resident=True: rank r
         copies those rows to its GPU once, as bf16 (n*d*2 bytes of HBM), and searches them there."""
-        import torch.distributed as dist
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
-        lo, hi = shard_bounds(host_docs.shape[0], rank, world)
+        lo, hi = _my_shard(host_docs.shape[0], group)
         rows = host_docs[lo:hi]
         if resident:
             dev = kw.pop("device", None)
@@ -629,11 +649,8 @@ class ShardedIndex:
         """Index build across ranks (third row: embarrassingly parallel over documents, no collective): every rank
         holds the same document list (documents.pkl order, backend/main.py:134-136), embeds ONLY its contiguous shard
         [lo, hi) with the document tower and keeps those rows; row i of the global index is documents[i] on every rank."""
-        import torch.distributed as dist
         from .evaluators import embed_corpus
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
-        lo, hi = shard_bounds(len(documents), rank, world)
+        lo, hi = _my_shard(len(documents), group)
         model.eval()
         with torch.no_grad():
             local = embed_corpus(model, tokenizer, documents[lo:hi], device)
@@ -680,9 +697,8 @@ class ShardedIndex:
 
     def search(self, q: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
         """One search, everything on the caller's stream; fresh result tensors."""
-        if q.dim() == 1:  # a single query vector: same path, squeezed result
-            v, i = self.search(q.unsqueeze(0), k)
-            return v[0], i[0]
+        if q.dim() == 1:
+            return _squeezed(self.search, q, k)
         kp = max(k, self.shard_k)
         sl = self._slot(q.shape[0], kp, k, 2)
         cur = torch.cuda.current_stream(sl.send.device)
@@ -749,7 +765,7 @@ class StreamedIndex:
         self._walk(lambda s, lo, n: None, stats=stats)
         dmax, amax = (float(x) for x in stats.tolist())
         self.dmax_norm = dmax
-        if not (dmax == dmax and amax < 6.0e4 and dmax < 6.0e4):
+        if not _fp16_range_ok(dmax, amax):
             self._d16 = [None, None]
 
     def _walk(self, visit, stats=None):
@@ -802,29 +818,26 @@ class StreamedIndex:
     def search(self, q: torch.Tensor, k: int = 10, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block)."""
         _need_cuda(q)
-        if q.dim() == 1:  # a single query vector: squeezed result, like BruteForceIndex
-            v, i = self.search(q.unsqueeze(0), k)
-            return v[0], i[0]
+        if q.dim() == 1:
+            return _squeezed(self.search, q, k)
         if q.device != self.device:
             raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
         if q.shape[1] != self.d:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
         q = _f32c(q)
-        run = [None, None]
+        run = []  # the running top-k: (values, indices)
 
         def visit(s, lo, n):
             blk = BruteForceIndex._from_buffers(self._d32[s][:n], self._d16[s][:n] if self._d16[s] is not None else None,
                                                 self.dmax_norm, self.idx_offset + lo)
             v, i = blk.search(q, k)
-            if run[0] is None:
-                run[0], run[1] = v, i
-            else:
-                run[0], run[1] = topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
 
         self._walk(visit)
-        if run[0] is None:
-            run = [torch.full((q.shape[0], k), float("-inf"), device=q.device),
-                   torch.full((q.shape[0], k), -1, dtype=torch.int64, device=q.device)]
+        if not run:
+            run = _out_pair(q.shape[0], k, q.device)  # an empty corpus: padding only
+            run[0].fill_(float("-inf"))
+            run[1].fill_(-1)
         if out is not None:
             out[0].copy_(run[0])
             out[1].copy_(run[1])
