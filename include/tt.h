@@ -130,6 +130,45 @@ int tt_score_topk_large_bf16(const float *Q, int B, int d, const void *D_bf16, i
                              size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * Masked exact search: the best k among the documents a keep-bitmask lets through -- deletions, and "the best k of this
+ * subset" (a tenant, a language, a date range, all but the documents a user has seen, hard-negative mining without the known
+ * positives).  Replaces  scores = torch.matmul(q, D.t()) ; scores[:, ~keep] = -inf ; torch.topk(scores, k)  (the masked form
+ * of backend/evaluators.py:185-186), which over-fetching from an unmasked search cannot emulate: a search for k sees only the
+ * best k, and a mask that removes more than the margin leaves the answer short or wrong.
+ * keep: device memory, 4-byte aligned, ceil(N/32) words; document n (the row of D passed to THIS call, before idx_offset) may
+ * be returned iff bit n & 31 of word n >> 5 is set; bits at or beyond N in the last word are ignored.  N/8 bytes next to
+ * N*d*4 (or N*d*2) of rows.
+ * Everything else is tt_score_topk_large_f32's / _bf16's: supported d per dtype, 1 <= k <= TT_TOPK_LARGE_KMAX, N < 2^31 - 64,
+ * asynchronous, capturable, no host synchronisation, the same status codes (a misaligned keep: TT_ERR_BAD_SHAPE).  The result
+ * is the exact top-k of the kept documents, (score desc, index asc) -- bit for bit the unmasked search over the kept rows with
+ * the indices mapped back, ties included -- and the tail is (-inf, -1) when fewer than k documents are kept, down to none.
+ * keep == NULL: every document is kept and the call IS the unmasked one (same launches, same bits).
+ * The mask acts in the append pass and in every pass that produces a threshold (the sample maxima that seed the main pass:
+ * a bound vouched for by a document that cannot be returned is not a bound of the masked k-th score), in the give-up redo,
+ * and, above k = 64, in the rescans of tiers 1 and 2.  A masked document is still read and scored: a selective mask pays
+ * the full scan (skipping the rows of fully masked tiles is not done).
+ * The workspace is the large call's (tt_score_topk_masked_workspace_bytes returns tt_score_topk_large_workspace_bytes), so
+ * tt_score_topk_large_tier_offset, tt_score_topk_redo_flags_offset and tt_score_topk_pace_timeouts_offset apply to a
+ * finished masked call as they are.
+ *
+ * tt_keep_mask_pack: keep_bool [N] device bytes (0 / non-0) -> keep, ceil(N/32) words, in one launch; the bits beyond N in
+ * the last word are written as zero.
+ * tt_keep_mask_clear_ids: clears bit ids[i] - idx_offset for each of the n_ids device int64 ids (atomically: duplicate ids and
+ * concurrent calls on one mask are fine); ids outside [idx_offset, idx_offset + N) are ignored without error, so a sharded
+ * caller hands every shard the same global id list.  In place: a search enqueued later on the stream sees the removal.
+ */
+size_t tt_score_topk_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_masked_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep, int k,
+                             int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                             size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep, int k,
+                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+int tt_keep_mask_pack(const uint8_t *keep_bool, int64_t N, uint32_t *keep, tt_stream_t stream);
+int tt_keep_mask_clear_ids(uint32_t *keep, int64_t N, const int64_t *ids, int64_t n_ids, int64_t idx_offset,
+                           tt_stream_t stream);
+
+/*
  * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
  * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
  * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it

@@ -92,7 +92,28 @@ struct ScoreParams {
     int thr0_stride, thr0_off;
     const int *run_if;  // optional device predicate per 32-query tile: tile t is skipped while run_if[t] == 0
     int draw_polls;     // bound of the wait for a chunk-mate's pool draw (DRAW_POLLS; the comparison build can force a give-up)
+    const unsigned *keep; // MASKED instantiations: keep-bitmask, one word per 32-document tile (bit n & 31 of word n >> 5 set ->
+                          // document n of D may be returned); nullptr in every other launch
 };
+
+// The keep word of one tile (MASKED).  It is wave-uniform, so it travels as a scalar load on the lgkmcnt side: the tile loop's
+// LDS-DMA ring lives on counted vmcnt waits, and a compiler-visible global load in the loop would make hipcc drain it
+// (vmcnt(0)) on every tile.  Issued in front of the tile's last slab of MFMAs, waited for in front of the epilogue: the
+// latency sits under that slab's multiply chain.  The wait names the destination, so no consumer is scheduled above it, and
+// the tile's accumulators, so that hipcc cannot hoist it above the MFMAs (register-only instructions, which "memory" does not
+// order) back to the load.
+// (first: the slab's first A operand(s), named so that the slab's MFMA chain stays below the load)
+template <class A>
+__device__ __forceinline__ void keep_word_issue(const unsigned *word, unsigned &kw, A &first)
+{
+    asm volatile("s_load_dword %[kw], %[word], 0x0" : [kw] "=s"(kw), "+v"(first) : [word] "s"(word) : "memory");
+}
+
+template <class Acc>
+__device__ __forceinline__ void keep_word_wait(unsigned &kw, Acc &acc)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(kw), "+v"(acc) : : "memory");
+}
 
 __device__ __forceinline__ int xcd_remap(int b, int nblk)
 {
@@ -187,7 +208,10 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // slabs; the same ring, swizzle and reads bring in the raw words and each A operand is widened in a register (bf16 -> fp32
 // is exact: the high half of the fp32 word), in the same ascending feature order -- the scores are tt_score_topk_f32's over
 // the widened rows, bit for bit.
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false>
+// MASKED: p.keep decides which documents may be returned (tt_score_topk_masked_f32 / _bf16).  A masked document is scored like
+// any other and then left out of every selection: the append pass, and the sample maxima (a bound taken from a document that
+// cannot be returned is no lower bound of the masked k-th score).  MASKED = false is the kernel as it always was.
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -344,6 +368,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             if (PACED && waits && in_blk == 0 && gb >= p.pace_lag)
                 pace_gate(gb - p.pace_lag);
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            unsigned kw = 0xffffffffu; // the tile's keep word (MASKED)
 #pragma unroll
             for (int s = 0; s < NSD; ++s) {
                 // slab (tile,s) has landed once at most (NST-2) younger slabs are pending
@@ -358,6 +383,10 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 #ifndef TT_K4_NO_LGKM0
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
+                // (MASKED: right behind the asm wait above, which already ends a scheduling region -- a statement further
+                //  down would pin dma_issue's address arithmetic in front of it instead of between the MFMAs)
+                if (MASKED && s == NSD - 1)
+                    keep_word_issue(p.keep + tile, kw, frag[0]);
                 dma_issue((stage + NST - 1) % NST);
                 if (BF) {
                     // chunk c holds features 8c..8c+7 of the slab; word w = features (8c+2w, 8c+2w+1) in its (low, high)
@@ -387,12 +416,20 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             // ---- epilogue: acc[r] = score(doc tile*32 + (r&3)+8(r>>2)+4h, query j) ----
             const int tile_base = tile * TILE_DOCS;
             const bool partial = tile_base + TILE_DOCS > p.N;
+            // MASKED: bit (r & 3) + 8 (r >> 2) of kwh = the keep bit of the lane's document r (bits at or beyond N: the
+            // doc < p.N test stays)
+            unsigned kwh = 0xffffffffu;
+            if (MASKED) {
+                keep_word_wait(kw, acc);
+                kwh = kw >> (4 * h);
+            }
+            auto kept = [&](int r) { return !MASKED || ((kwh >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0u; };
             if (MAXONLY) {
                 float m = -INFINITY;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int doc = tile_base + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    m = fmaxf(m, (!partial || doc < p.N) ? acc[r] : -INFINITY);
+                    m = fmaxf(m, ((!partial || doc < p.N) && kept(r)) ? acc[r] : -INFINITY);
                 }
                 runmax = fmaxf(runmax, m);
                 continue;
@@ -401,14 +438,16 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 #pragma unroll
             for (int r = 1; r < 16; ++r)
                 m = fmaxf(m, acc[r]);
-            if (__ballot(m >= thr) != 0ull) {
+            // (MASKED: m may come from a masked document -- that only costs the slow path a look; a tile with nothing kept
+            //  skips it)
+            if ((!MASKED || kw != 0u) && __ballot(m >= thr) != 0ull) {
                 // Append pass.  The store is inline asm on purpose: a compiler-visible global store
                 // (or the compaction's loads) inside this loop makes hipcc emit s_waitcnt vmcnt(0) at
                 // every join, which drains the LDS-DMA ring on each tile that has a candidate.
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int doc = tile_base + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const bool c = (!partial || doc < p.N) && acc[r] >= thr;
+                    const bool c = (!partial || doc < p.N) && kept(r) && acc[r] >= thr;
                     const unsigned long long mask = __ballot(c);
                     if (mask == 0ull)
                         continue;
@@ -531,7 +570,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 // (tools/experiments/mfma16_order.hip), so the oracle parity carries over.  Ring, DMA, thresholds, candidate
 // buffers, compaction, partial lists and merge are K4's; the launch is bound by HBM streaming (d * 4 bytes per doc).
 // ---------------------------------------------------------------------------
-template <int NS, int CAP, bool MAXONLY, bool NT = false>
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -631,6 +670,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
         int stage = 0;
         for (int tile = t0; tile < t1; ++tile) {
             f32x4 acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+            unsigned kw = 0xffffffffu; // the tile's keep word (MASKED: see score_topk_kernel)
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_SLAB * (NSTAGE - 2)) : "memory");
@@ -641,6 +681,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
                     for (int u = 0; u < 2; ++u)
                         a[u][t] = *(const float *)(rd[u] + stage * SLAB_BYTES + ((t ^ rsw[u]) << 4));
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (MASKED && s == NS - 1) {
+                    float a00[2] = {a[0][0], a[1][0]}; // (both chains' first operands)
+                    keep_word_issue(p.keep + tile, kw, a00);
+                    a[0][0] = a00[0];
+                    a[1][0] = a00[1];
+                }
                 dma_issue((stage + NSTAGE - 1) % NSTAGE);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
@@ -652,12 +698,18 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
             // ---- epilogue: acc[u][r] = score(doc tile*32 + 16u + 4kq + r, query n) ----
             const int tile_base = tile * TILE_DOCS;
             const bool partial = tile_base + TILE_DOCS > p.N;
-            float m = -INFINITY;
+            unsigned kwh = 0xffffffffu; // MASKED: bit 16u + r = the keep bit of the lane's document (u, r)
+            if (MASKED) {
+                keep_word_wait(kw, acc[1]);
+                kwh = kw >> (4 * kq);
+            }
+            auto kept = [&](int u, int r) { return !MASKED || ((kwh >> (16 * u + r)) & 1u) != 0u; };
+            float m = -INFINITY; // over the documents that may be returned
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    m = fmaxf(m, (!partial || tile_base + 16 * u + 4 * kq + r < p.N) ? acc[u][r] : -INFINITY);
+                    m = fmaxf(m, ((!partial || tile_base + 16 * u + 4 * kq + r < p.N) && kept(u, r)) ? acc[u][r] : -INFINITY);
             if (MAXONLY) {
                 runmax = fmaxf(runmax, m);
                 continue;
@@ -668,7 +720,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int doc = tile_base + 16 * u + 4 * kq + r;
-                        const bool c = (!partial || doc < p.N) && acc[u][r] >= thr;
+                        const bool c = (!partial || doc < p.N) && kept(u, r) && acc[u][r] >= thr;
                         const unsigned long long mask = __ballot(c);
                         if (mask == 0ull)
                             continue;
@@ -1251,39 +1303,46 @@ constexpr bool score_dim_ok(int d, bool bf16 = false)
 // The kernel families, for launch_ns: score_topk_kernel (32-query tiles) over fp32 and over bf16 rows, and
 // score_topk16_kernel (16-query tiles).
 struct Score32 {
-    template <int NS, int CAP, bool MAXONLY, bool NT>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
 };
 struct Score32Bf16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED>; }
     static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT>
-    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
 };
 
-template <class K, int NS>
-int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+template <class K, int NS, bool MASKED>
+int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
 {
     const void *fn;
     size_t smem = pl.smem;
     if (maxonly) {
-        fn = K::template fn<NS, 64, true, false>();
+        fn = K::template fn<NS, 64, true, false, MASKED>();
     } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
-        fn = pl.cap == 64 ? K::template fn<8, 64, false, true>() : K::template fn<8, 128, false, true>();
+        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED>() : K::template fn<8, 128, false, true, MASKED>();
         smem = K::smem_nt;
     } else {
-        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false>() : K::template fn<NS, 128, false, false>();
+        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED>() : K::template fn<NS, 128, false, false, MASKED>();
     }
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     ScoreParams args = sp;
     void *argv[] = {&args};
     TT_HIP_CHECK(hipLaunchKernel(fn, dim3((sp.n_tasks + WPB - 1) / WPB), dim3(WPB * 64), argv, smem, st));
     return TT_OK;
+}
+
+// sp.keep set: the MASKED instantiation of the same kernel
+template <class K, int NS>
+int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+{
+    return sp.keep ? launch_ns_m<K, NS, true>(sp, pl, st, maxonly) : launch_ns_m<K, NS, false>(sp, pl, st, maxonly);
 }
 
 int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly, bool bf16)
@@ -1352,6 +1411,7 @@ ScoreParams pass_params(const Pass &ps, const float *Q, int B, const void *D, in
     sp.thr0_off = 0;
     sp.run_if = nullptr;
     sp.draw_polls = TT_AB_SWITCH(TT_DRAW_POLLS, DRAW_POLLS);
+    sp.keep = nullptr;
     return sp;
 }
 
@@ -1366,7 +1426,8 @@ const char *score_dims(bool bf16)
 // lists of k = 64 (tt_score_topk_large_f32: a seed for the 64th score would drop documents ranked 65..k_seed)
 int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
                    void *workspace, size_t workspace_bytes, hipStream_t st, Plan *plan_out, const char *who,
-                   const int *run_if = nullptr, void *const *prof_events = nullptr, int k_seed = 0)
+                   const int *run_if = nullptr, void *const *prof_events = nullptr, int k_seed = 0,
+                   const unsigned *keep = nullptr)
 {
     if (B <= 0 || N <= 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
@@ -1391,8 +1452,11 @@ int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64
     if (pl.prepass && !run_if) {
         // sample pass over D[0:ns): per-(wave,query) maxima, then their k-th largest per query.
         // k distinct documents score at least that much, so it bounds the final k-th score from below.
+        // (keep: the maxima are over the kept documents of the sample -- the first words of the mask -- and a chunk with none
+        //  contributes -inf: only documents that may be returned vouch for the bound)
         ScoreParams pp = pass_params(pl.pre, Q, B, D, k, 0, ws, pl);
         pp.run_if = run_if;
+        pp.keep = keep;
         int rc = launch_score(d, pp, pl, st, true, bf16);
         if (rc != TT_OK)
             return rc;
@@ -1406,6 +1470,7 @@ int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64
     sp.thr0_stride = 1;
     sp.thr0_off = 0;
     sp.run_if = run_if;
+    sp.keep = keep;
     if (pl.main.tail_blocks > 0 && !run_if) {
         // (the predicated form keeps the static split: its launches sit behind every screened search as no-ops, and a
         //  counter reset would be one more)
@@ -1506,7 +1571,7 @@ __global__ __launch_bounds__(64) void redo_flag_kernel(const int64_t *__restrict
 namespace {
 int score_topk_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
                     float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, const int *run_if,
-                    hipStream_t st, const char *who)
+                    hipStream_t st, const char *who, const unsigned *keep = nullptr)
 {
     if (B < 0 || N < 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
@@ -1525,7 +1590,7 @@ int score_topk_pred(const float *Q, int B, int d, const void *D, bool bf16, int6
         return TT_OK;
     }
     Plan pl;
-    int rc = score_partials(Q, B, d, D, bf16, N, k, idx_offset, workspace, workspace_bytes, st, &pl, who, run_if);
+    int rc = score_partials(Q, B, d, D, bf16, N, k, idx_offset, workspace, workspace_bytes, st, &pl, who, run_if, nullptr, 0, keep);
     if (rc != TT_OK)
         return rc;
     const char *ws = (const char *)workspace;
@@ -1544,7 +1609,7 @@ int score_topk_pred(const float *Q, int B, int d, const void *D, bool bf16, int6
         hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, st, (const int64_t *)out_idx, B, k, redo);
         TT_LAUNCH_CHECK();
         return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, redo, st,
-                               who);
+                               who, keep);
     }
     return TT_OK;
 }
@@ -2064,9 +2129,10 @@ __global__ __launch_bounds__(LSEL_THREADS) void lk_analyze_kernel(const float *_
 
 // One corpus scan for the queries in COLLECT or HIST mode: 32-query x 128-document tiles, fp32 FMA chains over the features
 // in ascending order (the bits of the main pass and of the oracle), thread = 4 queries x 4 documents.
-template <bool BF>
+// MASKED: documents whose keep bit is clear are neither collected nor counted (keep: one word per 32 documents).
+template <bool BF, bool MASKED>
 __global__ __launch_bounds__(256) void lk_scan_kernel(const float *__restrict__ Q, const void *__restrict__ D, int B, int d, int N,
-                                                      LkState *st, Cand *buf, int *hist)
+                                                      LkState *st, Cand *buf, int *hist, const unsigned *__restrict__ keep)
 {
     __shared__ __attribute__((aligned(16))) float qs[32][32];                // [feature][query]
     __shared__ __attribute__((aligned(16))) float ds[32][LK_SCAN_DOCS + 4];  // [feature][document]
@@ -2103,6 +2169,10 @@ __global__ __launch_bounds__(256) void lk_scan_kernel(const float *__restrict__ 
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = 0.0f;
+            // the thread's four documents row0 + 4 dg + j share a keep word (row0 is a multiple of 128): their bits, from bit 0
+            unsigned kbits = 0xfu;
+            if (MASKED && dg * 4 < rem)
+                kbits = keep[(row0 + dg * 4) >> 5] >> ((dg * 4) & 31);
             for (int f0 = 0; f0 < d; f0 += 32) {
                 __syncthreads();
 #pragma unroll
@@ -2141,7 +2211,7 @@ __global__ __launch_bounds__(256) void lk_scan_kernel(const float *__restrict__ 
                 const int q = qt * 32 + qg * 4 + i;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (dg * 4 + j >= rem)
+                    if (dg * 4 + j >= rem || (MASKED && !((kbits >> j) & 1u)))
                         continue;
                     const int n = (int)(row0 + dg * 4 + j); // < N
 
@@ -2280,7 +2350,8 @@ LargePlan make_large_plan(int B, int64_t N, int d, int k, bool bf16)
 }
 
 int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
-                     float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, hipStream_t st, const char *who)
+                     float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, hipStream_t st, const char *who,
+                     const unsigned *keep = nullptr)
 {
     if (B < 0 || N < 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
@@ -2290,6 +2361,8 @@ int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d", who, k, TT_TOPK_LARGE_KMAX);
     if (N >= (int64_t)INT_MAX - 64)
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; shard the corpus", who, (long long)N);
+    if ((uintptr_t)keep & 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", who);
     if (B == 0)
         return TT_OK;
     if (!Q || !D || !out_val || !out_idx)
@@ -2303,7 +2376,8 @@ int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int
     int *tier = (int *)(ws + lp.tier_off);
     TT_RC_CHECK(tt_zero_async(tier, (size_t)B * sizeof(int), st));
     if (lp.small)
-        return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr, st, who);
+        return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr, st, who,
+                               keep);
     if (N == 0) {
         SegSource src{nullptr, nullptr, 0, 1, 0};
         hipLaunchKernelGGL(lk_merge_kernel, dim3(B), dim3(LSEL_THREADS), 0, st, src, k, out_val, out_idx);
@@ -2313,7 +2387,7 @@ int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int
     // tier 0: the k = 64 main pass, seeded with the k-th largest sample maximum
     Plan pl;
     TT_RC_CHECK(score_partials(Q, B, d, D, bf16, N, LK_M, idx_offset, workspace, workspace_bytes, st, &pl, who, nullptr,
-                               nullptr, k));
+                               nullptr, k, keep));
     const float *pval = (const float *)(ws + pl.pval_off);
     const int64_t *pidx = (const int64_t *)(ws + pl.pidx_off);
     const int M = pl.main.n_chunks * LK_M;
@@ -2322,7 +2396,8 @@ int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int
         int *redo = (int *)(ws + pl.redo_off);
         hipLaunchKernelGGL(lk_marker_kernel, dim3(pl.main.n_qtiles), dim3(256), 0, st, pidx, B, pl.main.n_chunks, redo);
         TT_LAUNCH_CHECK();
-        TT_RC_CHECK(score_partials(Q, B, d, D, bf16, N, LK_M, idx_offset, workspace, workspace_bytes, st, &pl, who, redo));
+        TT_RC_CHECK(score_partials(Q, B, d, D, bf16, N, LK_M, idx_offset, workspace, workspace_bytes, st, &pl, who, redo, nullptr,
+                                   0, keep));
     }
     LkState *sts = (LkState *)(ws + lp.st_off);
     Cand *buf = (Cand *)(ws + lp.buf_off);
@@ -2335,10 +2410,14 @@ int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int
     const int n_dt = (int)((N + LK_SCAN_DOCS - 1) / LK_SCAN_DOCS);
     const int grid = n_dt < LK_SCAN_BLOCKS ? n_dt : LK_SCAN_BLOCKS;
     for (int r = 0; r < LK_ROUNDS; ++r) {
-        if (bf16)
-            hipLaunchKernelGGL(lk_scan_kernel<true>, dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist);
+        if (keep && bf16)
+            hipLaunchKernelGGL((lk_scan_kernel<true, true>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
+        else if (keep)
+            hipLaunchKernelGGL((lk_scan_kernel<false, true>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
+        else if (bf16)
+            hipLaunchKernelGGL((lk_scan_kernel<true, false>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
         else
-            hipLaunchKernelGGL(lk_scan_kernel<false>, dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist);
+            hipLaunchKernelGGL((lk_scan_kernel<false, false>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
         TT_LAUNCH_CHECK();
         hipLaunchKernelGGL(lk_decide_kernel, dim3(B), dim3(256), 0, st, sts, tier, hist, k);
         TT_LAUNCH_CHECK();
@@ -2378,6 +2457,84 @@ TT_EXPORT int tt_score_topk_large_bf16(const float *Q, int B, int d, const void 
 {
     return score_topk_large(Q, B, d, D_bf16, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
                             (hipStream_t)stream, "tt_score_topk_large_bf16");
+}
+
+// ---- K4m: masked exact search (DESIGN.md "K4m") ------------------------------------------------------------------------------
+// The large call with a keep-bitmask: the same plan, workspace and launches, on the MASKED instantiations.  keep == NULL is the
+// unmasked call itself.
+TT_EXPORT size_t tt_score_topk_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return tt_score_topk_large_workspace_bytes(B, N, d, k, bf16);
+}
+
+TT_EXPORT int tt_score_topk_masked_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep, int k,
+                                       int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                       size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_large(Q, B, d, D, false, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
+                            (hipStream_t)stream, "tt_score_topk_masked_f32", keep);
+}
+
+TT_EXPORT int tt_score_topk_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep, int k,
+                                        int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                        size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_large(Q, B, d, D_bf16, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
+                            (hipStream_t)stream, "tt_score_topk_masked_bf16", keep);
+}
+
+namespace {
+// keep word w = the ballots of keep_bool[32 w .. 32 w + 31] != 0 (a wave packs two words); bits at or beyond N are zero
+__global__ __launch_bounds__(256) void keep_pack_kernel(const uint8_t *__restrict__ keep_bool, int64_t N, unsigned *__restrict__ keep)
+{
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long b = __ballot(n < N && keep_bool[n] != 0);
+    const int lane = threadIdx.x & 63;
+    if ((lane == 0 || lane == 32) && n < N)
+        keep[n >> 5] = (unsigned)(b >> lane);
+}
+
+// bit ids[i] - idx_offset cleared (vector atomic AND); ids outside [idx_offset, idx_offset + N) are somebody else's rows
+__global__ __launch_bounds__(256) void keep_clear_kernel(unsigned *keep, int64_t N, const int64_t *__restrict__ ids, int64_t n_ids,
+                                                         int64_t idx_offset)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_ids)
+        return;
+    const int64_t id = ids[i];
+    if (id < idx_offset || id - idx_offset >= N) // (ordered so that the subtraction cannot overflow for any id >= idx_offset)
+        return;
+    const int64_t n = id - idx_offset;
+    atomicAnd(keep + (n >> 5), ~(1u << (n & 31)));
+}
+} // namespace
+
+TT_EXPORT int tt_keep_mask_pack(const uint8_t *keep_bool, int64_t N, uint32_t *keep, tt_stream_t stream)
+{
+    if (N < 0 || N > (int64_t)INT_MAX * 256)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_pack: N=%lld", (long long)N);
+    if (N == 0)
+        return TT_OK;
+    if (!keep_bool || !keep || ((uintptr_t)keep & 3))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_pack: null pointer, or keep not 4-byte aligned");
+    hipLaunchKernelGGL(keep_pack_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep_bool, N, keep);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+TT_EXPORT int tt_keep_mask_clear_ids(uint32_t *keep, int64_t N, const int64_t *ids, int64_t n_ids, int64_t idx_offset,
+                                     tt_stream_t stream)
+{
+    if (N < 0 || n_ids < 0 || n_ids > (int64_t)INT_MAX * 256)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_clear_ids: N=%lld n_ids=%lld", (long long)N, (long long)n_ids);
+    if (N == 0 || n_ids == 0)
+        return TT_OK;
+    if (!keep || !ids || ((uintptr_t)keep & 3))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_clear_ids: null pointer, or keep not 4-byte aligned");
+    hipLaunchKernelGGL(keep_clear_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep, N, ids,
+                       n_ids, idx_offset);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
 }
 
 TT_EXPORT int tt_topk_merge_large(const float *in_val, const int64_t *in_idx, int B, int M, int k, float *out_val,

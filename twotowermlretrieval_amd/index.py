@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["GraphedSearch", "score_topk", "topk_merge", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
+__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
            "shard_bounds", "seed_union"]
 
 
@@ -99,26 +99,96 @@ def _squeezed(search: Callable, q: torch.Tensor, *args) -> Tuple[torch.Tensor, t
     return vals[0], idx[0]
 
 
+def _keep_words(n: int) -> int:
+    """Words of a keep-bitmask over n documents (one bit each, 32 per word)."""
+    return (n + 31) // 32
+
+
+_KEEP_DTYPES = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+
+
+def _check_keep(keep: torch.Tensor, n: int, device) -> torch.Tensor:
+    """A packed keep-bitmask over n documents on `device`, as the masked kernels read it (int32 view)."""
+    if keep.dtype not in _KEEP_DTYPES:
+        raise TypeError(f"keep must be a packed int32 / uint32 bitmask (pack_keep_mask), got {keep.dtype}")
+    if keep.device != device:
+        raise ValueError(f"keep on {keep.device} but the documents live on {device}")
+    if keep.dim() != 1 or keep.numel() != _keep_words(n):
+        raise ValueError(f"keep must hold exactly ceil(N/32) = {_keep_words(n)} words for N = {n}, got {tuple(keep.shape)}")
+    keep = keep if keep.is_contiguous() else keep.contiguous()
+    return keep if keep.dtype == torch.int32 else keep.view(torch.int32)
+
+
+def pack_keep_mask(keep_bool: torch.Tensor) -> torch.Tensor:
+    """keep_bool [N] on the device (bool, or any dtype: non-zero = keep) -> the packed keep-bitmask int32 [ceil(N/32)] that
+    score_topk(..., keep=) and the indexes' search(..., keep=) take: bit n & 31 of word n >> 5 = document n may be returned
+    (tt_keep_mask_pack, one launch; the bits beyond N are zero)."""
+    _need_cuda(keep_bool)
+    if keep_bool.dim() != 1:
+        raise ValueError(f"pack_keep_mask wants a [N] vector, got {tuple(keep_bool.shape)}")
+    b = keep_bool if keep_bool.dtype in (torch.bool, torch.uint8) else keep_bool != 0
+    b = b.contiguous().view(torch.uint8)
+    n = b.numel()
+    keep = torch.empty(_keep_words(n), dtype=torch.int32, device=b.device)
+    with torch.cuda.device(b.device):
+        _lib.check(_lib.lib().tt_keep_mask_pack(b.data_ptr(), n, keep.data_ptr(), _stream(b)))
+    return keep
+
+
+def _clear_ids(keep: Optional[torch.Tensor], n: int, device, ids, idx_offset: int) -> torch.Tensor:
+    """remove_ids of the indexes: `keep` (an all-ones mask over n documents when None) with the bits of the global ids that
+    fall in [idx_offset, idx_offset + n) cleared in place, one launch (tt_keep_mask_clear_ids); other ids are ignored."""
+    if keep is None:
+        keep = torch.full((_keep_words(n),), -1, dtype=torch.int32, device=device)
+        if n % 32:  # (the kernels ignore the bits beyond n; zero like pack_keep_mask's, so that the two compare equal)
+            keep[-1] = (1 << (n % 32)) - 1
+    ids = torch.as_tensor(ids, dtype=torch.int64, device=device).reshape(-1).contiguous()
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().tt_keep_mask_clear_ids(keep.data_ptr(), n, ids.data_ptr(), ids.numel(), idx_offset, _stream(keep)))
+    return keep
+
+
+def _and_keep(persistent: Optional[torch.Tensor], keep: Optional[torch.Tensor], n: int, device) -> Optional[torch.Tensor]:
+    """The mask a search runs under: the index's persistent mask, the caller's per-call one, or their AND (one torch op on
+    n/32 words); None = unmasked."""
+    if keep is None:
+        return persistent
+    keep = _check_keep(keep, n, device)
+    return keep if persistent is None else keep & persistent
+
+
 def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
-               workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               workspace: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """topk(q @ docs.T, k) fused.  q [B,d] or [d] float32; docs [N,d] (row i <-> document i), float32 or bfloat16.  A bf16
-    matrix is read as it is (d in {64, 128, 192, 256}); the result is that of its exact fp32 widening, bit for bit."""
+    matrix is read as it is (d in {64, 128, 192, 256}); the result is that of its exact fp32 widening, bit for bit.
+    keep: a packed keep-bitmask (pack_keep_mask: int32 / uint32, exactly ceil(N/32) words, on the documents' device) -> the
+    exact top-k of the documents whose bit is set (tt_score_topk_masked_f32 / _bf16, any k up to 1024), tail (-inf, -1) when
+    fewer than k are kept.  A masked document is still read and scored: a selective mask pays the full scan."""
     if q.dim() == 1:
-        return _squeezed(score_topk, q, docs, k, idx_offset, workspace)
+        return _squeezed(score_topk, q, docs, k, idx_offset, workspace, keep)
     _need_cuda(q, docs)
     q, docs = _f32c(q), _docs_c(docs)
     B, d = q.shape
     N = docs.shape[0]
     if docs.dim() != 2 or docs.shape[1] != d:
         raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    if keep is not None:
+        keep = _check_keep(keep, N, docs.device)
     vals, idx = _out_pair(B, k, q.device)
     with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
-        need = _topk_workspace_bytes(B, N, d, k, docs.dtype)
+        L = _lib.lib()
+        bf = docs.dtype == torch.bfloat16
+        need = (_topk_workspace_bytes(B, N, d, k, docs.dtype) if keep is None
+                else L.tt_score_topk_masked_workspace_bytes(B, N, d, k, int(bf)))
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        fn = getattr(_lib.lib(), _topk_fn(k, docs.dtype))
-        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(), idx.data_ptr(),
-                      workspace.data_ptr(), workspace.numel(), _stream(q)))
+        if keep is None:
+            _lib.check(getattr(L, _topk_fn(k, docs.dtype))(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(),
+                                                           idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q)))
+        else:
+            fn = L.tt_score_topk_masked_bf16 if bf else L.tt_score_topk_masked_f32
+            _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, keep.data_ptr(), k, idx_offset, vals.data_ptr(), idx.data_ptr(),
+                          workspace.data_ptr(), workspace.numel(), _stream(q)))
     return vals, idx
 
 
@@ -262,6 +332,13 @@ class BruteForceIndex:
     bytes, no shadow).  screen=True at d = 256 runs one statistics pass (tt_index_stats_bf16) and screens straight from the
     bf16 rows (converted to fp16 in LDS); otherwise, and outside the fp16 range, searches run the exact kernel over the bf16
     rows (tt_score_topk_bf16).  Either way the result is that of the widened fp32 rows, bit for bit.
+
+    Deletions and filtered search: remove_ids(ids) withdraws documents for good (a persistent keep-bitmask, N/8 bytes,
+    allocated on first use and mutated in place), search(q, k, keep=mask) answers over a subset for one call
+    (pack_keep_mask; ANDed with the persistent mask).  WITH ANY MASK IN EFFECT THE SEARCH RUNS THE MASKED EXACT KERNEL
+    (tt_score_topk_masked_f32 / _bf16), ALSO ON A screen=True INDEX: the screened kernels do not take a mask.  Its cost is
+    the exact kernel's -- HBM-bound at small B, fp32-MFMA-bound at large B, as the k > 64 route already is -- and a selective
+    mask pays the full scan.
     """
 
     def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False):
@@ -279,6 +356,7 @@ class BruteForceIndex:
         self.fallback_flags = torch.zeros(1, dtype=torch.int32, device=self.docs.device)  # per 32-query tile
         self.keep_stats = False   # True: the most recent screened search's workspace is kept for search_stats()
         self._last_ws = None
+        self._keep: Optional[torch.Tensor] = None  # the persistent keep-bitmask (remove_ids), None until the first removal
 
     @classmethod
     def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int):
@@ -297,6 +375,17 @@ class BruteForceIndex:
     def device(self) -> torch.device:
         return self.docs.device
 
+    @property
+    def keep_mask(self) -> Optional[torch.Tensor]:
+        """The persistent keep-bitmask (int32 [ceil(N/32)], bit n = document n not removed), or None: nothing removed yet."""
+        return self._keep
+
+    def remove_ids(self, ids) -> None:
+        """Withdraw documents: `ids` are GLOBAL ids (with this index's idx_offset; a tensor or a sequence), and ids that are
+        not this index's are ignored.  The mask is allocated all-ones on first use and then mutated in place with one launch on
+        the current stream, so later removals are seen by everything that holds it (a captured GraphedSearch included)."""
+        self._keep = _clear_ids(self._keep, self.docs.shape[0], self.docs.device, ids, self.idx_offset)
+
     def search_stats(self) -> Optional[torch.Tensor]:
         """int32 [B,2] = (pooled candidates, survivors rescored exactly) per query of the most recent screened search made
         with keep_stats = True, or None.  Diagnostic: what the fp16 filter let through on this corpus."""
@@ -308,33 +397,42 @@ class BruteForceIndex:
         return ws[off:off + 8 * B].view(torch.int32).view(B, 2).clone()
 
     def search(self, q: torch.Tensor, k: int = 10, _prof_events=None, out=None, _seed_union=None,
-               _k_seed: int = 0, _k_list: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+               _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) contiguous device tensors to write into (2-D q only).
+        keep: optional packed keep-bitmask over this index's rows for this call (pack_keep_mask), ANDed with the persistent
+        mask of remove_ids.  With either in effect the search is the masked exact kernel's, also on a screen=True index (the
+        class docstring has the cost); fallback_flags then reads all ones.
         _seed_union (ShardedIndex): a callable that turns this shard's seed list [B, _k_seed] f32 (its _k_seed largest
         sample maxima per query, _Screen.seed_list) into the seed thresholds [B] f32 -- the _k_seed-th largest of the UNION
         of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen then runs with that
         global seed and `out` holds this shard's documents above it."""
         if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank)
-            return _squeezed(self.search, q, k, _prof_events)
+            return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep)
         _need_cuda(q)
         if q.device != self.docs.device:
             raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
         if q.shape[-1] != self.docs.shape[1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        if self._screens(q.shape[0], k):
+        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        if self._screens(q.shape[0], k, keep is not None):
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list)
-        v, i = score_topk(q, self.docs, k, self.idx_offset)
+        if keep is not None and self._screen is not None:  # (the exact kernel took over every tile of a screened index)
+            self.fallback_flags = torch.ones((q.shape[0] + 31) // 32, dtype=torch.int32, device=self.docs.device)
+        v, i = score_topk(q, self.docs, k, self.idx_offset, keep=keep)
         if out is not None:
             out[0].copy_(v)
             out[1].copy_(i)
             return out
         return v, i
 
-    def _screens(self, B: int, k: int) -> bool:
+    def _screens(self, B: int, k: int, masked: Optional[bool] = None) -> bool:
         """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
-        whether they enter the seed exchange; the thresholds are the module's at the time of the call."""
+        whether they enter the seed exchange; the thresholds are the module's at the time of the call.
+        masked: a keep-bitmask is in effect (None: the persistent one, if any) -- a masked search never screens."""
         N, d = self.docs.shape
-        return (self._screen is not None and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
+        if masked is None:
+            masked = self._keep is not None
+        return (self._screen is not None and not masked and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
                 and N >= SCREEN_MIN_DOCS and k <= SMALL_KMAX)
 
     def _search_screened(self, q: torch.Tensor, k: int, _prof_events=None, out=None, _seed_union=None,
@@ -371,10 +469,14 @@ class GraphedSearch:
     exact kernels) become one graph launch, which matters at serving sizes where the whole search is < 1 ms.
     Everything in the library is asynchronous on the caller's stream with caller-owned memory, so plain
     stream capture works; queries are copied into a static buffer, results are returned in static buffers
-    (valid until the next call)."""
+    (valid until the next call).
+    Removals: a graph captured while the index has a persistent keep-bitmask reads that buffer at every replay, so later
+    remove_ids are honoured.  A graph captured BEFORE the index had one holds the unmasked launches: calling it after a
+    remove_ids raises RuntimeError (capture a new GraphedSearch) rather than return removed documents."""
 
     def __init__(self, index: "BruteForceIndex", batch: int, k: int = 10):
         self.index, self.B, self.k = index, int(batch), int(k)
+        self._masked = index.keep_mask is not None
         dev = index.docs.device
         d = index.docs.shape[1]
         self.q = torch.zeros((self.B, d), dtype=torch.float32, device=dev)
@@ -393,6 +495,9 @@ class GraphedSearch:
     def __call__(self, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         if tuple(q.shape) != tuple(self.q.shape):
             raise ValueError(f"GraphedSearch was captured for queries of shape {tuple(self.q.shape)}, got {tuple(q.shape)}")
+        if not self._masked and self.index.keep_mask is not None:
+            raise RuntimeError("GraphedSearch was captured before the index had a keep-bitmask (remove_ids): its graph would "
+                               "return removed documents; capture a new GraphedSearch")
         self.q.copy_(q)
         self.graph.replay()
         return self.vals, self.idx
@@ -576,7 +681,19 @@ class ShardedIndex:
     def _seed_plan(self, k: int):
         return seed_plan(self._coll.world, k, self._seed_exchange)
 
-    def _local_search(self, q: torch.Tensor, kp: int, k: int, sl: "_Slot", comm_stream=None) -> None:
+    @property
+    def keep_mask(self) -> Optional[torch.Tensor]:
+        """This rank's persistent keep-bitmask over its own rows (remove_ids), or None."""
+        return self._index.keep_mask
+
+    def remove_ids(self, ids) -> None:
+        """Withdraw documents by GLOBAL id.  Called by EVERY rank with the same ids, like every other call on this class: each
+        rank clears the bits of the ids in its shard and ignores the rest, and every rank allocates its mask, also where no
+        id falls in its shard -- whether a search is masked decides whether a rank enters the seed all-gather, so it has to be
+        a property of the job, not of a rank."""
+        self._index.remove_ids(ids)
+
+    def _local_search(self, q: torch.Tensor, kp: int, k: int, sl: "_Slot", comm_stream=None, keep=None) -> None:
         """This shard's list for the exchange: up to kp = max(k, shard_k) entries, best first.  The screen is seeded for
         the FINAL k with the UNION seed: every rank lists its k largest sample maxima per query, ONE small all-gather
         (k floats per query and rank: 40 KB per rank at B = 1024), and seed[q] = the k-th largest of the union -- k distinct
@@ -592,11 +709,13 @@ class ShardedIndex:
         plan = self._seed_plan(k)
         B = q.shape[0]
         # (a seed plan implies a resident shard: no rank exchanges seeds when any shard is streamed)
-        if plan is None or not self._index._screens(B, k) or (world == 1 and kp == k):
-            # no seed exchange on any rank (agreed in the constructor; B and k are the same everywhere): the shard's own search
+        masked = keep is not None or self._index.keep_mask is not None  # (the same on every rank: remove_ids, search)
+        if plan is None or not self._index._screens(B, k, masked) or (world == 1 and kp == k):
+            # no seed exchange on any rank (agreed in the constructor; B, k and masked are the same everywhere): the shard's own
+            # search -- the masked exact kernel when a mask is in effect; a short list's padding is ignored by the merge
             if comm_stream is not None:
                 self._flush()
-            self._index.search(q, kp, out=(sl.send_v, sl.send_i))
+            self._index.search(q, kp, out=(sl.send_v, sl.send_i), keep=keep)
             return
         ks, kth = plan
 
@@ -695,24 +814,27 @@ class ShardedIndex:
             _lib.check(merge(sl.recv.data_ptr(), self._coll.world, sl.stride, sl.nv, B, kp, k, sl.out_v.data_ptr(),
                              sl.out_i.data_ptr(), _stream(sl.recv)))
 
-    def search(self, q: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One search, everything on the caller's stream; fresh result tensors."""
+    def search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One search, everything on the caller's stream; fresh result tensors.
+        keep: a packed keep-bitmask over THIS RANK'S rows for this call (ANDed with the mask of remove_ids).  It must be given
+        on all ranks or on none: a masked search does not enter the seed exchange."""
         if q.dim() == 1:
-            return _squeezed(self.search, q, k)
+            return _squeezed(self.search, q, k, keep)
         kp = max(k, self.shard_k)
         sl = self._slot(q.shape[0], kp, k, 2)
         cur = torch.cuda.current_stream(sl.send.device)
         cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._local_search(q, kp, k, sl)
+        self._local_search(q, kp, k, sl, keep=keep)
         self._exchange_merge(sl, q.shape[0], kp, k)
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
 
-    def submit(self, q: torch.Tensor, k: int = 10) -> PendingSearch:
+    def submit(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> PendingSearch:
         """Pipelined search of a [B,d] batch: the local search is enqueued on the caller's stream now; its list exchange and
         merge go out on this index's second stream inside the NEXT submit() (behind that step's seed gather), or when
-        .result() / search() asks for them.  Call .result() when the answer is needed."""
+        .result() / search() asks for them.  Call .result() when the answer is needed.  keep: as in search() (all ranks or
+        none)."""
         if q.dim() != 2:
             raise ValueError("submit wants a [B,d] batch")
         kp = max(k, self.shard_k)
@@ -725,7 +847,7 @@ class ShardedIndex:
         cur = torch.cuda.current_stream(dev)
         self._flush(sl)                      # (the slot's own previous step, if nobody collected it: issue before reuse)
         cur.wait_event(sl.merged)            # the slot's previous exchange has read its send block
-        self._local_search(q, kp, k, sl, comm_stream=self._xs)
+        self._local_search(q, kp, k, sl, comm_stream=self._xs, keep=keep)
         self._flush()                        # (a local search without a seed exchange has not issued the previous step's yet)
         sl.searched.record(cur)
         self._deferred = (sl, B, kp, k)
@@ -767,6 +889,7 @@ class StreamedIndex:
         self.dmax_norm = dmax
         if not _fp16_range_ok(dmax, amax):
             self._d16 = [None, None]
+        self._keep: Optional[torch.Tensor] = None  # persistent keep-bitmask (remove_ids): N/8 bytes, on the device
 
     def _walk(self, visit, stats=None):
         L = _lib.lib()
@@ -815,22 +938,37 @@ class StreamedIndex:
     def ntotal(self) -> int:
         return self.N
 
-    def search(self, q: torch.Tensor, k: int = 10, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block)."""
+    @property
+    def keep_mask(self) -> Optional[torch.Tensor]:
+        """The persistent keep-bitmask over the whole corpus (int32 [ceil(N/32)], on the device), or None."""
+        return self._keep
+
+    def remove_ids(self, ids) -> None:
+        """Withdraw documents by global id (with idx_offset); other ids are ignored.  The mask stays on the device."""
+        self._keep = _clear_ids(self._keep, self.N, self.device, ids, self.idx_offset)
+
+    def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block).
+        keep: optional packed keep-bitmask over the whole corpus (on the device), ANDed with the mask of remove_ids.  Block i of
+        a masked search gets the word slice at lo / 32 and runs the masked exact kernel, so the blocks must start on word
+        boundaries: block_docs % 32 != 0 (with more than one block) raises ValueError."""
         _need_cuda(q)
         if q.dim() == 1:
-            return _squeezed(self.search, q, k)
+            return _squeezed(self.search, q, k, None, keep)
         if q.device != self.device:
             raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
         if q.shape[1] != self.d:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
         q = _f32c(q)
+        keep = _and_keep(self._keep, keep, self.N, self.device)
+        if keep is not None and self.block % 32 and self.N > self.block:
+            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
         run = []  # the running top-k: (values, indices)
 
         def visit(s, lo, n):
             blk = BruteForceIndex._from_buffers(self._d32[s][:n], self._d16[s][:n] if self._d16[s] is not None else None,
                                                 self.dmax_norm, self.idx_offset + lo)
-            v, i = blk.search(q, k)
+            v, i = blk.search(q, k, keep=None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)])
             run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
 
         self._walk(visit)
