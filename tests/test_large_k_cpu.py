@@ -72,12 +72,15 @@ def test_large_merge_refusals_without_gpu(libtt):
 def test_python_routing_by_k():
     import torch
     from twotowermlretrieval_amd import index
-    assert index._topk_fn(1, torch.float32) == "tt_score_topk_f32"
-    assert index._topk_fn(64, torch.float32) == "tt_score_topk_f32"
-    assert index._topk_fn(64, torch.bfloat16) == "tt_score_topk_bf16"
-    assert index._topk_fn(65, torch.float32) == "tt_score_topk_large_f32"
-    assert index._topk_fn(1024, torch.bfloat16) == "tt_score_topk_large_bf16"
-    assert index._topk_fn(1025, torch.float32) == "tt_score_topk_large_f32"  # the refusal comes from the new entry point
+    def fn(k, dtype):
+        return index._exact_route(dtype, k, False).fn
+
+    assert fn(1, torch.float32) == "tt_score_topk_f32"
+    assert fn(64, torch.float32) == "tt_score_topk_f32"
+    assert fn(64, torch.bfloat16) == "tt_score_topk_bf16"
+    assert fn(65, torch.float32) == "tt_score_topk_large_f32"
+    assert fn(1024, torch.bfloat16) == "tt_score_topk_large_bf16"
+    assert fn(1025, torch.float32) == "tt_score_topk_large_f32"  # the refusal comes from the new entry point
     assert index._merge_fn(64) == "tt_topk_merge"
     assert index._merge_fn(65) == "tt_topk_merge_large"
     assert index._merge_fn(10, 50, shards=True) == "tt_topk_merge_shards"
@@ -88,11 +91,12 @@ def test_python_routing_by_k():
 def test_python_workspace_sizing_by_k(libtt):
     import torch
     from twotowermlretrieval_amd import index
-    assert index._topk_workspace_bytes(8, 100_000, 256, 10, torch.float32) == libtt.tt_score_topk_workspace_bytes(8, 100_000, 256, 10)
-    assert (index._topk_workspace_bytes(8, 100_000, 256, 100, torch.float32)
-            == libtt.tt_score_topk_large_workspace_bytes(8, 100_000, 256, 100, 0))
-    assert (index._topk_workspace_bytes(8, 100_000, 128, 1000, torch.bfloat16)
-            == libtt.tt_score_topk_large_workspace_bytes(8, 100_000, 128, 1000, 1))
+    def ws_bytes(B, N, d, k, dtype):
+        return index._exact_route(dtype, k, False).workspace_bytes(B, N, d, k, dtype)
+
+    assert ws_bytes(8, 100_000, 256, 10, torch.float32) == libtt.tt_score_topk_workspace_bytes(8, 100_000, 256, 10)
+    assert ws_bytes(8, 100_000, 256, 100, torch.float32) == libtt.tt_score_topk_large_workspace_bytes(8, 100_000, 256, 100, 0)
+    assert ws_bytes(8, 100_000, 128, 1000, torch.bfloat16) == libtt.tt_score_topk_large_workspace_bytes(8, 100_000, 128, 1000, 1)
     # seed exchange stays off above 64
     assert index.seed_plan(8, 65) is None
 

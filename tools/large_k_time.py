@@ -29,7 +29,7 @@ def _tiers(B, N, d, k, dtype, Q, D):
     """One large call with its own workspace; the per-query tiers from tt_score_topk_large_tier_offset."""
     L = _lib.lib()
     bf = int(dtype == torch.bfloat16)
-    ws = torch.empty(index._topk_workspace_bytes(B, N, d, k, dtype), dtype=torch.uint8, device=Q.device)
+    ws = torch.empty(index._exact_route(dtype, k, False).workspace_bytes(B, N, d, k, dtype), dtype=torch.uint8, device=Q.device)
     index.score_topk(Q, D, k, workspace=ws)
     torch.cuda.synchronize()
     if k <= index.SMALL_KMAX:
@@ -42,7 +42,7 @@ def _tiers(B, N, d, k, dtype, Q, D):
 def time_case(name, Q, D, k, reps):
     B, d = Q.shape
     N = D.shape[0]
-    ws = torch.empty(index._topk_workspace_bytes(B, N, d, k, D.dtype), dtype=torch.uint8, device=Q.device)
+    ws = torch.empty(index._exact_route(D.dtype, k, False).workspace_bytes(B, N, d, k, D.dtype), dtype=torch.uint8, device=Q.device)
     index.score_topk(Q, D, k, workspace=ws)  # warm-up (code objects, allocator)
     torch.cuda.synchronize()
     ms = []

@@ -28,7 +28,7 @@
 //    k-th score becomes the new bound).  Ties: score desc, index asc.  Partial
 //    lists go to the workspace; topk_merge_kernel reduces them (also used for the
 //    sample-pass maxima and for the cross-shard merge after the RCCL all-gather).
-#include "tt_common.h"
+#include "score_topk.h"
 
 #include <limits.h>
 #include <math.h>
@@ -52,7 +52,6 @@ constexpr int DRAW_GAVE_UP = 0x7fffffff;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
 
-struct Cand;
 struct ScoreParams {
     const float *Q;
     const void *D; // [N][d] f32, or bf16 for the BF instantiations
@@ -123,12 +122,6 @@ __device__ __forceinline__ int xcd_remap(int b, int nblk)
     int x = b & 7, q = nblk >> 3, r = nblk & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
-
-// One candidate: (score, document index relative to D).  8 bytes, one store.
-struct __attribute__((aligned(8))) Cand {
-    float v;
-    int x;
-};
 
 __device__ __forceinline__ Cand cand_load_l2(const Cand *p)
 {
@@ -800,12 +793,6 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
 constexpr int MERGE_THREADS = 256;
 constexpr int MERGE_POOL = 6144;                 // LDS pool entries (12 B each)
 constexpr int MERGE_SEG = MERGE_THREADS * 16;    // candidates scanned between overflow checks
-constexpr int MERGE_KMAX = 64;
-
-__device__ __forceinline__ bool ranks_before(float sa, int64_t ia, float sb, int64_t ib)
-{
-    return sa > sb || (sa == sb && ia < ib);
-}
 
 // Block-wide: the best pool entry ranking strictly after (pv,pi).  Returns bi == INT64_MAX if none.
 __device__ __forceinline__ void pool_next_best(const float *pool_v, const int64_t *pool_i, int n, float pv,
@@ -945,17 +932,6 @@ __global__ __launch_bounds__(MERGE_THREADS) void topk_merge_kernel(const float *
 // k-th largest of M values per row (threshold seeding): 4-pass radix select on the order-preserving
 // integer image of the floats; one block per row, cost independent of k.  -inf when M < k.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned order_key(float f)
-{
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float order_key_to_float(unsigned key)
-{
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
-
 // top_out (nullable): [rows][k], receives the row's k largest values, UNORDERED (the values above the k-th in arrival
 // order, then copies of the k-th; -inf padding when M < k) -- what a shard contributes to the union seed of a sharded
 // search (tt_score_topk_screened_seed_list_f32).
@@ -1169,35 +1145,12 @@ __global__ __launch_bounds__(256) void score_all_kernel(const float *__restrict_
         S[(size_t)b * N + n0 + lane] = acc;
 }
 
-// One launch of score_topk_kernel over docs [0,N): how the work is cut and where its
-// partial lists live inside the workspace.
-struct Pass {
-    int n_qtiles, n_tiles, n_chunks, tiles_per_chunk, n_tasks;
-    int tail_own, static_tiles, tail_g, tail_blocks; // with the pool on: tail_own tiles per chunk are static (see ScoreParams)
-    int64_t N;
-};
-
-struct Plan {
-    int cap;       // candidate-buffer entries per (wave, query): 64 (k <= 16) or 128
-    size_t smem;   // dynamic LDS per block
-    Pass main, pre;
-    bool prepass;  // sample pass first: its k-th scores seed the main pass's thresholds
-    // workspace layout (byte offsets)
-    size_t cand_off, pval_off, pidx_off, pre_val_off, pre_idx_off, tailctr_off, ws_bytes;
-    // three or more query tiles on the 32-query kernel: pacing counters and the chunks' pool draws behind the pool counter(s)
-    bool paced;
-    int pace_g, pace_lag;
-    int grp_maxseg;
-    size_t pace_off, grp_off, ctr_bytes; // ctr_bytes: pool counter(s) + pacing + draws, zeroed together before the main pass
-    size_t redo_off; // one int per query tile: a wave of the tile gave up a pool draw -> the static-split pass redoes the tile
-};
-
 bool tt_score_pacing() // TT_SCORE_PACE=0: every wave for itself (measurement)
 {
     return TT_AB_SWITCH(TT_SCORE_PACE, 1) != 0;
 }
 
-Pass make_pass(int B, int64_t N, int slots, int qt, bool tail = false)
+Pass make_pass(int B, int64_t N, int slots, int qt, bool tail)
 {
     Pass ps;
     ps.N = N;
@@ -1227,9 +1180,9 @@ constexpr int64_t PREPASS_MIN_N = 262144;
 constexpr int PREPASS_MAX_CHUNK_DOCS = 65536;
 constexpr int64_t PREPASS_MIN_SAMPLE = 16384;
 
-// bf16: bf16 document rows (tt_score_topk_bf16), which run on 32-query tiles at every batch size; for B > 16 the
-// workspace layout is the fp32 one (only the pacing block length, a kernel argument, depends on the row bytes)
-Plan make_plan(int B, int64_t N, int k, int d, bool bf16 = false)
+} // namespace
+
+Plan make_plan(int B, int64_t N, int k, int d, bool bf16)
 {
     Plan pl;
     const int qt = (!bf16 && (d > 256 || B <= 16)) ? 16 : 32; // 16-query tiles: wide embeddings, and batches that fit one such tile
@@ -1243,10 +1196,10 @@ Plan make_plan(int B, int64_t N, int k, int d, bool bf16 = false)
         int64_t ns = N / 256;
         ns = ns < PREPASS_MIN_SAMPLE ? PREPASS_MIN_SAMPLE : ns;
         ns = (ns + TILE_DOCS - 1) / TILE_DOCS * TILE_DOCS;
-        pl.pre = make_pass(B, ns, slots, qt);
+        pl.pre = make_pass(B, ns, slots, qt, false);
         max_tasks = pl.pre.n_tasks > max_tasks ? pl.pre.n_tasks : max_tasks;
     } else {
-        pl.pre = make_pass(B, 0, slots, qt);
+        pl.pre = make_pass(B, 0, slots, qt, false);
     }
     const size_t rows = (size_t)pl.main.n_qtiles * qt;
     size_t max_chunks = pl.main.n_chunks;
@@ -1259,7 +1212,7 @@ Plan make_plan(int B, int64_t N, int k, int d, bool bf16 = false)
     pl.pre_val_off = ws.take(rows * k * sizeof(float));
     pl.pre_idx_off = ws.take(rows * k * sizeof(int64_t));
     pl.tailctr_off = ws.take((size_t)pl.main.n_qtiles * sizeof(int));
-    // (32-query tiles only: the redo pass in tt_score_topk_f32_pred keeps one flag per 32 queries)
+    // (32-query tiles only: the give-up redo, redo_gave_up, keeps one flag per 32 queries)
     pl.paced = qt == 32 && pl.main.n_qtiles >= 3; // (two query tiles: +0.7 % with it, 1.7x fetched either way)
     {
         // the chunks of one XCD (an eighth of them) share its 4 MiB L2: a chunk's waves must stay within its part of
@@ -1293,7 +1246,9 @@ Plan make_plan(int B, int64_t N, int k, int d, bool bf16 = false)
     return pl;
 }
 
-constexpr bool score_dim_ok(int d, bool bf16 = false)
+namespace {
+
+constexpr bool score_dim_ok(int d, bool bf16)
 {
     if (bf16)
         return d == 64 || d == 128 || d == 192 || d == 256;
@@ -1379,15 +1334,15 @@ int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, b
     }
 }
 
-ScoreParams pass_params(const Pass &ps, const float *Q, int B, const void *D, int k, int64_t idx_offset, char *ws,
-                        const Plan &pl)
+ScoreParams pass_params(const Pass &ps, const ExactCall &c, int list_k, int64_t idx_offset, const Plan &pl)
 {
+    char *ws = (char *)c.workspace;
     ScoreParams sp;
-    sp.Q = Q;
-    sp.D = D;
-    sp.B = B;
+    sp.Q = c.Q;
+    sp.D = c.D;
+    sp.B = c.B;
     sp.N = (int)ps.N;
-    sp.k = k;
+    sp.k = list_k;
     sp.n_qtiles = ps.n_qtiles;
     sp.n_chunks = ps.n_chunks;
     sp.tiles_per_chunk = ps.tiles_per_chunk;
@@ -1411,7 +1366,7 @@ ScoreParams pass_params(const Pass &ps, const float *Q, int B, const void *D, in
     sp.thr0_off = 0;
     sp.run_if = nullptr;
     sp.draw_polls = TT_AB_SWITCH(TT_DRAW_POLLS, DRAW_POLLS);
-    sp.keep = nullptr;
+    sp.keep = c.keep;
     return sp;
 }
 
@@ -1421,56 +1376,91 @@ const char *score_dims(bool bf16)
     return bf16 ? "64, 128, 192, 256" : "32, 64, 96, 128, 192, 256, 320, 384, 448, 512";
 }
 
-// D: fp32 rows, or bf16 rows when bf16 is set.
-// k_seed (0 = k): the rank whose sample score seeds the main pass -- the FINAL k of a large-k search, whose main pass keeps
-// lists of k = 64 (tt_score_topk_large_f32: a seed for the 64th score would drop documents ranked 65..k_seed)
-int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
-                   void *workspace, size_t workspace_bytes, hipStream_t st, Plan *plan_out, const char *who,
-                   const int *run_if = nullptr, void *const *prof_events = nullptr, int k_seed = 0,
-                   const unsigned *keep = nullptr)
+// The waves of this plan's main pass may wait for a chunk-mate's pool draw, and give up: redo_gave_up has work to look for.
+bool draws_in_step(const Plan &pl)
 {
-    if (B <= 0 || N <= 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
-    if (!score_dim_ok(d, bf16))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", who, d, score_dims(bf16));
-    if (k > 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, k);
-    if (N >= (int64_t)INT_MAX - 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; shard the corpus", who, (long long)N);
-    if (!Q || !D)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
-    const Plan pl = make_plan(B, N, k, d, bf16);
-    if (!workspace || workspace_bytes < pl.ws_bytes)
-        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, pl.ws_bytes);
-    if (((uintptr_t)D & 15) || ((uintptr_t)Q & 3) || ((uintptr_t)workspace & 255))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: D must be 16-byte and the workspace 256-byte aligned", who);
-    char *ws = (char *)workspace;
-    *plan_out = pl;
+    return pl.paced && pl.main.tail_blocks > 0 && tt_score_pacing();
+}
+
+// topk_merge_kernel over the partial lists of a k <= 64 search (run_if: only the flagged query tiles)
+int merge_partials(const ExactCall &c, const Plan &pl, const int *run_if)
+{
+    const char *ws = (const char *)c.workspace;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(c.B), dim3(MERGE_THREADS), 0, c.stream, (const float *)(ws + pl.pval_off),
+                       (const int64_t *)(ws + pl.pidx_off), pl.main.n_chunks * c.k, c.k, c.out_val, c.out_idx, run_if,
+                       pl.main.n_chunks * c.k, (size_t)0);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+} // namespace
+
+// The entries grew their checks one by one and do not take them in one order: the k <= 64 entries accept an empty batch
+// before they look at d, k and N, ask for their outputs before N's size, and with an empty corpus need nothing but the
+// outputs; the large and masked entries (kmax > MERGE_KMAX) check the shape in full first, and the pointers together.  With
+// B == 0 and an unsupported d the former return TT_OK and the latter refuse.  Every entry keeps the answers it gave before
+// this function existed; which order is right is a question of its own.
+int exact_validate(const ExactCall &c, int kmax, Plan *pl)
+{
+    const bool large = kmax > MERGE_KMAX;
+    if (c.B < 0 || c.N < 0 || c.k <= 0 || (c.partials && (c.B == 0 || c.N == 0)))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", c.who, c.B, (long long)c.N, c.k);
+    if (c.B == 0 && !large)
+        return TT_OK;
+    if (!score_dim_ok(c.d, c.bf16))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", c.who, c.d, score_dims(c.bf16));
+    if (c.k > kmax)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d", c.who, c.k, kmax);
+    if (!large && !c.partials && (!c.out_val || !c.out_idx))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null output pointer", c.who);
+    if (c.N == 0 && !large)
+        return TT_OK; // (the merge over zero candidates reads neither Q, D nor the workspace)
+    if (c.N >= (int64_t)INT_MAX - 64)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; shard the corpus", c.who, (long long)c.N);
+    if ((uintptr_t)c.keep & 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", c.who);
+    if (c.B == 0)
+        return TT_OK;
+    if (!c.Q || !c.D || (large && (!c.out_val || !c.out_idx)))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", c.who);
+    *pl = make_plan(c.B, c.N, c.k < MERGE_KMAX ? c.k : MERGE_KMAX, c.d, c.bf16);
+    const size_t need = large ? score_topk_large_ws_bytes(*pl, c.B, c.k) : pl->ws_bytes;
+    if (!c.workspace || c.workspace_bytes < need)
+        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", c.who, c.workspace_bytes, need);
+    if (((uintptr_t)c.D & 15) || ((uintptr_t)c.Q & 3) || ((uintptr_t)c.workspace & 255))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: D must be 16-byte and the workspace 256-byte aligned", c.who);
+    return TT_OK;
+}
+
+int score_partials(const ExactCall &c, const Plan &pl, const ExactPass &ps)
+{
+    char *ws = (char *)c.workspace;
+    const hipStream_t st = c.stream;
+    const int *run_if = ps.run_if;
     const float *thr0 = nullptr;
     // (the predicated form -- the screened search's on-device fallback, a no-op unless a flag is raised -- skips
     //  the sample pass: it only seeds thresholds, and two fewer empty launches sit behind every screened search)
     if (pl.prepass && !run_if) {
         // sample pass over D[0:ns): per-(wave,query) maxima, then their k-th largest per query.
         // k distinct documents score at least that much, so it bounds the final k-th score from below.
+        // (the rank is the call's k, not the list length: under a large k the main pass keeps lists of 64, and a seed for
+        //  the 64th score would drop documents ranked 65..k)
         // (keep: the maxima are over the kept documents of the sample -- the first words of the mask -- and a chunk with none
         //  contributes -inf: only documents that may be returned vouch for the bound)
-        ScoreParams pp = pass_params(pl.pre, Q, B, D, k, 0, ws, pl);
-        pp.run_if = run_if;
-        pp.keep = keep;
-        int rc = launch_score(d, pp, pl, st, true, bf16);
+        ScoreParams pp = pass_params(pl.pre, c, ps.list_k, 0, pl);
+        int rc = launch_score(c.d, pp, pl, st, true, c.bf16);
         if (rc != TT_OK)
             return rc;
-        hipLaunchKernelGGL(kth_largest_kernel, dim3(B), dim3(256), 0, st, (const float *)pp.pval, pl.pre.n_chunks,
-                           k_seed > 0 ? k_seed : k, (float *)(ws + pl.pre_val_off), run_if, (float *)nullptr);
+        hipLaunchKernelGGL(kth_largest_kernel, dim3(c.B), dim3(256), 0, st, (const float *)pp.pval, pl.pre.n_chunks, c.k,
+                           (float *)(ws + pl.pre_val_off), run_if, (float *)nullptr);
         TT_LAUNCH_CHECK();
         thr0 = (const float *)(ws + pl.pre_val_off);
     }
-    ScoreParams sp = pass_params(pl.main, Q, B, D, k, idx_offset, ws, pl);
+    ScoreParams sp = pass_params(pl.main, c, ps.list_k, c.idx_offset, pl);
     sp.thr0 = thr0;
     sp.thr0_stride = 1;
     sp.thr0_off = 0;
     sp.run_if = run_if;
-    sp.keep = keep;
     if (pl.main.tail_blocks > 0 && !run_if) {
         // (the predicated form keeps the static split: its launches sit behind every screened search as no-ops, and a
         //  counter reset would be one more)
@@ -1492,67 +1482,22 @@ int score_partials(const float *Q, int B, int d, const void *D, bool bf16, int64
     }
     if (sp.tail_ctr || sp.pace)
         TT_RC_CHECK(tt_zero_async(ws + pl.tailctr_off, pl.ctr_bytes, st));
-    if (prof_events)
-        TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    const int rc = launch_score(d, sp, pl, st, false, bf16);
-    if (prof_events && rc == TT_OK)
-        TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
+    if (ps.prof_events)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)ps.prof_events[0], st));
+    const int rc = launch_score(c.d, sp, pl, st, false, c.bf16);
+    if (ps.prof_events && rc == TT_OK)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)ps.prof_events[1], st));
     return rc;
 }
 
-} // namespace
-
-// Byte offset, in the workspace of a finished tt_score_topk(_partials)_f32 call of this shape, of an int32 that counts the waves
-// whose pacing wait ran into its bound (0 when the launch was not paced): (size_t)-1 if the shape is never paced.
-TT_EXPORT size_t tt_score_topk_pace_timeouts_offset(int B, int64_t N, int d, int k)
+int redo_gave_up(const ExactCall &c, const Plan &pl, int list_k, FlagGaveUp flag, bool merge)
 {
-    if (B <= 0 || N <= 0 || k <= 0)
-        return (size_t)-1;
-    const Plan pl = make_plan(B, N, k, d);
-    return pl.paced ? pl.pace_off + (size_t)pl.main.n_chunks * PACE_R * sizeof(int) : (size_t)-1;
-}
-
-// Diagnostic: byte offset of the per-query-tile flags (int32 each) that say which tiles the last tt_score_topk_f32 call of this
-// shape did again because a wave had given up a pool draw; (size_t)-1 = the shape never draws from a shared pool.
-TT_EXPORT size_t tt_score_topk_redo_flags_offset(int B, int64_t N, int d, int k)
-{
-    if (B <= 0 || N <= 0 || k <= 0)
-        return (size_t)-1;
-    const Plan pl = make_plan(B, N, k, d);
-    return (pl.paced && pl.main.tail_blocks > 0) ? pl.redo_off : (size_t)-1;
-}
-
-TT_EXPORT size_t tt_score_topk_workspace_bytes(int B, int64_t N, int d, int k)
-{
-    if (B <= 0 || N < 0 || k <= 0)
-        return 0;
-    return make_plan(B, N, k, d).ws_bytes;
-}
-
-TT_EXPORT size_t tt_score_topk_bf16_workspace_bytes(int B, int64_t N, int d, int k)
-{
-    if (B <= 0 || N < 0 || k <= 0)
-        return 0;
-    return make_plan(B, N, k, d, true).ws_bytes;
-}
-
-TT_EXPORT int tt_score_topk_partials_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
-                                         int64_t idx_offset, void *workspace, size_t workspace_bytes,
-                                         const float **part_val, const int64_t **part_idx, int *part_m,
-                                         void *const *prof_events, tt_stream_t stream)
-{
-    Plan pl;
-    int rc = score_partials(Q, B, d, D, false, N, k, idx_offset, workspace, workspace_bytes, (hipStream_t)stream, &pl,
-                            "tt_score_topk_partials_f32", nullptr, prof_events);
-    if (rc != TT_OK)
-        return rc;
-    if (part_val)
-        *part_val = (const float *)((const char *)workspace + pl.pval_off);
-    if (part_idx)
-        *part_idx = (const int64_t *)((const char *)workspace + pl.pidx_off);
-    if (part_m)
-        *part_m = pl.main.n_chunks * k;
-    return TT_OK;
+    if (!draws_in_step(pl))
+        return TT_OK;
+    int *redo = (int *)((char *)c.workspace + pl.redo_off);
+    TT_RC_CHECK(flag(c, pl, redo));
+    TT_RC_CHECK(score_partials(c, pl, ExactPass{list_k, redo, nullptr}));
+    return merge ? merge_partials(c, pl, redo) : TT_OK;
 }
 
 namespace {
@@ -1565,71 +1510,113 @@ __global__ __launch_bounds__(64) void redo_flag_kernel(const int64_t *__restrict
     if (threadIdx.x == 0)
         flags[blockIdx.x] = any != 0ull;
 }
-} // namespace
 
-// Exact path over fp32 (bf16 = false) or bf16 rows, optionally predicated on a device flag (the screened path's fallback).
-namespace {
-int score_topk_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
-                    float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, const int *run_if,
-                    hipStream_t st, const char *who, const unsigned *keep = nullptr)
+int flag_merged(const ExactCall &c, const Plan &pl, int *flags)
 {
-    if (B < 0 || N < 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
-    if (B == 0)
-        return TT_OK;
-    if (!score_dim_ok(d, bf16))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", who, d, score_dims(bf16));
-    if (k > 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, k);
-    if (!out_val || !out_idx)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null output pointer", who);
-    if (N == 0) { // merge over zero candidates writes the (-inf,-1) tail
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(MERGE_THREADS), 0, st, (const float *)nullptr,
-                           (const int64_t *)nullptr, 0, k, out_val, out_idx, (const int *)nullptr, 1, (size_t)0);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-    }
-    Plan pl;
-    int rc = score_partials(Q, B, d, D, bf16, N, k, idx_offset, workspace, workspace_bytes, st, &pl, who, run_if, nullptr, 0, keep);
-    if (rc != TT_OK)
-        return rc;
-    const char *ws = (const char *)workspace;
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(MERGE_THREADS), 0, st, (const float *)(ws + pl.pval_off),
-                       (const int64_t *)(ws + pl.pidx_off), pl.main.n_chunks * k, k, out_val, out_idx, run_if,
-                       pl.main.n_chunks * k, (size_t)0);
+    hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, c.stream, (const int64_t *)c.out_idx, c.B, c.k, flags);
     TT_LAUNCH_CHECK();
-    if (!run_if && pl.paced && pl.main.tail_blocks > 0 && tt_score_pacing()) {
-        // The one wait of this path that cannot be skipped without losing documents is a wave's wait for a chunk-mate's pool
-        // draw; a wave whose budget ran out marked its lists (+inf, TT_TOPK_INVALID_INDEX + t).  Nothing downstream reads that
-        // marker, so it is dealt with HERE, on the device: the query tiles whose merged list starts with it are done again on
-        // the static split (the predicated form: no pool, no pacing, nobody to wait for) -- three small launches that find
-        // nothing to do in every run observed so far (~10 us behind a search of >= 4 ms).
-        // (only paced plans get here, and make_plan paces 32-query tiles only: one flag per 32 queries)
-        int *redo = (int *)((char *)workspace + pl.redo_off);
-        hipLaunchKernelGGL(redo_flag_kernel, dim3(pl.main.n_qtiles), dim3(64), 0, st, (const int64_t *)out_idx, B, k, redo);
-        TT_LAUNCH_CHECK();
-        return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, redo, st,
-                               who, keep);
-    }
     return TT_OK;
+}
+
+// Both public k <= 64 searches and their predicated forms.
+int exact_small(const ExactCall &c, const int *run_if)
+{
+    Plan pl;
+    const int rc = exact_validate(c, MERGE_KMAX, &pl);
+    return rc != TT_OK || c.B == 0 ? rc : score_topk_pred(c, pl, run_if);
 }
 } // namespace
 
-// The predicated forms, for the screened path's fallback (csrc/screen.hip).
+// Exact path over fp32 or bf16 rows, optionally predicated on a device flag (the screened path's fallback).
+int score_topk_pred(const ExactCall &c, const Plan &pl, const int *run_if)
+{
+    if (c.N == 0) { // merge over zero candidates writes the (-inf,-1) tail
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(c.B), dim3(MERGE_THREADS), 0, c.stream, (const float *)nullptr,
+                           (const int64_t *)nullptr, 0, c.k, c.out_val, c.out_idx, (const int *)nullptr, 1, (size_t)0);
+        TT_LAUNCH_CHECK();
+        return TT_OK;
+    }
+    TT_RC_CHECK(score_partials(c, pl, ExactPass{c.k, run_if, nullptr}));
+    TT_RC_CHECK(merge_partials(c, pl, run_if));
+    return run_if ? TT_OK : redo_gave_up(c, pl, c.k, flag_merged, true);
+}
+
+// The two diagnostic offsets into a paced fp32 call's workspace: the pacing time-out count, or (redo) the redo flags, which only
+// a plan with a shared pool has.
+static size_t paced_offset(int B, int64_t N, int d, int k, bool redo)
+{
+    if (B <= 0 || N <= 0 || k <= 0)
+        return (size_t)-1;
+    const Plan pl = make_plan(B, N, k, d, false);
+    if (!pl.paced || (redo && pl.main.tail_blocks <= 0))
+        return (size_t)-1;
+    return redo ? pl.redo_off : pl.pace_off + (size_t)pl.main.n_chunks * PACE_R * sizeof(int);
+}
+
+// Byte offset, in the workspace of a finished tt_score_topk(_partials)_f32 call of this shape, of an int32 that counts the waves
+// whose pacing wait ran into its bound (0 when the launch was not paced): (size_t)-1 if the shape is never paced.
+TT_EXPORT size_t tt_score_topk_pace_timeouts_offset(int B, int64_t N, int d, int k)
+{
+    return paced_offset(B, N, d, k, false);
+}
+
+// Diagnostic: byte offset of the per-query-tile flags (int32 each) that say which tiles the last tt_score_topk_f32 call of this
+// shape did again because a wave had given up a pool draw; (size_t)-1 = the shape never draws from a shared pool.
+TT_EXPORT size_t tt_score_topk_redo_flags_offset(int B, int64_t N, int d, int k)
+{
+    return paced_offset(B, N, d, k, true);
+}
+
+static size_t small_workspace_bytes(int B, int64_t N, int d, int k, bool bf16)
+{
+    if (B <= 0 || N < 0 || k <= 0)
+        return 0;
+    return make_plan(B, N, k, d, bf16).ws_bytes;
+}
+
+TT_EXPORT size_t tt_score_topk_workspace_bytes(int B, int64_t N, int d, int k)
+{
+    return small_workspace_bytes(B, N, d, k, false);
+}
+
+TT_EXPORT size_t tt_score_topk_bf16_workspace_bytes(int B, int64_t N, int d, int k)
+{
+    return small_workspace_bytes(B, N, d, k, true);
+}
+
+TT_EXPORT int tt_score_topk_partials_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
+                                         int64_t idx_offset, void *workspace, size_t workspace_bytes,
+                                         const float **part_val, const int64_t **part_idx, int *part_m,
+                                         void *const *prof_events, tt_stream_t stream)
+{
+    const ExactCall c{Q, B, d, D, false, N, k, idx_offset, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                      (hipStream_t)stream, "tt_score_topk_partials_f32", true};
+    Plan pl;
+    TT_RC_CHECK(exact_validate(c, MERGE_KMAX, &pl));
+    TT_RC_CHECK(score_partials(c, pl, ExactPass{k, nullptr, prof_events}));
+    if (part_val)
+        *part_val = (const float *)((const char *)workspace + pl.pval_off);
+    if (part_idx)
+        *part_idx = (const int64_t *)((const char *)workspace + pl.pidx_off);
+    if (part_m)
+        *part_m = pl.main.n_chunks * k;
+    return TT_OK;
+}
+
 int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
                            const int *run_if, hipStream_t st)
 {
-    return score_topk_pred(Q, B, d, D, false, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, run_if, st,
-                           "tt_score_topk_f32");
+    return exact_small(ExactCall{Q, B, d, D, false, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes, st,
+                                 "tt_score_topk_f32"}, run_if);
 }
 
 int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
                             float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
                             const int *run_if, hipStream_t st)
 {
-    return score_topk_pred(Q, B, d, D, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, run_if, st,
-                           "tt_score_topk_bf16");
+    return exact_small(ExactCall{Q, B, d, D, true, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes, st,
+                                 "tt_score_topk_bf16"}, run_if);
 }
 
 TT_EXPORT int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
@@ -1718,6 +1705,18 @@ TT_EXPORT int tt_topk_merge(const float *in_val, const int64_t *in_idx, int B, i
     return TT_OK;
 }
 
+int merge_shards_layout_ok(const ShardsCall &s, const float *out_val, const int64_t *out_idx)
+{
+    if ((int64_t)s.world * s.kp > INT_MAX)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: world*kp too large", s.who);
+    if (!s.gathered || !out_val || !out_idx || ((uintptr_t)s.gathered & 7) || (s.rank_stride & 7) || (s.idx_byte_offset & 7) ||
+        s.idx_byte_offset < (size_t)s.B * s.kp * sizeof(float) ||
+        s.rank_stride < s.idx_byte_offset + (size_t)s.B * s.kp * sizeof(int64_t))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: layout (stride %zu, idx offset %zu) does not hold [B,kp] f32 + i64, 8-byte aligned",
+                       s.who, s.rank_stride, s.idx_byte_offset);
+    return TT_OK;
+}
+
 TT_EXPORT int tt_topk_merge_shards(const void *gathered, int world, size_t rank_stride, size_t idx_byte_offset, int B,
                                    int kp, int k, float *out_val, int64_t *out_idx, tt_stream_t stream)
 {
@@ -1725,12 +1724,8 @@ TT_EXPORT int tt_topk_merge_shards(const void *gathered, int world, size_t rank_
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_topk_merge_shards: world=%d B=%d kp=%d k=%d", world, B, kp, k);
     if (k > MERGE_KMAX)
         return tt_fail(TT_ERR_UNSUPPORTED, "tt_topk_merge_shards: k=%d > %d", k, MERGE_KMAX);
-    if ((int64_t)world * kp > INT_MAX)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_topk_merge_shards: world*kp too large");
-    if (!gathered || !out_val || !out_idx || ((uintptr_t)gathered & 7) || (rank_stride & 7) || (idx_byte_offset & 7) ||
-        idx_byte_offset < (size_t)B * kp * sizeof(float) || rank_stride < idx_byte_offset + (size_t)B * kp * sizeof(int64_t))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_topk_merge_shards: layout (stride %zu, idx offset %zu) does not hold [B,kp] f32 + i64, 8-byte aligned",
-                       rank_stride, idx_byte_offset);
+    TT_RC_CHECK(merge_shards_layout_ok(ShardsCall{gathered, world, rank_stride, idx_byte_offset, B, kp, "tt_topk_merge_shards"},
+                                       out_val, out_idx));
     if (B == 0)
         return TT_OK;
     hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(MERGE_THREADS), 0, (hipStream_t)stream, (const float *)gathered,
@@ -1771,809 +1766,3 @@ TT_EXPORT int tt_score_rank_f32(const float *Q, int B, int d, const float *D, in
     return TT_OK;
 }
 
-// ===========================================================================
-// K4L: exact top-k for 64 < k <= TT_TOPK_LARGE_KMAX (DESIGN.md "Large k").
-//
-// Tier 0  the main pass above, unchanged, with per-(wave, query) lists of m = 64 (seeded with the k-th -- not the 64th --
-//         largest sample maximum); t_q = max(k-th largest entry of the union of the lists, seed).  The chunks are disjoint, so
-//         k distinct documents score >= t_q: t_q <= the exact k-th score.  A list is SATURATED when it holds m entries and its
-//         smallest is >= t_q (>=: a full list may have dropped a document that ties t_q).  No saturated list -> the union holds
-//         every document scoring >= t_q, and the answer is the union's top-k (lk_final_kernel).
-// Tier 1  a query with a saturated list is rescanned (lk_scan_kernel: the same ascending fp32 FMA chain, so the same bits):
-//         every document scoring >= t_q goes to a per-query buffer of LK_CAP entries; if they fit, its top-k is the answer.
-// Tier 2  otherwise the k-th (score, index) key is narrowed down by radix histograms of the 63-bit composite key
-//         (order key of the score << 31 | 2^31-1 - doc): each pass scans the corpus once and fixes 11 more bits; as soon as
-//         the documents at or above the current key prefix fit the buffer, one more scan collects them.  The composite key
-//         orders (score desc, index asc), so ties at the k-th score resolve to the lowest indices however many there are.
-// Every decision is taken on the device: the LK_ROUNDS (scan, decide) launches run for every call and skip the queries (and
-// the query tiles) with nothing to do.
-// ===========================================================================
-namespace {
-constexpr int LK_M = 64;              // list length of the main pass
-constexpr int LK_CAP = 4096;          // rescan buffer entries per query
-constexpr int LK_BINS = 2048;         // 11-bit digits of the composite key
-constexpr int LK_ROUNDS = 8;          // collect, up to 6 histogram passes (63 bits), collect
-constexpr int LK_SCAN_DOCS = 128;     // documents per scan tile
-constexpr int LK_SCAN_BLOCKS = 2048;  // scan grid (each block walks doc tiles with this stride)
-constexpr int LSEL_THREADS = 1024;    // one block per row: a few blocks (small B) must still stream a 131 072-entry union fast
-
-enum { LK_DONE = 0, LK_COLLECT = 1, LK_HIST = 2 };
-
-struct LkState {
-    unsigned long long lo;  // collect / count only documents whose composite key is >= lo
-    unsigned long long P;   // histogram passes: the k-th key lies in [P, P + 2^s)
-    long long above;        // documents with key >= lo above that range
-    int cnt;                // COLLECT: documents appended (may exceed LK_CAP)
-    int mode;
-    int s;
-    int pad;
-};
-
-__device__ __forceinline__ unsigned lk_key(float f)
-{
-    return order_key(f == 0.0f ? 0.0f : f); // -0 and +0 compare equal: one key
-}
-
-__device__ __forceinline__ unsigned long long lk_comp(float v, int n)
-{
-    return ((unsigned long long)lk_key(v) << 31) | (unsigned long long)(0x7fffffff - n);
-}
-
-// ---- row selection: the k best of a row's candidates, (score desc, index asc), sorted; tail (-inf, -1) -----------------
-// Radix select of the k-th score key over the valid entries (idx >= 0), then -- only when the k-th score's tie group is larger
-// than the places left -- a radix select of the index that closes it, then compaction into LDS and a bitonic sort.  Exact for
-// any tie group size: nothing but the k survivors is ever held in LDS.
-struct SegSource { // topk_merge_kernel's layout: candidate m of row b in segment m / seg_len
-    const float *val;
-    const int64_t *idx;
-    int M, seg_len;
-    size_t seg_stride;
-    __device__ int len(int) const { return M; }
-    __device__ void load(int b, int m, float &v, int64_t &i) const
-    {
-        const int sg = m / seg_len, wi = m - sg * seg_len;
-        v = ((const float *)((const char *)val + (size_t)sg * seg_stride))[(size_t)b * seg_len + wi];
-        i = ((const int64_t *)((const char *)idx + (size_t)sg * seg_stride))[(size_t)b * seg_len + wi];
-    }
-};
-
-struct SearchSource { // tier 0: the union of the partial lists [rows][M]; tiers 1, 2: the query's rescan buffer
-    const float *pval;
-    const int64_t *pidx;
-    int M;
-    const Cand *buf;
-    const LkState *st;
-    const int *tier;
-    int64_t idx_offset;
-    __device__ int len(int b) const { return tier[b] == 0 ? M : min(st[b].cnt, LK_CAP); }
-    __device__ void load(int b, int m, float &v, int64_t &i) const
-    {
-        if (tier[b] == 0) {
-            v = pval[(size_t)b * M + m];
-            i = pidx[(size_t)b * M + m];
-        } else {
-            const Cand c = buf[(size_t)b * LK_CAP + m];
-            v = c.v;
-            i = idx_offset + c.x;
-        }
-    }
-};
-
-// One wave (threads 0..63): pick the bin of 256 (4 per lane; high bins first when desc) in which the rank-th entry lies.
-// sel[0] = bin, sel[1] = entries in bins before it, sel[2] = its count, sel[3] = the row's total.
-__device__ __forceinline__ void lk_pick_bin(const int *hist, int rank, bool desc, int *sel)
-{
-    const int lane = threadIdx.x & 63;
-    int c[4], s = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int bin = desc ? 255 - (lane * 4 + i) : lane * 4 + i;
-        c[i] = hist[bin];
-        s += c[i];
-    }
-    int incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off);
-        if (lane >= off)
-            incl += y;
-    }
-    const int total = __shfl(incl, 63);
-    int before = incl - s;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (before < rank && before + c[i] >= rank) {
-            sel[0] = desc ? 255 - (lane * 4 + i) : lane * 4 + i;
-            sel[1] = before;
-            sel[2] = c[i];
-        }
-        before += c[i];
-    }
-    if (lane == 0)
-        sel[3] = total;
-}
-
-template <class S>
-__device__ void lk_select_row(const S &src, int b, int k, float *out_val, int64_t *out_idx)
-{
-    __shared__ int hist[256];
-    __shared__ int sel[4];
-    __shared__ int npos;
-    __shared__ float sv[TT_TOPK_LARGE_KMAX];
-    __shared__ int64_t si[TT_TOPK_LARGE_KMAX];
-    const int tid = threadIdx.x;
-    const int M = src.len(b);
-
-    // 1. the k-th score key (kv = min(k, valid entries))
-    unsigned prefix = 0u, mask = 0u;
-    int krem = k, kv = 0, ties = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        if (tid < 256)
-            hist[tid] = 0;
-        __syncthreads();
-        for (int m = tid; m < M; m += LSEL_THREADS) {
-            float v;
-            int64_t i;
-            src.load(b, m, v, i);
-            const unsigned key = lk_key(v);
-            if (i >= 0 && (key & mask) == prefix)
-                atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid < 64) {
-            if (pass == 0) { // the first pass sees every valid entry: fewer than k -> take them all
-                int s = 0;
-                for (int j = tid; j < 256; j += 64)
-                    s += hist[j];
-                for (int off = 32; off >= 1; off >>= 1)
-                    s += __shfl_xor(s, off);
-                if (tid == 0)
-                    npos = min(k, s);
-            }
-        }
-        __syncthreads();
-        if (pass == 0) {
-            kv = npos;
-            krem = kv;
-            if (kv == 0)
-                break; // block-uniform
-        }
-        if (tid < 64)
-            lk_pick_bin(hist, krem, true, sel);
-        __syncthreads();
-        prefix |= (unsigned)sel[0] << shift;
-        mask |= 0xffu << shift;
-        krem -= sel[1];
-        ties = sel[2];
-        __syncthreads();
-    }
-
-    // 2. krem of the `ties` entries with the k-th key are taken: the krem lowest indices (radix select on the index)
-    int64_t idx_cut = INT64_MAX; // take ties with idx < idx_cut, then copies of idx_cut up to kv
-    int need_cut = 0;
-    if (kv > 0 && ties > krem) {
-        unsigned long long ip = 0ull, im = 0ull;
-        int r = krem;
-        for (int pass = 0; pass < 8; ++pass) {
-            const int shift = 56 - 8 * pass;
-            if (tid < 256)
-                hist[tid] = 0;
-            __syncthreads();
-            for (int m = tid; m < M; m += LSEL_THREADS) {
-                float v;
-                int64_t i;
-                src.load(b, m, v, i);
-                if (i >= 0 && lk_key(v) == prefix && ((unsigned long long)i & im) == ip)
-                    atomicAdd(&hist[((unsigned long long)i >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid < 64)
-                lk_pick_bin(hist, r, false, sel);
-            __syncthreads();
-            ip |= (unsigned long long)sel[0] << shift;
-            im |= 0xffull << shift;
-            r -= sel[1];
-            __syncthreads();
-        }
-        idx_cut = (int64_t)ip;
-        need_cut = 1;
-    }
-
-    // 3. compaction: the strictly better entries first, then copies of the cut (identical pairs) up to kv
-    if (tid == 0)
-        npos = 0;
-    __syncthreads();
-    for (int phase = 0; phase <= need_cut && kv > 0; ++phase) {
-        for (int m = tid; m < M; m += LSEL_THREADS) {
-            float v;
-            int64_t i;
-            src.load(b, m, v, i);
-            if (i < 0)
-                continue;
-            const unsigned key = lk_key(v);
-            const bool take = phase == 0 ? (key > prefix || (key == prefix && i < idx_cut)) : (key == prefix && i == idx_cut);
-            if (take) {
-                const int slot = atomicAdd(&npos, 1);
-                if (slot < kv) {
-                    sv[slot] = v;
-                    si[slot] = i;
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    // 4. bitonic sort of the kv survivors (padding ranks last), then out
-    int P2 = 1;
-    while (P2 < kv)
-        P2 <<= 1;
-    for (int t = kv + tid; t < P2; t += LSEL_THREADS) {
-        sv[t] = -INFINITY;
-        si[t] = INT64_MAX;
-    }
-    __syncthreads();
-    for (int k2 = 2; k2 <= P2; k2 <<= 1) {
-        for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (int t = tid; t < P2; t += LSEL_THREADS) {
-                const int l = t ^ j2;
-                if (l > t) {
-                    const bool up = (t & k2) == 0;
-                    if (up == ranks_before(sv[l], si[l], sv[t], si[t])) {
-                        const float fv = sv[t];
-                        const int64_t fi = si[t];
-                        sv[t] = sv[l];
-                        si[t] = si[l];
-                        sv[l] = fv;
-                        si[l] = fi;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int t = tid; t < k; t += LSEL_THREADS) {
-        out_val[(size_t)b * k + t] = t < kv ? sv[t] : -INFINITY;
-        out_idx[(size_t)b * k + t] = t < kv ? si[t] : -1;
-    }
-}
-
-__global__ __launch_bounds__(LSEL_THREADS) void lk_merge_kernel(SegSource src, int k, float *out_val, int64_t *out_idx)
-{
-    lk_select_row(src, blockIdx.x, k, out_val, out_idx);
-}
-
-__global__ __launch_bounds__(LSEL_THREADS) void lk_final_kernel(SearchSource src, int k, float *out_val, int64_t *out_idx)
-{
-    lk_select_row(src, blockIdx.x, k, out_val, out_idx);
-}
-
-// flags[t] = 1 when a list of 32-query tile t carries the give-up marker (tt_score_topk_f32's redo, before t_q is taken)
-__global__ __launch_bounds__(256) void lk_marker_kernel(const int64_t *__restrict__ pidx, int B, int n_chunks, int *flags)
-{
-    const int q0 = blockIdx.x * 32;
-    bool bad = false;
-    for (int e = threadIdx.x; e < 32 * n_chunks; e += 256) {
-        const int q = q0 + e / n_chunks;
-        if (q < B && pidx[((size_t)q * n_chunks + e % n_chunks) * LK_M] >= (int64_t)TT_TOPK_INVALID_INDEX)
-            bad = true;
-    }
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0)
-        flags[blockIdx.x] = bad ? 1 : 0;
-}
-
-// Tier decision per query: t_q = max(k-th largest entry of the union (-inf when it has fewer than k entries), seed);
-// a saturated list -> rescan from t_q.  One block per query: a 4-pass radix select over the union, then the saturation test.
-__global__ __launch_bounds__(LSEL_THREADS) void lk_analyze_kernel(const float *__restrict__ pval, const int64_t *__restrict__ pidx,
-                                                                  int n_chunks, int k, const float *__restrict__ seed, LkState *st,
-                                                                  int *tier)
-{
-    __shared__ int hist[256];
-    __shared__ int sel[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int M = n_chunks * LK_M;
-    const float *v = pval + (size_t)b * M;
-    float t = -INFINITY;
-    if (M >= k) { // the k-th largest of all M entries, padding (-inf) included: kth_largest_kernel's value
-        unsigned prefix = 0u, mask = 0u;
-        int krem = k;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (tid < 256)
-                hist[tid] = 0;
-            __syncthreads();
-            for (int m = tid; m < M; m += LSEL_THREADS) {
-                const unsigned key = order_key(v[m]);
-                if ((key & mask) == prefix)
-                    atomicAdd(&hist[(key >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid < 64)
-                lk_pick_bin(hist, krem, true, sel);
-            __syncthreads();
-            prefix |= (unsigned)sel[0] << shift;
-            mask |= 0xffu << shift;
-            krem -= sel[1];
-            __syncthreads();
-        }
-        t = order_key_to_float(prefix);
-    }
-    if (seed)
-        t = fmaxf(t, seed[b]);
-    bool sat = false;
-    for (int c = tid; c < n_chunks; c += LSEL_THREADS) {
-        const size_t o = ((size_t)b * n_chunks + c) * LK_M;
-        if (pidx[o + LK_M - 1] < 0)
-            continue; // not full: it holds every document of its chunk above the seed
-        float mn = INFINITY;
-        for (int e = 0; e < LK_M; ++e)
-            mn = fminf(mn, pval[o + e]);
-        if (mn >= t)
-            sat = true;
-    }
-    sat = __syncthreads_or(sat);
-    if (tid == 0) {
-        LkState s;
-        s.lo = (unsigned long long)lk_key(t) << 31; // every document scoring >= t
-        s.P = 0ull;
-        s.above = 0;
-        s.cnt = 0;
-        s.mode = sat ? LK_COLLECT : LK_DONE;
-        s.s = 63;
-        s.pad = 0;
-        st[b] = s;
-        tier[b] = sat ? 1 : 0;
-    }
-}
-
-// One corpus scan for the queries in COLLECT or HIST mode: 32-query x 128-document tiles, fp32 FMA chains over the features
-// in ascending order (the bits of the main pass and of the oracle), thread = 4 queries x 4 documents.
-// MASKED: documents whose keep bit is clear are neither collected nor counted (keep: one word per 32 documents).
-template <bool BF, bool MASKED>
-__global__ __launch_bounds__(256) void lk_scan_kernel(const float *__restrict__ Q, const void *__restrict__ D, int B, int d, int N,
-                                                      LkState *st, Cand *buf, int *hist, const unsigned *__restrict__ keep)
-{
-    __shared__ __attribute__((aligned(16))) float qs[32][32];                // [feature][query]
-    __shared__ __attribute__((aligned(16))) float ds[32][LK_SCAN_DOCS + 4];  // [feature][document]
-    const int tid = threadIdx.x, qg = tid >> 5, dg = tid & 31;
-    const int n_qt = (B + 31) / 32, n_dt = (N + LK_SCAN_DOCS - 1) / LK_SCAN_DOCS;
-    for (int qt = 0; qt < n_qt; ++qt) {
-        const bool live = tid < 32 && qt * 32 + tid < B && st[qt * 32 + tid].mode != LK_DONE;
-        if (!__syncthreads_or(live))
-            continue; // block-uniform
-        int md[4], sh[4];
-        unsigned long long lo[4], P[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = qt * 32 + qg * 4 + i;
-            md[i] = LK_DONE;
-            lo[i] = P[i] = 0ull;
-            sh[i] = 0;
-            if (q < B) {
-                md[i] = st[q].mode;
-                lo[i] = st[q].lo;
-                P[i] = st[q].P;
-                sh[i] = st[q].s;
-            }
-        }
-        for (int dt = blockIdx.x; dt < n_dt; dt += gridDim.x) {
-            // documents of this tile: rem of them from row0 on (64-bit: N may come within 65 of INT_MAX)
-            const int64_t row0 = (int64_t)dt * LK_SCAN_DOCS;
-            const int rem = (int)min((int64_t)LK_SCAN_DOCS, (int64_t)N - row0);
-            const float *D32 = (const float *)D + row0 * d;
-            const unsigned short *D16 = (const unsigned short *)D + row0 * d;
-            float acc[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = 0.0f;
-            // the thread's four documents row0 + 4 dg + j share a keep word (row0 is a multiple of 128): their bits, from bit 0
-            unsigned kbits = 0xfu;
-            if (MASKED && dg * 4 < rem)
-                kbits = keep[(row0 + dg * 4) >> 5] >> ((dg * 4) & 31);
-            for (int f0 = 0; f0 < d; f0 += 32) {
-                __syncthreads();
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int e = tid + 256 * r, qi = e >> 5, fi = e & 31, q = qt * 32 + qi;
-                    qs[fi][qi] = q < B ? Q[(size_t)q * d + f0 + fi] : 0.0f;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int e = tid + 256 * r, di = e >> 5, fi = e & 31;
-                    float v = 0.0f;
-                    if (di < rem) {
-                        if (BF)
-                            v = __uint_as_float((unsigned)D16[di * d + f0 + fi] << 16);
-                        else
-                            v = D32[di * d + f0 + fi];
-                    }
-                    ds[fi][di] = v;
-                }
-                __syncthreads();
-#pragma unroll 8
-                for (int f = 0; f < 32; ++f) {
-                    const f32x4 a = *(const f32x4 *)&qs[f][qg * 4];
-                    const f32x4 c = *(const f32x4 *)&ds[f][dg * 4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            acc[i][j] = fmaf(a[i], c[j], acc[i][j]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (md[i] == LK_DONE)
-                    continue;
-                const int q = qt * 32 + qg * 4 + i;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (dg * 4 + j >= rem || (MASKED && !((kbits >> j) & 1u)))
-                        continue;
-                    const int n = (int)(row0 + dg * 4 + j); // < N
-
-                    const unsigned long long comp = lk_comp(acc[i][j], n);
-                    if (comp < lo[i])
-                        continue;
-                    if (md[i] == LK_COLLECT) {
-                        const int slot = atomicAdd(&st[q].cnt, 1);
-                        if (slot < LK_CAP) {
-                            Cand c;
-                            c.v = acc[i][j];
-                            c.x = n;
-                            buf[(size_t)q * LK_CAP + slot] = c;
-                        }
-                    } else if ((comp >> sh[i]) == (P[i] >> sh[i])) {
-                        const int w = min(11, sh[i]);
-                        atomicAdd(&hist[(size_t)q * LK_BINS + ((comp >> (sh[i] - w)) & ((1ull << w) - 1))], 1);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// After a scan: COLLECT that fit -> done; COLLECT that overflowed -> histogram passes; HIST -> fix the next digit, and collect
-// as soon as the documents at or above the prefix fit the buffer.
-__global__ __launch_bounds__(256) void lk_decide_kernel(LkState *st, int *tier, int *hist, int k)
-{
-    __shared__ int pre[256];
-    __shared__ int sel[3];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    LkState s = st[b];
-    int *h = hist + (size_t)b * LK_BINS;
-    if (s.mode == LK_DONE)
-        return;
-    bool zero = false;
-    if (s.mode == LK_COLLECT) {
-        if (s.cnt <= LK_CAP) {
-            s.mode = LK_DONE;
-        } else {
-            s.mode = LK_HIST;
-            s.P = 0ull;
-            s.s = 63;
-            s.above = 0;
-            zero = true;
-        }
-    } else {
-        const int w = min(11, s.s), nb = 1 << w;
-        const long long krem = (long long)k - s.above;
-        int c[8], sum = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { // thread t: bins nb-1-8t .. nb-8-8t (high bins first)
-            const int bin = nb - 1 - (tid * 8 + i);
-            c[i] = bin >= 0 ? h[bin] : 0;
-            sum += c[i];
-        }
-        pre[tid] = sum;
-        if (tid == 0) {
-            sel[0] = -1;
-            sel[1] = 0;
-            sel[2] = 0;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int run = 0;
-            for (int t = 0; t < 256; ++t) {
-                const int x = pre[t];
-                pre[t] = run;
-                run += x;
-            }
-        }
-        __syncthreads();
-        long long before = pre[tid];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (before < krem && before + c[i] >= krem) {
-                sel[0] = nb - 1 - (tid * 8 + i);
-                sel[1] = (int)before;
-                sel[2] = c[i];
-            }
-            before += c[i];
-        }
-        __syncthreads();
-        if (sel[0] < 0) { // (cannot happen: k documents score >= t_q) -- collect everything counted
-            s.mode = LK_COLLECT;
-            s.cnt = 0;
-        } else {
-            s.P |= (unsigned long long)sel[0] << (s.s - w);
-            s.s -= w;
-            s.above += sel[1];
-            if (s.above + sel[2] <= LK_CAP) {
-                s.mode = LK_COLLECT;
-                s.lo = s.P > s.lo ? s.P : s.lo;
-                s.cnt = 0;
-            } else {
-                zero = true;
-            }
-        }
-    }
-    if (zero)
-        for (int i = tid; i < LK_BINS; i += 256)
-            h[i] = 0;
-    __syncthreads();
-    if (tid == 0) {
-        if (s.mode == LK_HIST)
-            tier[b] = 2;
-        st[b] = s;
-    }
-}
-
-// Workspace of a large-k search: the k = 64 plan's, then the large-k state.
-struct LargePlan {
-    Plan pl;
-    bool small; // k <= 64: the call is tt_score_topk_f32 / _bf16's own
-    size_t tier_off, st_off, buf_off, hist_off, ws_bytes;
-};
-
-LargePlan make_large_plan(int B, int64_t N, int d, int k, bool bf16)
-{
-    LargePlan lp;
-    lp.small = k <= LK_M;
-    lp.pl = make_plan(B, N, lp.small ? k : LK_M, d, bf16);
-    TTWorkspace ws;
-    ws.off = tt_align_up(lp.pl.ws_bytes, 256);
-    const size_t rows = tt_align_up((size_t)B, 32);
-    lp.tier_off = ws.take(rows * sizeof(int));
-    if (lp.small) {
-        lp.st_off = lp.buf_off = lp.hist_off = 0;
-    } else {
-        lp.st_off = ws.take(rows * sizeof(LkState));
-        lp.buf_off = ws.take(rows * LK_CAP * sizeof(Cand));
-        lp.hist_off = ws.take(rows * LK_BINS * sizeof(int));
-    }
-    lp.ws_bytes = ws.off;
-    return lp;
-}
-
-int score_topk_large(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, int k, int64_t idx_offset,
-                     float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes, hipStream_t st, const char *who,
-                     const unsigned *keep = nullptr)
-{
-    if (B < 0 || N < 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
-    if (!score_dim_ok(d, bf16))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", who, d, score_dims(bf16));
-    if (k > TT_TOPK_LARGE_KMAX)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d", who, k, TT_TOPK_LARGE_KMAX);
-    if (N >= (int64_t)INT_MAX - 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; shard the corpus", who, (long long)N);
-    if ((uintptr_t)keep & 3)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", who);
-    if (B == 0)
-        return TT_OK;
-    if (!Q || !D || !out_val || !out_idx)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
-    const LargePlan lp = make_large_plan(B, N, d, k, bf16);
-    if (!workspace || workspace_bytes < lp.ws_bytes)
-        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, lp.ws_bytes);
-    if (((uintptr_t)D & 15) || ((uintptr_t)Q & 3) || ((uintptr_t)workspace & 255))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: D must be 16-byte and the workspace 256-byte aligned", who);
-    char *ws = (char *)workspace;
-    int *tier = (int *)(ws + lp.tier_off);
-    TT_RC_CHECK(tt_zero_async(tier, (size_t)B * sizeof(int), st));
-    if (lp.small)
-        return score_topk_pred(Q, B, d, D, bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr, st, who,
-                               keep);
-    if (N == 0) {
-        SegSource src{nullptr, nullptr, 0, 1, 0};
-        hipLaunchKernelGGL(lk_merge_kernel, dim3(B), dim3(LSEL_THREADS), 0, st, src, k, out_val, out_idx);
-        TT_LAUNCH_CHECK();
-        return TT_OK;
-    }
-    // tier 0: the k = 64 main pass, seeded with the k-th largest sample maximum
-    Plan pl;
-    TT_RC_CHECK(score_partials(Q, B, d, D, bf16, N, LK_M, idx_offset, workspace, workspace_bytes, st, &pl, who, nullptr,
-                               nullptr, k, keep));
-    const float *pval = (const float *)(ws + pl.pval_off);
-    const int64_t *pidx = (const int64_t *)(ws + pl.pidx_off);
-    const int M = pl.main.n_chunks * LK_M;
-    if (pl.paced && pl.main.tail_blocks > 0 && tt_score_pacing()) {
-        // the give-up redo of tt_score_topk_f32, on the lists themselves: a marker must never reach t_q
-        int *redo = (int *)(ws + pl.redo_off);
-        hipLaunchKernelGGL(lk_marker_kernel, dim3(pl.main.n_qtiles), dim3(256), 0, st, pidx, B, pl.main.n_chunks, redo);
-        TT_LAUNCH_CHECK();
-        TT_RC_CHECK(score_partials(Q, B, d, D, bf16, N, LK_M, idx_offset, workspace, workspace_bytes, st, &pl, who, redo, nullptr,
-                                   0, keep));
-    }
-    LkState *sts = (LkState *)(ws + lp.st_off);
-    Cand *buf = (Cand *)(ws + lp.buf_off);
-    int *hist = (int *)(ws + lp.hist_off);
-    hipLaunchKernelGGL(lk_analyze_kernel, dim3(B), dim3(LSEL_THREADS), 0, st, pval, pidx, pl.main.n_chunks, k,
-                       pl.prepass ? (const float *)(ws + pl.pre_val_off) : (const float *)nullptr, sts, tier);
-    TT_LAUNCH_CHECK();
-    TT_RC_CHECK(tt_zero_async(hist, (size_t)B * LK_BINS * sizeof(int), st));
-    // tiers 1 and 2: a fixed chain of (scan, decide) launches, each a no-op for the queries that are done
-    const int n_dt = (int)((N + LK_SCAN_DOCS - 1) / LK_SCAN_DOCS);
-    const int grid = n_dt < LK_SCAN_BLOCKS ? n_dt : LK_SCAN_BLOCKS;
-    for (int r = 0; r < LK_ROUNDS; ++r) {
-        if (keep && bf16)
-            hipLaunchKernelGGL((lk_scan_kernel<true, true>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
-        else if (keep)
-            hipLaunchKernelGGL((lk_scan_kernel<false, true>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
-        else if (bf16)
-            hipLaunchKernelGGL((lk_scan_kernel<true, false>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
-        else
-            hipLaunchKernelGGL((lk_scan_kernel<false, false>), dim3(grid), dim3(256), 0, st, Q, D, B, d, (int)N, sts, buf, hist, keep);
-        TT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(lk_decide_kernel, dim3(B), dim3(256), 0, st, sts, tier, hist, k);
-        TT_LAUNCH_CHECK();
-    }
-    SearchSource src{pval, pidx, M, buf, sts, tier, idx_offset};
-    hipLaunchKernelGGL(lk_final_kernel, dim3(B), dim3(LSEL_THREADS), 0, st, src, k, out_val, out_idx);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-} // namespace
-
-TT_EXPORT size_t tt_score_topk_large_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
-{
-    if (B <= 0 || N < 0 || k <= 0 || k > TT_TOPK_LARGE_KMAX)
-        return 0;
-    return make_large_plan(B, N, d, k, bf16 != 0).ws_bytes;
-}
-
-TT_EXPORT size_t tt_score_topk_large_tier_offset(int B, int64_t N, int d, int k, int bf16)
-{
-    if (B <= 0 || N < 0 || k <= 0 || k > TT_TOPK_LARGE_KMAX)
-        return (size_t)-1;
-    return make_large_plan(B, N, d, k, bf16 != 0).tier_off;
-}
-
-TT_EXPORT int tt_score_topk_large_f32(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                                      float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                                      tt_stream_t stream)
-{
-    return score_topk_large(Q, B, d, D, false, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
-                            (hipStream_t)stream, "tt_score_topk_large_f32");
-}
-
-TT_EXPORT int tt_score_topk_large_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, int64_t idx_offset,
-                                       float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                                       tt_stream_t stream)
-{
-    return score_topk_large(Q, B, d, D_bf16, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
-                            (hipStream_t)stream, "tt_score_topk_large_bf16");
-}
-
-// ---- K4m: masked exact search (DESIGN.md "K4m") ------------------------------------------------------------------------------
-// The large call with a keep-bitmask: the same plan, workspace and launches, on the MASKED instantiations.  keep == NULL is the
-// unmasked call itself.
-TT_EXPORT size_t tt_score_topk_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
-{
-    return tt_score_topk_large_workspace_bytes(B, N, d, k, bf16);
-}
-
-TT_EXPORT int tt_score_topk_masked_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep, int k,
-                                       int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
-                                       size_t workspace_bytes, tt_stream_t stream)
-{
-    return score_topk_large(Q, B, d, D, false, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
-                            (hipStream_t)stream, "tt_score_topk_masked_f32", keep);
-}
-
-TT_EXPORT int tt_score_topk_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep, int k,
-                                        int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
-                                        size_t workspace_bytes, tt_stream_t stream)
-{
-    return score_topk_large(Q, B, d, D_bf16, true, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
-                            (hipStream_t)stream, "tt_score_topk_masked_bf16", keep);
-}
-
-namespace {
-// keep word w = the ballots of keep_bool[32 w .. 32 w + 31] != 0 (a wave packs two words); bits at or beyond N are zero
-__global__ __launch_bounds__(256) void keep_pack_kernel(const uint8_t *__restrict__ keep_bool, int64_t N, unsigned *__restrict__ keep)
-{
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long b = __ballot(n < N && keep_bool[n] != 0);
-    const int lane = threadIdx.x & 63;
-    if ((lane == 0 || lane == 32) && n < N)
-        keep[n >> 5] = (unsigned)(b >> lane);
-}
-
-// bit ids[i] - idx_offset cleared (vector atomic AND); ids outside [idx_offset, idx_offset + N) are somebody else's rows
-__global__ __launch_bounds__(256) void keep_clear_kernel(unsigned *keep, int64_t N, const int64_t *__restrict__ ids, int64_t n_ids,
-                                                         int64_t idx_offset)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_ids)
-        return;
-    const int64_t id = ids[i];
-    if (id < idx_offset || id - idx_offset >= N) // (ordered so that the subtraction cannot overflow for any id >= idx_offset)
-        return;
-    const int64_t n = id - idx_offset;
-    atomicAnd(keep + (n >> 5), ~(1u << (n & 31)));
-}
-} // namespace
-
-TT_EXPORT int tt_keep_mask_pack(const uint8_t *keep_bool, int64_t N, uint32_t *keep, tt_stream_t stream)
-{
-    if (N < 0 || N > (int64_t)INT_MAX * 256)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_pack: N=%lld", (long long)N);
-    if (N == 0)
-        return TT_OK;
-    if (!keep_bool || !keep || ((uintptr_t)keep & 3))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_pack: null pointer, or keep not 4-byte aligned");
-    hipLaunchKernelGGL(keep_pack_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep_bool, N, keep);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-
-TT_EXPORT int tt_keep_mask_clear_ids(uint32_t *keep, int64_t N, const int64_t *ids, int64_t n_ids, int64_t idx_offset,
-                                     tt_stream_t stream)
-{
-    if (N < 0 || n_ids < 0 || n_ids > (int64_t)INT_MAX * 256)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_clear_ids: N=%lld n_ids=%lld", (long long)N, (long long)n_ids);
-    if (N == 0 || n_ids == 0)
-        return TT_OK;
-    if (!keep || !ids || ((uintptr_t)keep & 3))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_keep_mask_clear_ids: null pointer, or keep not 4-byte aligned");
-    hipLaunchKernelGGL(keep_clear_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep, N, ids,
-                       n_ids, idx_offset);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-
-TT_EXPORT int tt_topk_merge_large(const float *in_val, const int64_t *in_idx, int B, int M, int k, float *out_val,
-                                  int64_t *out_idx, tt_stream_t stream)
-{
-    if (B < 0 || M < 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_topk_merge_large: B=%d M=%d k=%d", B, M, k);
-    if (k > TT_TOPK_LARGE_KMAX)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_topk_merge_large: k=%d > %d", k, TT_TOPK_LARGE_KMAX);
-    if (k <= MERGE_KMAX)
-        return tt_topk_merge(in_val, in_idx, B, M, k, out_val, out_idx, stream);
-    if (B == 0)
-        return TT_OK;
-    SegSource src{in_val, in_idx, M, M > 0 ? M : 1, 0};
-    hipLaunchKernelGGL(lk_merge_kernel, dim3(B), dim3(LSEL_THREADS), 0, (hipStream_t)stream, src, k, out_val, out_idx);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-
-TT_EXPORT int tt_topk_merge_shards_large(const void *gathered, int world, size_t rank_stride, size_t idx_byte_offset, int B,
-                                         int kp, int k, float *out_val, int64_t *out_idx, tt_stream_t stream)
-{
-    if (B < 0 || world <= 0 || kp <= 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_topk_merge_shards_large: world=%d B=%d kp=%d k=%d", world, B, kp, k);
-    if (k > TT_TOPK_LARGE_KMAX)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_topk_merge_shards_large: k=%d > %d", k, TT_TOPK_LARGE_KMAX);
-    if (k <= MERGE_KMAX)
-        return tt_topk_merge_shards(gathered, world, rank_stride, idx_byte_offset, B, kp, k, out_val, out_idx, stream);
-    if ((int64_t)world * kp > INT_MAX)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_topk_merge_shards_large: world*kp too large");
-    if (!gathered || !out_val || !out_idx || ((uintptr_t)gathered & 7) || (rank_stride & 7) || (idx_byte_offset & 7) ||
-        idx_byte_offset < (size_t)B * kp * sizeof(float) || rank_stride < idx_byte_offset + (size_t)B * kp * sizeof(int64_t))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_topk_merge_shards_large: layout (stride %zu, idx offset %zu) does not hold [B,kp] f32 + i64, 8-byte aligned",
-                       rank_stride, idx_byte_offset);
-    if (B == 0)
-        return TT_OK;
-    SegSource src{(const float *)gathered, (const int64_t *)((const char *)gathered + idx_byte_offset), world * kp, kp,
-                  rank_stride};
-    hipLaunchKernelGGL(lk_merge_kernel, dim3(B), dim3(LSEL_THREADS), 0, (hipStream_t)stream, src, k, out_val, out_idx);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}

@@ -31,22 +31,12 @@
 //   screen_stream_kernel  B <= 64: every wave an independent streaming engine (32 or 64 queries) with a private 4-slab ring; bound by
 //                         HBM streaming of the fp16 copy (N * 512 B)
 // The accumulators start at minus the query's threshold, so "any candidate in this wave-tile?" is one integer max.
-#include "tt_common.h"
+#include "score_topk.h" // the predicated exact search (the fallback) and the threshold selections
 #include <cmath>
 
 #include <hip/hip_fp16.h>
 #include <limits.h>
 #include <math.h>
-
-int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                           const int *run_if, hipStream_t st);
-int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
-                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                            const int *run_if, hipStream_t st);
-
-int tt_kth_largest(const float *vals, int B, int M, int k, float *out, hipStream_t st);
-int tt_k_largest_list(const float *vals, int B, int M, int k, float *list, hipStream_t st);
 
 namespace {
 

@@ -36,7 +36,7 @@ static inline size_t tt_align_up(size_t x, size_t a) { return (x + a - 1) / a * 
 // Compute units of the current device; 256 (MI355X) when the query fails, so that workspace-size queries work without a device.
 int tt_device_cus();
 
-// Host-side planning pieces shared by the search planners (score_topk.hip, screen.hip); each planner keeps its own policy.
+// Host-side planning pieces shared by the search planners (score_topk.hip with score_topk_large.hip, screen.hip); each planner keeps its own policy.
 // n_tiles tiles in chunks of whole tiles: about `want` chunks, at most max_chunks, at least one (one empty chunk for no tiles).
 struct TTChunks {
     int tiles_per_chunk, n_chunks;
@@ -117,3 +117,21 @@ static inline int tt_ab_env(const char *name, int dflt)
 #endif
 
 #define TT_WAVE 64
+
+// The order-preserving integer image of a float (radix selections: score_topk.hip, score_topk_large.hip) and its inverse.
+static __device__ __forceinline__ unsigned order_key(float f)
+{
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+static __device__ __forceinline__ float order_key_to_float(unsigned key)
+{
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+// The order of every top-k list: score descending, index ascending.
+static __device__ __forceinline__ bool ranks_before(float sa, int64_t ia, float sb, int64_t ib)
+{
+    return sa > sb || (sa == sb && ia < ib);
+}

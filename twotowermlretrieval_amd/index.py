@@ -15,7 +15,7 @@ PyTorch/CPU fallback: inputs must be CUDA(ROCm) tensors.
 from __future__ import annotations
 
 from functools import lru_cache
-from typing import Callable, Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -54,12 +54,33 @@ def _docs_c(t: torch.Tensor) -> torch.Tensor:
 SMALL_KMAX = 64
 
 
-def _topk_fn(k: int, dtype: torch.dtype) -> str:
-    """The C entry point an exact search for k over a matrix of this dtype calls."""
-    bf = dtype == torch.bfloat16
+class _ExactRoute(NamedTuple):
+    """Where an exact search goes: the C entry point, its workspace query, and how the two take their arguments."""
+    fn: str
+    ws_fn: str
+    ws_takes_dtype: bool  # the workspace query ends in a bf16 flag (the large and masked ones; the k <= 64 ones come per dtype)
+    masked: bool          # the entry point takes the keep-bitmask, in front of k
+
+    def workspace_bytes(self, B: int, N: int, d: int, k: int, dtype: torch.dtype) -> int:
+        tail = (int(dtype == torch.bfloat16),) if self.ws_takes_dtype else ()
+        return getattr(_lib.lib(), self.ws_fn)(B, N, d, k, *tail)
+
+    def args(self, q_ptr: int, B: int, d: int, docs_ptr: int, N: int, keep_ptr: Optional[int], k: int, tail: tuple) -> tuple:
+        """The entry point's arguments; tail = (idx_offset, values, indices, workspace, workspace bytes, stream)."""
+        return (q_ptr, B, d, docs_ptr, N, *((keep_ptr,) if self.masked else ()), k, *tail)
+
+
+@lru_cache(maxsize=None)  # (eight routes)
+def _exact_route(dtype: torch.dtype, k: int, masked: bool) -> _ExactRoute:
+    """The one place that names the exact entry points.  A mask takes the masked call at any k; without one k <= 64 stays
+    on the calls it always used (the large entry point costs a launch and a larger workspace more)."""
+    t = "bf16" if dtype == torch.bfloat16 else "f32"
+    if masked:
+        return _ExactRoute(f"tt_score_topk_masked_{t}", "tt_score_topk_masked_workspace_bytes", True, True)
     if k > SMALL_KMAX:
-        return "tt_score_topk_large_bf16" if bf else "tt_score_topk_large_f32"
-    return "tt_score_topk_bf16" if bf else "tt_score_topk_f32"
+        return _ExactRoute(f"tt_score_topk_large_{t}", "tt_score_topk_large_workspace_bytes", True, False)
+    return _ExactRoute(f"tt_score_topk_{t}", "tt_score_topk_bf16_workspace_bytes" if t == "bf16" else "tt_score_topk_workspace_bytes",
+                       False, False)
 
 
 def _merge_fn(k: int, kp: int = 0, shards: bool = False) -> str:
@@ -75,15 +96,6 @@ def _screened_fn(phase: str, bf16: bool) -> str:
     """The C entry point of one phase of a screened search: "whole", or "seed_list" then "seeded" (ShardedIndex's union seed)."""
     infix = {"whole": "", "seed_list": "seed_list_", "seeded": "seeded_"}[phase]
     return f"tt_score_topk_screened_{infix}{'bf16' if bf16 else 'f32'}"
-
-
-def _topk_workspace_bytes(B: int, N: int, d: int, k: int, dtype: torch.dtype) -> int:
-    L = _lib.lib()
-    if k > SMALL_KMAX:
-        return L.tt_score_topk_large_workspace_bytes(B, N, d, k, int(dtype == torch.bfloat16))
-    if dtype == torch.bfloat16:
-        return L.tt_score_topk_bf16_workspace_bytes(B, N, d, k)
-    return L.tt_score_topk_workspace_bytes(B, N, d, k)
 
 
 def _out_pair(B: int, k: int, device, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -176,19 +188,13 @@ def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
         keep = _check_keep(keep, N, docs.device)
     vals, idx = _out_pair(B, k, q.device)
     with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
-        L = _lib.lib()
-        bf = docs.dtype == torch.bfloat16
-        need = (_topk_workspace_bytes(B, N, d, k, docs.dtype) if keep is None
-                else L.tt_score_topk_masked_workspace_bytes(B, N, d, k, int(bf)))
+        route = _exact_route(docs.dtype, k, keep is not None)
+        need = route.workspace_bytes(B, N, d, k, docs.dtype)
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        if keep is None:
-            _lib.check(getattr(L, _topk_fn(k, docs.dtype))(q.data_ptr(), B, d, docs.data_ptr(), N, k, idx_offset, vals.data_ptr(),
-                                                           idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q)))
-        else:
-            fn = L.tt_score_topk_masked_bf16 if bf else L.tt_score_topk_masked_f32
-            _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, keep.data_ptr(), k, idx_offset, vals.data_ptr(), idx.data_ptr(),
-                          workspace.data_ptr(), workspace.numel(), _stream(q)))
+        tail = (idx_offset, vals.data_ptr(), idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(q))
+        _lib.check(getattr(_lib.lib(), route.fn)(*route.args(q.data_ptr(), B, d, docs.data_ptr(), N,
+                                                             None if keep is None else keep.data_ptr(), k, tail)))
     return vals, idx
 
 
