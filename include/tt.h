@@ -271,6 +271,57 @@ int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, const float 
                                       void *const *prof_events /*host, nullable*/, tt_stream_t stream);
 
 /*
+ * Masked screened search: the screened calls above under a keep-bitmask, so that deletions and filtered search keep the fast
+ * path.  Replaces  scores = torch.matmul(q, D.t()) ; scores[:, ~keep] = -inf ; torch.topk(scores, k)  (the masked form of
+ * backend/evaluators.py:185-186) like tt_score_topk_masked_f32, at the screened search's cost.  Each call takes the arguments
+ * of its unmasked namesake plus `keep` behind N, in tt_score_topk_masked_f32's format: device memory, ceil(N/32) words,
+ * 4-byte aligned (a misaligned keep: TT_ERR_BAD_SHAPE), document n of THIS call's rows kept iff bit n & 31 of word n >> 5 is
+ * set, bits at or beyond N ignored.
+ * keep == NULL IS the unmasked screened call: same launches, same bits, same flags, same statistics.  Otherwise the result
+ * is bit for bit that of tt_score_topk_masked_f32 / _bf16: the exact top-k of the kept documents, (score desc, index asc),
+ * tail (-inf, -1) when fewer than k are kept, down to none.  fallback_flag and the statistics
+ * (tt_score_topk_screened_stats_offset, which depends on (B, N, k) only) mean what they mean for the unmasked calls; a flagged
+ * 32-query tile is recomputed by the MASKED exact kernel, predicated on the flag on the device.  Asynchronous, capturable, no
+ * host synchronisation; d = 256, k <= 64 and dmax_norm < 6e4 as for the unmasked calls.
+ * Why it is exact: the screen's guarantee -- a document can be in the exact top-k only if s16 >= A_k - 2 eps_q, A_k the k-th
+ * largest approximate score over ANY subset of the corpus -- holds pair by pair, so applied to the kept documents it needs
+ * every A_k to be formed from kept documents only.  A masked document's accumulators are set to -inf before either epilogue
+ * of the screen kernels looks at them (the mechanism that drops rows at or beyond N), so the sample maxima, a workgroup's
+ * running k-th and the finish kernel's pooled k-th all see kept documents alone (csrc/screen.hip header, DESIGN.md "Masked
+ * screened top-k").  A masked document is still streamed and multiplied: a selective mask pays the full scan.
+ * tt_score_topk_screened_masked_workspace_bytes: the workspace of all three masked calls (bf16 != 0: the _bf16 ones).
+ * Sharded two-call form: in a masked job the seed lists hold kept documents' maxima only -- distinct kept documents of
+ * disjoint shards -- so tt_seed_union_f32's union seed is a valid global bound as it is.
+ */
+size_t tt_score_topk_screened_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_screened_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
+                                      const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset, float *out_val,
+                                      int64_t *out_idx, int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
+                                      void *const *prof_events /*host, nullable*/, tt_stream_t stream);
+int tt_score_topk_screened_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep,
+                                       int k, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                       int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
+                                       void *const *prof_events /*host, nullable*/, tt_stream_t stream);
+int tt_score_topk_screened_seed_list_masked_f32(const float *Q, int B, int d, const void *D16, int64_t N, const uint32_t *keep,
+                                                int k, int k_seed, float dmax_norm, int32_t *fallback_flag,
+                                                float *seed_list /*[B][k_seed] out*/, void *workspace, size_t workspace_bytes,
+                                                tt_stream_t stream);
+int tt_score_topk_screened_seed_list_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
+                                                 const uint32_t *keep, int k, int k_seed, float dmax_norm,
+                                                 int32_t *fallback_flag, float *seed_list /*[B][k_seed] out*/, void *workspace,
+                                                 size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_screened_seeded_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
+                                             const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset, float *out_val,
+                                             int64_t *out_idx, int32_t *fallback_flag, const float *seed /*[B]*/,
+                                             void *workspace, size_t workspace_bytes,
+                                             void *const *prof_events /*host, nullable*/, tt_stream_t stream);
+int tt_score_topk_screened_seeded_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
+                                              const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset, float *out_val,
+                                              int64_t *out_idx, int32_t *fallback_flag, const float *seed /*[B]*/,
+                                              void *workspace, size_t workspace_bytes,
+                                              void *const *prof_events /*host, nullable*/, tt_stream_t stream);
+
+/*
  * Merge of partial top-k lists (per tile, per shard after the RCCL all-gather:
  * SURVEY 8e) into the global top-k: in_val/in_idx [B,M] candidates in any
  * order, idx < 0 = padding; out [B,k], (score desc, index asc), tail (-inf,-1).

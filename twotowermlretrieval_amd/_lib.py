@@ -65,6 +65,13 @@ SIGNATURES = {
     "tt_seed_union_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "tt_score_topk_screened_seeded_f32": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tt_score_topk_screened_f32": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tt_score_topk_screened_masked_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "tt_score_topk_screened_masked_f32": (_i, [_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tt_score_topk_screened_masked_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tt_score_topk_screened_seed_list_masked_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_screened_seed_list_masked_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_screened_seeded_masked_f32": (_i, [_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _f, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tt_score_topk_screened_seeded_masked_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _f, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tt_event_create": (_i, [_vp]),
     "tt_event_destroy": (_i, [_vp]),
     "tt_event_elapsed_ms": (_i, [_vp, _vp, _vp]),

@@ -98,6 +98,11 @@ int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t
 int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
                             float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
                             const int *run_if, hipStream_t st);
+// The same under a keep-bitmask (fp32 or bf16 rows): the masked screened path's fallback.  The workspace is the unmasked
+// k <= 64 search's (tt_score_topk_workspace_bytes / _bf16_workspace_bytes); keep == nullptr is the unmasked search.
+int tt_score_topk_masked_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, const unsigned *keep, int k,
+                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                              const int *run_if, hipStream_t st);
 
 // k-th largest of each row of vals [B][M] -> out [B] (threshold seeding of both search paths)
 int tt_kth_largest(const float *vals, int B, int M, int k, float *out, hipStream_t st);

@@ -29,6 +29,7 @@
 //    lists go to the workspace; topk_merge_kernel reduces them (also used for the
 //    sample-pass maxima and for the cross-shard merge after the RCCL all-gather).
 #include "score_topk.h"
+#include "keep_word.h"
 
 #include <limits.h>
 #include <math.h>
@@ -95,24 +96,9 @@ struct ScoreParams {
                           // document n of D may be returned); nullptr in every other launch
 };
 
-// The keep word of one tile (MASKED).  It is wave-uniform, so it travels as a scalar load on the lgkmcnt side: the tile loop's
-// LDS-DMA ring lives on counted vmcnt waits, and a compiler-visible global load in the loop would make hipcc drain it
-// (vmcnt(0)) on every tile.  Issued in front of the tile's last slab of MFMAs, waited for in front of the epilogue: the
-// latency sits under that slab's multiply chain.  The wait names the destination, so no consumer is scheduled above it, and
-// the tile's accumulators, so that hipcc cannot hoist it above the MFMAs (register-only instructions, which "memory" does not
-// order) back to the load.
-// (first: the slab's first A operand(s), named so that the slab's MFMA chain stays below the load)
-template <class A>
-__device__ __forceinline__ void keep_word_issue(const unsigned *word, unsigned &kw, A &first)
-{
-    asm volatile("s_load_dword %[kw], %[word], 0x0" : [kw] "=s"(kw), "+v"(first) : [word] "s"(word) : "memory");
-}
-
-template <class Acc>
-__device__ __forceinline__ void keep_word_wait(unsigned &kw, Acc &acc)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(kw), "+v"(acc) : : "memory");
-}
+// The keep word of one tile (MASKED): keep_word_issue / keep_word_wait (keep_word.h, shared with screen.hip).  Here the load is
+// issued in front of the tile's last slab of MFMAs, naming the slab's first A operand(s), and waited for in front of the
+// epilogue: the latency sits under that slab's multiply chain.
 
 __device__ __forceinline__ int xcd_remap(int b, int nblk)
 {
@@ -1617,6 +1603,15 @@ int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t
 {
     return exact_small(ExactCall{Q, B, d, D, true, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes, st,
                                  "tt_score_topk_bf16"}, run_if);
+}
+
+// The masked k <= 64 search, predicated: the masked screened search's fallback (the K4m instantiations under run_if)
+int tt_score_topk_masked_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, const unsigned *keep, int k,
+                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                              const int *run_if, hipStream_t st)
+{
+    return exact_small(ExactCall{Q, B, d, D, bf16, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes, st,
+                                 bf16 ? "tt_score_topk_masked_bf16" : "tt_score_topk_masked_f32"}, run_if);
 }
 
 TT_EXPORT int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,

@@ -31,7 +31,22 @@
 //   screen_stream_kernel  B <= 64: every wave an independent streaming engine (32 or 64 queries) with a private 4-slab ring; bound by
 //                         HBM streaming of the fp16 copy (N * 512 B)
 // The accumulators start at minus the query's threshold, so "any candidate in this wave-tile?" is one integer max.
+//
+// Under a keep-bitmask (MASKED instantiations; tt_score_topk_screened_masked_f32 and its kin).  Let K be the kept documents.
+// A document's s16 and its exact score s depend on no other document, and |s16 - s| <= eps_q holds pair by pair; the
+// guarantee of step 1 never uses tile or chunk boundaries.  Applied to the corpus D[K] it reads: a kept document can be in
+// the exact top-k of K only if s16 >= A_k^K - 2 eps_q, A_k^K the k-th largest approximate score over any subset of K.  So it
+// is enough that every quantity used as an A_k is formed from kept documents only.  There are three: (1) the sample maxima
+// -- the seed is the k-th largest tile maximum, "k distinct kept documents reach this", and a tile with nothing kept
+// contributes -inf; (2) the running k-th of a workgroup's candidate buffer (screen_compact); (3) the pooled A_k of
+// screen_finish_kernel.  (2) and (3) see only what the append pass stored, so forcing a masked document's accumulators to
+// -inf before either epilogue looks at them gives all three, with the finish kernel unchanged: the mechanism of the
+// `partial` branch (rows at or beyond N), taken by every tile whose keep word is not all ones.  Masking the append pass
+// alone would not do: a seed vouched for by documents that cannot be returned may exceed every kept score, and the main
+// pass would then drop everything (tests/test_masked_screened_gpu.py, the plantings of test_threshold_passes_see_the_mask).
+// The predicated fallback is the MASKED exact search.  A masked document is still streamed and multiplied.
 #include "score_topk.h" // the predicated exact search (the fallback) and the threshold selections
+#include "keep_word.h"  // the scalar load of a tile's keep word and its wait
 #include <cmath>
 
 #include <hip/hip_fp16.h>
@@ -132,6 +147,9 @@ struct ScreenParams {
     // test-only (tt_debug_screen_s16): MAXONLY pass whose accumulators start at -dbg_thr[query] like the main
     // pass's, so the raw value t = fl(sum - thr) the filter compares with +0 can be observed; null in the product
     const float *dbg_thr;
+    // MASKED instantiations: keep-bitmask, one word per 32-document tile (bit n & 31 of word n >> 5 set -> document n of D16
+    // may be returned; the sample pass reads the first words of the same mask); nullptr in every other launch
+    const unsigned *keep;
 };
 
 // store (v, x) at wave-uniform base + per-lane 32-bit byte offset (SGPR-base addressing: no 64-bit VALU math)
@@ -273,7 +291,11 @@ __global__ __launch_bounds__(128) void q_image_kernel(const float *__restrict__ 
 // workgroup, round 4) for the batches a 512-query group would leave a quarter or more empty: B = 257 .. 384 (one group) and
 // 513 .. 768 (two groups of 384 instead of a full one and a nearly empty one -- a group costs a pass whatever it holds: B = 513
 // took 3.6 ms where 512 took 2.1, profiles/r04_p_batch_sweep.log).
-template <bool MAXONLY, int NSET, bool BF = false>
+// MASKED: p.keep decides which documents may be returned.  A masked document is multiplied like any other and dropped in the
+// epilogue (accumulators -> -inf, what `partial` does to the rows at or beyond N), in the main pass and in the sample pass
+// alike; a tile whose word is 0 skips the append pass (every accumulator is -inf).  The word is wave-uniform and read by keep_word_issue under the
+// tile's MFMAs -- never a compiler-visible global access in the tile loop, which would drain the DMA ring.
+template <bool MAXONLY, int NSET, bool BF = false, bool MASKED = false>
 __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char ring[]; // [SRING][STILE_BYTES]
@@ -398,16 +420,28 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
         const bool late = TT_SCREEN_STAGGER && w >= 4;
         bool pending = false;
         int ptile = 0;
-        auto epilogue = [&](int tile) {
+        unsigned pkw = 0xffffffffu; // MASKED: the deferred tile's keep word travels with its accumulators
+        // kw: the tile's keep word (MASKED; landed: keep_word_wait ran behind the tile's MFMAs)
+        auto epilogue = [&](int tile, unsigned kw) {
                 const int tile_base = tile * 32;
             const bool partial = tile_base + 32 > p.N;
+            // MASKED: a word that is not all ones makes the tile partial in the same sense; bit 16u + r of kwg = the keep bit of
+            // the lane's document (u, r) = row 16u + 4g + r (bits at or beyond N: the doc < N test stays)
+            const bool holes = MASKED && kw != 0xffffffffu;
+            const unsigned kwg = MASKED ? kw >> (4 * g) : 0xffffffffu;
+            auto dropped = [&](int u, int r) {
+                return tile_base + 16 * u + 4 * g + r >= p.N || (MASKED && ((kwg >> (16 * u + r)) & 1u) == 0u);
+            };
             if (!MAXONLY) {
-                if (partial) { // rows past the corpus never pass: -inf has its sign bit set
+                // rows past the corpus (and masked documents) never pass: -inf has its sign bit set.  (A word of 0 leaves
+                // nothing but -inf, so the gate below skips the append pass; a branch of its own around the epilogue cost
+                // screen_kernel<., 4> -- at the 256-VGPR limit -- a spilled register)
+                if (partial || holes) {
 #pragma unroll
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (tile_base + 16 * u + 4 * g + r >= p.N) {
+                            if (dropped(u, r)) {
 #pragma unroll
                                 for (int c = 0; c < NSET; ++c)
                                     acc[u][c][r] = -INFINITY;
@@ -462,10 +496,11 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
 #pragma unroll
                 for (int c = 0; c < NSET; ++c) { // one maximum per (tile, query): the k-th largest of them seeds the thresholds
                     float m = -INFINITY;
-                    if (!partial) {
+                    if (!partial && !holes) {
                         // signed-integer max of the raw bits = the float max when any value is >= 0, else the
                         // smallest one: still the score of a real document of this tile, which is all the
-                        // threshold argument needs (v_max3_i32: no NaN canonicalisation, 4 instructions)
+                        // threshold argument needs (v_max3_i32: no NaN canonicalisation, 4 instructions).
+                        // (MASKED: valid for an all-ones word only -- "a real document" has to be a kept one)
                         int mi = INT_MIN;
 #pragma unroll
                         for (int u = 0; u < 2; ++u)
@@ -478,7 +513,7 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                         for (int u = 0; u < 2; ++u)
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
-                                m = fmaxf(m, tile_base + 16 * u + 4 * g + r < p.N ? acc[u][c][r] : -INFINITY);
+                                m = fmaxf(m, !dropped(u, r) ? acc[u][c][r] : -INFINITY);
                     }
                     m = fmaxf(m, __shfl_xor(m, 16));
                     m = fmaxf(m, __shfl_xor(m, 32));
@@ -524,7 +559,7 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
             }
             if (wave_live) {
                 if (late && pending)
-                    epilogue(ptile);
+                    epilogue(ptile, pkw);
                 // acc[u][c][r] = s16(doc tile*32 + 16u + 4g + r, query qbase + 16c + n)
                 // (main pass: minus the query's threshold, see negthr)
                 const char *buf = ring + stage * STILE_BYTES + rd_base;
@@ -538,10 +573,17 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                 };
                 a_read(0);
                 a_read(1);
+                unsigned kw = 0xffffffffu; // the tile's keep word (MASKED)
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     if (s + 2 < 8)
                         a_read(s + 2);
+                    // (MASKED: the word's load goes out in front of the tile's first MFMAs and is waited for behind its last,
+                    //  so the whole multiply block covers it; tile is wave-uniform -- a pool draw arrives through LDS, hence
+                    //  the readfirstlane -- and no LDS read of this tile is issued after k-step 5, so the counted lgkmcnt waits
+                    //  hipcc puts in front of the MFMAs only get stricter by this one operation until it has landed)
+                    if (MASKED && s == 0)
+                        keep_word_issue(p.keep + __builtin_amdgcn_readfirstlane(tile), kw, a0[0]);
                     if (s == 2)
                         dma_piece(0, fill_stage);
                     if (s == 6)
@@ -556,17 +598,20 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                if (MASKED)
+                    keep_word_wait(kw, acc[1][NSET - 1]); // (the block's last MFMA writes this one)
                 if (late) { // this tile's selection runs after the next barrier, beside the other half's MFMAs
                     pending = true;
                     ptile = tile;
+                    pkw = kw;
                 } else {
-                    epilogue(tile);
+                    epilogue(tile, kw);
                 }
             }
             stage = (stage + 1) % SRING;
         }
         if (wave_live && late && pending)
-            epilogue(ptile);
+            epilogue(ptile, pkw);
     }
     if (MAXONLY || p.tail_blocks == 0)
         break;
@@ -626,7 +671,9 @@ constexpr int TSTREAM_AUX = 2;
 
 // NQS = 16-query sets per wave: 2 (B <= 32), or 4 (33 <= B <= 64: ONE pass of the stream for 64 queries instead of the
 // shared-tile form's 1.03 ms; twice the MFMAs per tile, still a fifth of what the stream allows)
-template <bool MAXONLY, int NQS = 2, bool BF = false>
+// MASKED: as in screen_kernel; the word's load goes out in front of the tile's last slab of MFMAs, behind that slab's
+// lgkmcnt(0) wait (the placement of the exact kernel's, score_topk.hip), and is waited for in front of the epilogue.
+template <bool MAXONLY, int NQS = 2, bool BF = false, bool MASKED = false>
 __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams p)
 {
     constexpr int QPT = 16 * NQS; // queries per task
@@ -731,6 +778,7 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
         const int rsw = n & 7;
         for (int tile = t0; tile < t1; ++tile) {
             f32x4 acc[2][NQS]; // acc[u][c][r] = s16(doc tile*32 + 16u + 4g + r, query qbase + 16c + n) - thr
+            unsigned kw = 0xffffffffu; // the tile's keep word (MASKED)
 #pragma unroll
             for (int kq = 0; kq < 4; ++kq) {
                 // slab (tile,kq) has landed once at most TSTAGE-2 younger slabs are pending (candidate stores
@@ -749,6 +797,10 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
                         a[u][s2] = *(const h8 *)(buf + u * 2048 + (((4 * s2 + g) ^ rsw) << 4));
                 // the ring slot consumed one step ago is free once its reads have returned
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                // (MASKED: right behind the asm wait above, which already ends a scheduling region; no LDS read of this tile
+                //  follows, so nothing else waits on lgkmcnt until keep_word_wait)
+                if (MASKED && kq == 3)
+                    keep_word_issue(p.keep + tile, kw, a[0][0]);
                 dma_issue((stage + TSTAGE - 1) % TSTAGE);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2)
@@ -763,13 +815,23 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
             }
             const int tile_base = tile * 32;
             const bool partial = tile_base + 32 > p.N;
+            // MASKED: see screen_kernel's epilogue
+            if (MASKED)
+                keep_word_wait(kw, acc[1][NQS - 1]); // (the slab's last MFMA writes this one)
+            const bool holes = MASKED && kw != 0xffffffffu;
+            const unsigned kwg = MASKED ? kw >> (4 * g) : 0xffffffffu;
+            auto dropped = [&](int u, int r) {
+                return tile_base + 16 * u + 4 * g + r >= p.N || (MASKED && ((kwg >> (16 * u + r)) & 1u) == 0u);
+            };
             if (!MAXONLY) {
-                if (partial) {
+                if (MASKED && kw == 0u)
+                    continue; // nothing kept: no candidate can come from this tile
+                if (partial || holes) {
 #pragma unroll
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (tile_base + 16 * u + 4 * g + r >= p.N) {
+                            if (dropped(u, r)) {
 #pragma unroll
                                 for (int c = 0; c < NQS; ++c)
                                     acc[u][c][r] = -INFINITY;
@@ -813,7 +875,7 @@ __global__ __launch_bounds__(TW * 64, 2) void screen_stream_kernel(ScreenParams 
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            m = fmaxf(m, (!partial || tile_base + 16 * u + 4 * g + r < p.N) ? acc[u][c][r] : -INFINITY);
+                            m = fmaxf(m, ((!partial && !holes) || !dropped(u, r)) ? acc[u][c][r] : -INFINITY);
                     m = fmaxf(m, __shfl_xor(m, 16));
                     m = fmaxf(m, __shfl_xor(m, 32));
                     const int qrow = qbase + 16 * c + n;
@@ -1292,27 +1354,34 @@ SPlan make_splan(int B, int64_t N, int k)
 
 // The screen kernel of one form: streaming (q_per_block 32 or 64: 2 or 4 query sets per wave) or shared-tile (nset 16-query
 // sets per wave, 1..4).  MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).
-// BF: the corpus is bf16 rows, converted in LDS (bf16_to_f16_lds).
-template <bool MAXONLY, bool BF>
+// BF: the corpus is bf16 rows, converted in LDS (bf16_to_f16_lds).  MASKED: under p.keep.
+template <bool MAXONLY, bool BF, bool MASKED>
 const void *screen_fn(bool stream, int q_per_block, int nset)
 {
     if (stream)
-        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4, BF>
-                                 : (const void *)screen_stream_kernel<MAXONLY, 2, BF>;
+        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4, BF, MASKED>
+                                 : (const void *)screen_stream_kernel<MAXONLY, 2, BF, MASKED>;
     switch (nset) {
-    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF>;
-    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF>;
-    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF>;
-    default: return (const void *)screen_kernel<MAXONLY, 1, BF>;
+    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF, MASKED>;
+    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF, MASKED>;
+    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF, MASKED>;
+    default: return (const void *)screen_kernel<MAXONLY, 1, BF, MASKED>;
     }
 }
 
-// One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
-int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st,
-                  bool bf16 = false)
+template <bool MAXONLY, bool BF>
+const void *screen_fn(bool stream, int q_per_block, int nset, bool masked)
 {
-    const void *fn = maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset) : screen_fn<true, false>(stream, q_per_block, nset))
-                             : (bf16 ? screen_fn<false, true>(stream, q_per_block, nset) : screen_fn<false, false>(stream, q_per_block, nset));
+    return masked ? screen_fn<MAXONLY, BF, true>(stream, q_per_block, nset) : screen_fn<MAXONLY, BF, false>(stream, q_per_block, nset);
+}
+
+// One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
+// masked: the MASKED instantiation (p.keep is set); otherwise p.keep is not read.
+int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st,
+                  bool bf16 = false, bool masked = false)
+{
+    const void *fn = maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset, masked) : screen_fn<true, false>(stream, q_per_block, nset, masked))
+                             : (bf16 ? screen_fn<false, true>(stream, q_per_block, nset, masked) : screen_fn<false, false>(stream, q_per_block, nset, masked));
     const size_t lds = stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
     const int blocks = stream ? (n_tasks + TW - 1) / TW : n_tasks;
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1396,10 +1465,12 @@ enum class Phase {
 };
 
 // bf16: D32 and D16 are both the bf16 corpus (the screen converts it in LDS, the finish kernel and the fallback widen it).
+// keep: the keep-bitmask of the masked entry points (nullptr: the unmasked search, launch for launch): the sample pass and the
+// main pass run their MASKED instantiations, the finish kernel sees kept documents only, the fallback is the masked exact search.
 int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, const void *D32, const void *D16, int64_t N, int k,
                   int k_seed, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
                   float *seed, void *workspace, size_t workspace_bytes, void *const *prof_events, hipStream_t st,
-                  bool bf16 = false)
+                  bool bf16 = false, const unsigned *keep = nullptr)
 {
     if (B <= 0 || N <= 0 || k <= 0)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
@@ -1417,6 +1488,8 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
     if (seed_only && (k_seed < 1 || k_seed > k))
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: k_seed=%d outside [1, k=%d]", who, k_seed, k);
+    if ((uintptr_t)keep & 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", who);
     const SPlan pl = make_splan(B, N, k);
     const size_t need = pl.ws_bytes + (bf16 ? tt_score_topk_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_workspace_bytes(B, N, d, k));
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255) || (bf16 && ((uintptr_t)D16 & 15)))
@@ -1452,6 +1525,8 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
     sp.qnorm = (const float *)(ws + pl.qnorm_off);
     sp.dbg_thr = nullptr;
+    sp.keep = keep;
+    const bool masked = keep != nullptr;
     if (caller_seed) {
         sp.thr0 = seed;
         sp.thr0_stride = 1;
@@ -1469,7 +1544,8 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
             ss.static_tiles = pl.s_tiles;
             ss.tail_blocks = 0;
             ss.max_val = (float *)(ws + pl.smax_val_off);
-            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st, bf16));
+            // (masked: the sample is the first s_docs rows, its words the first s_tiles of the mask)
+            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st, bf16, masked));
             if (phase == Phase::SeedList)
                 TT_RC_CHECK(tt_k_largest_list(ss.max_val, B, pl.s_tiles, k_seed, seed, st));
             else
@@ -1486,7 +1562,7 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
         return TT_OK;
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st, bf16));
+    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st, bf16, masked));
     if (prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
 
@@ -1510,6 +1586,9 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     hipLaunchKernelGGL(screen_finish_kernel, dim3(B), dim3(256), (size_t)(2 * pl.n_chunks + 1) * sizeof(int), st, fp);
     TT_LAUNCH_CHECK();
     // exact kernel, a no-op unless a workgroup raised the flag; then it rewrites every output row
+    if (masked) // ... of the flagged tiles with the MASKED exact answer
+        return tt_score_topk_masked_pred(Q, B, d, D32, bf16, N, keep, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
+                                         workspace_bytes - pl.ws_bytes, fallback_flag, st);
     if (bf16)
         return tt_score_topk_bf16_pred(Q, B, d, D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
                                        workspace_bytes - pl.ws_bytes, fallback_flag, st);
@@ -1606,6 +1685,73 @@ TT_EXPORT int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, co
                          out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events, (hipStream_t)stream);
 }
 
+// ---- the same six calls under a keep-bitmask (include/tt.h "Masked screened search"); keep == NULL is the unmasked call
+TT_EXPORT size_t tt_score_topk_screened_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return bf16 ? tt_score_topk_screened_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_screened_workspace_bytes(B, N, d, k);
+}
+
+TT_EXPORT int tt_score_topk_screened_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
+                                                const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset, float *out_val,
+                                                int64_t *out_idx, int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
+                                                void *const *prof_events, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_masked_f32", Phase::Whole, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset,
+                         out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream,
+                         false, keep);
+}
+
+TT_EXPORT int tt_score_topk_screened_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep,
+                                                 int k, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                                 int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
+                                                 void *const *prof_events, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_masked_bf16", Phase::Whole, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
+                         idx_offset, out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events,
+                         (hipStream_t)stream, true, keep);
+}
+
+TT_EXPORT int tt_score_topk_screened_seed_list_masked_f32(const float *Q, int B, int d, const void *D16, int64_t N,
+                                                          const uint32_t *keep, int k, int k_seed, float dmax_norm,
+                                                          int32_t *fallback_flag, float *seed_list, void *workspace,
+                                                          size_t workspace_bytes, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seed_list_masked_f32", Phase::SeedList, Q, B, d, nullptr, D16, N, k, k_seed,
+                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
+                         (hipStream_t)stream, false, keep);
+}
+
+TT_EXPORT int tt_score_topk_screened_seed_list_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
+                                                           const uint32_t *keep, int k, int k_seed, float dmax_norm,
+                                                           int32_t *fallback_flag, float *seed_list, void *workspace,
+                                                           size_t workspace_bytes, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seed_list_masked_bf16", Phase::SeedList, Q, B, d, nullptr, D_bf16, N, k, k_seed,
+                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
+                         (hipStream_t)stream, true, keep);
+}
+
+TT_EXPORT int tt_score_topk_screened_seeded_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
+                                                       const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset,
+                                                       float *out_val, int64_t *out_idx, int32_t *fallback_flag, const float *seed,
+                                                       void *workspace, size_t workspace_bytes, void *const *prof_events,
+                                                       tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seeded_masked_f32", Phase::Seeded, Q, B, d, D32, D16, N, k, k, dmax_norm,
+                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
+                         (hipStream_t)stream, false, keep);
+}
+
+TT_EXPORT int tt_score_topk_screened_seeded_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
+                                                        const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset,
+                                                        float *out_val, int64_t *out_idx, int32_t *fallback_flag,
+                                                        const float *seed, void *workspace, size_t workspace_bytes,
+                                                        void *const *prof_events, tt_stream_t stream)
+{
+    return screened_impl("tt_score_topk_screened_seeded_masked_bf16", Phase::Seeded, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
+                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
+                         (hipStream_t)stream, true, keep);
+}
 
 // ------------------------------------------------------------------ test-only: observe the screen's raw scores
 // include/tt_debug.h.  Runs the REAL screen kernels (q_image_kernel + the MAXONLY form of screen_stream_kernel /
@@ -1684,6 +1830,7 @@ int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_n
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
     sp.qnorm = (const float *)(ws + pl.qnorm_off);
     sp.dbg_thr = thr;
+    sp.keep = nullptr;
     hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
                        (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0);
     TT_LAUNCH_CHECK();

@@ -91,11 +91,12 @@ def _merge_fn(k: int, kp: int = 0, shards: bool = False) -> str:
     return "tt_topk_merge_large" if large else "tt_topk_merge"
 
 
-@lru_cache(maxsize=None)  # (six names; composed once each, not per search)
-def _screened_fn(phase: str, bf16: bool) -> str:
-    """The C entry point of one phase of a screened search: "whole", or "seed_list" then "seeded" (ShardedIndex's union seed)."""
+@lru_cache(maxsize=None)  # (twelve names; composed once each, not per search)
+def _screened_fn(phase: str, bf16: bool, masked: bool = False) -> str:
+    """The C entry point of one phase of a screened search: "whole", or "seed_list" then "seeded" (ShardedIndex's union seed).
+    masked: the form that takes a keep-bitmask behind N (screen_masked=True indexes under a mask)."""
     infix = {"whole": "", "seed_list": "seed_list_", "seeded": "seeded_"}[phase]
-    return f"tt_score_topk_screened_{infix}{'bf16' if bf16 else 'f32'}"
+    return f"tt_score_topk_screened_{infix}{'masked_' if masked else ''}{'bf16' if bf16 else 'f32'}"
 
 
 def _out_pair(B: int, k: int, device, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -302,27 +303,34 @@ class _Screen:
                       "this index runs the exact bf16 kernel", RuntimeWarning, stacklevel=3)  # BruteForceIndex(...)'s caller
         return None
 
-    def workspace_bytes(self, B: int, k: int) -> int:
+    def workspace_bytes(self, B: int, k: int, masked: bool = False) -> int:
+        if masked:
+            return _lib.lib().tt_score_topk_screened_masked_workspace_bytes(B, self.n, 256, k, int(self.bf16))
         name = "tt_score_topk_screened_bf16_workspace_bytes" if self.bf16 else "tt_score_topk_screened_workspace_bytes"
         return getattr(_lib.lib(), name)(B, self.n, 256, k)
 
-    def seed_list(self, q: torch.Tensor, k: int, ks: int, flags: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
-        """Query image + sample pass of a search of q [B,256] for k: [B,ks] f32, each query's ks largest sample maxima."""
+    def seed_list(self, q: torch.Tensor, k: int, ks: int, flags: torch.Tensor, ws: torch.Tensor,
+                  keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Query image + sample pass of a search of q [B,256] for k: [B,ks] f32, each query's ks largest sample maxima (with
+        `keep`, a checked keep-bitmask over the rows: the maxima of the kept documents, the masked entry point)."""
         B, d = q.shape
         lst = torch.empty((B, ks), dtype=torch.float32, device=q.device)
-        fn = getattr(_lib.lib(), _screened_fn("seed_list", self.bf16))
-        _lib.check(fn(q.data_ptr(), B, d, self.filt.data_ptr(), self.n, k, ks, self.dmax_norm, flags.data_ptr(),
+        fn = getattr(_lib.lib(), _screened_fn("seed_list", self.bf16, keep is not None))
+        mask = () if keep is None else (keep.data_ptr(),)
+        _lib.check(fn(q.data_ptr(), B, d, self.filt.data_ptr(), self.n, *mask, k, ks, self.dmax_norm, flags.data_ptr(),
                       lst.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
         return lst
 
     def run(self, q: torch.Tensor, k: int, idx_offset: int, vals: torch.Tensor, idx: torch.Tensor, flags: torch.Tensor,
-            ws: torch.Tensor, seed: Optional[torch.Tensor] = None, prof_events=None) -> None:
-        """The screened search of q [B,256] into (vals, idx); with `seed` [B] f32, what follows seed_list() on the same ws."""
+            ws: torch.Tensor, seed: Optional[torch.Tensor] = None, prof_events=None, keep: Optional[torch.Tensor] = None) -> None:
+        """The screened search of q [B,256] into (vals, idx); with `seed` [B] f32, what follows seed_list() on the same ws;
+        with `keep` (a checked keep-bitmask over the rows), the masked entry point of the same phase."""
         B, d = q.shape
-        fn = getattr(_lib.lib(), _screened_fn("whole" if seed is None else "seeded", self.bf16))
+        fn = getattr(_lib.lib(), _screened_fn("whole" if seed is None else "seeded", self.bf16, keep is not None))
         corpus = (self.rows.data_ptr(),) if self.bf16 else (self.rows.data_ptr(), self.filt.data_ptr())
+        mask = () if keep is None else (keep.data_ptr(),)
         thr = () if seed is None else (seed.data_ptr(),)
-        _lib.check(fn(q.data_ptr(), B, d, *corpus, self.n, k, self.dmax_norm, idx_offset, vals.data_ptr(),
+        _lib.check(fn(q.data_ptr(), B, d, *corpus, self.n, *mask, k, self.dmax_norm, idx_offset, vals.data_ptr(),
                       idx.data_ptr(), flags.data_ptr(), *thr, ws.data_ptr(), ws.numel(), prof_events, _stream(q)))
 
 
@@ -341,13 +349,17 @@ class BruteForceIndex:
 
     Deletions and filtered search: remove_ids(ids) withdraws documents for good (a persistent keep-bitmask, N/8 bytes,
     allocated on first use and mutated in place), search(q, k, keep=mask) answers over a subset for one call
-    (pack_keep_mask; ANDed with the persistent mask).  WITH ANY MASK IN EFFECT THE SEARCH RUNS THE MASKED EXACT KERNEL
-    (tt_score_topk_masked_f32 / _bf16), ALSO ON A screen=True INDEX: the screened kernels do not take a mask.  Its cost is
-    the exact kernel's -- HBM-bound at small B, fp32-MFMA-bound at large B, as the k > 64 route already is -- and a selective
-    mask pays the full scan.
+    (pack_keep_mask; ANDed with the persistent mask).  By default a search under any mask runs the masked exact kernel
+    (tt_score_topk_masked_f32 / _bf16), also on a screen=True index, at the exact kernel's cost -- HBM-bound at small B,
+    fp32-MFMA-bound at large B, as the k > 64 route already is.  screen_masked=True (with screen=True) keeps masked searches
+    on the screened path: the screen kernels' MASKED instantiations take the keep-bitmask (tt_score_topk_screened_masked_f32
+    and its kin; every threshold is formed from kept documents only, DESIGN.md "Masked screened top-k"), the result is the
+    masked exact kernel's bit for bit, and fallback_flags / search_stats() report the screen's own values.  It is opt-in:
+    without it nothing changes.  k > 64 runs the exact route either way, and a masked document is still streamed and
+    multiplied: a selective mask pays the full scan.
     """
 
-    def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False):
+    def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False, screen_masked: bool = False):
         # (screen may also be a ready _Screen over doc_embeddings: _from_buffers)
         _need_cuda(doc_embeddings)
         self.docs = _docs_c(doc_embeddings)
@@ -356,6 +368,7 @@ class BruteForceIndex:
             build = _Screen.for_bf16 if self.docs.dtype == torch.bfloat16 else _Screen.for_f32
             screen = build(self.docs) if screen and self.docs.shape[0] > 0 else None
         self._screen: Optional[_Screen] = screen
+        self.screen_masked = bool(screen_masked)  # masked searches stay on the screened path (where an unmasked one screens)
         # for callers to read: the fp16 shadow [N,256] (None for screened bf16 rows) and the largest row norm
         self.docs16 = screen.filt if screen is not None and not screen.bf16 else None
         self.dmax_norm = screen.dmax_norm if screen is not None else float("nan")
@@ -365,9 +378,11 @@ class BruteForceIndex:
         self._keep: Optional[torch.Tensor] = None  # the persistent keep-bitmask (remove_ids), None until the first removal
 
     @classmethod
-    def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int):
+    def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int,
+                      screen_masked: bool = False):
         """An index over caller-managed device buffers (StreamedIndex's per-block view)."""
-        return cls(docs32, idx_offset, _Screen(docs32, docs16, False, dmax_norm) if docs16 is not None else False)
+        return cls(docs32, idx_offset, _Screen(docs32, docs16, False, dmax_norm) if docs16 is not None else False,
+                   screen_masked=screen_masked)
 
     @property
     def _screen_bf16(self) -> bool:  # bf16 rows screened as they are (no docs16)
@@ -407,7 +422,8 @@ class BruteForceIndex:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) contiguous device tensors to write into (2-D q only).
         keep: optional packed keep-bitmask over this index's rows for this call (pack_keep_mask), ANDed with the persistent
         mask of remove_ids.  With either in effect the search is the masked exact kernel's, also on a screen=True index (the
-        class docstring has the cost); fallback_flags then reads all ones.
+        class docstring has the cost); fallback_flags then reads all ones.  On a screen_masked=True index it is the masked
+        screened search wherever the unmasked one would screen, and fallback_flags are the screen's.
         _seed_union (ShardedIndex): a callable that turns this shard's seed list [B, _k_seed] f32 (its _k_seed largest
         sample maxima per query, _Screen.seed_list) into the seed thresholds [B] f32 -- the _k_seed-th largest of the UNION
         of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen then runs with that
@@ -421,7 +437,7 @@ class BruteForceIndex:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
         keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
         if self._screens(q.shape[0], k, keep is not None):
-            return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list)
+            return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list, keep)
         if keep is not None and self._screen is not None:  # (the exact kernel took over every tile of a screened index)
             self.fallback_flags = torch.ones((q.shape[0] + 31) // 32, dtype=torch.int32, device=self.docs.device)
         v, i = score_topk(q, self.docs, k, self.idx_offset, keep=keep)
@@ -434,16 +450,17 @@ class BruteForceIndex:
     def _screens(self, B: int, k: int, masked: Optional[bool] = None) -> bool:
         """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
         whether they enter the seed exchange; the thresholds are the module's at the time of the call.
-        masked: a keep-bitmask is in effect (None: the persistent one, if any) -- a masked search never screens."""
+        masked: a keep-bitmask is in effect (None: the persistent one, if any) -- a masked search screens only on a
+        screen_masked=True index."""
         N, d = self.docs.shape
         if masked is None:
             masked = self._keep is not None
-        return (self._screen is not None and not masked and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH)
-                and N >= SCREEN_MIN_DOCS and k <= SMALL_KMAX)
+        return (self._screen is not None and (not masked or self.screen_masked)
+                and B >= (SCREEN_MIN_BATCH if d == 256 else SCREEN_PADDED_MIN_BATCH) and N >= SCREEN_MIN_DOCS and k <= SMALL_KMAX)
 
     def _search_screened(self, q: torch.Tensor, k: int, _prof_events=None, out=None, _seed_union=None,
-                         _k_seed: int = 0, _k_list: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        """search()'s screened path for a 2-D q; the arguments are search()'s."""
+                         _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search()'s screened path for a 2-D q; the arguments are search()'s, keep the ANDed mask (checked) or None."""
         B, d = q.shape
         sc = self._screen
         q = _f32c(q)
@@ -454,17 +471,17 @@ class BruteForceIndex:
         vals, idx = _out_pair(B, k, q.device, out)
         with torch.cuda.device(self.docs.device):  # workspace sizing depends on the device's CU count
             # per-call workspace and flags (cached allocator blocks): safe for concurrent callers and streams
-            ws = torch.empty(sc.workspace_bytes(B, k), dtype=torch.uint8, device=self.docs.device)
+            ws = torch.empty(sc.workspace_bytes(B, k, keep is not None), dtype=torch.uint8, device=self.docs.device)
             flags = torch.empty((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
             if self.keep_stats:
                 self._last_ws = (ws, B, k)
             seed = None
             if _seed_union is not None:
                 ks = min(_k_list or _k_seed or k, k)  # entries per seed list (the caller ranks the union)
-                seed = _seed_union(sc.seed_list(q, k, ks, flags, ws))
+                seed = _seed_union(sc.seed_list(q, k, ks, flags, ws, keep))
                 if seed.shape != (B,) or seed.dtype != torch.float32 or not seed.is_contiguous():
                     raise ValueError("_seed_union must return a contiguous float32 [B] tensor")
-            sc.run(q, k, self.idx_offset, vals, idx, flags, ws, seed, _prof_events)
+            sc.run(q, k, self.idx_offset, vals, idx, flags, ws, seed, _prof_events, keep)
         self.fallback_flags = flags  # of the most recent search (per 32-query tile; non-zero = exact kernel took over)
         return vals, idx
 
@@ -477,7 +494,7 @@ class GraphedSearch:
     stream capture works; queries are copied into a static buffer, results are returned in static buffers
     (valid until the next call).
     Removals: a graph captured while the index has a persistent keep-bitmask reads that buffer at every replay, so later
-    remove_ids are honoured.  A graph captured BEFORE the index had one holds the unmasked launches: calling it after a
+    remove_ids are honoured (on a screen_masked=True index the replayed launches are the masked screened search's).  A graph captured BEFORE the index had one holds the unmasked launches: calling it after a
     remove_ids raises RuntimeError (capture a new GraphedSearch) rather than return removed documents."""
 
     def __init__(self, index: "BruteForceIndex", batch: int, k: int = 10):
@@ -642,7 +659,7 @@ class ShardedIndex:
     minimum, one shard outside the fp16 range) would leave some ranks in an all-gather the others never enter."""
 
     def __init__(self, local_docs, row_offset: int, group=None, shard_k: int = 50, screen: bool = False,
-                 comm=None, block_docs: int = 1 << 20, device=None):
+                 comm=None, block_docs: int = 1 << 20, device=None, screen_masked: bool = False):
         """local_docs: this rank's rows [row_offset, row_offset + n) of the corpus, as
           * a device fp32 [n,d] tensor: resident shard (BruteForceIndex; BASELINE configs[3]),
           * a device bf16 [n,d] tensor: resident shard kept as bf16 (BruteForceIndex over it; with screen=True it screens from
@@ -654,7 +671,9 @@ class ShardedIndex:
         A job may mix the two kinds (a rank that has the HBM keeps its shard resident).  The seed exchange is a property of the
         whole job: with ANY streamed shard no rank exchanges seeds.  (A streamed shard searches block by block, each block
         seeded by its own sample pass, which is valid on its own; a union seed would need the sample maxima of the whole
-        shard before the first block is screened, i.e. one more pass over PCIe, which is what binds.)"""
+        shard before the first block is screened, i.e. one more pass over PCIe, which is what binds.)
+        screen_masked: the shard's index keeps masked searches on the screened path (BruteForceIndex); like `screen` it is a
+        property of the job, the same on every rank (a ready StreamedIndex brings its own)."""
         from .collective import Collective
         self.group = group
         self.row_offset = int(row_offset)
@@ -664,9 +683,11 @@ class ShardedIndex:
                 raise ValueError(f"the StreamedIndex numbers its rows from {local_docs.idx_offset}, the shard starts at {row_offset}")
             self._index = local_docs
         elif not local_docs.is_cuda and local_docs.dtype == torch.bfloat16:
-            self._index = StreamedIndex(local_docs, block_docs=block_docs, device=device, idx_offset=row_offset, screen=True)
+            self._index = StreamedIndex(local_docs, block_docs=block_docs, device=device, idx_offset=row_offset, screen=True,
+                                        screen_masked=screen_masked)
         else:
-            self._index = BruteForceIndex(local_docs, idx_offset=row_offset, screen=screen)
+            self._index = BruteForceIndex(local_docs, idx_offset=row_offset, screen=screen, screen_masked=screen_masked)
+        self.screen_masked = self._index.screen_masked
         self.streamed = isinstance(self._index, StreamedIndex)
         self._dev = self._index.device
         self._coll = Collective(group, self._dev, comm=comm)
@@ -696,7 +717,8 @@ class ShardedIndex:
         """Withdraw documents by GLOBAL id.  Called by EVERY rank with the same ids, like every other call on this class: each
         rank clears the bits of the ids in its shard and ignores the rest, and every rank allocates its mask, also where no
         id falls in its shard -- whether a search is masked decides whether a rank enters the seed all-gather, so it has to be
-        a property of the job, not of a rank."""
+        a property of the job, not of a rank.  So does screen_masked: with it a masked search enters the seed exchange like an
+        unmasked one, without it none does, and the ranks must agree."""
         self._index.remove_ids(ids)
 
     def _local_search(self, q: torch.Tensor, kp: int, k: int, sl: "_Slot", comm_stream=None, keep=None) -> None:
@@ -715,10 +737,12 @@ class ShardedIndex:
         plan = self._seed_plan(k)
         B = q.shape[0]
         # (a seed plan implies a resident shard: no rank exchanges seeds when any shard is streamed)
-        masked = keep is not None or self._index.keep_mask is not None  # (the same on every rank: remove_ids, search)
+        # (masked and screen_masked, which _screens weighs it with, are the same on every rank: remove_ids, search, __init__)
+        masked = keep is not None or self._index.keep_mask is not None
         if plan is None or not self._index._screens(B, k, masked) or (world == 1 and kp == k):
             # no seed exchange on any rank (agreed in the constructor; B, k and masked are the same everywhere): the shard's own
-            # search -- the masked exact kernel when a mask is in effect; a short list's padding is ignored by the merge
+            # search -- the masked exact kernel when a mask is in effect and the index does not screen under one; a short
+            # list's padding is ignored by the merge
             if comm_stream is not None:
                 self._flush()
             self._index.search(q, kp, out=(sl.send_v, sl.send_i), keep=keep)
@@ -745,7 +769,9 @@ class ShardedIndex:
                 cur.wait_event(sl.seeded)    # (the event, not the stream: the screen does not wait for that exchange)
             return seed_union(recv, world, kth)
 
-        self._index.search(q, kp, out=(sl.send_v, sl.send_i), _seed_union=union, _k_seed=k, _k_list=ks)
+        # (under a mask the seed lists hold kept documents' maxima only: distinct kept documents of disjoint shards, so the
+        #  union seed bounds the masked global k-th score as it is)
+        self._index.search(q, kp, out=(sl.send_v, sl.send_i), _seed_union=union, _k_seed=k, _k_list=ks, keep=keep)
 
     @property
     def collective(self) -> str:
@@ -823,7 +849,8 @@ class ShardedIndex:
     def search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """One search, everything on the caller's stream; fresh result tensors.
         keep: a packed keep-bitmask over THIS RANK'S rows for this call (ANDed with the mask of remove_ids).  It must be given
-        on all ranks or on none: a masked search does not enter the seed exchange."""
+        on all ranks or on none: a masked search does not enter the seed exchange (with screen_masked=True it does, on every
+        rank alike)."""
         if q.dim() == 1:
             return _squeezed(self.search, q, k, keep)
         kp = max(k, self.shard_k)
@@ -872,7 +899,7 @@ class StreamedIndex:
     """
 
     def __init__(self, host_docs: torch.Tensor, block_docs: int = 1 << 20, device=None, idx_offset: int = 0,
-                 screen: bool = True):
+                 screen: bool = True, screen_masked: bool = False):
         if host_docs.is_cuda or host_docs.dtype != torch.bfloat16 or host_docs.dim() != 2:
             raise ValueError("StreamedIndex wants a CPU bfloat16 [N,d] tensor (pinned for full PCIe speed)")
         self.host = host_docs if (host_docs.shape[0] == 0 or host_docs.is_pinned()) else host_docs.pin_memory()
@@ -880,6 +907,7 @@ class StreamedIndex:
         self.block = int(min(block_docs, max(self.N, 1)))
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.idx_offset = int(idx_offset)
+        self.screen_masked = bool(screen_masked)  # the per-block views screen masked searches too (BruteForceIndex)
         dev = self.device
         self._stage = [torch.empty((self.block, self.d), dtype=torch.bfloat16, device=dev) for _ in range(2)]
         self._d32 = [torch.empty((self.block, self.d), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -926,7 +954,7 @@ class StreamedIndex:
         dtype=torch.bfloat16: the rows are copied to HBM as they are (N*d*2 bytes, 6.4 GB for that shard) and searched by
         the exact bf16 kernel (same results)."""
         if dtype == torch.bfloat16:
-            return BruteForceIndex(self.host.to(self.device), idx_offset=self.idx_offset)
+            return BruteForceIndex(self.host.to(self.device), idx_offset=self.idx_offset, screen_masked=self.screen_masked)
         if dtype != torch.float32:
             raise ValueError(f"resident() keeps float32 or bfloat16 rows, not {dtype}")
         d32 = torch.empty((self.N, self.d), dtype=torch.float32, device=self.device)
@@ -938,7 +966,7 @@ class StreamedIndex:
                 d16[lo:lo + n].copy_(self._d16[s][:n])
 
         self._walk(visit)
-        return BruteForceIndex._from_buffers(d32, d16, self.dmax_norm, self.idx_offset)
+        return BruteForceIndex._from_buffers(d32, d16, self.dmax_norm, self.idx_offset, self.screen_masked)
 
     @property
     def ntotal(self) -> int:
@@ -956,8 +984,9 @@ class StreamedIndex:
     def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block).
         keep: optional packed keep-bitmask over the whole corpus (on the device), ANDed with the mask of remove_ids.  Block i of
-        a masked search gets the word slice at lo / 32 and runs the masked exact kernel, so the blocks must start on word
-        boundaries: block_docs % 32 != 0 (with more than one block) raises ValueError."""
+        a masked search gets the word slice at lo / 32 and runs the masked exact kernel (the masked screen where the block
+        screens and screen_masked is set), so the blocks must start on word boundaries: block_docs % 32 != 0 (with more than
+        one block) raises ValueError."""
         _need_cuda(q)
         if q.dim() == 1:
             return _squeezed(self.search, q, k, None, keep)
@@ -973,7 +1002,7 @@ class StreamedIndex:
 
         def visit(s, lo, n):
             blk = BruteForceIndex._from_buffers(self._d32[s][:n], self._d16[s][:n] if self._d16[s] is not None else None,
-                                                self.dmax_norm, self.idx_offset + lo)
+                                                self.dmax_norm, self.idx_offset + lo, self.screen_masked)
             v, i = blk.search(q, k, keep=None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)])
             run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
 
