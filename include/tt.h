@@ -352,6 +352,28 @@ int tt_topk_merge_shards_large(const void *gathered, int world, size_t rank_stri
                                int B, int kp, int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
 
 /*
+ * Per-query exclusion: every query leaves out documents of its own -- the ones this user has seen, this training query's
+ * known positives.  Replaces, per row b,
+ *   scores[b, exclude[b]] = -inf ; torch.topk(scores, k)      the per-query form of backend/trainer.py:62-65,
+ *                                                             backend/evaluators.py:185-186
+ * which the keep-bitmask (one mask for the whole batch) cannot express.  Exactness: removing at most E documents from the exact
+ * top-(k + E) leaves the exact top-k of the rest, in the same order, ties included -- a document of the remaining top-k has
+ * fewer than k + E documents ranked before it, so it is in the longer list.  The caller therefore searches (or merges) for
+ * k + E <= TT_TOPK_LARGE_KMAX with any entry point above and hands the rows to this filter; no search kernel takes the lists.
+ * in_val / in_idx [B,M]: rows as the searches and merges write them, (score desc, index asc), padding (-inf, idx < 0) at the
+ * tail.  exclude [B,E] device int64 (8-byte aligned): ids in in_idx's id space (global, i.e. after idx_offset); negative
+ * entries are padding, duplicates and ids that occur nowhere are fine; E = 0 (exclude may be NULL) copies the first k columns.
+ * out_val / out_idx [B,k]: the first k entries of row b whose index is >= 0 and not in exclude[b], in input order, then
+ * (-inf, -1).  out must not overlap in.  1 <= k <= M (else TT_ERR_BAD_SHAPE, like negative sizes, null or misaligned pointers
+ * and overlap), 0 <= E <= TT_TOPK_LARGE_KMAX - 1 (above: TT_ERR_UNSUPPORTED), any M (read in chunks, up to the k-th kept
+ * entry); B = 0 does nothing.  One launch, one workgroup per row: the list sits in LDS (8 KB at most), compared directly up to
+ * 32 ids, sorted once and binary-searched above.  Asynchronous, capturable: no workspace, no host synchronisation, no atomics;
+ * the result depends only on the inputs.
+ */
+int tt_topk_exclude_ids(const float *in_val, const int64_t *in_idx, int B, int M, const int64_t *exclude /*[B][E]*/, int E,
+                        int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
+
+/*
  * Rank (1-based) of one designated document per query under (score desc,
  * index asc), what BatchEvaluator extracts from a full sort per row.
  *   backend/evaluators.py:50,58-65

@@ -1,0 +1,372 @@
+"""Per-query exclusion lists: tt_topk_exclude_ids / topk_exclude alone, and search(..., exclude=) on every index.
+
+The expected value of a search is the reference idiom itself: oracle.score_all, the excluded (and masked) entries of each row
+set to -inf, sorted by (score desc, index asc), first k, with (-inf, -1) where -inf is reached.  Values and indices are
+compared with equality.  Every query excludes its own true top documents, so an implementation that searched for k and
+filtered afterwards would come back short."""
+import numpy as np
+import pytest
+import torch
+
+import synth
+from test_masked_gpu import host_f32, queries, rows_on_device
+from test_search_aux_gpu import par_rows
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def tt():
+    import twotowermlretrieval_amd as m
+    from twotowermlretrieval_amd import _lib
+    _lib.lib()
+    assert torch.cuda.is_available()
+    return m
+
+
+@pytest.fixture(autouse=True)
+def product_thresholds(monkeypatch):
+    """The routing thresholds of the product (other test modules lower them for the rest of the session)."""
+    from twotowermlretrieval_amd import index as _index
+    monkeypatch.setattr(_index, "SCREEN_MIN_DOCS", 65536)
+    monkeypatch.setattr(_index, "SCREEN_MIN_BATCH", 1)
+    monkeypatch.setattr(_index, "SCREEN_PADDED_MIN_BATCH", 33)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def same(got, want):
+    torch.cuda.synchronize()
+    gv, gi = got[0].cpu().numpy(), got[1].cpu().numpy()
+    bad_i, bad_v = int((gi != want[1]).sum()), int((gv != want[0]).sum())
+    print(f"index mismatches {bad_i}, value mismatches {bad_v} of {gi.size}")
+    assert gi.shape == want[1].shape and gi.dtype == np.int64 and gv.dtype == np.float32
+    assert bad_i == 0 and bad_v == 0
+
+
+# ---- the filter alone --------------------------------------------------------------------------------------------------------
+
+def filter_ref(v, i, ex, k):
+    """The first k entries of each row whose index is >= 0 and not listed, in input order, then (-inf, -1)."""
+    B = v.shape[0]
+    ov = np.full((B, k), -np.inf, dtype=np.float32)
+    oi = np.full((B, k), -1, dtype=np.int64)
+    for b in range(B):
+        sel = np.flatnonzero((i[b] >= 0) & ~np.isin(i[b], ex[b]))[:k]
+        ov[b, :len(sel)], oi[b, :len(sel)] = v[b, sel], i[b, sel]
+    return ov, oi
+
+
+def sorted_rows(seed, B, M, n_pad=0):
+    """[B,M] rows as a search writes them: scores descending with runs of equal scores (index ascending inside a run),
+    distinct ids per row from [0, 4M), the last n_pad entries padding."""
+    rs = np.random.RandomState(seed)
+    v = -np.sort(-rs.randint(0, max(M // 3, 2), size=(B, M)).astype(np.float32), axis=1)
+    i = np.stack([rs.choice(4 * M, M, replace=False) for _ in range(B)]).astype(np.int64)
+    for b in range(B):
+        i[b] = i[b][np.lexsort((i[b], -v[b]))]
+    if n_pad:
+        v[:, M - n_pad:], i[:, M - n_pad:] = -np.inf, -1
+    return v, i
+
+
+def lists_for(rs, i, E):
+    """name -> exclude [B,E] over the rows i."""
+    B, M = i.shape
+    present = np.stack([rs.choice(i[b][i[b] >= 0], E) if E else np.zeros(0, dtype=np.int64) for b in range(B)])  # with repeats
+    mixed = np.where(rs.rand(B, E) < 0.3, -1, present)
+    mixed = np.where(rs.rand(B, E) < 0.2, 4 * M + rs.randint(0, 1000, size=(B, E)), mixed)
+    head = np.full((B, E), -7, dtype=np.int64)                  # exactly the first min(E, M) entries of the row
+    head[:, :min(E, M)] = i[:, :min(E, M)]
+    out = {"all_padding": np.full((B, E), -1, dtype=np.int64), "duplicates": present[:, rs.randint(0, max(E, 1), size=E)],
+           "absent": 4 * M + rs.randint(0, 1000, size=(B, E)).astype(np.int64), "mixed": mixed, "head": head}
+    if E >= M:
+        whole = np.full((B, E), -1, dtype=np.int64)
+        whole[:, E - M:] = i[:, ::-1]                           # every entry of the row, descending behind padding
+        out["whole_row"] = whole
+    return {name: np.ascontiguousarray(x, dtype=np.int64).reshape(B, E) for name, x in out.items()}
+
+
+@pytest.mark.parametrize("E", (0, 1, 31, 32, 33, 257, 1023))
+@pytest.mark.parametrize("M", (5, 64, 300, 1024, 2500))
+@pytest.mark.parametrize("B", (1, 33))
+def test_filter_alone(tt, B, M, E):
+    """E crosses direct (<= 32) / sorted, M the 256-entry chunk; k = M, a short k and k = 1."""
+    rs = np.random.RandomState(1000 * B + M + 7 * E)
+    for n_pad in sorted({0, min(3, M - 1), M // 2}):
+        v, i = sorted_rows(M + E + n_pad, B, M, n_pad)
+        vd, id_ = dev(v), dev(i)
+        for name, ex in lists_for(rs, i, E).items():
+            exd = dev(ex)
+            for k in sorted({1, min(M, 10), M}):
+                got = tt.topk_exclude(vd, id_, exd, k)
+                want = filter_ref(v, i, ex, k)
+                torch.cuda.synchronize()
+                assert np.array_equal(got[1].cpu().numpy(), want[1]) and np.array_equal(got[0].cpu().numpy(), want[0]), \
+                    (name, n_pad, k)
+            if name == "whole_row":
+                assert (want[1] == -1).all() and np.isneginf(want[0]).all()
+            if name == "head" and E >= M:
+                assert (want[1] == -1).all()
+            if E == 0:
+                assert np.array_equal(want[1][:, :M - n_pad], i[:, :M - n_pad])      # E = 0 copies the columns
+
+
+def test_filter_writes_into_out_and_depends_only_on_its_inputs(tt):
+    v, i = sorted_rows(5, 33, 300)
+    ex = lists_for(np.random.RandomState(6), i, 257)["mixed"]
+    vd, id_, exd = dev(v), dev(i), dev(ex)
+    out = (torch.full((33, 40), 7.0, device="cuda"), torch.full((33, 40), 7, dtype=torch.int64, device="cuda"))
+    got = tt.topk_exclude(vd, id_, exd, 40, out=out)
+    assert got[0] is out[0] and got[1] is out[1]
+    same(got, filter_ref(v, i, ex, 40))
+    again = tt.topk_exclude(vd, id_, exd, 40)
+    torch.cuda.synchronize()
+    assert torch.equal(again[0], got[0]) and torch.equal(again[1], got[1])
+    from twotowermlretrieval_amd import _lib
+    with pytest.raises(_lib.TTError, match="E=1024"):
+        tt.topk_exclude(vd, id_, torch.zeros((33, 1024), dtype=torch.int64, device="cuda"), 10)
+    with pytest.raises(ValueError, match="k=301"):
+        tt.topk_exclude(vd, id_, exd, 301)
+
+
+# ---- the reference idiom -----------------------------------------------------------------------------------------------------
+
+def idiom(S, ex, k, idx_offset=0, mask=None):
+    """scores[b, exclude[b]] = -inf (and the masked columns) ; sort by (score desc, index asc) ; first k.  S [B,N] is left
+    unchanged (it is shared among the cases)."""
+    B, N = S.shape
+    ov = np.full((B, k), -np.inf, dtype=np.float32)
+    oi = np.full((B, k), -1, dtype=np.int64)
+    for b in range(B):
+        s = S[b].copy()
+        loc = ex[b] - idx_offset
+        s[loc[(loc >= 0) & (loc < N) & (ex[b] >= 0)]] = -np.inf
+        if mask is not None:
+            s[~mask] = -np.inf
+        order = np.lexsort((np.arange(N), -s))[:k]
+        order = order[~np.isneginf(s[order])]
+        ov[b, :len(order)], oi[b, :len(order)] = s[order], order + idx_offset
+    return ov, oi
+
+
+def own_top(S, E, rs, n_random, idx_offset=0, mask=None):
+    """exclude [B,E]: each query's own true top-(E - n_random) (of the kept documents), then n_random random ids."""
+    B, N = S.shape
+    ex = np.empty((B, E), dtype=np.int64)
+    for b in range(B):
+        s = S[b] if mask is None else np.where(mask, S[b], -np.inf)
+        top = np.lexsort((np.arange(N), -s))[:E - n_random]
+        ex[b] = np.concatenate([top, rs.randint(0, N, size=E - len(top))]) + idx_offset
+    return ex
+
+
+@pytest.fixture(scope="module")
+def small(tt, oracle):
+    """(bf16, d) -> (index over 3000 rows, queries [33,d], oracle.score_all [33,3000]), made once."""
+    made = {}
+
+    def get(bf16, d):
+        if (bf16, d) not in made:
+            D = rows_on_device(40 + d, 3000, d, bf16)
+            Q = queries(41 + d, 33, d)
+            S = par_rows(lambda q: oracle.score_all(q, host_f32(D)), Q.cpu().numpy())
+            S.setflags(write=False)
+            made[(bf16, d)] = (tt.BruteForceIndex(D), Q, S)
+        return made[(bf16, d)]
+
+    yield get
+    made.clear()
+
+
+K_E = ((1, 1), (10, 5), (10, 54), (10, 55), (64, 1), (100, 200), (24, 1000))  # k + E on both sides of 64, and 1024
+
+
+@pytest.mark.parametrize("k,E", K_E)
+@pytest.mark.parametrize("B", (1, 33))
+@pytest.mark.parametrize("d", (64, 256))
+@pytest.mark.parametrize("bf16", (False, True))
+def test_index_excludes_each_querys_own_top(tt, small, bf16, d, B, k, E):
+    ix, Q, S = small(bf16, d)
+    ex = own_top(S[:B], E, np.random.RandomState(k + E), min(3, E // 4))
+    same(ix.search(Q[:B], k, exclude=dev(ex)), idiom(S[:B], ex, k))
+    if B == 1:                                                  # a single query vector takes [E]
+        v, i = ix.search(Q[0], k, exclude=dev(ex[0]))
+        assert v.shape == (k,) and i.shape == (k,)
+        same((v[None], i[None]), idiom(S[:1], ex, k))
+
+
+def test_index_argument_checks(tt, small):
+    ix, Q, S = small(False, 64)
+    ex = torch.zeros((33, 5), dtype=torch.int64, device="cuda")
+    with pytest.raises(ValueError, match=r"k \+ E = 20 \+ 1005 = 1025 > 1024"):
+        ix.search(Q, 20, exclude=torch.zeros((33, 1005), dtype=torch.int64, device="cuda"))
+    for bad in (ex.to(torch.int32), ex.cpu(), ex[:32], ex[0]):
+        with pytest.raises(ValueError):
+            ix.search(Q, 10, exclude=bad)
+    with pytest.raises(ValueError):
+        ix.search(Q[0], 10, exclude=ex)
+    a, b = ix.search(Q, 10), ix.search(Q, 10, exclude=None)      # None: the plain call
+    e0 = ix.search(Q, 10, exclude=ex[:, :0])                      # an empty list excludes nothing
+    torch.cuda.synchronize()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[0], e0[0]) and torch.equal(a[1], e0[1])
+
+
+def test_tie_group_is_cut_in_index_order(tt, oracle):
+    """Small-integer coordinates: every score is exact and ties abound.  40 identical rows are query 0's best documents; the
+    list removes some of them, and what is left of the group comes back in index order, in front of everything else."""
+    rs = np.random.RandomState(3)
+    N, d, B = 3000, 64, 33
+    Dn = rs.randint(-2, 3, size=(N, d)).astype(np.float32)
+    group = np.sort(rs.choice(N, 40, replace=False))
+    Dn[group] = np.where(rs.rand(d) < 0.5, -3.0, 3.0).astype(np.float32)   # longer than any other row: the unique maximum of q0
+    Qn = rs.randint(-2, 3, size=(B, d)).astype(np.float32)
+    Qn[0] = Dn[group[0]]
+    S = par_rows(lambda q: oracle.score_all(q, Dn), Qn)
+    assert (S[0, group] == 9.0 * d).all() and (np.delete(S[0], group) < 9.0 * d).all()
+    ix = tt.BruteForceIndex(dev(Dn))
+    for k, E in ((10, 13), (30, 13), (40, 40)):
+        ex = own_top(S, E, rs, 0)
+        ex[0] = np.resize(group[::3], E)                          # every third member of the group (repeated when E > 14)
+        got = ix.search(dev(Qn), k, exclude=dev(ex))
+        same(got, idiom(S, ex, k))
+        left = np.setdiff1d(group, ex[0])
+        assert got[1][0, :min(k, len(left))].cpu().tolist() == left[:k].tolist()
+
+
+def test_fewer_than_k_left(tt, oracle):
+    D = rows_on_device(9, 20, 64)
+    Q = queries(10, 33, 64)
+    S = par_rows(lambda q: oracle.score_all(q, host_f32(D)), Q.cpu().numpy())
+    ex = own_top(S, 15, np.random.RandomState(1), 0)
+    got = tt.BruteForceIndex(D).search(Q, 10, exclude=dev(ex))    # k + E = 25 > N = 20, and 5 documents left
+    same(got, idiom(S, ex, 10))
+    assert bool((got[1][:, 5:] == -1).all()) and bool((got[1][:, :5] >= 0).all()) and bool(torch.isneginf(got[0][:, 5:]).all())
+
+
+@pytest.mark.parametrize("bf16", (False, True))
+def test_composes_with_keep_remove_ids_and_idx_offset(tt, oracle, bf16):
+    N, d, B, OFF = 3000, 64, 33, 1000
+    rs = np.random.RandomState(12)
+    D = rows_on_device(13, N, d, bf16)
+    Q = queries(14, B, d)
+    S = par_rows(lambda q: oracle.score_all(q, host_f32(D)), Q.cpu().numpy())
+    ix = tt.BruteForceIndex(D, idx_offset=OFF)
+    for k, E in ((10, 5), (10, 60)):
+        ex = own_top(S, E, rs, 2, OFF)
+        ex[:, -1] = rs.randint(0, OFF, size=B)                    # an id below the offset: some other index's document
+        ex[:, -2] = ex[:, 0] - OFF                                # the best document's LOCAL number: not its id
+        same(ix.search(Q, k, exclude=dev(ex)), idiom(S, ex, k, OFF))
+    call = rs.rand(N) < 0.5
+    keep = tt.pack_keep_mask(dev(call))
+    for k, E in ((10, 5), (10, 60)):
+        ex = own_top(S, E, rs, 2, OFF, call)                      # the top of the KEPT documents
+        same(ix.search(Q, k, keep=keep, exclude=dev(ex)), idiom(S, ex, k, OFF, call))
+    removed = np.unique(own_top(S, 3, rs, 0).ravel())             # every query's three best are withdrawn
+    ix.remove_ids(dev(removed + OFF))
+    mask = np.ones(N, dtype=bool)
+    mask[removed] = False
+    for k, E in ((10, 5), (10, 60)):
+        ex = own_top(S, E, rs, 2, OFF, mask)
+        same(ix.search(Q, k, exclude=dev(ex)), idiom(S, ex, k, OFF, mask))
+        ex = own_top(S, E, rs, 2, OFF, mask & call)
+        same(ix.search(Q, k, keep=keep, exclude=dev(ex)), idiom(S, ex, k, OFF, mask & call))
+
+
+# ---- a screened index --------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def screened(tt, oracle):
+    """65 536 x 256 (the smallest corpus that screens): device rows, queries [33,256], oracle.score_all, made once."""
+    D = rows_on_device(77, 65536, 256)
+    Q = queries(78, 33, 256)
+    S = par_rows(lambda q: oracle.score_all(q, host_f32(D)), Q.cpu().numpy())
+    S.setflags(write=False)
+    yield D, Q, S
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("B", (1, 33))
+def test_screened_index(tt, screened, B):
+    D, Q, S = screened
+    Q, S = Q[:B], S[:B]
+    plain, ix = tt.BruteForceIndex(D), tt.BruteForceIndex(D, screen=True)
+    rs = np.random.RandomState(B)
+    for k, E in ((10, 5), (10, 60)):
+        assert ix._screens(B, k + E) is (k + E <= 64) and ix._screens(B, k)
+        ex = own_top(S, E, rs, 2)
+        ix.fallback_flags = None
+        got = ix.search(Q, k, exclude=dev(ex))
+        same(got, idiom(S, ex, k))
+        ref = plain.search(Q, k, exclude=dev(ex))
+        torch.cuda.synchronize()
+        assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+        if k + E <= 64:    # the screened search for k + E ran: one flag per 32-query tile (their values are the data's)
+            assert ix.fallback_flags.shape == ((B + 31) // 32,) and ix.fallback_flags.dtype == torch.int32
+        else:              # the exact large-k route of an unmasked search leaves the flags alone
+            assert ix.fallback_flags is None
+
+
+@pytest.mark.parametrize("B", (1, 33))
+def test_screened_masked_index_with_a_removal(tt, screened, B):
+    D, Q, S = screened
+    Q, S = Q[:B], S[:B]
+    ix = tt.BruteForceIndex(D, screen=True, screen_masked=True)
+    rs = np.random.RandomState(10 + B)
+    removed = np.unique(own_top(S, 2, rs, 0).ravel())
+    ix.remove_ids(dev(removed))
+    mask = np.ones(D.shape[0], dtype=bool)
+    mask[removed] = False
+    for k, E in ((10, 5), (10, 60)):
+        assert ix._screens(B, k + E) is (k + E <= 64)
+        ex = own_top(S, E, rs, 2, mask=mask)
+        same(ix.search(Q, k, exclude=dev(ex)), idiom(S, ex, k, mask=mask))
+        assert ix.fallback_flags.shape == ((B + 31) // 32,) and ix.fallback_flags.dtype == torch.int32
+        if k + E > 64:     # a masked search for more than 64: the exact kernel took every tile
+            assert bool((ix.fallback_flags == 1).all())
+
+
+# ---- graph replay and the streamed index -------------------------------------------------------------------------------------
+
+def test_graphed_search_replays_with_new_lists(tt, small):
+    ix, Q, S = small(False, 64)
+    B, k, W = 4, 10, 8
+    g = tt.GraphedSearch(ix, B, k, exclude_width=W)
+    assert g.exclude.shape == (B, W) and bool((g.exclude == -1).all())
+    rs = np.random.RandomState(5)
+    for step, E in enumerate((8, 8, 3)):                          # the third list is narrower: padded with -1
+        q = Q[step * B:(step + 1) * B].contiguous()
+        ex = dev(own_top(S[step * B:(step + 1) * B], E, rs, 1 if step else 0))
+        v, i = g(q, exclude=ex)
+        ev, ei = ix.search(q, k, exclude=ex)
+        torch.cuda.synchronize()
+        assert torch.equal(v, ev) and torch.equal(i, ei), step
+        same((v, i), idiom(S[step * B:(step + 1) * B], ex.cpu().numpy(), k))
+    v, i = g(Q[:B].contiguous())                                  # no list: nothing excluded
+    ev, ei = ix.search(Q[:B].contiguous(), k)
+    torch.cuda.synchronize()
+    assert torch.equal(v, ev) and torch.equal(i, ei) and bool((g.exclude == -1).all())
+    with pytest.raises(ValueError, match="exclude_width = 8"):
+        g(Q[:B].contiguous(), exclude=torch.zeros((B, 9), dtype=torch.int64, device="cuda"))
+    with pytest.raises(ValueError, match="exclude_width = 0"):
+        tt.GraphedSearch(ix, B, k)(Q[:B].contiguous(), exclude=torch.zeros((B, 1), dtype=torch.int64, device="cuda"))
+    with pytest.raises(ValueError, match=r"k \+ E = 1000 \+ 25 = 1025 > 1024"):
+        tt.GraphedSearch(ix, B, 1000, exclude_width=25)
+
+
+def test_streamed_index_three_blocks(tt, oracle):
+    N, d, B, block, OFF = 3 * 1024 - 5, 64, 33, 1024, 500
+    host = torch.from_numpy(synth.unit_rows(31, N, d)).to(torch.bfloat16)
+    Qn = synth.unit_rows(32, B, d)
+    wide = host.to(torch.float32).numpy()
+    S = par_rows(lambda q: oracle.score_all(q, wide), Qn)
+    ix = tt.StreamedIndex(host, block_docs=block, idx_offset=OFF, screen=False)
+    rs = np.random.RandomState(33)
+    for k, E in ((10, 6), (10, 60)):
+        ex = own_top(S, E, rs, 1, OFF)
+        assert sum(len(np.unique((ex[b, :E - 1] - OFF) // block)) > 1 for b in range(B)) > B // 2   # lists that span blocks
+        same(ix.search(dev(Qn), k, exclude=dev(ex)), idiom(S, ex, k, OFF))
+    v, i = ix.search(dev(Qn[0]), 10, exclude=dev(ex[0]))
+    same((v[None], i[None]), idiom(S[:1], ex[:1], 10, OFF))

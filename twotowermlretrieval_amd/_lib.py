@@ -79,6 +79,7 @@ SIGNATURES = {
     "tt_topk_merge_shards": (_i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _vp]),
     "tt_topk_merge_large": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tt_topk_merge_shards_large": (_i, [_vp, _i, _sz, _sz, _i, _i, _i, _vp, _vp, _vp]),
+    "tt_topk_exclude_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "tt_score_rank_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "tt_score_all_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp]),
     "tt_tok_create": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
+__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
            "shard_bounds", "seed_union"]
 
 
@@ -211,6 +211,56 @@ def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Ten
     with torch.cuda.device(vals.device):
         _lib.check(getattr(_lib.lib(), _merge_fn(k))(vals.data_ptr(), idx.data_ptr(), B, M, k, ov.data_ptr(),
                                                      oi.data_ptr(), _stream(vals)))
+    return ov, oi
+
+
+EXCLUDE_KMAX = 1024  # k + E of a search with an exclusion list: TT_TOPK_LARGE_KMAX, what every path answers exactly
+
+
+def _check_exclude(exclude: torch.Tensor, B: int, k: int, device) -> Tuple[torch.Tensor, int]:
+    """A per-query exclusion list for B queries on `device` as tt_topk_exclude_ids reads it (int64 [B,E], contiguous), and the
+    k + E the search in front of the filter runs for."""
+    if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64:
+        raise ValueError(f"exclude must be an int64 tensor of document ids, got {getattr(exclude, 'dtype', type(exclude))}")
+    if exclude.device != device:
+        raise ValueError(f"exclude on {exclude.device} but the search runs on {device}")
+    if exclude.dim() != 2 or exclude.shape[0] != B:
+        raise ValueError(f"exclude must be [B,E] = [{B},E] (one list per query; [E] for a single query), got {tuple(exclude.shape)}")
+    E = exclude.shape[1]
+    if k < 1:
+        raise ValueError(f"k = {k} < 1")
+    if k + E > EXCLUDE_KMAX:
+        raise ValueError(f"k + E = {k} + {E} = {k + E} > {EXCLUDE_KMAX}: a search with an exclusion list runs for k + E")
+    return (exclude if exclude.is_contiguous() else exclude.contiguous()), k + E
+
+
+def _exclude_row(exclude: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The [1,E] list of a single query's [E] list."""
+    if exclude is None:
+        return None
+    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 1:
+        raise ValueError(f"a single query takes exclude [E], got {tuple(getattr(exclude, 'shape', ()))}")
+    return exclude.unsqueeze(0)
+
+
+def topk_exclude(vals: torch.Tensor, idx: torch.Tensor, exclude: torch.Tensor, k: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-query exclusion over sorted lists the caller holds: vals f32 / idx int64 [B,M] as the searches and merges return
+    them ((score desc, index asc), padding at the tail), exclude int64 [B,E] (ids as in idx; negative = padding) -> the first k
+    entries of each row whose index is not in that row's list, then (-inf, -1) (tt_topk_exclude_ids, one launch).  Rows that
+    are the exact top-(k + E) give the exact top-k of the documents not listed.  out: optional (vals [B,k], idx [B,k])."""
+    _need_cuda(vals, idx, exclude)
+    vals = _f32c(vals)
+    if idx.dtype != torch.int64 or vals.shape != idx.shape or vals.dim() != 2:
+        raise ValueError("topk_exclude wants vals f32 [B,M] and idx int64 [B,M]")
+    idx = idx.contiguous()
+    B, M = vals.shape
+    if exclude.dtype != torch.int64 or exclude.device != vals.device or exclude.dim() != 2 or exclude.shape[0] != B:
+        raise ValueError(f"topk_exclude wants exclude int64 [{B},E] on {vals.device}, got {exclude.dtype} {tuple(exclude.shape)} on {exclude.device}")
+    exclude = exclude.contiguous()
+    ov, oi = _out_pair(B, k, vals.device, out)
+    with torch.cuda.device(vals.device):
+        _lib.check(_lib.lib().tt_topk_exclude_ids(vals.data_ptr(), idx.data_ptr(), B, M, exclude.data_ptr(), exclude.shape[1], k,
+                                                  ov.data_ptr(), oi.data_ptr(), _stream(vals)))
     return ov, oi
 
 
@@ -418,8 +468,15 @@ class BruteForceIndex:
         return ws[off:off + 8 * B].view(torch.int32).view(B, 2).clone()
 
     def search(self, q: torch.Tensor, k: int = 10, _prof_events=None, out=None, _seed_union=None,
-               _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None,
+               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) contiguous device tensors to write into (2-D q only).
+        exclude: optional per-query exclusion lists, int64 [B,E] on the index's device ([E] with a 1-D q): GLOBAL ids (with
+        idx_offset) query b must not return; negative entries are padding, duplicates and ids of other indexes are fine.  The
+        search is this index's ordinary search for k + E into a scratch pair -- every routing decision sees k + E: it screens
+        up to k + E = 64 and takes the exact large-k route above, fallback_flags are that search's, k + E > 1024 raises
+        ValueError -- followed by one filter launch (tt_topk_exclude_ids).  The result is the exact top-k of the documents
+        that are not listed, in the usual order, tail (-inf, -1); keep= and remove_ids compose with it.
         keep: optional packed keep-bitmask over this index's rows for this call (pack_keep_mask), ANDed with the persistent
         mask of remove_ids.  With either in effect the search is the masked exact kernel's, also on a screen=True index (the
         class docstring has the cost); fallback_flags then reads all ones.  On a screen_masked=True index it is the masked
@@ -429,12 +486,16 @@ class BruteForceIndex:
         of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen then runs with that
         global seed and `out` holds this shard's documents above it."""
         if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank)
-            return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep)
+            return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep, _exclude_row(exclude))
         _need_cuda(q)
         if q.device != self.docs.device:
             raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
         if q.shape[-1] != self.docs.shape[1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        if exclude is not None:
+            exclude, kk = _check_exclude(exclude, q.shape[0], k, self.docs.device)
+            v, i = self.search(q, kk, _prof_events, None, _seed_union, _k_seed, _k_list, keep)
+            return topk_exclude(v, i, exclude, k, out)
         keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
         if self._screens(q.shape[0], k, keep is not None):
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list, keep)
@@ -497,30 +558,48 @@ class GraphedSearch:
     remove_ids are honoured (on a screen_masked=True index the replayed launches are the masked screened search's).  A graph captured BEFORE the index had one holds the unmasked launches: calling it after a
     remove_ids raises RuntimeError (capture a new GraphedSearch) rather than return removed documents."""
 
-    def __init__(self, index: "BruteForceIndex", batch: int, k: int = 10):
+    def __init__(self, index: "BruteForceIndex", batch: int, k: int = 10, exclude_width: int = 0):
         self.index, self.B, self.k = index, int(batch), int(k)
         self._masked = index.keep_mask is not None
         dev = index.docs.device
         d = index.docs.shape[1]
         self.q = torch.zeros((self.B, d), dtype=torch.float32, device=dev)
         self.vals, self.idx = _out_pair(self.B, self.k, dev)
+        if exclude_width < 0:
+            raise ValueError(f"exclude_width = {exclude_width} < 0")
+        # a static [B, exclude_width] list (-1 = padding): the graph holds the k + exclude_width search and the filter
+        self.exclude = torch.full((self.B, int(exclude_width)), -1, dtype=torch.int64, device=dev) if exclude_width else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up outside capture: workspaces get allocated, kernels loaded
             for _ in range(2):
-                index.search(self.q, self.k, out=(self.vals, self.idx))
+                index.search(self.q, self.k, out=(self.vals, self.idx), exclude=self.exclude)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            index.search(self.q, self.k, out=(self.vals, self.idx))
+            index.search(self.q, self.k, out=(self.vals, self.idx), exclude=self.exclude)
 
-    def __call__(self, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def __call__(self, q: torch.Tensor, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """exclude: int64 [B,E] with E <= exclude_width (a narrower list is padded with -1; None = nothing excluded)."""
         if tuple(q.shape) != tuple(self.q.shape):
             raise ValueError(f"GraphedSearch was captured for queries of shape {tuple(self.q.shape)}, got {tuple(q.shape)}")
         if not self._masked and self.index.keep_mask is not None:
             raise RuntimeError("GraphedSearch was captured before the index had a keep-bitmask (remove_ids): its graph would "
                                "return removed documents; capture a new GraphedSearch")
+        if exclude is not None:
+            width = 0 if self.exclude is None else self.exclude.shape[1]
+            if (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64 or exclude.device != self.q.device
+                    or exclude.dim() != 2 or exclude.shape[0] != self.B or exclude.shape[1] > width):
+                raise ValueError(f"GraphedSearch was captured with exclude_width = {width}: exclude must be int64 "
+                                 f"[{self.B}, E <= {width}] on {self.q.device}, got {getattr(exclude, 'dtype', None)} "
+                                 f"{tuple(getattr(exclude, 'shape', ()))}")
+        if self.exclude is not None:
+            E = 0 if exclude is None else exclude.shape[1]
+            if E < self.exclude.shape[1]:
+                self.exclude[:, E:].fill_(-1)
+            if E:
+                self.exclude[:, :E].copy_(exclude)
         self.q.copy_(q)
         self.graph.replay()
         return self.vals, self.idx
@@ -620,14 +699,22 @@ class PendingSearch:
     synchronisation) and returns (values, indices) views valid until two more submits of the same shape on the same
     index (search() has a slot of its own and never overwrites them)."""
 
-    def __init__(self, slot: _Slot, index: "ShardedIndex"):
+    def __init__(self, slot: _Slot, index: "ShardedIndex", exclude: Optional[torch.Tensor] = None, k: int = 0):
         self._slot, self._index = slot, index
+        self._exclude, self._k, self._filtered = exclude, k, None  # submit(exclude=): the filter runs in result(), once
 
     def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(A COLLECTIVE when this step's exchange has not been issued yet -- it normally goes out inside the NEXT submit():
-        every rank must then call result() at the same point of its sequence of submit / search / result calls.)"""
+        every rank must then call result() at the same point of its sequence of submit / search / result calls.)
+        A step submitted with exclude= is filtered here, on the current stream, from the merged k + E rows into tensors of
+        its own: the list must stay as it was until then."""
+        if self._filtered is not None:
+            return self._filtered
         self._index._flush(self._slot)
         torch.cuda.current_stream(self._slot.out_v.device).wait_event(self._slot.merged)
+        if self._exclude is not None:
+            self._filtered = topk_exclude(self._slot.out_v, self._slot.out_i, self._exclude, self._k)
+            return self._filtered
         return self._slot.out_v, self._slot.out_i
 
 
@@ -846,13 +933,20 @@ class ShardedIndex:
             _lib.check(merge(sl.recv.data_ptr(), self._coll.world, sl.stride, sl.nv, B, kp, k, sl.out_v.data_ptr(),
                              sl.out_i.data_ptr(), _stream(sl.recv)))
 
-    def search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
+               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """One search, everything on the caller's stream; fresh result tensors.
         keep: a packed keep-bitmask over THIS RANK'S rows for this call (ANDed with the mask of remove_ids).  It must be given
         on all ranks or on none: a masked search does not enter the seed exchange (with screen_masked=True it does, on every
-        rank alike)."""
+        rank alike).
+        exclude: per-query exclusion lists of GLOBAL ids, int64 [B,E] ([E] with a 1-D q), the same on every rank like q.  The
+        local search, the exchange and the merge are those of a search for k + E (per-shard lists of max(k + E, shard_k));
+        the filter (tt_topk_exclude_ids) runs once, on the merged rows."""
         if q.dim() == 1:
-            return _squeezed(self.search, q, k, keep)
+            return _squeezed(self.search, q, k, keep, _exclude_row(exclude))
+        k_out = k
+        if exclude is not None:
+            exclude, k = _check_exclude(exclude, q.shape[0], k, self._dev)
         kp = max(k, self.shard_k)
         sl = self._slot(q.shape[0], kp, k, 2)
         cur = torch.cuda.current_stream(sl.send.device)
@@ -860,16 +954,24 @@ class ShardedIndex:
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
         self._local_search(q, kp, k, sl, keep=keep)
         self._exchange_merge(sl, q.shape[0], kp, k)
+        if exclude is not None:
+            res = topk_exclude(sl.out_v, sl.out_i, exclude, k_out)  # (reads the slot: before it is handed on)
+            sl.merged.record(cur)
+            return res
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
 
-    def submit(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> PendingSearch:
+    def submit(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
+               exclude: Optional[torch.Tensor] = None) -> PendingSearch:
         """Pipelined search of a [B,d] batch: the local search is enqueued on the caller's stream now; its list exchange and
         merge go out on this index's second stream inside the NEXT submit() (behind that step's seed gather), or when
         .result() / search() asks for them.  Call .result() when the answer is needed.  keep: as in search() (all ranks or
-        none)."""
+        none).  exclude: as in search(); the step runs for k + E and .result() filters the merged rows."""
         if q.dim() != 2:
             raise ValueError("submit wants a [B,d] batch")
+        k_out = k
+        if exclude is not None:
+            exclude, k = _check_exclude(exclude, q.shape[0], k, self._dev)
         kp = max(k, self.shard_k)
         B = q.shape[0]
         sl = self._slot(B, kp, k, self._n_submitted % 2)
@@ -884,7 +986,7 @@ class ShardedIndex:
         self._flush()                        # (a local search without a seed exchange has not issued the previous step's yet)
         sl.searched.record(cur)
         self._deferred = (sl, B, kp, k)
-        return PendingSearch(sl, self)
+        return PendingSearch(sl, self, exclude, k_out)
 
 
 class StreamedIndex:
@@ -981,19 +1083,26 @@ class StreamedIndex:
         """Withdraw documents by global id (with idx_offset); other ids are ignored.  The mask stays on the device."""
         self._keep = _clear_ids(self._keep, self.N, self.device, ids, self.idx_offset)
 
-    def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None,
+               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block).
+        exclude: optional per-query exclusion lists of global ids, int64 [B,E] on the device ([E] with a 1-D q): the blocks are
+        searched and merged for k + E (<= 1024) and the running list is filtered once at the end (tt_topk_exclude_ids).
         keep: optional packed keep-bitmask over the whole corpus (on the device), ANDed with the mask of remove_ids.  Block i of
         a masked search gets the word slice at lo / 32 and runs the masked exact kernel (the masked screen where the block
         screens and screen_masked is set), so the blocks must start on word boundaries: block_docs % 32 != 0 (with more than
         one block) raises ValueError."""
         _need_cuda(q)
         if q.dim() == 1:
-            return _squeezed(self.search, q, k, None, keep)
+            return _squeezed(self.search, q, k, None, keep, _exclude_row(exclude))
         if q.device != self.device:
             raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
         if q.shape[1] != self.d:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        if exclude is not None:
+            exclude, kk = _check_exclude(exclude, q.shape[0], k, self.device)
+            v, i = self.search(q, kk, None, keep)
+            return topk_exclude(v, i, exclude, k, out)
         q = _f32c(q)
         keep = _and_keep(self._keep, keep, self.N, self.device)
         if keep is not None and self.block % 32 and self.N > self.block:
