@@ -374,6 +374,34 @@ int tt_topk_exclude_ids(const float *in_val, const int64_t *in_idx, int B, int M
                         int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
 
 /*
+ * Threshold search (FAISS users: range_search): how many documents score at least min_score[b] for query b, and the best k
+ * of them.  Replaces
+ *   s = torch.matmul(q, D.t()) ; (s >= t).sum(1) ; torch.topk(s, k) with the entries below t masked
+ *                                                             after backend/evaluators.py:185-186
+ * without forming the [B,N] matrix.  The rows need no kernel of their own: every search above returns rows sorted by (score
+ * desc, index asc), so the best k at or above t are its first k cut at t (tt_topk_cut_below).  The count does: it has to see
+ * every document, and to agree bit for bit with the scores the searches return, so it is a mode of the exact kernels -- the same
+ * fp32 MFMA chain (tt_score_topk_f32's scores), the same tiles, ring and keep word, the epilogue counting instead of selecting.
+ * tt_score_count_f32 / _bf16: count[b] (device int64, 8-byte aligned) = #{n in [0,N): n kept and s(b,n) >= min_score[b]},
+ * IEEE fp32 >= (-0 == +0; a NaN threshold counts nothing, -inf counts the kept documents, +inf nothing: inputs are finite).
+ * min_score [B] device f32.  keep: as tt_score_topk_masked_f32's (ceil(N/32) words, bits at or beyond N ignored), or NULL.
+ * accumulate != 0 adds to count instead of overwriting it (block-wise callers).  Supported d per dtype, N < 2^31 - 64 and the
+ * status codes are the exact searches'; every check runs before any HIP call.  B = 0 does nothing; N = 0 writes zeros (leaves
+ * count alone under accumulate) and needs only count.  One pass over D on a static split of the corpus, one small sum over the
+ * per-wave integers: the result depends only on the inputs.  Asynchronous, capturable, no host synchronisation.
+ * tt_topk_cut_below: in place, every entry of row b of val / idx [B,k] with !(val >= min_score[b]) or idx < 0 becomes
+ * (-inf, -1); sorted rows keep a sorted prefix.  Any k >= 1; one launch.
+ */
+size_t tt_score_count_workspace_bytes(int B, int64_t N, int d, int bf16);
+int tt_score_count_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep,
+                       const float *min_score, int64_t *count, int accumulate, void *workspace, size_t workspace_bytes,
+                       tt_stream_t stream);
+int tt_score_count_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep,
+                        const float *min_score, int64_t *count, int accumulate, void *workspace, size_t workspace_bytes,
+                        tt_stream_t stream);
+int tt_topk_cut_below(float *val, int64_t *idx, int B, int k, const float *min_score, tt_stream_t stream);
+
+/*
  * Rank (1-based) of one designated document per query under (score desc,
  * index asc), what BatchEvaluator extracts from a full sort per row.
  *   backend/evaluators.py:50,58-65

@@ -104,6 +104,9 @@ int tt_score_topk_masked_pred(const float *Q, int B, int d, const void *D, bool 
                               int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
                               const int *run_if, hipStream_t st);
 
+// range.hip: count[b] (+)= the sum of part[b][0, n_chunks), the counting pass's per-(query, chunk) integers; n_chunks = 0 writes zeros
+int tt_count_finish(const int64_t *part, int B, int n_chunks, int64_t *count, int accumulate, hipStream_t st);
+
 // k-th largest of each row of vals [B][M] -> out [B] (threshold seeding of both search paths)
 int tt_kth_largest(const float *vals, int B, int M, int k, float *out, hipStream_t st);
 // the k largest of each row of vals [B][M] -> list [B][k], unordered (-inf padding when M < k)

@@ -190,11 +190,16 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // MASKED: p.keep decides which documents may be returned (tt_score_topk_masked_f32 / _bf16).  A masked document is scored like
 // any other and then left out of every selection: the append pass, and the sample maxima (a bound taken from a document that
 // cannot be returned is no lower bound of the masked k-th score).  MASKED = false is the kernel as it always was.
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false>
+// COUNT: the counting pass (tt_score_count_f32 / _bf16, DESIGN.md "Threshold search").  thr is the caller's min_score and never
+// moves; the epilogue counts the documents the append pass would have taken (the same predicate) in a lane-local integer and one
+// count per (query, chunk) goes out in pidx -- no candidate buffers, no compaction, no lists.  Launched on the static split only
+// (no pool draw, so no give-up); the pacing gate stays (a wait that times out loses nothing).  COUNT = false is the kernel as it was.
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false, bool COUNT = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!BF || NS % 2 == 0, "bf16 rows: d a multiple of 64");
+    static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     constexpr int NST = NT ? NSTAGE_NT : NSTAGE;
     constexpr int WAVE_LDS = NST * SLAB_BYTES;
     constexpr int NSD = BF ? NS / 2 : NS; // 128-B slabs per document row
@@ -255,6 +260,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
     if (qrow < p.B)
         thr = (!MAXONLY && p.thr0) ? p.thr0[(size_t)qrow * p.thr0_stride + p.thr0_off] : -INFINITY;
     int cnt = 0;
+    int nmatch = 0; // COUNT: this lane's documents with score >= thr (16 of a tile's 32 per lane half)
     float runmax = -INFINITY;
     Cand *const cbase = p.cand + ((size_t)task * 32 + j) * CAP; // this lane's query buffer
 
@@ -413,13 +419,20 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 runmax = fmaxf(runmax, m);
                 continue;
             }
+            if (COUNT) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int doc = tile_base + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    nmatch += ((!partial || doc < p.N) && kept(r) && acc[r] >= thr) ? 1 : 0;
+                }
+            }
             float m = acc[0];
 #pragma unroll
             for (int r = 1; r < 16; ++r)
                 m = fmaxf(m, acc[r]);
             // (MASKED: m may come from a masked document -- that only costs the slow path a look; a tile with nothing kept
             //  skips it)
-            if ((!MASKED || kw != 0u) && __ballot(m >= thr) != 0ull) {
+            if (!COUNT && (!MASKED || kw != 0u) && __ballot(m >= thr) != 0ull) {
                 // Append pass.  The store is inline asm on purpose: a compiler-visible global store
                 // (or the compaction's loads) inside this loop makes hipcc emit s_waitcnt vmcnt(0) at
                 // every join, which drains the LDS-DMA ring on each tile that has a candidate.
@@ -509,6 +522,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
         }
         return;
     }
+    if (COUNT) {
+        nmatch += __shfl_xor(nmatch, 32);
+        if (h == 0 && qrow < p.B)
+            p.pidx[(size_t)qrow * p.n_chunks + chunk] = nmatch;
+        return;
+    }
 
     // ---- final compaction + partial lists out ---------------------------------
     {
@@ -549,10 +568,11 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 // (tools/experiments/mfma16_order.hip), so the oracle parity carries over.  Ring, DMA, thresholds, candidate
 // buffers, compaction, partial lists and merge are K4's; the launch is bound by HBM streaming (d * 4 bytes per doc).
 // ---------------------------------------------------------------------------
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false>
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     constexpr int WAVE_LDS = NSTAGE * SLAB_BYTES;
     constexpr int ROW_BYTES = NS * 128;
     const int lane = threadIdx.x & 63;
@@ -583,6 +603,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
     if (qrow < p.B)
         thr = (!MAXONLY && p.thr0) ? p.thr0[(size_t)qrow * p.thr0_stride + p.thr0_off] : -INFINITY;
     int cnt = 0; // the same value in the four lanes of a query
+    int nmatch = 0; // COUNT: this lane's documents with score >= thr (8 of a tile's 32 per lane quarter)
     float runmax = -INFINITY;
     Cand *const cbase = p.cand + ((size_t)task * 16 + n) * CAP;
 
@@ -693,7 +714,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
                 runmax = fmaxf(runmax, m);
                 continue;
             }
-            if (__ballot(m >= thr) != 0ull) {
+            if (COUNT) { // (see score_topk_kernel)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        nmatch += ((!partial || tile_base + 16 * u + 4 * kq + r < p.N) && kept(u, r) && acc[u][r] >= thr) ? 1 : 0;
+            }
+            if (!COUNT && __ballot(m >= thr) != 0ull) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -742,6 +770,13 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
             p.pval[o] = runmax;
             p.pidx[o] = t0 < t1 ? (int64_t)chunk : -1;
         }
+        return;
+    }
+    if (COUNT) {
+        nmatch += __shfl_xor(nmatch, 16);
+        nmatch += __shfl_xor(nmatch, 32);
+        if (kq == 0 && qrow < p.B)
+            p.pidx[(size_t)qrow * p.n_chunks + chunk] = nmatch;
         return;
     }
     {
@@ -1243,29 +1278,39 @@ constexpr bool score_dim_ok(int d, bool bf16)
 
 // The kernel families, for launch_ns: score_topk_kernel (32-query tiles) over fp32 and over bf16 rows, and
 // score_topk16_kernel (16-query tiles).
+// What a launch of the family does with the scores: the main pass's lists, the sample pass's maxima, or the counting pass.
+enum PassKind { PASS_LISTS, PASS_MAXONLY, PASS_COUNT };
+
 struct Score32 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
 };
 struct Score32Bf16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT>; }
     static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED>
-    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
 };
 
 template <class K, int NS, bool MASKED>
-int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
     const void *fn;
     size_t smem = pl.smem;
-    if (maxonly) {
+    if (kind == PASS_MAXONLY) {
         fn = K::template fn<NS, 64, true, false, MASKED>();
+    } else if (kind == PASS_COUNT) { // (the nt form under the main pass's own rule: one query tile at d = 256)
+        if (NS == 8 && sp.n_qtiles == 1) {
+            fn = K::template fn<8, 64, false, true, MASKED, true>();
+            smem = K::smem_nt;
+        } else {
+            fn = K::template fn<NS, 64, false, false, MASKED, true>();
+        }
     } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
         fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED>() : K::template fn<8, 128, false, true, MASKED>();
         smem = K::smem_nt;
@@ -1281,42 +1326,42 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxo
 
 // sp.keep set: the MASKED instantiation of the same kernel
 template <class K, int NS>
-int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly)
+int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
-    return sp.keep ? launch_ns_m<K, NS, true>(sp, pl, st, maxonly) : launch_ns_m<K, NS, false>(sp, pl, st, maxonly);
+    return sp.keep ? launch_ns_m<K, NS, true>(sp, pl, st, kind) : launch_ns_m<K, NS, false>(sp, pl, st, kind);
 }
 
-int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, bool maxonly, bool bf16)
+int launch_score(int d, const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind, bool bf16)
 {
     if (bf16) { // (score_dim_ok: 64 <= d <= 256, 32-query tiles at every B)
         switch (d) {
-        case 64: return launch_ns<Score32Bf16, 2>(sp, pl, st, maxonly);
-        case 128: return launch_ns<Score32Bf16, 4>(sp, pl, st, maxonly);
-        case 192: return launch_ns<Score32Bf16, 6>(sp, pl, st, maxonly);
-        default: return launch_ns<Score32Bf16, 8>(sp, pl, st, maxonly);
+        case 64: return launch_ns<Score32Bf16, 2>(sp, pl, st, kind);
+        case 128: return launch_ns<Score32Bf16, 4>(sp, pl, st, kind);
+        case 192: return launch_ns<Score32Bf16, 6>(sp, pl, st, kind);
+        default: return launch_ns<Score32Bf16, 8>(sp, pl, st, kind);
         }
     }
     if (d <= 256 && sp.B <= 16) { // half the MFMA work of a 32-query tile: the launch stays on the HBM roofline
         switch (d) {
-        case 32: return launch_ns<Score16, 1>(sp, pl, st, maxonly);
-        case 64: return launch_ns<Score16, 2>(sp, pl, st, maxonly);
-        case 96: return launch_ns<Score16, 3>(sp, pl, st, maxonly);
-        case 128: return launch_ns<Score16, 4>(sp, pl, st, maxonly);
-        case 192: return launch_ns<Score16, 6>(sp, pl, st, maxonly);
-        default: return launch_ns<Score16, 8>(sp, pl, st, maxonly);
+        case 32: return launch_ns<Score16, 1>(sp, pl, st, kind);
+        case 64: return launch_ns<Score16, 2>(sp, pl, st, kind);
+        case 96: return launch_ns<Score16, 3>(sp, pl, st, kind);
+        case 128: return launch_ns<Score16, 4>(sp, pl, st, kind);
+        case 192: return launch_ns<Score16, 6>(sp, pl, st, kind);
+        default: return launch_ns<Score16, 8>(sp, pl, st, kind);
         }
     }
     switch (d) {
-    case 320: return launch_ns<Score16, 10>(sp, pl, st, maxonly);
-    case 384: return launch_ns<Score16, 12>(sp, pl, st, maxonly);
-    case 448: return launch_ns<Score16, 14>(sp, pl, st, maxonly);
-    case 512: return launch_ns<Score16, 16>(sp, pl, st, maxonly);
-    case 32: return launch_ns<Score32, 1>(sp, pl, st, maxonly);
-    case 64: return launch_ns<Score32, 2>(sp, pl, st, maxonly);
-    case 96: return launch_ns<Score32, 3>(sp, pl, st, maxonly);
-    case 128: return launch_ns<Score32, 4>(sp, pl, st, maxonly);
-    case 192: return launch_ns<Score32, 6>(sp, pl, st, maxonly);
-    default: return launch_ns<Score32, 8>(sp, pl, st, maxonly);
+    case 320: return launch_ns<Score16, 10>(sp, pl, st, kind);
+    case 384: return launch_ns<Score16, 12>(sp, pl, st, kind);
+    case 448: return launch_ns<Score16, 14>(sp, pl, st, kind);
+    case 512: return launch_ns<Score16, 16>(sp, pl, st, kind);
+    case 32: return launch_ns<Score32, 1>(sp, pl, st, kind);
+    case 64: return launch_ns<Score32, 2>(sp, pl, st, kind);
+    case 96: return launch_ns<Score32, 3>(sp, pl, st, kind);
+    case 128: return launch_ns<Score32, 4>(sp, pl, st, kind);
+    case 192: return launch_ns<Score32, 6>(sp, pl, st, kind);
+    default: return launch_ns<Score32, 8>(sp, pl, st, kind);
     }
 }
 
@@ -1434,7 +1479,7 @@ int score_partials(const ExactCall &c, const Plan &pl, const ExactPass &ps)
         // (keep: the maxima are over the kept documents of the sample -- the first words of the mask -- and a chunk with none
         //  contributes -inf: only documents that may be returned vouch for the bound)
         ScoreParams pp = pass_params(pl.pre, c, ps.list_k, 0, pl);
-        int rc = launch_score(c.d, pp, pl, st, true, c.bf16);
+        int rc = launch_score(c.d, pp, pl, st, PASS_MAXONLY, c.bf16);
         if (rc != TT_OK)
             return rc;
         hipLaunchKernelGGL(kth_largest_kernel, dim3(c.B), dim3(256), 0, st, (const float *)pp.pval, pl.pre.n_chunks, c.k,
@@ -1470,7 +1515,7 @@ int score_partials(const ExactCall &c, const Plan &pl, const ExactPass &ps)
         TT_RC_CHECK(tt_zero_async(ws + pl.tailctr_off, pl.ctr_bytes, st));
     if (ps.prof_events)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)ps.prof_events[0], st));
-    const int rc = launch_score(c.d, sp, pl, st, false, c.bf16);
+    const int rc = launch_score(c.d, sp, pl, st, PASS_LISTS, c.bf16);
     if (ps.prof_events && rc == TT_OK)
         TT_HIP_CHECK(hipEventRecord((hipEvent_t)ps.prof_events[1], st));
     return rc;
@@ -1628,6 +1673,99 @@ TT_EXPORT int tt_score_topk_bf16(const float *Q, int B, int d, const void *D_bf1
 {
     return tt_score_topk_bf16_pred(Q, B, d, D_bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
                                    nullptr, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// The counting pass (DESIGN.md "Threshold search"): the COUNT instantiations of the two kernels over the main pass's cut of the
+// corpus, static split (every wave does the same work on every tile: nothing to steal for, and no pool draw means no give-up to
+// repair), paced like the main pass where that is paced; then range.hip's sum of the per-(query, chunk) integers.
+// ---------------------------------------------------------------------------
+namespace {
+struct CountPlan {
+    Plan pl;         // the k = 1 search's plan: its main pass's chunks and pacing (its workspace layout is not used)
+    size_t part_off; // int64 [B][n_chunks]
+    size_t pace_off; // the pacing slots + the time-out count (paced plans)
+    size_t ws_bytes;
+};
+
+CountPlan make_count_plan(int B, int64_t N, int d, bool bf16)
+{
+    CountPlan cp;
+    cp.pl = make_plan(B, N, 1, d, bf16);
+    TTWorkspace ws;
+    cp.part_off = ws.take((size_t)B * cp.pl.main.n_chunks * sizeof(int64_t));
+    cp.pace_off = ws.off;
+    if (cp.pl.paced)
+        ws.take(((size_t)cp.pl.main.n_chunks * PACE_R + 1) * sizeof(int));
+    cp.ws_bytes = ws.off;
+    return cp;
+}
+
+int score_count(const ExactCall &c, const float *min_score, int64_t *count, int accumulate)
+{
+    if (c.B < 0 || c.N < 0)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld", c.who, c.B, (long long)c.N);
+    if (c.B == 0)
+        return TT_OK;
+    if (!score_dim_ok(c.d, c.bf16))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: %s)", c.who, c.d, score_dims(c.bf16));
+    if (!count || ((uintptr_t)count & 7))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: count must be a non-null, 8-byte aligned pointer", c.who);
+    if (c.N == 0)
+        return tt_count_finish(nullptr, c.B, 0, count, accumulate, c.stream);
+    if (c.N >= (int64_t)INT_MAX - 64)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N=%lld >= 2^31-64; count block by block with accumulate", c.who, (long long)c.N);
+    if ((uintptr_t)c.keep & 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", c.who);
+    if (!c.Q || !c.D || !min_score)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", c.who);
+    const CountPlan cp = make_count_plan(c.B, c.N, c.d, c.bf16);
+    if (!c.workspace || c.workspace_bytes < cp.ws_bytes)
+        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", c.who, c.workspace_bytes, cp.ws_bytes);
+    if (((uintptr_t)c.D & 15) || (((uintptr_t)c.Q | (uintptr_t)min_score) & 3) || ((uintptr_t)c.workspace & 255))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: D must be 16-byte and the workspace 256-byte aligned", c.who);
+
+    char *ws = (char *)c.workspace;
+    const Plan &pl = cp.pl;
+    ScoreParams sp = pass_params(pl.main, c, 1, 0, pl); // (static split)
+    sp.pval = nullptr;
+    sp.cand = nullptr;
+    sp.pidx = (int64_t *)(ws + cp.part_off);
+    sp.thr0 = min_score;
+    sp.thr0_stride = 1;
+    if (pl.paced && tt_score_pacing()) {
+        sp.pace = (int *)(ws + cp.pace_off);
+        sp.pace_timeouts = sp.pace + (size_t)pl.main.n_chunks * PACE_R;
+        sp.pace_g = pl.pace_g;
+        sp.pace_lag = pl.pace_lag;
+        TT_RC_CHECK(tt_zero_async(sp.pace, ((size_t)pl.main.n_chunks * PACE_R + 1) * sizeof(int), c.stream));
+    }
+    TT_RC_CHECK(launch_score(c.d, sp, pl, c.stream, PASS_COUNT, c.bf16));
+    return tt_count_finish(sp.pidx, c.B, pl.main.n_chunks, count, accumulate, c.stream);
+}
+} // namespace
+
+TT_EXPORT size_t tt_score_count_workspace_bytes(int B, int64_t N, int d, int bf16)
+{
+    if (B <= 0 || N < 0)
+        return 0;
+    return make_count_plan(B, N, d, bf16 != 0).ws_bytes;
+}
+
+TT_EXPORT int tt_score_count_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep,
+                                 const float *min_score, int64_t *count, int accumulate, void *workspace,
+                                 size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_count(ExactCall{Q, B, d, D, false, N, 1, 0, keep, nullptr, nullptr, workspace, workspace_bytes,
+                                 (hipStream_t)stream, "tt_score_count_f32"}, min_score, count, accumulate);
+}
+
+TT_EXPORT int tt_score_count_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep,
+                                  const float *min_score, int64_t *count, int accumulate, void *workspace,
+                                  size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_count(ExactCall{Q, B, d, D_bf16, true, N, 1, 0, keep, nullptr, nullptr, workspace, workspace_bytes,
+                                 (hipStream_t)stream, "tt_score_count_bf16"}, min_score, count, accumulate);
 }
 
 // k-th largest of each row of vals [B][M] -> out [B] (internal: threshold seeding of both search paths)

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 
 __all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
-           "shard_bounds", "seed_union"]
+           "shard_bounds", "seed_union", "score_count", "topk_cut_below"]
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -262,6 +262,95 @@ def topk_exclude(vals: torch.Tensor, idx: torch.Tensor, exclude: torch.Tensor, k
         _lib.check(_lib.lib().tt_topk_exclude_ids(vals.data_ptr(), idx.data_ptr(), B, M, exclude.data_ptr(), exclude.shape[1], k,
                                                   ov.data_ptr(), oi.data_ptr(), _stream(vals)))
     return ov, oi
+
+
+def _min_score(min_score, B: int, device) -> torch.Tensor:
+    """The thresholds of a threshold search of B queries on `device` as the C calls read them (float32 [B], contiguous): a
+    Python number for every query, or a float32 [B] tensor on the device (a 0-d tensor or [1] for a single query vector)."""
+    if isinstance(min_score, torch.Tensor):
+        if min_score.dtype != torch.float32:
+            raise TypeError(f"min_score must be a float or a float32 tensor, got {min_score.dtype}")
+        if min_score.device != device:
+            raise ValueError(f"min_score on {min_score.device} but the search runs on {device}")
+        if min_score.dim() == 0 and B == 1:
+            min_score = min_score.reshape(1)
+        if tuple(min_score.shape) != (B,):
+            raise ValueError(f"min_score must be one threshold per query, [B] = [{B}], got {tuple(min_score.shape)}")
+        return min_score if min_score.is_contiguous() else min_score.contiguous()
+    if isinstance(min_score, bool) or not isinstance(min_score, (int, float)):
+        raise TypeError(f"min_score must be a float or a float32 tensor, got {type(min_score).__name__}")
+    return torch.full((B,), float(min_score), dtype=torch.float32, device=device)
+
+
+def _count_into(q: torch.Tensor, docs: torch.Tensor, thr: torch.Tensor, keep: Optional[torch.Tensor], count: torch.Tensor,
+                accumulate: bool) -> None:
+    """tt_score_count_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, thr [B] f32, keep a checked
+    keep-bitmask or None, count int64 [B] (added to when `accumulate`)."""
+    B, d = q.shape
+    N = docs.shape[0]
+    bf16 = docs.dtype == torch.bfloat16
+    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
+        L = _lib.lib()
+        ws = torch.empty(max(L.tt_score_count_workspace_bytes(B, N, d, int(bf16)), 16), dtype=torch.uint8, device=q.device)
+        fn = L.tt_score_count_bf16 if bf16 else L.tt_score_count_f32
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, None if keep is None else keep.data_ptr(), thr.data_ptr(),
+                      count.data_ptr(), int(accumulate), ws.data_ptr(), ws.numel(), _stream(q)))
+
+
+def score_count(q: torch.Tensor, docs: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(q @ docs.T >= min_score).sum(1) fused: int64 [B] (0-d for a single query [d]), the number of documents whose score --
+    score_topk's fp32 chain, bit for bit -- is at least the query's threshold.  min_score: a Python float, or a float32 [B]
+    device tensor (one threshold per query); NaN counts nothing, -inf counts every (kept) document.  docs float32 or
+    bfloat16 like score_topk's; keep: a packed keep-bitmask (pack_keep_mask) -> only the kept documents are counted.  One
+    pass of the exact kernel over docs in its counting mode (tt_score_count_f32 / _bf16): the cost of an exact search."""
+    if q.dim() == 1:
+        return score_count(q.unsqueeze(0), docs, min_score, keep)[0]
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), _docs_c(docs)
+    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    thr = _min_score(min_score, q.shape[0], q.device)
+    if keep is not None:
+        keep = _check_keep(keep, docs.shape[0], docs.device)
+    count = torch.empty(q.shape[0], dtype=torch.int64, device=q.device)
+    _count_into(q, docs, thr, keep, count, False)
+    return count
+
+
+def topk_cut_below(vals: torch.Tensor, idx: torch.Tensor, min_score) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cut sorted top-k rows at a per-query threshold, IN PLACE: every entry of row b of vals f32 / idx int64 [B,k] that is
+    not >= min_score[b] (or is padding) becomes (-inf, -1) (tt_topk_cut_below, one launch).  Returns (vals, idx)."""
+    _need_cuda(vals, idx)
+    if (vals.dtype != torch.float32 or idx.dtype != torch.int64 or vals.shape != idx.shape or vals.dim() != 2
+            or not vals.is_contiguous() or not idx.is_contiguous()):
+        raise ValueError("topk_cut_below wants contiguous vals f32 [B,k] and idx int64 [B,k]")
+    B, k = vals.shape
+    thr = _min_score(min_score, B, vals.device)
+    if B and k:
+        with torch.cuda.device(vals.device):
+            _lib.check(_lib.lib().tt_topk_cut_below(vals.data_ptr(), idx.data_ptr(), B, k, thr.data_ptr(), _stream(vals)))
+    return vals, idx
+
+
+def _range_search(index, q: torch.Tensor, min_score, k: int, keep: Optional[torch.Tensor]):
+    """range_search of every index: its count, and its own search for k cut at the thresholds."""
+    if q.dim() == 1:
+        c, v, i = _range_search(index, q.unsqueeze(0), min_score, k, keep)
+        return c[0], v[0], i[0]
+    _need_cuda(q)
+    thr = _min_score(min_score, q.shape[0], index.device)
+    counts = index.count(q, thr, keep=keep)
+    vals, idx = index.search(q, k, keep=keep)
+    vals, idx = topk_cut_below(vals.contiguous(), idx.contiguous(), thr)
+    return counts, vals, idx
+
+
+_RANGE_DOC = """(counts int64 [B], vals f32 [B,k], idx int64 [B,k]): counts[b] = the number of (kept, not removed) documents with
+        score >= min_score[b] (count()), and row b = search(q, k, keep=keep) -- whatever route this index takes -- with the
+        entries below the threshold replaced by the (-inf, -1) tail: min(counts[b], k) real entries, the best of the
+        counts[b] matches, in the usual order.  min_score: a float, or a float32 [B] device tensor.  exclude= is not taken.
+        Cost: the rows are the search's; the count is one more pass of the EXACT kernel over the corpus whatever route the
+        search took -- on a screened index at B = 1024 that is tens of ms next to a search of a few ms."""
 
 
 def score_rank(q: torch.Tensor, docs: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -507,6 +596,21 @@ class BruteForceIndex:
             out[1].copy_(i)
             return out
         return v, i
+
+    def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 [B] (0-d for a single query): how many documents of this index -- not removed (remove_ids), and kept by
+        `keep` when given -- score at least min_score (a float, or a float32 [B] device tensor) for each query.  The scores
+        are the ones search() returns, bit for bit, so a returned entry at the threshold is always counted.  One exact pass
+        over the rows (score_count), also on a screen=True index."""
+        _need_cuda(q)
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        return score_count(q, self.docs, min_score, _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device))
+
+    def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
+        return _range_search(self, q, min_score, k, keep)
+
+    range_search.__doc__ = _RANGE_DOC
 
     def _screens(self, B: int, k: int, masked: Optional[bool] = None) -> bool:
         """Whether a search of B queries for k takes the screened path.  ShardedIndex's ranks decide by this same rule
@@ -961,6 +1065,31 @@ class ShardedIndex:
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
 
+    def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The count of the whole corpus, identical on every rank: this rank's count over its shard under its mask (keep: over
+        THIS RANK'S rows, on all ranks or on none, as in search()), then one all_reduce(SUM) of the int64 [B] on the index's
+        group.  A COLLECTIVE: every rank calls it at the same point."""
+        counts = self._index.count(q, min_score, keep=keep)
+        if self._coll.world > 1:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' counts and add)
+                recv = torch.empty((self._coll.world,) + tuple(counts.shape), dtype=torch.int64, device=counts.device)
+                self._coll.all_gather_blocks(counts.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
+                counts = recv.sum(0)
+        return counts
+
+    def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
+        return _range_search(self, q, min_score, k, keep)
+
+    range_search.__doc__ = _RANGE_DOC + """
+        Sharded: counts are count()'s (one all_reduce), the rows the sharded search()'s, cut on every rank alike."""
+
+    @property
+    def device(self) -> torch.device:
+        return self._dev
+
     def submit(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
                exclude: Optional[torch.Tensor] = None) -> PendingSearch:
         """Pipelined search of a [B,d] batch: the local search is enqueued on the caller's stream now; its list exchange and
@@ -1125,3 +1254,34 @@ class StreamedIndex:
             out[1].copy_(run[1])
             return out
         return run[0], run[1]
+
+    def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 [B] (0-d for a single query): the documents of the whole corpus (not removed, kept by `keep`: a mask over the
+        whole corpus, on the device) scoring at least min_score.  The walk counts every block with the counting pass, adding
+        into one tensor (accumulate) under the block's slice of the mask; masked, block_docs must be a multiple of 32 as in
+        search().  The blocks are the widened fp32 rows (bf16 -> fp32 is exact): the count of the resident index."""
+        _need_cuda(q)
+        if q.dim() == 1:
+            return self.count(q.unsqueeze(0), min_score, keep)[0]
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        q = _f32c(q)
+        thr = _min_score(min_score, q.shape[0], self.device)
+        keep = _and_keep(self._keep, keep, self.N, self.device)
+        if keep is not None and self.block % 32 and self.N > self.block:
+            raise ValueError(f"a masked StreamedIndex count needs block_docs to be a multiple of 32, got {self.block}")
+        counts = torch.zeros(q.shape[0], dtype=torch.int64, device=self.device)
+
+        def visit(s, lo, n):
+            _count_into(q, self._d32[s][:n], thr, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], counts, True)
+
+        self._walk(visit)
+        return counts
+
+    def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
+        return _range_search(self, q, min_score, k, keep)
+
+    range_search.__doc__ = _RANGE_DOC + """
+        Streamed: two walks over the host rows, one for the rows and one for the counts."""
