@@ -32,13 +32,30 @@
 //                         HBM streaming of the fp16 copy (N * 512 B)
 // The accumulators start at minus the query's threshold, so "any candidate in this wave-tile?" is one integer max.
 //
+// Seed.  A sample pass (the MAXONLY kernels over the first s_docs rows) gives the main pass its first threshold.  Streaming
+// form: one maximum per 32-document sample tile, the seed is the k-th largest of them.  Shared-tile form (ONCHIP): the seed is
+// the k-th largest of the KEPT SLICE MAXIMA.  A lane (n,g) of a wave holds, for a query, the scores of 8 documents of every
+// tile -- rows 16u + 4g + r, a slice; the slices partition the sample -- and keeps the STOP = 2 largest slice maxima of its
+// workgroup's tiles in registers (compare-and-swap on float order, entries start at -inf, rows at or beyond N and masked
+// documents count as -inf).  Nothing is shuffled or stored in the tile loop; behind it every lane stores its STOP values
+// once, [query][(chunk * 4 + g) * STOP + j], and the same select runs over those M = 4 STOP s_chunks <= 2048 values, from
+// registers (the per-tile matrix was 4 883 values per query at 10M rows: 20 MB written, read back in four dependent passes).
+// Validity: every kept value is the s16 of a document of its slice (the integer-max shortcut of full tiles still returns the
+// score of a real document), different entries come from different slices, hence from different documents; so at least k
+// distinct (kept) documents reach the k-th largest value of the union, which is all the A_k argument of step 1 uses.  With
+// fewer than k finite values the select returns -inf and the floor threshold applies.  What the list can lose: when more than
+// STOP of a query's k best slices meet in one of its 4 s_chunks streams (512 at B = 1024: about C(10,3) / 512^2 = 5e-4 per
+// query at k = 10) the seed sits one rank lower -- a slightly weaker filter, never a wrong result; and slices are finer than
+// tiles, so two of the k best in one tile now count twice (N = 1M, B = 1024, k = 10: 278.26 pooled candidates per query against
+// 278.70, profiles/sample_onchip.md).  Below STOP_MIN_CHUNKS sample chunks (B beyond 2048 on 256 CUs) the per-tile maxima stay.
+//
 // Under a keep-bitmask (MASKED instantiations; tt_score_topk_screened_masked_f32 and its kin).  Let K be the kept documents.
 // A document's s16 and its exact score s depend on no other document, and |s16 - s| <= eps_q holds pair by pair; the
 // guarantee of step 1 never uses tile or chunk boundaries.  Applied to the corpus D[K] it reads: a kept document can be in
 // the exact top-k of K only if s16 >= A_k^K - 2 eps_q, A_k^K the k-th largest approximate score over any subset of K.  So it
 // is enough that every quantity used as an A_k is formed from kept documents only.  There are three: (1) the sample maxima
-// -- the seed is the k-th largest tile maximum, "k distinct kept documents reach this", and a tile with nothing kept
-// contributes -inf; (2) the running k-th of a workgroup's candidate buffer (screen_compact); (3) the pooled A_k of
+// -- the seed is the k-th largest tile (shared-tile form: kept slice) maximum, "k distinct kept documents reach this", and a
+// tile or slice with nothing kept contributes -inf; (2) the running k-th of a workgroup's candidate buffer (screen_compact); (3) the pooled A_k of
 // screen_finish_kernel.  (2) and (3) see only what the append pass stored, so forcing a masked document's accumulators to
 // -inf before either epilogue looks at them gives all three, with the finish kernel unchanged: the mechanism of the
 // `partial` branch (rows at or beyond N), taken by every tile whose keep word is not all ones.  Masking the append pass
@@ -74,6 +91,8 @@ constexpr int SURV_MAX = 1024;        // survivors per query the finish kernel c
                                       // corpus the predicated exact kernel then cost more than the screen saved: DESIGN K4s)
 constexpr int POOL_MAX = 8192;        // candidates per query the finish kernel can pool
 constexpr int FIN_MAX_CHUNKS = 2048;  // document chunks per query the finish kernel can pool
+constexpr int STOP = 2;               // sample pass, shared-tile form: slice maxima a lane keeps per query (header, "Seed")
+constexpr int STOP_MIN_CHUNKS = 64;   // ... when the sample has at least this many chunks (256 streams per query)
 
 struct SCand {
     float v;
@@ -138,7 +157,10 @@ struct ScreenParams {
     int *flag;     // overflow / unsupported -> exact fallback
     // sample pass (MAXONLY): per-(tile, query) maximum approximate score
     float *max_val;      // [rows_pad][n_tiles]
-    const float *thr0;   // main pass: k-th largest sample maximum per query, stride thr0_stride (or null)
+    // sample pass of the shared-tile form: instead of max_val, every lane's STOP largest slice maxima, stored once after the
+    // last tile at top_val[query][(chunk * 4 + g) * STOP + j] (row stride n_chunks * 4 * STOP); null: per-tile maxima
+    float *top_val;
+    const float *thr0;  // main pass: k-th largest sample maximum per query, stride thr0_stride (or null)
     int thr0_stride;
     // queries as MFMA B operands, prepared once per search by q_image_kernel:
     // qimg[((S * 8 + s) * 64 + lane)] = 8 f16 of query 16 S + (lane & 15), features 32 s + 8 (lane >> 4) .. +7
@@ -295,7 +317,9 @@ __global__ __launch_bounds__(128) void q_image_kernel(const float *__restrict__ 
 // epilogue (accumulators -> -inf, what `partial` does to the rows at or beyond N), in the main pass and in the sample pass
 // alike; a tile whose word is 0 skips the append pass (every accumulator is -inf).  The word is wave-uniform and read by keep_word_issue under the
 // tile's MFMAs -- never a compiler-visible global access in the tile loop, which would drain the DMA ring.
-template <bool MAXONLY, int NSET, bool BF = false, bool MASKED = false>
+// ONCHIP (with MAXONLY; the product's sample pass): p.top_val instead of p.max_val.  A template mode because the run-time test
+// cost screen_kernel<true, 4> -- 246 VGPRs without it -- 12 to 36 bytes of scratch per lane.
+template <bool MAXONLY, int NSET, bool BF = false, bool MASKED = false, bool ONCHIP = false>
 __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char ring[]; // [SRING][STILE_BYTES]
@@ -402,6 +426,16 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
         __builtin_amdgcn_global_load_lds((gbl_void *)rowp[i], (lds_void *)dst, 16, 0, DMA_AUX);
     };
 
+    // ONCHIP: lane (n,g) sees, for query set c, the scores of 8 documents of every
+    // tile (rows 16u + 4g + r: a SLICE) and keeps the STOP largest slice maxima of its workgroup's tiles here, best first.  No
+    // shuffle and no store in the tile loop; one store per lane behind it.
+    float top[ONCHIP ? NSET : 1][STOP];
+#pragma unroll
+    for (int c = 0; c < (ONCHIP ? NSET : 1); ++c)
+#pragma unroll
+        for (int j = 0; j < STOP; ++j)
+            top[c][j] = -INFINITY;
+
     for (;;) { // segments: the own range, then pool blocks
     if (t0 < t1) {
         // DMA runs SRING - STPB tiles ahead; one barrier per STPB tiles.
@@ -494,7 +528,7 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                 }
             } else {
 #pragma unroll
-                for (int c = 0; c < NSET; ++c) { // one maximum per (tile, query): the k-th largest of them seeds the thresholds
+                for (int c = 0; c < NSET; ++c) { // one maximum per (tile, query), or per (slice, query) into the lane's list (ONCHIP)
                     float m = -INFINITY;
                     if (!partial && !holes) {
                         // signed-integer max of the raw bits = the float max when any value is >= 0, else the
@@ -514,6 +548,16 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
                                 m = fmaxf(m, !dropped(u, r) ? acc[u][c][r] : -INFINITY);
+                    }
+                    if (ONCHIP) { // m = this slice's maximum: compare-and-swap into the lane's list
+#pragma unroll
+                        for (int j = 0; j < STOP; ++j) {
+                            float &t = top[ONCHIP ? c : 0][j];
+                            const float hi = fmaxf(t, m);
+                            m = fminf(t, m);
+                            t = hi;
+                        }
+                        continue;
                     }
                     m = fmaxf(m, __shfl_xor(m, 16));
                     m = fmaxf(m, __shfl_xor(m, 32));
@@ -633,8 +677,21 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier(); // no wave may leave while a sibling's LDS-DMA could still be consumed
 
-    if (MAXONLY)
+    if (MAXONLY) {
+        if (ONCHIP) {
+#pragma unroll
+            for (int c = 0; c < NSET; ++c) {
+                const int qrow = qbase + 16 * c + n;
+                if (qrow < p.B) {
+                    float *dst = p.top_val + ((size_t)qrow * p.n_chunks + chunk) * (4 * STOP) + g * STOP;
+#pragma unroll
+                    for (int j = 0; j < STOP; ++j)
+                        dst[j] = top[ONCHIP ? c : 0][j];
+                }
+            }
+        }
         return;
+    }
     // final compaction (bounds the pool the finish kernel sees) and counts out: quarter g's count in byte g
 #pragma unroll
     for (int c = 0; c < NSET; ++c) {
@@ -935,11 +992,14 @@ __device__ __forceinline__ float f32_from_order_key(unsigned k)
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-__global__ __launch_bounds__(256) void screen_finish_kernel(FinishParams p)
+// Four workgroups per CU, so that the B = 1024 workgroups of the bench step are one round on 256 CUs (three per CU -- 43 296 B
+// of LDS, 140 VGPRs -- made it a round and a third: 44.1 -> 31.9 us, profiles/sample_onchip.md): 39 200 B static + 1 028 B
+// dynamic at 128 chunks <= 40 960 B, and the launch bound holds the registers at 128 or fewer (92, no scratch).
+__global__ __launch_bounds__(256, 4) void screen_finish_kernel(FinishParams p)
 {
     __shared__ float pool_v[POOL_MAX];
     __shared__ float qs[256];
-    __shared__ float sv_v[SURV_MAX];
+    float *const sv_v = pool_v; // [SURV_MAX]: the pool is dead behind the survivor selection, whose closing barrier precedes the first write
     __shared__ int sv_x[SURV_MAX];
     __shared__ float red_v[4];
     __shared__ int hist[256];
@@ -1013,8 +1073,7 @@ __global__ __launch_bounds__(256) void screen_finish_kernel(FinishParams p)
     if (total > POOL_MAX)
         too_many = true;
     // pooled position m -> its entry in the candidate buffers (chunk by binary search, then quarter and slot).
-    // Only the scores are pooled in LDS (52 KB per workgroup -> three workgroups per CU); the few survivors
-    // fetch their document index through the same mapping.
+    // Only the scores are pooled in LDS; the few survivors fetch their document index through the same mapping.
     auto locate = [&](int m) -> const SCand * {
         int lo = 0, hi = p.n_chunks; // largest c with pre[c] <= m
         while (hi - lo > 1) {
@@ -1276,6 +1335,8 @@ struct SPlan {
     bool sample;
     int s_tiles, s_chunks, s_tiles_per_chunk;
     int64_t s_docs;
+    bool s_onchip; // the sample pass keeps its maxima in registers (ScreenParams::top_val)
+    int s_vals;    // values per query the seed is selected from: s_chunks * 4 * STOP kept slice maxima, or s_tiles tile maxima
     size_t cand_off, pcnt_off, smax_val_off, sthr_val_off, qimg_off, qnorm_off, stats_off, ws_bytes;
     int rows_pad; // n_qgroups * q_per_block
 };
@@ -1339,15 +1400,26 @@ SPlan make_splan(int B, int64_t N, int k)
     const TTChunks sc = tt_chunks(pl.s_tiles, one_round(pl.stream, pl.n_qgroups), INT_MAX); // one maximum per TILE
     pl.s_tiles_per_chunk = sc.tiles_per_chunk;
     pl.s_chunks = pl.sample ? sc.n_chunks : 0;
+    // Shared-tile form: 4 s_chunks lanes ("streams") share a query's sample, each keeps STOP maxima.  With few streams (B beyond
+    // 2048 on 256 CUs) several of a query's k best slices would often meet in one and the seed would sink by more than a rank:
+    // the per-tile maxima stay.  (TT_SCREEN_SAMPLE_ONCHIP = 0, comparison build only: the per-tile maxima at every size.)
+    // The kept maxima are dead once the seed is selected and the candidate buffers are first written by the main pass, so the
+    // former lie in the latter (n_chunks KiB per query against 32 s_chunks bytes: it fits wherever both passes get a round of
+    // chunks) and the workspace has no sample buffer of its own in this form.
+    const size_t cand_bytes = (size_t)n_tasks * pl.q_per_block * SCAP * sizeof(SCand);
+    pl.s_onchip = pl.sample && !pl.stream && pl.s_chunks >= STOP_MIN_CHUNKS && TT_AB_SWITCH(TT_SCREEN_SAMPLE_ONCHIP, 1) != 0 &&
+                  rows * (size_t)pl.s_chunks * 4 * STOP * sizeof(float) <= cand_bytes;
+    pl.s_vals = pl.s_onchip ? pl.s_chunks * 4 * STOP : pl.s_tiles;
     TTWorkspace ws;
-    pl.cand_off = ws.take((size_t)n_tasks * pl.q_per_block * SCAP * sizeof(SCand));
+    pl.cand_off = ws.take(cand_bytes);
     pl.pcnt_off = ws.take(rows * pl.n_chunks * sizeof(int));
-    pl.smax_val_off = ws.take(rows * (size_t)(pl.sample ? pl.s_tiles : 1) * sizeof(float));
     pl.sthr_val_off = ws.take(rows * sizeof(float));
     pl.qimg_off = ws.take(rows * 256 * sizeof(_Float16));
     pl.qnorm_off = ws.take(rows * sizeof(float));
     pl.tailctr_off = ws.take((size_t)pl.n_qgroups * sizeof(int));
     pl.stats_off = ws.take(rows * 2 * sizeof(int));
+    // (last: the one buffer that depends on the form of the sample pass, so every other offset is the same in both)
+    pl.smax_val_off = pl.s_onchip ? pl.cand_off : ws.take(rows * (size_t)(pl.sample ? pl.s_tiles : 1) * sizeof(float));
     pl.ws_bytes = ws.off;
     return pl;
 }
@@ -1355,17 +1427,17 @@ SPlan make_splan(int B, int64_t N, int k)
 // The screen kernel of one form: streaming (q_per_block 32 or 64: 2 or 4 query sets per wave) or shared-tile (nset 16-query
 // sets per wave, 1..4).  MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).
 // BF: the corpus is bf16 rows, converted in LDS (bf16_to_f16_lds).  MASKED: under p.keep.
-template <bool MAXONLY, bool BF, bool MASKED>
+template <bool MAXONLY, bool BF, bool MASKED, bool ONCHIP = false>
 const void *screen_fn(bool stream, int q_per_block, int nset)
 {
     if (stream)
         return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4, BF, MASKED>
                                  : (const void *)screen_stream_kernel<MAXONLY, 2, BF, MASKED>;
     switch (nset) {
-    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF, MASKED>;
-    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF, MASKED>;
-    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF, MASKED>;
-    default: return (const void *)screen_kernel<MAXONLY, 1, BF, MASKED>;
+    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF, MASKED, ONCHIP>;
+    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF, MASKED, ONCHIP>;
+    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF, MASKED, ONCHIP>;
+    default: return (const void *)screen_kernel<MAXONLY, 1, BF, MASKED, ONCHIP>;
     }
 }
 
@@ -1375,12 +1447,22 @@ const void *screen_fn(bool stream, int q_per_block, int nset, bool masked)
     return masked ? screen_fn<MAXONLY, BF, true>(stream, q_per_block, nset) : screen_fn<MAXONLY, BF, false>(stream, q_per_block, nset);
 }
 
+// the sample pass of the shared-tile form with its maxima kept in registers (p.top_val)
+template <bool BF>
+const void *screen_onchip_fn(int nset, bool masked)
+{
+    return masked ? screen_fn<true, BF, true, true>(false, 0, nset) : screen_fn<true, BF, false, true>(false, 0, nset);
+}
+
 // One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
-// masked: the MASKED instantiation (p.keep is set); otherwise p.keep is not read.
+// masked: the MASKED instantiation (p.keep is set); otherwise p.keep is not read.  p.top_val (maxonly, shared-tile): ONCHIP.
 int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st,
                   bool bf16 = false, bool masked = false)
 {
-    const void *fn = maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset, masked) : screen_fn<true, false>(stream, q_per_block, nset, masked))
+    if (p.top_val && (!maxonly || stream))
+        return tt_fail(TT_ERR_UNSUPPORTED, "launch_screen: top_val outside the shared-tile sample pass");
+    const void *fn = p.top_val ? (bf16 ? screen_onchip_fn<true>(nset, masked) : screen_onchip_fn<false>(nset, masked))
+                     : maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset, masked) : screen_fn<true, false>(stream, q_per_block, nset, masked))
                              : (bf16 ? screen_fn<false, true>(stream, q_per_block, nset, masked) : screen_fn<false, false>(stream, q_per_block, nset, masked));
     const size_t lds = stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
     const int blocks = stream ? (n_tasks + TW - 1) / TW : n_tasks;
@@ -1520,6 +1602,7 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     sp.pcnt = (int *)(ws + pl.pcnt_off);
     sp.flag = fallback_flag;
     sp.max_val = nullptr;
+    sp.top_val = nullptr;
     sp.thr0 = nullptr;
     sp.thr0_stride = k;
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
@@ -1543,13 +1626,14 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
             ss.tiles_per_chunk = pl.s_tiles_per_chunk;
             ss.static_tiles = pl.s_tiles;
             ss.tail_blocks = 0;
-            ss.max_val = (float *)(ws + pl.smax_val_off);
+            float *const s_val = (float *)(ws + pl.smax_val_off); // [rows][s_vals]
+            (pl.s_onchip ? ss.top_val : ss.max_val) = s_val;
             // (masked: the sample is the first s_docs rows, its words the first s_tiles of the mask)
             TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st, bf16, masked));
             if (phase == Phase::SeedList)
-                TT_RC_CHECK(tt_k_largest_list(ss.max_val, B, pl.s_tiles, k_seed, seed, st));
+                TT_RC_CHECK(tt_k_largest_list(s_val, B, pl.s_vals, k_seed, seed, st));
             else
-                TT_RC_CHECK(tt_kth_largest(ss.max_val, B, pl.s_tiles, k_thr, thr_out, st));
+                TT_RC_CHECK(tt_kth_largest(s_val, B, pl.s_vals, k_thr, thr_out, st));
             sp.thr0 = (const float *)(ws + pl.sthr_val_off);
             sp.thr0_stride = 1;
         } else if (seed_only) {
@@ -1825,6 +1909,7 @@ int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_n
     sp.pcnt = nullptr;
     sp.flag = (int *)(ws + pl.flag_off);
     sp.max_val = out_t; // [B][n_tiles]
+    sp.top_val = nullptr;
     sp.thr0 = nullptr;
     sp.thr0_stride = 1;
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
