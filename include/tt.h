@@ -255,7 +255,9 @@ int tt_score_topk_screened_f32(const float *Q, int B, int d, const float *D32, c
  *                                         kernels; writes this shard's documents above the global threshold (up to k, best first,
  *                                         the rest padded with -inf / -1): merged over the shards they contain the exact global
  *                                         top-k_seed (any valid lower bound works as seed[]: a single shard's own, or the union's)
- * Both calls take the SAME (B, N, k), flags and workspace; nothing else may use the workspace in between.
+ * Both calls take the SAME (B, N, k), flags and workspace; nothing else may use the workspace in between.  ONE seeded call
+ * per seed / seed_list call on a given workspace: the seed phase zeroes the workspace's pool counters and per-query threshold
+ * ladders, the seeded call consumes them (a second seeded call would draw no pool block and would count every document twice).
  */
 int tt_score_topk_screened_seed_f32(const float *Q, int B, int d, const void *D16, int64_t N, int k, int k_seed, float dmax_norm,
                                     int32_t *fallback_flag, float *seed /*[B] out*/, void *workspace, size_t workspace_bytes,

@@ -49,6 +49,33 @@
 // tiles, so two of the k best in one tile now count twice (N = 1M, B = 1024, k = 10: 278.26 pooled candidates per query against
 // 278.70, profiles/sample_onchip.md).  Below STOP_MIN_CHUNKS sample chunks (B beyond 2048 on 256 CUs) the per-tile maxima stay.
 //
+// Refresh (shared-tile main pass; SPlan::refresh: a seed, and chunks of REFRESH_MIN_TILES tiles or more).  Left alone every
+// threshold stays at its seed for the whole pass: a workgroup sees N / n_chunks documents per query, fewer than the sample did,
+// so its own running k-th never beats the seed, and at k = 10 12 % of the wave-tiles (48 % at k = 50) leave the fast path for
+// candidates the finish kernel throws away.  The chip as a whole knows better: after a fraction f of the pass it has scored f N
+// documents per query.  So every query has a LADDER of REFRESH_LEVELS counters in the workspace (ScreenParams::hist, zeroed by
+// q_image_kernel), level j standing for the edge  e_j = base + (j - 1/4) w,  base = the query's initial threshold + 2 eps_q (the
+// seed, whoever supplied it), w = REFRESH_STEP * 2 eps_q; every workgroup derives both from the same inputs.  The append path
+// counts a lane's best stored candidate of a tile and query set, v >= base, at level min(L - 1, int((v - base) * (1 / w))) with
+// one no-return atomic; at checkpoints T/32 .. T/2 into its own range of T tiles, and before every pool block, each wave reads
+// its queries' ladders past the XCD's caches, sums them from the top level down, and raises the threshold to e_j - 2 eps_q for
+// the highest level j whose suffix count reaches k (compaction raises with max as well; nothing ever lowers a threshold).
+// Validity: every count is a distinct document of that query -- chunks and pool blocks partition the tiles, each (document,
+// query) pair is scored once, and a lane counts at most one document per tile.  A count at level j' >= j means
+// fl(fl(v - base) * fl(1 / w)) >= j, hence v - base >= j w (1 - 2^-20) >= (j - 1/8) w for j <= 15: three roundings of 2^-24 and a
+// reciprocal within 2^-22 against a margin of w / 8, and the reader's fl(fma(j - 1/4, w, base)) lies below that by w / 8 less
+// half an ulp of a score, thousands of times smaller than w >= 4e-6 (|q| + Dmax) (widths below 1e-30 count nothing).  So a
+// suffix count >= k at level j means k distinct documents with s16 >= e_j: A_k >= e_j for that subset of the corpus, and
+// every true top-k document has s16 >= e_j - 2 eps_q, the argument of step 1.  A stale view of the counters, candidates that a
+// later compaction drops, documents a lane did not count (two candidates of one query among a lane's 8 documents of a tile)
+// and visibility delays between XCDs only make the threshold lower, never wrong; no workgroup waits for another.  Under a
+// keep-bitmask this is a fourth quantity formed from kept documents only: masked documents and rows at or beyond N are -inf
+// before the append path sees them.  With lists of k = 50 seeded for k_seed = 10 (sharded search) the ladder is compared with
+// p.k = 50: valid and conservative.  Results are bit-identical with and without; the pooled-candidate statistics depend on
+// timing once the refresh is active, which is why the gate stays above the chunk lengths whose statistics tests compare.
+// Measured (profiles/thr_refresh.md): 10M rows, B = 1024: 737 -> 98 pooled candidates per query at k = 10, 3669 -> 476 at
+// k = 50; on 306-tile chunks (1.25M-row shard) the checkpoints cost more than they save, hence the gate.
+//
 // Under a keep-bitmask (MASKED instantiations; tt_score_topk_screened_masked_f32 and its kin).  Let K be the kept documents.
 // A document's s16 and its exact score s depend on no other document, and |s16 - s| <= eps_q holds pair by pair; the
 // guarantee of step 1 never uses tile or chunk boundaries.  Applied to the corpus D[K] it reads: a kept document can be in
@@ -93,6 +120,13 @@ constexpr int POOL_MAX = 8192;        // candidates per query the finish kernel 
 constexpr int FIN_MAX_CHUNKS = 2048;  // document chunks per query the finish kernel can pool
 constexpr int STOP = 2;               // sample pass, shared-tile form: slice maxima a lane keeps per query (header, "Seed")
 constexpr int STOP_MIN_CHUNKS = 64;   // ... when the sample has at least this many chunks (256 streams per query)
+// Threshold refresh of the shared-tile main pass (header, "Refresh"): a ladder of REFRESH_LEVELS counters per query; a score
+// v >= base is counted at level min(L - 1, floor((v - base) / w)), w = REFRESH_STEP * 2 eps_q, and level j stands for the edge
+// base + (j - 1/4) w at the reader
+constexpr int REFRESH_LEVELS = 16;       // four per lane (n,g): one 16-byte group of the query's ladder
+constexpr int REFRESH_STEP = 2;          // level width in units of 2 eps_q
+constexpr int REFRESH_FIRST_SHIFT = 5;   // checkpoints at T >> 5, T >> 4, .. T >> 1 tiles into a workgroup's own range of T tiles
+constexpr int REFRESH_MIN_TILES = 1024;  // chunks shorter than this do not refresh (SPlan::refresh)
 
 struct SCand {
     float v;
@@ -151,6 +185,10 @@ struct ScreenParams {
     // atomicAdd) once their own range is done.  static_tiles == n_tiles, tail_blocks == 0: everything static.
     int static_tiles, tail_g, tail_blocks;
     int *tail_ctr; // [n_qgroups], zeroed by q_image_kernel
+    // Shared-tile main pass with a seed and long own ranges (SPlan::refresh), else null: hist[query][REFRESH_LEVELS], the chip-wide
+    // count of stored candidates per threshold level, zeroed by q_image_kernel (Seeded phase: by the seed phase's, so one
+    // seeded call per seed call on a workspace -- the contract tail_ctr already has, include/tt.h)
+    unsigned *hist;
     float dmax;
     SCand *cand;   // [n_blocks][512][SCAP]
     int *pcnt;     // [rows_pad][n_chunks]
@@ -180,6 +218,23 @@ __device__ __forceinline__ void scand_store_async(const SCand *base, unsigned by
     const unsigned long long bits = ((unsigned long long)(unsigned)x << 32) | (unsigned long long)__float_as_uint(v);
     asm volatile("global_store_dwordx2 %0, %1, %2\n\ts_nop 1" ::"v"(byte_off), "v"(bits), "s"(base) : "memory");
 }
+
+// hist[...] += 1 at wave-uniform base + per-lane byte offset: no-return, agent scope (the encoding hipcc gives atomicAdd), and
+// like the stores above invisible to the compiler's vmcnt bookkeeping
+__device__ __forceinline__ void u32_inc_async(const unsigned *base, unsigned byte_off)
+{
+    asm volatile("global_atomic_add %0, %1, %2\n\ts_nop 0" ::"v"(byte_off), "v"(1u), "s"(base) : "memory");
+}
+
+// The ladder of a query (header, "Refresh"): the edge level j stands for at the reader, a quarter of a level below base + j w,
+// and the level a stored score v >= base is counted at by the writer -- a count at level j or above implies v >= edge j with a
+// margin of w / 8 over every rounding of the two expressions.
+__device__ __forceinline__ float refresh_edge(int j, float width, float base) { return __fmaf_rn((float)j - 0.25f, width, base); }
+__device__ __forceinline__ int refresh_level(float v, float base, float inv_width)
+{
+    return (int)fminf((v - base) * inv_width, (float)(REFRESH_LEVELS - 1)); // (clamped as a float: the product may exceed INT_MAX; NaN -> L - 1 never arises, v >= base is finite)
+}
+constexpr float REFRESH_MIN_WIDTH = 1e-30f;
 
 __device__ __forceinline__ void f32_store_async(float *dst, float v)
 {
@@ -267,12 +322,15 @@ __device__ __forceinline__ void screen_compact(SCand *base, const int (&n)[4], i
 // One workgroup of two waves per 32-query tile, one wave per 16-query set; rows >= B read as zeros.
 __global__ __launch_bounds__(128) void q_image_kernel(const float *__restrict__ Q, int B, h8 *__restrict__ img,
                                                       float *__restrict__ qnorm, int *__restrict__ flag, int n_flags,
-                                                      int *__restrict__ tail_ctr, int n_ctr)
+                                                      int *__restrict__ tail_ctr, int n_ctr, unsigned *__restrict__ hist)
 {
     __shared__ int any_bad[2];
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < n_ctr; i += 128)
             tail_ctr[i] = 0;
+    if (hist) // the ladders of this workgroup's 32 query rows (rows_pad = 32 gridDim.x)
+        for (int i = threadIdx.x; i < 32 * REFRESH_LEVELS; i += 128)
+            hist[(size_t)blockIdx.x * (32 * REFRESH_LEVELS) + i] = 0u;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int S = blockIdx.x * 2 + wv;
     const int g = lane >> 4, n = lane & 15;
@@ -339,6 +397,11 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
     constexpr int QW = 16 * NSET, QB = SW * QW; // queries per wave / per workgroup
     const int qbase = qgroup * QB + w * QW;
     const bool wave_live = qbase < p.B;
+    // Refresh (main pass, p.hist): the ladder's base per query of this workgroup = its initial threshold + 2 eps_q, the seed
+    // whoever supplied it -- every workgroup derives it from the same inputs.  In LDS: the kernel has no register to spare.
+    __shared__ float ladder_base[SW * 64];
+    const bool refresh = !MAXONLY && p.hist != nullptr;
+    const unsigned *const hwave = p.hist + (size_t)qbase * REFRESH_LEVELS;
 
     // ---- query operands (B of v_mfma_f32_16x16x32_f16): set c holds queries qbase + 16c + n;
     //      lane (n,g) keeps features 32s + 8g .. +7 of k-step s ----
@@ -376,6 +439,8 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
         if (MAXONLY) // sample pass: plain scores (C = +0); the debug export may plant a threshold instead
             c_init = (p.dbg_thr && live) ? -p.dbg_thr[qrow] : 0.0f;
         negthr[c] = f32x4{c_init, c_init, c_init, c_init};
+        if (!MAXONLY && g == 0) // (dead rows: +inf, no score reaches it; read behind the first tile's barrier at the earliest)
+            ladder_base[w * QW + 16 * c + n] = t_init + eps2[c];
     }
 
     SCand *const cwave = p.cand + ((size_t)blockIdx.x * QB + w * QW) * SCAP;
@@ -396,9 +461,54 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                 atomicOr(p.flag + ((qbase + 16 * c) >> 5), 1);
             if (n == q) {
                 cnt[c] = (n_new - g + 3) >> 2; // ranks r < n_new with r & 3 == g
-                if (have)
-                    negthr[c] = f32x4{-tn, -tn, -tn, -tn};
+                if (have) { // raise, never overwrite: a refresh may already have put the threshold above this workgroup's own k-th
+                    const float nt = fminf(negthr[c][0], -tn);
+                    negthr[c] = f32x4{nt, nt, nt, nt};
+                }
             }
+        }
+    };
+
+    // Refresh: each lane (n,g) reads levels 4g .. 4g+3 of its queries' ladders (agent scope: past the XCD's own caches), forms
+    // the suffix counts from the top level down, and the query's threshold rises to the edge of the highest level that k stored
+    // candidates have reached, minus 2 eps_q.  A cold branch like compact_where: drain, then plain code.  The caller holds no
+    // accumulator computed under the old threshold (the epilogue forms v = acc + thr).
+    auto refresh_thresholds = [&]() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // (the lane index passes through an empty asm so that the addresses below are formed here, in the cold branch, and
+        //  not hoisted into registers that would live across the tile loop: screen_kernel<false, 4> has none to spare)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int n = ln & 15, g = ln >> 4;
+#pragma unroll
+        for (int c = 0; c < NSET; ++c) {
+            const unsigned *hp = hwave + (unsigned)((16 * c + n) * REFRESH_LEVELS + 4 * g);
+            int sfx[4]; // sfx[i]: candidates at levels >= 4g + i
+            int run = 0;
+#pragma unroll
+            for (int i = 3; i >= 0; --i) {
+                run += (int)__hip_atomic_load(hp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                sfx[i] = run;
+            }
+            const int x16 = (ln ^ 16) << 2, x32 = (ln ^ 32) << 2; // (ds_bpermute addresses, formed here for the same reason)
+            const int t16 = __builtin_amdgcn_ds_bpermute(x16, run), t32 = __builtin_amdgcn_ds_bpermute(x32, run),
+                      t48 = __builtin_amdgcn_ds_bpermute(x32, t16); // the totals of lanes g^1, g^2, g^3
+            const int above = ((g ^ 1) > g ? t16 : 0) + ((g ^ 2) > g ? t32 : 0) + ((g ^ 3) > g ? t48 : 0);
+            int jtop = -1;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (above + sfx[i] >= k)
+                    jtop = 4 * g + i;
+            jtop = max(jtop, __builtin_amdgcn_ds_bpermute(x16, jtop));
+            jtop = max(jtop, __builtin_amdgcn_ds_bpermute(x32, jtop));
+            if (jtop > 0) { // (level 0 is the initial threshold itself)
+                const float base = ladder_base[w * QW + 16 * c + n];
+                float le = eps2[c];
+                asm volatile("" : "+v"(le));
+                const float nt = fminf(negthr[c][0], le - refresh_edge(jtop, (float)REFRESH_STEP * le, base));
+                negthr[c] = f32x4{nt, nt, nt, nt};
+            }
+            __builtin_amdgcn_sched_barrier(0); // one set at a time: its loads and sums are not hoisted over the previous set's
         }
     };
 
@@ -519,6 +629,25 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                                 }
                             }
                         }
+                        // Refresh: count the lane's best candidate of this tile and set on the query's ladder.  (One per lane
+                        // and tile, not one per candidate: two candidates of one query among a lane's 8 documents of a tile are
+                        // rare, a document left out only makes the count -- and the threshold -- lower, and the count runs
+                        // here, behind the stores, where their operands are dead: the kernel has no register to spare.  The
+                        // raw maximum of non-negative accumulators is their float maximum, as in the gate above.)
+                        if (refresh) {
+                            const int mbest = max(mu[0], mu[1]);
+                            if (mbest >= 0) {
+                                int lq = n; // (through an empty asm: the addresses and the level width are formed in this
+                                float le = eps2[c]; // branch and not kept per set across the tile loop, see refresh_thresholds)
+                                asm volatile("" : "+v"(lq), "+v"(le));
+                                lq += 16 * c;
+                                const float lwidth = (float)REFRESH_STEP * le;
+                                const float lbase = ladder_base[w * QW + lq];
+                                const float v = __int_as_float(mbest) + thr_c;
+                                if (lwidth >= REFRESH_MIN_WIDTH && v >= lbase)
+                                    u32_inc_async(hwave, (unsigned)((lq * REFRESH_LEVELS + refresh_level(v, lbase, 1.0f / lwidth)) * sizeof(unsigned)));
+                            }
+                        }
                         unsigned long long full = __ballot(cnt[c] > SQ_TRIGGER);
                         full = (full | (full >> 32));
                         full = (full | (full >> 16)) & 0xffffull;
@@ -567,7 +696,21 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
                 }
             }
                 };
-        for (int tile = t0; tile < t1; ++tile) {
+        // Refresh: checkpoints REFRESH_FIRST_SHIFT .. 1 halvings into the own range, each on a barrier tile; the tile loop runs
+        // from one to the next and is itself unchanged.  A pool block has none (its thresholds were refreshed at the draw).
+        int cp_shift = refresh && t0 < p.static_tiles ? REFRESH_FIRST_SHIFT : 0;
+        int tile = t0;
+        for (;;) {
+        int tend = t1;
+        while (cp_shift > 0) {
+            const int cp = t0 + (((t1 - t0) >> cp_shift) & ~(STPB - 1));
+            --cp_shift;
+            if (cp > tile) {
+                tend = cp;
+                break;
+            }
+        }
+        for (; tile < tend; ++tile) {
             if ((tile - t0) % STPB == 0) {
                 // own DMAs of this interval's tiles have landed; the barrier extends that to every wave's
                 // and guarantees every wave is done reading the tiles of the previous interval
@@ -654,8 +797,15 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
             }
             stage = (stage + 1) % SRING;
         }
-        if (wave_live && late && pending)
+        if (wave_live && late && pending) {
             epilogue(ptile, pkw);
+            pending = false;
+        }
+        if (tend == t1)
+            break;
+        if (wave_live) // between the deferred selection above and the next tile's multiply: no accumulator is live
+            refresh_thresholds();
+        }
     }
     if (MAXONLY || p.tail_blocks == 0)
         break;
@@ -665,6 +815,8 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
     // blocks: whoever is done draws the next one (a fresh pipeline per block: ring primed again, ~3 us per ~30-50 us).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the clamped over-prefetch of the segment's end
     __builtin_amdgcn_s_barrier();                    // ... has landed for every wave; nobody reads the ring any more
+    if (refresh && wave_live) // the ring is drained: what the chip has counted by now, for the pool block to come
+        refresh_thresholds();
     if (threadIdx.x == 0)
         next_block = atomicAdd(p.tail_ctr + qgroup, 1);
     __syncthreads();
@@ -693,6 +845,8 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
         return;
     }
     // final compaction (bounds the pool the finish kernel sees) and counts out: quarter g's count in byte g
+    int nf = n; // (through an empty asm: the query rows are formed again here instead of living in registers from the prologue on)
+    asm volatile("" : "+v"(nf));
 #pragma unroll
     for (int c = 0; c < NSET; ++c) {
         int tot = cnt[c] + __shfl_xor(cnt[c], 16);
@@ -703,7 +857,7 @@ __global__ __launch_bounds__(SW * 64, 2) void screen_kernel(ScreenParams p)
         int packed = cnt[c] << (8 * g);
         packed |= __shfl_xor(packed, 16);
         packed |= __shfl_xor(packed, 32);
-        const int qrow = qbase + 16 * c + n;
+        const int qrow = qbase + 16 * c + nf;
         if (g == 0 && qrow < p.B)
             p.pcnt[(size_t)qrow * p.n_chunks + chunk] = packed;
     }
@@ -1331,6 +1485,12 @@ struct SPlan {
     int n_tiles, n_chunks, tiles_per_chunk;
     int static_tiles, tail_g, tail_blocks; // shared-tile main pass: see ScreenParams
     size_t tailctr_off;
+    // Shared-tile main pass: thresholds are refreshed from the chip-wide ladders (ScreenParams::hist) when the search has a seed
+    // and a chunk's share is at least REFRESH_MIN_TILES tiles long.  With refresh the pooled-candidate statistics
+    // depend on timing (the results never do), so searches whose statistics the tests compare -- own ranges up to 245 tiles --
+    // must stay below the gate.
+    bool refresh;
+    size_t hist_off; // [rows_pad][REFRESH_LEVELS] u32 (shared-tile form; 0: none)
     // sample pass
     bool sample;
     int s_tiles, s_chunks, s_tiles_per_chunk;
@@ -1418,6 +1578,10 @@ SPlan make_splan(int B, int64_t N, int k)
     pl.qnorm_off = ws.take(rows * sizeof(float));
     pl.tailctr_off = ws.take((size_t)pl.n_qgroups * sizeof(int));
     pl.stats_off = ws.take(rows * 2 * sizeof(int));
+    pl.hist_off = pl.stream ? 0 : ws.take(rows * REFRESH_LEVELS * sizeof(unsigned));
+    const int refresh_min = TT_AB_SWITCH(TT_SCREEN_REFRESH_MIN_TILES, REFRESH_MIN_TILES);
+    // (the gate looks at a chunk's whole share, c.tiles_per_chunk, pool part included: the figure the plan is known by)
+    pl.refresh = !pl.stream && TT_AB_SWITCH(TT_SCREEN_THR_REFRESH, 1) != 0 && c.tiles_per_chunk >= (refresh_min < 8 ? 8 : refresh_min);
     // (last: the one buffer that depends on the form of the sample pass, so every other offset is the same in both)
     pl.smax_val_off = pl.s_onchip ? pl.cand_off : ws.take(rows * (size_t)(pl.sample ? pl.s_tiles : 1) * sizeof(float));
     pl.ws_bytes = ws.off;
@@ -1597,6 +1761,8 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     sp.tail_g = pl.tail_g;
     sp.tail_blocks = pl.tail_blocks;
     sp.tail_ctr = (int *)(ws + pl.tailctr_off);
+    // (the sample pass never reads it; a plan without a sample has a seed only when the caller brings one)
+    sp.hist = pl.refresh && (pl.sample || caller_seed) ? (unsigned *)(ws + pl.hist_off) : nullptr;
     sp.dmax = dmax_norm;
     sp.cand = (SCand *)(ws + pl.cand_off);
     sp.pcnt = (int *)(ws + pl.pcnt_off);
@@ -1616,7 +1782,7 @@ int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, co
     } else {
         hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
                            (float *)(ws + pl.qnorm_off), fallback_flag, (B + 31) / 32, (int *)(ws + pl.tailctr_off),
-                           pl.n_qgroups);
+                           pl.n_qgroups, pl.hist_off ? (unsigned *)(ws + pl.hist_off) : nullptr);
         TT_LAUNCH_CHECK();
         if (pl.sample) {
             ScreenParams ss = sp;
@@ -1904,6 +2070,7 @@ int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_n
     sp.tail_g = 1;
     sp.tail_blocks = 0;
     sp.tail_ctr = nullptr;
+    sp.hist = nullptr;
     sp.dmax = dmax_norm;
     sp.cand = nullptr;
     sp.pcnt = nullptr;
@@ -1917,7 +2084,7 @@ int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_n
     sp.dbg_thr = thr;
     sp.keep = nullptr;
     hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
-                       (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0);
+                       (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0, (unsigned *)nullptr);
     TT_LAUNCH_CHECK();
     return launch_screen(form == 0, pl.q_per_block, form, true, sp, pl.n_qgroups * pl.n_chunks, st, bf16);
 }
