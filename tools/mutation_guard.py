@@ -20,7 +20,8 @@ MASKS = {1: "K2 gru_seq16 / gru_seq16x4p (forward recurrence)", 2: "K7 gru_bwd16
 # compares GRADIENTS (their names say so), not by a forward test that happens to share a code path
 GRADIENT_TESTS = ("backward", "gradient", "autograd", "train_step_at_bench_size", "table_grad", "dropout_forward_and_backward")
 MUST_FAIL = {1: ("test_",), 2: GRADIENT_TESTS, 4: ("test_",), 8: GRADIENT_TESTS, 16: GRADIENT_TESTS}
-TESTS = ["tests/test_encoder_gpu.py", "tests/test_train_gpu.py", "tests/test_bench_size_gpu.py"]
+TESTS = ["tests/test_encoder_gpu.py", "tests/test_train_gpu.py", "tests/test_bench_size_gpu.py",
+         "tests/test_encoder_f64_gpu.py", "tests/test_train_f64_gpu.py"]
 
 
 def run_tests(tag):
