@@ -421,6 +421,39 @@ int tt_score_rank_f32(const float *Q, int B, int d, const float *D, int64_t N, c
  */
 int tt_score_all_f32(const float *Q, int B, int d, const float *D, int64_t N, float *S, tt_stream_t stream);
 
+/*
+ * Candidate search: the exact scores of a per-query list of C document ids (C << N) -- the second stage of a retrieval
+ * pipeline, whose ids came from TF-IDF, a first-stage ranker, a user's shortlist, another index.  Replaces
+ *   torch.matmul(q, D.t())[b, ids[b]]                          the gathered form of backend/evaluators.py:185-186
+ *   the dense scores the /search handler blends per candidate  frontend/main.py:151-198
+ * without reading the other N - C rows: B*C rows are gathered by id, where every search above streams all N.
+ * ids [B][C] device int64 (8-byte aligned): GLOBAL ids, in the id space the searches return.  For every (b, c): g = ids[b][c],
+ * n = g - idx_offset in 64-bit arithmetic.  If g < 0, or n lies outside [0, N), or keep is given and bit n is clear, the
+ * entry yields nothing: out_val[b][c] = -inf, out_idx[b][c] = -1.  Ids of other shards are therefore padding like negative
+ * ids: a sharded caller hands every shard the same global id lists.  keep: tt_score_topk_masked_f32's format (ceil(N/32)
+ * words, 4-byte aligned, bit n & 31 of word n >> 5), or NULL.
+ * Otherwise out_val[b][c] = the fp32 fmaf chain of <Q[b], D[n]> over the feature index ascending, acc0 = 0: tt_score_all_f32's
+ * definition, bit for bit what tt_score_topk_f32 / _bf16 return for that document (bf16 rows are widened exactly, bits << 16,
+ * into the same chain); out_idx[b][c] = g.  out_idx may be NULL (scores only).
+ * The outputs are position-aligned with ids; a duplicate id is scored at each of its positions and yields identical
+ * (value, index) pairs.  tt_topk_merge over (out_val, out_idx) picks "strictly after the previous pick", so for k <= 64 it
+ * returns the deduplicated exact top-k of the candidates with no further kernel; tt_topk_merge_large (k > 64) keeps identical
+ * pairs as it finds them, so a caller that may repeat an id turns the repeats into padding first.
+ * Supported: d a multiple of 4 (f32) / of 8 (bf16), at most 512 (otherwise TT_ERR_UNSUPPORTED, the message names d); any
+ * B >= 0, C >= 0 (B = 0 or C = 0 does nothing), N >= 0 (N = 0: everything is padding, D may be NULL).  Row addresses are
+ * 64-bit: N * d may exceed 2^31 elements.  TT_ERR_BAD_SHAPE: negative sizes, a NULL Q / ids / out_val (D with N > 0), Q or D not
+ * 16-byte aligned, ids / out_idx not 8-byte, out_val / keep not 4-byte aligned, out overlapping an input or the other output.
+ * Every check runs before any HIP call.  One launch (one workgroup per query and 256 candidates, the grid flattened: no limit
+ * on B below 2^31 workgroups), no workspace, no atomics, no host synchronisation: capturable, and the result depends only on
+ * the inputs.
+ */
+int tt_score_ids_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *keep /*nullable*/,
+                     const int64_t *ids /*[B][C]*/, int C, int64_t idx_offset, float *out_val /*[B][C]*/,
+                     int64_t *out_idx /*[B][C], nullable*/, tt_stream_t stream);
+int tt_score_ids_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep /*nullable*/,
+                      const int64_t *ids /*[B][C]*/, int C, int64_t idx_offset, float *out_val /*[B][C]*/,
+                      int64_t *out_idx /*[B][C], nullable*/, tt_stream_t stream);
+
 /* ------------------------------------------------------------------ */
 /* Encoder tower (GloVe gather -> GRU -> L2-normalise)                 */
 /* ------------------------------------------------------------------ */

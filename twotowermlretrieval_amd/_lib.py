@@ -86,6 +86,8 @@ SIGNATURES = {
     "tt_topk_cut_below": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "tt_score_rank_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "tt_score_all_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp]),
+    "tt_score_ids_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "tt_score_ids_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "tt_tok_create": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "tt_tok_destroy": (None, [_vp]),
     "tt_tok_encode": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i]),

@@ -26,10 +26,14 @@ from .index import BruteForceIndex, score_all
 
 class HybridSearcher:
     def __init__(self, inferencer, documents: Sequence[str], doc_embeddings: torch.Tensor = None, tfidf_vectorizer=None,
-                 doc_tfidf_matrix=None, n_candidates: int = 50, dense_score: str = "cosine", index: BruteForceIndex = None):
+                 doc_tfidf_matrix=None, n_candidates: int = 50, dense_score: str = "cosine", index: BruteForceIndex = None,
+                 lexical_candidates: int = 0):
         """documents: documents.pkl's list (row i of the embeddings <-> documents[i]); any object with __len__ and __getitem__
         is used as it is (a corpus too large for a Python list: an mmap-backed or generated sequence), other iterables are
-        listed.  index: an existing BruteForceIndex over the embedding matrix instead of doc_embeddings (one is built otherwise)."""
+        listed.  index: an existing BruteForceIndex over the embedding matrix instead of doc_embeddings (one is built otherwise).
+        lexical_candidates: 0 (the default) blends over the dense top-`n_candidates` only, as the reference does -- the best
+        lexical match is lost when it ranks below them by cosine.  n > 0 adds the query's n best TF-IDF matches over the
+        whole corpus (similarity > 1e-5) to the candidates; their dense scores come from index.score_ids."""
         if dense_score not in ("cosine", "chroma_l2"):
             raise ValueError("dense_score must be 'cosine' or 'chroma_l2'")
         if (index is None) == (doc_embeddings is None):
@@ -43,6 +47,9 @@ class HybridSearcher:
             raise ValueError(f"{len(self.documents)} documents for {self.index.ntotal} embedding rows")
         self.n_candidates = int(n_candidates)
         self.dense_score = dense_score
+        self.lexical_candidates = int(lexical_candidates)
+        if self.lexical_candidates < 0:
+            raise ValueError(f"lexical_candidates = {lexical_candidates} < 0")
         if tfidf_vectorizer is None:  # same construction as backend/main.py:142-143
             from sklearn.feature_extraction.text import TfidfVectorizer
             tfidf_vectorizer = TfidfVectorizer(stop_words="english", max_features=20000)
@@ -62,8 +69,18 @@ class HybridSearcher:
         vals, idx = self.index.search(q, k)
         cos = vals.cpu().numpy()
         cand = [int(i) for i in idx.cpu().tolist() if i >= 0]
-        dense = cos[:len(cand)] if self.dense_score == "cosine" else 2.0 * cos[:len(cand)] - 1.0
         q_tfidf = self.tfidf.transform([query])
+        if self.lexical_candidates > 0 and q_tfidf.nnz > 0:
+            # the best lexical matches of the whole corpus join the dense top-k, with their exact dense scores
+            sims = cosine_similarity(q_tfidf, self.doc_tfidf).flatten()
+            have = set(cand)
+            extra = [int(i) for i in np.argsort(-sims, kind="stable")[:self.lexical_candidates] if sims[i] > 1e-5 and int(i) not in have]
+            if extra:
+                s = self.index.score_ids(q, torch.tensor(extra, dtype=torch.int64, device=q.device)).cpu().numpy()
+                live = np.isfinite(s)  # (a removed document scores -inf: it is no candidate)
+                cos = np.concatenate([cos[:len(cand)], s[live]])
+                cand += [i for i, ok in zip(extra, live) if ok]
+        dense = cos[:len(cand)] if self.dense_score == "cosine" else 2.0 * cos[:len(cand)] - 1.0
         if q_tfidf.nnz > 0:
             tf = np.nan_to_num(cosine_similarity(q_tfidf, self.tfidf.transform([self.documents[i] for i in cand]))[0])
         else:

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
+__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
            "shard_bounds", "seed_union", "score_count", "topk_cut_below"]
 
 
@@ -385,6 +385,89 @@ def score_all(q: torch.Tensor, docs: torch.Tensor) -> torch.Tensor:
     return out[0] if squeeze else out
 
 
+def _check_ids(ids: torch.Tensor, B: int, device, what: str = "ids") -> torch.Tensor:
+    """Per-query candidate lists for B queries on `device` as tt_score_ids_f32 / _bf16 read them (int64 [B,C], contiguous)."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
+        raise TypeError(f"{what} must be an int64 tensor of document ids, got {getattr(ids, 'dtype', type(ids))}")
+    if ids.device != device:
+        raise ValueError(f"{what} on {ids.device} but the search runs on {device}")
+    if ids.dim() != 2 or ids.shape[0] != B:
+        raise ValueError(f"{what} must be [B,C] = [{B},C] (one list per query; [C] for a single query), got {tuple(ids.shape)}")
+    return ids if ids.is_contiguous() else ids.contiguous()
+
+
+def _ids_row(ids: Optional[torch.Tensor], what: str = "ids") -> Optional[torch.Tensor]:
+    """The [1,C] lists of a single query's [C] list."""
+    if ids is None:
+        return None
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+        raise ValueError(f"a single query takes {what} [C], got {tuple(getattr(ids, 'shape', ()))}")
+    return ids.unsqueeze(0)
+
+
+def _score_ids_into(q: torch.Tensor, docs: torch.Tensor, ids: torch.Tensor, idx_offset: int, keep: Optional[torch.Tensor],
+                    out_val: torch.Tensor, out_idx: Optional[torch.Tensor]) -> None:
+    """tt_score_ids_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, ids int64 [B,C], keep a checked
+    keep-bitmask or None -> out_val f32 [B,C] and, unless None, out_idx int64 [B,C], both contiguous."""
+    B, d = q.shape
+    L = _lib.lib()
+    fn = L.tt_score_ids_bf16 if docs.dtype == torch.bfloat16 else L.tt_score_ids_f32
+    with torch.cuda.device(q.device):
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr() if docs.shape[0] else None, docs.shape[0],
+                      None if keep is None else keep.data_ptr(), ids.data_ptr(), ids.shape[1], idx_offset, out_val.data_ptr(),
+                      None if out_idx is None else out_idx.data_ptr(), _stream(q)))
+
+
+def score_ids(q: torch.Tensor, docs: torch.Tensor, ids: torch.Tensor, idx_offset: int = 0,
+              keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(q @ docs.T)[b, ids[b] - idx_offset] without the other rows: float32 [B,C], the exact score -- score_topk's fp32 chain,
+    bit for bit -- of every listed document, position-aligned with ids (tt_score_ids_f32 / _bf16: one launch that gathers
+    B*C rows by id).  q [B,d] or [d] float32; docs [N,d] float32 (d a multiple of 4) or bfloat16 (a multiple of 8), d <= 512;
+    ids int64 [B,C] on the documents' device ([C] with a 1-D q).  An entry that is negative, lies outside
+    [idx_offset, idx_offset + N) or names a document whose bit in `keep` (pack_keep_mask) is clear scores -inf; a repeated
+    id is scored at each of its positions."""
+    if q.dim() == 1:
+        return score_ids(q.unsqueeze(0), docs, _ids_row(ids), idx_offset, keep)[0]
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), _docs_c(docs)
+    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    ids = _check_ids(ids, q.shape[0], docs.device)
+    if keep is not None:
+        keep = _check_keep(keep, docs.shape[0], docs.device)
+    out = torch.empty(ids.shape, dtype=torch.float32, device=q.device)
+    _score_ids_into(q, docs, ids, int(idx_offset), keep, out, None)
+    return out
+
+
+def _unique_pairs(vals: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rows of (value, id) pairs in which a repeated id -- an identical pair: one document, one score -- is kept once and its
+    repeats become (-inf, -1) padding, for the merge above k = 64 (tt_topk_merge_large counts identical pairs as it finds
+    them; the k <= 64 merge skips them by itself).  The rows come back sorted by id."""
+    si, order = idx.sort(dim=1)
+    sv = vals.gather(1, order)
+    dup = torch.zeros_like(si, dtype=torch.bool)
+    dup[:, 1:] = si[:, 1:] == si[:, :-1]
+    return sv.masked_fill_(dup, float("-inf")), si.masked_fill_(dup, -1)
+
+
+def _merge_candidates(vals: torch.Tensor, idx: torch.Tensor, k: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exact top-k of the distinct candidates of scored rows (vals f32 / idx int64 [B,C] as tt_score_ids_* wrote them),
+    (score desc, index asc), tail (-inf, -1): the existing merges, into `out` when given."""
+    B, C = vals.shape
+    ov, oi = _out_pair(B, k, vals.device, out)
+    if C == 0 or B == 0:
+        ov.fill_(float("-inf"))
+        oi.fill_(-1)
+        return ov, oi
+    if k > SMALL_KMAX:
+        vals, idx = _unique_pairs(vals, idx)
+    with torch.cuda.device(vals.device):
+        _lib.check(getattr(_lib.lib(), _merge_fn(k))(vals.data_ptr(), idx.data_ptr(), B, C, k, ov.data_ptr(), oi.data_ptr(),
+                                                     _stream(vals)))
+    return ov, oi
+
+
 SCREEN_MIN_BATCH = 1     # the screened path wins at every batch size once the corpus is large enough to sample:
                          # B <= 64 streaming form (half the bytes of the fp32 kernel), above it the shared-tile form
 SCREEN_PADDED_MIN_BATCH = 33  # d < 256 (zero-padded screen copy): only where the exact kernel is MFMA-bound
@@ -558,8 +641,14 @@ class BruteForceIndex:
 
     def search(self, q: torch.Tensor, k: int = 10, _prof_events=None, out=None, _seed_union=None,
                _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None,
-               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) contiguous device tensors to write into (2-D q only).
+        candidates: optional per-query candidate lists, int64 [B,C] on the index's device ([C] with a 1-D q): GLOBAL ids (with
+        idx_offset).  The search then reads those rows only: tt_score_ids_f32 / _bf16 into scratch [B,C] pairs, then the
+        existing merge into `out` -- the exact top-k of the distinct, present (not removed, kept by keep=) candidates,
+        (score desc, index asc), tail (-inf, -1) when fewer than k are left (k > C is fine).  Negative ids and ids that are
+        not this index's are padding, a repeated id counts once.  It never screens and leaves fallback_flags as they were;
+        exclude= composes (the candidate search runs for k + E).
         exclude: optional per-query exclusion lists, int64 [B,E] on the index's device ([E] with a 1-D q): GLOBAL ids (with
         idx_offset) query b must not return; negative entries are padding, duplicates and ids of other indexes are fine.  The
         search is this index's ordinary search for k + E into a scratch pair -- every routing decision sees k + E: it screens
@@ -575,7 +664,8 @@ class BruteForceIndex:
         of the ranks' lists (one all-gather + tt_seed_union_f32) -- on the current stream; the screen then runs with that
         global seed and `out` holds this shard's documents above it."""
         if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank)
-            return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep, _exclude_row(exclude))
+            return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep, _exclude_row(exclude),
+                             _ids_row(candidates, "candidates"))
         _need_cuda(q)
         if q.device != self.docs.device:
             raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
@@ -583,9 +673,11 @@ class BruteForceIndex:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
         if exclude is not None:
             exclude, kk = _check_exclude(exclude, q.shape[0], k, self.docs.device)
-            v, i = self.search(q, kk, _prof_events, None, _seed_union, _k_seed, _k_list, keep)
+            v, i = self.search(q, kk, _prof_events, None, _seed_union, _k_seed, _k_list, keep, None, candidates)
             return topk_exclude(v, i, exclude, k, out)
         keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        if candidates is not None:
+            return _merge_candidates(*self._score_ids(q, candidates, keep, True, "candidates"), k, out)
         if self._screens(q.shape[0], k, keep is not None):
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list, keep)
         if keep is not None and self._screen is not None:  # (the exact kernel took over every tile of a screened index)
@@ -596,6 +688,29 @@ class BruteForceIndex:
             out[1].copy_(i)
             return out
         return v, i
+
+    def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], want_idx: bool, what: str = "ids"):
+        """tt_score_ids_* of q [B,d] over this index's rows under the ANDed mask `keep` (checked) or None: (scores f32 [B,C],
+        global ids int64 [B,C] with -1 where the entry yields nothing -- None unless want_idx)."""
+        q = _f32c(q)
+        ids = _check_ids(ids, q.shape[0], self.docs.device, what)
+        vals = torch.empty(ids.shape, dtype=torch.float32, device=q.device)
+        idx = torch.empty_like(ids) if want_idx else None
+        _score_ids_into(q, self.docs, ids, self.idx_offset, keep, vals, idx)
+        return vals, idx
+
+    def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float32 [B,C] ([C] for a single query): the exact dense score -- the value search() returns for the document, bit
+        for bit -- of every id of ids int64 [B,C] (GLOBAL ids, with idx_offset), position-aligned.  -inf where the id is
+        negative, not this index's, removed (remove_ids) or not kept by `keep`.  One launch that gathers B*C rows."""
+        if q.dim() == 1:
+            return self.score_ids(q.unsqueeze(0), _ids_row(ids), keep)[0]
+        _need_cuda(q)
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        if q.shape[-1] != self.docs.shape[1]:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        return self._score_ids(q, ids, _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device), False)[0]
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 [B] (0-d for a single query): how many documents of this index -- not removed (remove_ids), and kept by
@@ -912,7 +1027,7 @@ class ShardedIndex:
         unmasked one, without it none does, and the ranks must agree."""
         self._index.remove_ids(ids)
 
-    def _local_search(self, q: torch.Tensor, kp: int, k: int, sl: "_Slot", comm_stream=None, keep=None) -> None:
+    def _local_search(self, q: torch.Tensor, kp: int, k: int, sl: "_Slot", comm_stream=None, keep=None, candidates=None) -> None:
         """This shard's list for the exchange: up to kp = max(k, shard_k) entries, best first.  The screen is seeded for
         the FINAL k with the UNION seed: every rank lists its k largest sample maxima per query, ONE small all-gather
         (k floats per query and rank: 40 KB per rank at B = 1024), and seed[q] = the k-th largest of the union -- k distinct
@@ -925,6 +1040,13 @@ class ShardedIndex:
         comm_stream: the stream the seed all-gather is issued on (submit(): the index's exchange stream; the previous step's
         deferred list exchange is issued right behind it); None = the caller's."""
         coll, world = self._coll, self._coll.world
+        if candidates is not None:
+            # a candidate search never screens, so no rank exchanges seeds: this shard's candidates (the other shards' ids
+            # are padding to it), merged to kp
+            if comm_stream is not None:
+                self._flush()
+            self._index.search(q, kp, out=(sl.send_v, sl.send_i), keep=keep, candidates=candidates)
+            return
         plan = self._seed_plan(k)
         B = q.shape[0]
         # (a seed plan implies a resident shard: no rank exchanges seeds when any shard is streamed)
@@ -1038,8 +1160,11 @@ class ShardedIndex:
                              sl.out_i.data_ptr(), _stream(sl.recv)))
 
     def search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
-               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """One search, everything on the caller's stream; fresh result tensors.
+        candidates: per-query candidate lists of GLOBAL ids, int64 [B,C] ([C] with a 1-D q), the same on every rank like q.
+        Every rank scores the candidates of its own shard (the others are padding to it) and merges them to its list; the
+        exchange and the shard merge are the ordinary search's.  A COLLECTIVE like every search of this class.
         keep: a packed keep-bitmask over THIS RANK'S rows for this call (ANDed with the mask of remove_ids).  It must be given
         on all ranks or on none: a masked search does not enter the seed exchange (with screen_masked=True it does, on every
         rank alike).
@@ -1047,16 +1172,18 @@ class ShardedIndex:
         local search, the exchange and the merge are those of a search for k + E (per-shard lists of max(k + E, shard_k));
         the filter (tt_topk_exclude_ids) runs once, on the merged rows."""
         if q.dim() == 1:
-            return _squeezed(self.search, q, k, keep, _exclude_row(exclude))
+            return _squeezed(self.search, q, k, keep, _exclude_row(exclude), _ids_row(candidates, "candidates"))
         k_out = k
         if exclude is not None:
             exclude, k = _check_exclude(exclude, q.shape[0], k, self._dev)
+        if candidates is not None:
+            candidates = _check_ids(candidates, q.shape[0], self._dev, "candidates")
         kp = max(k, self.shard_k)
         sl = self._slot(q.shape[0], kp, k, 2)
         cur = torch.cuda.current_stream(sl.send.device)
         cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._local_search(q, kp, k, sl, keep=keep)
+        self._local_search(q, kp, k, sl, keep=keep, candidates=candidates)
         self._exchange_merge(sl, q.shape[0], kp, k)
         if exclude is not None:
             res = topk_exclude(sl.out_v, sl.out_i, exclude, k_out)  # (reads the slot: before it is handed on)
@@ -1064,6 +1191,24 @@ class ShardedIndex:
             return res
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
+
+    def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float32 [B,C] ([C] for a single query), identical on every rank: the exact dense score of every id of ids int64
+        [B,C] (GLOBAL ids, the same on every rank like q), -inf where the id is negative, beyond the corpus, removed or not
+        kept (keep: over THIS RANK'S rows, on all ranks or on none).  Each rank scores against its own shard, where the other
+        shards' ids are padding (-inf); exactly one rank holds a real value, so the result is the elementwise MAX over the
+        ranks: one all_reduce(MAX) of the [B,C] floats on the index's group.  A COLLECTIVE: every rank calls it at the same
+        point."""
+        scores = self._index.score_ids(q, ids, keep=keep)
+        if self._coll.world > 1:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(scores, op=dist.ReduceOp.MAX, group=self.group)
+            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' scores and take the maximum)
+                recv = torch.empty((self._coll.world,) + tuple(scores.shape), dtype=torch.float32, device=scores.device)
+                self._coll.all_gather_blocks(scores.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
+                scores = recv.amax(0)
+        return scores
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The count of the whole corpus, identical on every rank: this rank's count over its shard under its mask (keep: over
@@ -1091,16 +1236,19 @@ class ShardedIndex:
         return self._dev
 
     def submit(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
-               exclude: Optional[torch.Tensor] = None) -> PendingSearch:
+               exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> PendingSearch:
         """Pipelined search of a [B,d] batch: the local search is enqueued on the caller's stream now; its list exchange and
         merge go out on this index's second stream inside the NEXT submit() (behind that step's seed gather), or when
         .result() / search() asks for them.  Call .result() when the answer is needed.  keep: as in search() (all ranks or
-        none).  exclude: as in search(); the step runs for k + E and .result() filters the merged rows."""
+        none).  exclude: as in search(); the step runs for k + E and .result() filters the merged rows.  candidates: as in
+        search(): the step's local search is the candidate search."""
         if q.dim() != 2:
             raise ValueError("submit wants a [B,d] batch")
         k_out = k
         if exclude is not None:
             exclude, k = _check_exclude(exclude, q.shape[0], k, self._dev)
+        if candidates is not None:
+            candidates = _check_ids(candidates, q.shape[0], self._dev, "candidates")
         kp = max(k, self.shard_k)
         B = q.shape[0]
         sl = self._slot(B, kp, k, self._n_submitted % 2)
@@ -1111,7 +1259,7 @@ class ShardedIndex:
         cur = torch.cuda.current_stream(dev)
         self._flush(sl)                      # (the slot's own previous step, if nobody collected it: issue before reuse)
         cur.wait_event(sl.merged)            # the slot's previous exchange has read its send block
-        self._local_search(q, kp, k, sl, comm_stream=self._xs, keep=keep)
+        self._local_search(q, kp, k, sl, comm_stream=self._xs, keep=keep, candidates=candidates)
         self._flush()                        # (a local search without a seed exchange has not issued the previous step's yet)
         sl.searched.record(cur)
         self._deferred = (sl, B, kp, k)
@@ -1155,6 +1303,7 @@ class StreamedIndex:
         if not _fp16_range_ok(dmax, amax):
             self._d16 = [None, None]
         self._keep: Optional[torch.Tensor] = None  # persistent keep-bitmask (remove_ids): N/8 bytes, on the device
+        self._gather = None  # two pinned [block,d] host buffers of the candidate gather (_score_ids), allocated on first use
 
     def _walk(self, visit, stats=None):
         L = _lib.lib()
@@ -1212,9 +1361,75 @@ class StreamedIndex:
         """Withdraw documents by global id (with idx_offset); other ids are ignored.  The mask stays on the device."""
         self._keep = _clear_ids(self._keep, self.N, self.device, ids, self.idx_offset)
 
+    def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], what: str = "ids"):
+        """(scores f32 [B,C], global ids int64 [B,C], -1 where the entry yields nothing) of checked q [B,d] under the ANDed
+        mask `keep` or None.  The rows are in host memory, so the gather happens there: the distinct present ids of the
+        batch (one synchronising copy to the host), their rows through the staging buffers in pieces of at most block_docs
+        rows, each piece scored by tt_score_ids_bf16 with the candidates' POSITIONS among the gathered rows as ids."""
+        ids = _check_ids(ids, q.shape[0], self.device, what)
+        dev, N = self.device, self.N
+        vals = torch.full(ids.shape, float("-inf"), dtype=torch.float32, device=dev)
+        if N == 0 or ids.numel() == 0:
+            return vals, torch.full_like(ids, -1)
+        n = ids - self.idx_offset
+        ok = (ids >= 0) & (ids >= self.idx_offset) & (n >= 0) & (n < N)
+        if keep is not None:  # removed or unkept ids are neutralised on the device: a bit test against the keep words
+            nc = n.clamp(0, N - 1)
+            ok &= ((keep[nc >> 5] >> (nc & 31).to(torch.int32)) & 1).bool()
+        uniq, inv = torch.unique(torch.where(ok, n, torch.full_like(n, -1)), return_inverse=True)
+        rows = uniq.cpu()  # (the one synchronisation: which rows to fetch)
+        pad = int(rows.numel() > 0 and int(rows[0]) < 0)  # padding sorts first
+        rows = rows[pad:]
+        pos = (inv - pad).contiguous()  # the candidate's position among the gathered rows, -1 = nothing
+        U = rows.numel()
+        need = min(self.block, U)  # rows per pinned buffer: grown on demand, never beyond a staging buffer
+        bufs = 1 if U <= self.block else 2
+        if self._gather is None or self._gather[0].shape[0] < need or len(self._gather) < bufs:
+            self._gather = [torch.empty((need, self.d), dtype=torch.bfloat16).pin_memory() for _ in range(bufs)]
+        cur = torch.cuda.current_stream(dev)
+        for s in range(2):
+            self._free[s].record(cur)
+        for j, p0 in enumerate(range(0, U, self.block)):
+            s = j % 2
+            m = min(self.block, U - p0)
+            if j >= 2:
+                self._ready[s].synchronize()  # the copy out of this pinned buffer two pieces ago has finished
+            torch.index_select(self.host, 0, rows[p0:p0 + m], out=self._gather[s][:m])
+            with torch.cuda.stream(self._copy):
+                self._copy.wait_event(self._free[s])
+                self._stage[s][:m].copy_(self._gather[s][:m], non_blocking=True)
+                self._ready[s].record(self._copy)
+            cur.wait_event(self._ready[s])
+            piece = vals if U <= self.block else torch.empty_like(vals)  # (a single piece writes the result itself)
+            _score_ids_into(q, self._stage[s][:m], pos, p0, None, piece, None)  # positions outside the piece: padding
+            self._free[s].record(cur)
+            if piece is not vals:
+                vals = torch.maximum(vals, piece)
+        if U:
+            self._ready[(U - 1) // self.block % 2].synchronize()  # (the pinned buffers are reusable when this returns)
+        return vals, torch.where(ok, ids, torch.full_like(ids, -1))
+
+    def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float32 [B,C] ([C] for a single query): the exact dense score of every id of ids int64 [B,C] on the device (global
+        ids, with idx_offset), -inf where the id is negative, outside the corpus, removed or not kept by `keep` (a mask over
+        the whole corpus): the resident bf16 index's values.  Traffic is at most B*C rows instead of the N-row walk.
+        SYNCHRONISES with the host once: the distinct ids of the batch are copied to the host, where their rows are
+        gathered (index_select from the pinned corpus) and sent through the staging buffers in pieces of block_docs rows."""
+        _need_cuda(q)
+        if q.dim() == 1:
+            return self.score_ids(q.unsqueeze(0), _ids_row(ids), keep)[0]
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        return self._score_ids(_f32c(q), ids, _and_keep(self._keep, keep, self.N, self.device))[0]
+
     def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None,
-               exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """out: optional (vals f32 [B,k], idx int64 [B,k]) device tensors to write the result into (ShardedIndex's send block).
+        candidates: optional per-query candidate lists of global ids, int64 [B,C] on the device ([C] with a 1-D q): no walk --
+        the candidates' rows are gathered on the host and scored (score_ids: it synchronises with the host once), then
+        merged: the exact top-k of the distinct, present candidates.
         exclude: optional per-query exclusion lists of global ids, int64 [B,E] on the device ([E] with a 1-D q): the blocks are
         searched and merged for k + E (<= 1024) and the running list is filtered once at the end (tt_topk_exclude_ids).
         keep: optional packed keep-bitmask over the whole corpus (on the device), ANDed with the mask of remove_ids.  Block i of
@@ -1223,17 +1438,19 @@ class StreamedIndex:
         one block) raises ValueError."""
         _need_cuda(q)
         if q.dim() == 1:
-            return _squeezed(self.search, q, k, None, keep, _exclude_row(exclude))
+            return _squeezed(self.search, q, k, None, keep, _exclude_row(exclude), _ids_row(candidates, "candidates"))
         if q.device != self.device:
             raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
         if q.shape[1] != self.d:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
         if exclude is not None:
             exclude, kk = _check_exclude(exclude, q.shape[0], k, self.device)
-            v, i = self.search(q, kk, None, keep)
+            v, i = self.search(q, kk, None, keep, None, candidates)
             return topk_exclude(v, i, exclude, k, out)
         q = _f32c(q)
         keep = _and_keep(self._keep, keep, self.N, self.device)
+        if candidates is not None:
+            return _merge_candidates(*self._score_ids(q, candidates, keep, "candidates"), k, out)
         if keep is not None and self.block % 32 and self.N > self.block:
             raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
         run = []  # the running top-k: (values, indices)
