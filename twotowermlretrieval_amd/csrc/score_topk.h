@@ -91,18 +91,10 @@ int redo_gave_up(const ExactCall &c, const Plan &pl, int list_k, FlagGaveUp flag
 // score_topk_large.hip: the workspace of a large or masked call whose main pass runs under pl.
 size_t score_topk_large_ws_bytes(const Plan &pl, int B, int k);
 
-// The predicated k <= 64 searches, for the screened path's fallback (screen.hip).
-int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                           const int *run_if, hipStream_t st);
-int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
-                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                            const int *run_if, hipStream_t st);
-// The same under a keep-bitmask (fp32 or bf16 rows): the masked screened path's fallback.  The workspace is the unmasked
-// k <= 64 search's (tt_score_topk_workspace_bytes / _bf16_workspace_bytes); keep == nullptr is the unmasked search.
-int tt_score_topk_masked_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, const unsigned *keep, int k,
-                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                              const int *run_if, hipStream_t st);
+// A whole k <= 64 search, checks included: both public entries, and under run_if (one device flag per 32-query tile, see
+// ExactPass) the screened path's fallback, which names the public entry it stands for in c.who (screen.hip).  The workspace
+// is the unmasked search's (tt_score_topk_workspace_bytes / _bf16_workspace_bytes) with or without c.keep.
+int exact_small(const ExactCall &c, const int *run_if);
 
 // range.hip: count[b] (+)= the sum of part[b][0, n_chunks), the counting pass's per-(query, chunk) integers; n_chunks = 0 writes zeros
 int tt_count_finish(const int64_t *part, int B, int n_chunks, int64_t *count, int accumulate, hipStream_t st);

@@ -1549,14 +1549,15 @@ int flag_merged(const ExactCall &c, const Plan &pl, int *flags)
     return TT_OK;
 }
 
-// Both public k <= 64 searches and their predicated forms.
+} // namespace
+
+// Both public k <= 64 searches and, under run_if, the screened path's fallback (score_topk.h).
 int exact_small(const ExactCall &c, const int *run_if)
 {
     Plan pl;
     const int rc = exact_validate(c, MERGE_KMAX, &pl);
     return rc != TT_OK || c.B == 0 ? rc : score_topk_pred(c, pl, run_if);
 }
-} // namespace
 
 // Exact path over fp32 or bf16 rows, optionally predicated on a device flag (the screened path's fallback).
 int score_topk_pred(const ExactCall &c, const Plan &pl, const int *run_if)
@@ -1634,45 +1635,20 @@ TT_EXPORT int tt_score_topk_partials_f32(const float *Q, int B, int d, const flo
     return TT_OK;
 }
 
-int tt_score_topk_f32_pred(const float *Q, int B, int d, const float *D, int64_t N, int k, int64_t idx_offset,
-                           float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                           const int *run_if, hipStream_t st)
-{
-    return exact_small(ExactCall{Q, B, d, D, false, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes, st,
-                                 "tt_score_topk_f32"}, run_if);
-}
-
-int tt_score_topk_bf16_pred(const float *Q, int B, int d, const void *D, int64_t N, int k, int64_t idx_offset,
-                            float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                            const int *run_if, hipStream_t st)
-{
-    return exact_small(ExactCall{Q, B, d, D, true, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes, st,
-                                 "tt_score_topk_bf16"}, run_if);
-}
-
-// The masked k <= 64 search, predicated: the masked screened search's fallback (the K4m instantiations under run_if)
-int tt_score_topk_masked_pred(const float *Q, int B, int d, const void *D, bool bf16, int64_t N, const unsigned *keep, int k,
-                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
-                              const int *run_if, hipStream_t st)
-{
-    return exact_small(ExactCall{Q, B, d, D, bf16, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes, st,
-                                 bf16 ? "tt_score_topk_masked_bf16" : "tt_score_topk_masked_f32"}, run_if);
-}
-
 TT_EXPORT int tt_score_topk_f32(const float *Q, int B, int d, const float *D, int64_t N, int k,
                                 int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
                                 size_t workspace_bytes, tt_stream_t stream)
 {
-    return tt_score_topk_f32_pred(Q, B, d, D, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes, nullptr,
-                                  (hipStream_t)stream);
+    return exact_small(ExactCall{Q, B, d, D, false, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes,
+                                 (hipStream_t)stream, "tt_score_topk_f32"}, nullptr);
 }
 
 TT_EXPORT int tt_score_topk_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
                                  int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
                                  size_t workspace_bytes, tt_stream_t stream)
 {
-    return tt_score_topk_bf16_pred(Q, B, d, D_bf16, N, k, idx_offset, out_val, out_idx, workspace, workspace_bytes,
-                                   nullptr, (hipStream_t)stream);
+    return exact_small(ExactCall{Q, B, d, D_bf16, true, N, k, idx_offset, nullptr, out_val, out_idx, workspace, workspace_bytes,
+                                 (hipStream_t)stream, "tt_score_topk_bf16"}, nullptr);
 }
 
 // ---------------------------------------------------------------------------

@@ -176,40 +176,41 @@ __device__ __forceinline__ SCand scand_load_l2(const SCand *p)
 }
 
 struct ScreenParams {
-    const float *Q;
-    const _Float16 *D16;
-    int B, N, k;
-    int n_chunks, tiles_per_chunk, n_tiles;
+    // (the initialisers are the values of a launch that does not use the member; the host fills the rest: screen_params)
+    const float *Q = nullptr;
+    const _Float16 *D16 = nullptr;
+    int B = 0, N = 0, k = 0;
+    int n_chunks = 0, tiles_per_chunk = 0, n_tiles = 0;
     // Shared-tile main pass: tiles [0, static_tiles) are split evenly over the chunks; tiles [static_tiles, n_tiles) are a
     // POOL of tail_blocks blocks of tail_g tiles per query group that the workgroups draw from (tail_ctr[qgroup],
     // atomicAdd) once their own range is done.  static_tiles == n_tiles, tail_blocks == 0: everything static.
-    int static_tiles, tail_g, tail_blocks;
-    int *tail_ctr; // [n_qgroups], zeroed by q_image_kernel
+    int static_tiles = 0, tail_g = 1, tail_blocks = 0;
+    int *tail_ctr = nullptr; // [n_qgroups], zeroed by q_image_kernel
     // Shared-tile main pass with a seed and long own ranges (SPlan::refresh), else null: hist[query][REFRESH_LEVELS], the chip-wide
     // count of stored candidates per threshold level, zeroed by q_image_kernel (Seeded phase: by the seed phase's, so one
     // seeded call per seed call on a workspace -- the contract tail_ctr already has, include/tt.h)
-    unsigned *hist;
-    float dmax;
-    SCand *cand;   // [n_blocks][512][SCAP]
-    int *pcnt;     // [rows_pad][n_chunks]
-    int *flag;     // overflow / unsupported -> exact fallback
+    unsigned *hist = nullptr;
+    float dmax = 0.0f;
+    SCand *cand = nullptr;   // [n_blocks][512][SCAP]
+    int *pcnt = nullptr;     // [rows_pad][n_chunks]
+    int *flag = nullptr;     // overflow / unsupported -> exact fallback
     // sample pass (MAXONLY): per-(tile, query) maximum approximate score
-    float *max_val;      // [rows_pad][n_tiles]
+    float *max_val = nullptr;      // [rows_pad][n_tiles]
     // sample pass of the shared-tile form: instead of max_val, every lane's STOP largest slice maxima, stored once after the
     // last tile at top_val[query][(chunk * 4 + g) * STOP + j] (row stride n_chunks * 4 * STOP); null: per-tile maxima
-    float *top_val;
-    const float *thr0;  // main pass: k-th largest sample maximum per query, stride thr0_stride (or null)
-    int thr0_stride;
+    float *top_val = nullptr;
+    const float *thr0 = nullptr;  // main pass: k-th largest sample maximum per query, stride thr0_stride (or null)
+    int thr0_stride = 1;
     // queries as MFMA B operands, prepared once per search by q_image_kernel:
     // qimg[((S * 8 + s) * 64 + lane)] = 8 f16 of query 16 S + (lane & 15), features 32 s + 8 (lane >> 4) .. +7
-    const h8 *qimg;
-    const float *qnorm;  // |q| per (padded) query row
+    const h8 *qimg = nullptr;
+    const float *qnorm = nullptr;  // |q| per (padded) query row
     // test-only (tt_debug_screen_s16): MAXONLY pass whose accumulators start at -dbg_thr[query] like the main
     // pass's, so the raw value t = fl(sum - thr) the filter compares with +0 can be observed; null in the product
-    const float *dbg_thr;
+    const float *dbg_thr = nullptr;
     // MASKED instantiations: keep-bitmask, one word per 32-document tile (bit n & 31 of word n >> 5 set -> document n of D16
     // may be returned; the sample pass reads the first words of the same mask); nullptr in every other launch
-    const unsigned *keep;
+    const unsigned *keep = nullptr;
 };
 
 // store (v, x) at wave-uniform base + per-lane 32-bit byte offset (SGPR-base addressing: no 64-bit VALU math)
@@ -1588,52 +1589,51 @@ SPlan make_splan(int B, int64_t N, int k)
     return pl;
 }
 
-// The screen kernel of one form: streaming (q_per_block 32 or 64: 2 or 4 query sets per wave) or shared-tile (nset 16-query
-// sets per wave, 1..4).  MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).
-// BF: the corpus is bf16 rows, converted in LDS (bf16_to_f16_lds).  MASKED: under p.keep.
-template <bool MAXONLY, bool BF, bool MASKED, bool ONCHIP = false>
-const void *screen_fn(bool stream, int q_per_block, int nset)
-{
-    if (stream)
-        return q_per_block == 64 ? (const void *)screen_stream_kernel<MAXONLY, 4, BF, MASKED>
-                                 : (const void *)screen_stream_kernel<MAXONLY, 2, BF, MASKED>;
-    switch (nset) {
-    case 4: return (const void *)screen_kernel<MAXONLY, 4, BF, MASKED, ONCHIP>;
-    case 3: return (const void *)screen_kernel<MAXONLY, 3, BF, MASKED, ONCHIP>;
-    case 2: return (const void *)screen_kernel<MAXONLY, 2, BF, MASKED, ONCHIP>;
-    default: return (const void *)screen_kernel<MAXONLY, 1, BF, MASKED, ONCHIP>;
-    }
-}
+// Every screen kernel there is, by what a launch does with the scores, by the rows it reads (BF: bf16 rows, converted in LDS:
+// bf16_to_f16_lds), by whether it runs under ScreenParams::keep (MASKED), and by form.
+// KIND_MAIN: candidates.  KIND_MAXONLY: tile maxima only (the sample pass and tt_debug_screen_s16).  KIND_ONCHIP: the sample pass
+// of the shared-tile form with its maxima kept in registers (ScreenParams::top_val).
+enum ScreenKind { KIND_MAIN, KIND_MAXONLY, KIND_ONCHIP };
+// form 0, 1: streaming with 2, 4 query sets per wave (q_per_block 32, 64); form 1 + nset: shared-tile, nset = 1..4 16-query sets
+// per wave.  (KIND_ONCHIP has no streaming form: launch_screen refuses; the two places hold the MAXONLY kernels.)
+#define SCREEN_FORMS(MAXONLY, BF, MASKED, ONCHIP)                                                                             \
+    {(const void *)screen_stream_kernel<MAXONLY, 2, BF, MASKED>, (const void *)screen_stream_kernel<MAXONLY, 4, BF, MASKED>, \
+     (const void *)screen_kernel<MAXONLY, 1, BF, MASKED, ONCHIP>, (const void *)screen_kernel<MAXONLY, 2, BF, MASKED, ONCHIP>, \
+     (const void *)screen_kernel<MAXONLY, 3, BF, MASKED, ONCHIP>, (const void *)screen_kernel<MAXONLY, 4, BF, MASKED, ONCHIP>}
+#define SCREEN_KIND(MAXONLY, ONCHIP)                                                             \
+    {{SCREEN_FORMS(MAXONLY, false, false, ONCHIP), SCREEN_FORMS(MAXONLY, false, true, ONCHIP)}, \
+     {SCREEN_FORMS(MAXONLY, true, false, ONCHIP), SCREEN_FORMS(MAXONLY, true, true, ONCHIP)}}
+const void *const SCREEN_FN[3][2][2][6] = {SCREEN_KIND(false, false), SCREEN_KIND(true, false), SCREEN_KIND(true, true)}; // [kind][BF][MASKED][form]
+#undef SCREEN_KIND
+#undef SCREEN_FORMS
 
-template <bool MAXONLY, bool BF>
-const void *screen_fn(bool stream, int q_per_block, int nset, bool masked)
+// One screen launch over pl's query groups x p.n_chunks document chunks: a wave per task when streaming, a workgroup otherwise.
+// p says what it is: maxima into p.top_val or p.max_val, else candidates; the MASKED instantiation when p.keep is set.
+int launch_screen(const SPlan &pl, ScreenParams p, bool bf16, hipStream_t st)
 {
-    return masked ? screen_fn<MAXONLY, BF, true>(stream, q_per_block, nset) : screen_fn<MAXONLY, BF, false>(stream, q_per_block, nset);
-}
-
-// the sample pass of the shared-tile form with its maxima kept in registers (p.top_val)
-template <bool BF>
-const void *screen_onchip_fn(int nset, bool masked)
-{
-    return masked ? screen_fn<true, BF, true, true>(false, 0, nset) : screen_fn<true, BF, false, true>(false, 0, nset);
-}
-
-// One screen launch over n_tasks (query group, document chunk) tasks: a wave each when streaming, a workgroup otherwise.
-// masked: the MASKED instantiation (p.keep is set); otherwise p.keep is not read.  p.top_val (maxonly, shared-tile): ONCHIP.
-int launch_screen(bool stream, int q_per_block, int nset, bool maxonly, ScreenParams p, int n_tasks, hipStream_t st,
-                  bool bf16 = false, bool masked = false)
-{
-    if (p.top_val && (!maxonly || stream))
+    if (p.top_val && pl.stream)
         return tt_fail(TT_ERR_UNSUPPORTED, "launch_screen: top_val outside the shared-tile sample pass");
-    const void *fn = p.top_val ? (bf16 ? screen_onchip_fn<true>(nset, masked) : screen_onchip_fn<false>(nset, masked))
-                     : maxonly ? (bf16 ? screen_fn<true, true>(stream, q_per_block, nset, masked) : screen_fn<true, false>(stream, q_per_block, nset, masked))
-                             : (bf16 ? screen_fn<false, true>(stream, q_per_block, nset, masked) : screen_fn<false, false>(stream, q_per_block, nset, masked));
-    const size_t lds = stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
-    const int blocks = stream ? (n_tasks + TW - 1) / TW : n_tasks;
+    const ScreenKind kind = p.top_val ? KIND_ONCHIP : p.max_val ? KIND_MAXONLY : KIND_MAIN;
+    const void *fn = SCREEN_FN[kind][bf16][p.keep != nullptr][pl.stream ? pl.q_per_block == 64 : 1 + pl.nset];
+    const int n_tasks = pl.n_qgroups * p.n_chunks;
+    const size_t lds = pl.stream ? (size_t)TW * TSTAGE * TSLAB_BYTES : (size_t)SRING * STILE_BYTES;
+    const int blocks = pl.stream ? (n_tasks + TW - 1) / TW : n_tasks;
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void *args[] = {&p};
-    TT_HIP_CHECK(hipLaunchKernel(fn, dim3(blocks), dim3((stream ? TW : SW) * 64), args, lds, st));
+    TT_HIP_CHECK(hipLaunchKernel(fn, dim3(blocks), dim3((pl.stream ? TW : SW) * 64), args, lds, st));
     return TT_OK;
+}
+
+// The exact fallback's workspace, which lies behind the screen's own (SPlan::ws_bytes): the k <= 64 search's over the same rows
+size_t fallback_ws_bytes(int B, int64_t N, int d, int k, bool bf16)
+{
+    return bf16 ? tt_score_topk_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_workspace_bytes(B, N, d, k);
+}
+
+// The screened size and offset queries: 0 for a shape without queries or documents; else `behind` + the plan's `what`
+size_t splan_query(int B, int64_t N, int k, size_t SPlan::*what, size_t behind)
+{
+    return B <= 0 || N <= 0 ? 0 : make_splan(B, N, k).*what + behind;
 }
 
 } // namespace
@@ -1674,11 +1674,21 @@ TT_EXPORT int tt_index_build_from_bf16(const void *D_bf16, int64_t N, int d, flo
     return TT_OK;
 }
 
+// ---- the workspace of a screened call: over fp32 rows + fp16 shadow, over a bf16 corpus kept as bf16 (D_bf16 replaces
+// D32 + D16, include/tt.h), and of the masked entries, which take either
 TT_EXPORT size_t tt_score_topk_screened_workspace_bytes(int B, int64_t N, int d, int k)
 {
-    if (B <= 0 || N <= 0)
-        return 0;
-    return make_splan(B, N, k).ws_bytes + tt_score_topk_workspace_bytes(B, N, d, k);
+    return splan_query(B, N, k, &SPlan::ws_bytes, fallback_ws_bytes(B, N, d, k, false));
+}
+
+TT_EXPORT size_t tt_score_topk_screened_bf16_workspace_bytes(int B, int64_t N, int d, int k)
+{
+    return splan_query(B, N, k, &SPlan::ws_bytes, fallback_ws_bytes(B, N, d, k, true));
+}
+
+TT_EXPORT size_t tt_score_topk_screened_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return splan_query(B, N, k, &SPlan::ws_bytes, fallback_ws_bytes(B, N, d, k, bf16 != 0));
 }
 
 // Where a finished screened search left its per-query statistics in the caller's workspace: int32 [B][2] = (pooled
@@ -1687,9 +1697,7 @@ TT_EXPORT size_t tt_score_topk_screened_workspace_bytes(int B, int64_t N, int d,
 TT_EXPORT size_t tt_score_topk_screened_stats_offset(int B, int64_t N, int d, int k)
 {
     (void)d;
-    if (B <= 0 || N <= 0)
-        return 0;
-    return make_splan(B, N, k).stats_off;
+    return splan_query(B, N, k, &SPlan::stats_off, 0);
 }
 
 namespace {
@@ -1700,7 +1708,12 @@ __global__ void seed_fill_kernel(float *seed, int n)
         seed[i] = -3.0e38f; // no sample pass for this corpus size: no information (the floor threshold applies)
 }
 
-// What one call of screened_impl does: one per TT_EXPORT entry point below.
+// What one screened call does, and with it which steps `screened` runs:
+//                  query image   sample pass (plans with one), thresholds            main pass, finish, fallback
+//   Whole          yes           k-th largest maximum -> the workspace               yes, under the workspace's thresholds
+//   SeedThreshold  yes           k_seed-th largest -> seed[q]; no sample: filled     -
+//   SeedList       yes           the k_seed largest -> seed[q][..]; no sample: filled -
+//   Seeded         -             -                                                   yes, under the caller's seed[]
 enum class Phase {
     Whole,         // the whole search
     SeedThreshold, // query image + sample pass; seed[q] <- the k_seed-th largest sample maximum (nothing else)
@@ -1710,150 +1723,243 @@ enum class Phase {
                    // image and flags), finish, predicated exact kernels
 };
 
-// bf16: D32 and D16 are both the bf16 corpus (the screen converts it in LDS, the finish kernel and the fallback widen it).
-// keep: the keep-bitmask of the masked entry points (nullptr: the unmasked search, launch for launch): the sample pass and the
-// main pass run their MASKED instantiations, the finish kernel sees kept documents only, the fallback is the masked exact search.
-int screened_impl(const char *who, Phase phase, const float *Q, int B, int d, const void *D32, const void *D16, int64_t N, int k,
-                  int k_seed, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
-                  float *seed, void *workspace, size_t workspace_bytes, void *const *prof_events, hipStream_t st,
-                  bool bf16 = false, const unsigned *keep = nullptr)
-{
-    if (B <= 0 || N <= 0 || k <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, B, (long long)N, k);
-    if (d != 256)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: 256)", who, d);
-    if (k > 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, k);
-    if (N >= (int64_t)INT_MAX - 64)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N too large; shard the corpus", who);
-    if (!(dmax_norm >= 0.0f) || !(dmax_norm < 60000.0f))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: corpus norm %g outside the fp16 range", who, dmax_norm);
-    const bool seed_only = phase == Phase::SeedThreshold || phase == Phase::SeedList; // stop after the sample pass
-    const bool caller_seed = phase == Phase::Seeded; // thresholds from seed[]: no query image, no sample pass
-    if (!Q || !D16 || !fallback_flag || (!seed_only && (!D32 || !out_val || !out_idx)) || (phase != Phase::Whole && !seed))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
-    if (seed_only && (k_seed < 1 || k_seed > k))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: k_seed=%d outside [1, k=%d]", who, k_seed, k);
-    if ((uintptr_t)keep & 3)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", who);
-    const SPlan pl = make_splan(B, N, k);
-    const size_t need = pl.ws_bytes + (bf16 ? tt_score_topk_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_workspace_bytes(B, N, d, k));
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255) || (bf16 && ((uintptr_t)D16 & 15)))
-        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    char *ws = (char *)workspace;
-    // the sample maximum that becomes a threshold, and where it goes
-    const int k_thr = phase == Phase::SeedThreshold ? k_seed : k;
-    float *thr_out = phase == Phase::SeedThreshold ? seed : (float *)(ws + pl.sthr_val_off);
-    // (the fallback flags are initialised by q_image_kernel below -- a kernel, not hipMemsetAsync: a 16-byte-multiple
-    //  memset node captured in a HIP graph came back with garbage from the second replay on; ROCm 7.2, found with
-    //  GraphedSearch at B=128)
+// One screened call as its entry point received it, in the four runs of arguments every entry has: an entry hands over four
+// short braced lists of different types, not twenty positional arguments.
+struct QueryArgs { const float *Q; int B, d, k; float dmax_norm; };
+struct RowArgs {
+    const void *D16; // the rows the screen reads: the fp16 shadow, or the bf16 corpus (converted in LDS)
+    const void *D32; // the rows the finish kernel and the fallback read: fp32, or the same bf16 corpus (they widen it); the seed
+                     // phases read none
+    bool bf16;
+    int64_t N;
+    // keep-bitmask of the masked entries (nullptr: the unmasked search, launch for launch): the sample pass and the main pass run
+    // their MASKED instantiations, the finish kernel sees kept documents only, the fallback is the masked exact search
+    const unsigned *keep;
+};
+struct OutArgs { int64_t idx_offset; float *out_val; int64_t *out_idx; void *const *prof_events; }; // (all zero in the seed phases)
+struct ScratchArgs { int32_t *fallback_flag; void *workspace; size_t workspace_bytes; hipStream_t stream; };
+struct ScreenedCall : QueryArgs, RowArgs, OutArgs, ScratchArgs {
+    const char *who; // the exported name of the entry that was called: every message starts with it
+    Phase phase;
+    int k_seed;  // the seed phases: which sample maxima become the seed (otherwise k)
+    float *seed; // written by SeedThreshold [B] and SeedList [B][k_seed], read by Seeded [B]; Whole: nullptr
+};
 
+RowArgs f32_rows(const float *D32, const void *D16, int64_t N, const unsigned *keep) { return {D16, D32, false, N, keep}; }
+RowArgs bf16_rows(const void *D_bf16, int64_t N, const unsigned *keep) { return {D_bf16, D_bf16, true, N, keep}; }
+
+// Every argument check of a screened call, once; what lies below trusts them.  TT_OK: *pl is the call's plan.
+int screened_validate(const ScreenedCall &c, SPlan *pl)
+{
+    const char *who = c.who;
+    if (c.B <= 0 || c.N <= 0 || c.k <= 0) // (B == 0 is refused here; the exact entries answer TT_OK to it)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d N=%lld k=%d", who, c.B, (long long)c.N, c.k);
+    if (c.d != 256)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: d=%d (supported: 256)", who, c.d);
+    if (c.k > 64)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > 64", who, c.k);
+    if (c.N >= (int64_t)INT_MAX - 64)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: N too large; shard the corpus", who);
+    if (!(c.dmax_norm >= 0.0f) || !(c.dmax_norm < 60000.0f))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: corpus norm %g outside the fp16 range", who, c.dmax_norm);
+    const bool seed_only = c.phase == Phase::SeedThreshold || c.phase == Phase::SeedList;
+    if (!c.Q || !c.D16 || !c.fallback_flag || (!seed_only && (!c.D32 || !c.out_val || !c.out_idx)) ||
+        (c.phase != Phase::Whole && !c.seed))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    if (seed_only && (c.k_seed < 1 || c.k_seed > c.k))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: k_seed=%d outside [1, k=%d]", who, c.k_seed, c.k);
+    if ((uintptr_t)c.keep & 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: keep must be 4-byte aligned", who);
+    *pl = make_splan(c.B, c.N, c.k);
+    const size_t need = pl->ws_bytes + fallback_ws_bytes(c.B, c.N, c.d, c.k, c.bf16);
+    // (a missing or misaligned workspace, and misaligned bf16 rows, are all reported as a workspace that is too small, in a
+    //  message that may then compare a size with itself; the fp16 shadow has no alignment check.  Callers match the code.)
+    if (!c.workspace || c.workspace_bytes < need || ((uintptr_t)c.workspace & 255) || (c.bf16 && ((uintptr_t)c.D16 & 15)))
+        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, c.workspace_bytes, need);
+    return TT_OK;
+}
+
+// ScreenParams is filled here and nowhere else: what every screen launch over pl's cut of the corpus reads.  What stays at its
+// initialiser is not used by a launch until the step that needs it sets it.
+ScreenParams screen_params(const ScreenedCall &c, const SPlan &pl)
+{
+    char *ws = (char *)c.workspace;
     ScreenParams sp;
-    sp.Q = Q;
-    sp.D16 = (const _Float16 *)D16;
-    sp.B = B;
-    sp.N = (int)N;
-    sp.k = k;
+    sp.Q = c.Q;
+    sp.D16 = (const _Float16 *)c.D16;
+    sp.B = c.B;
+    sp.N = (int)c.N;
+    sp.k = c.k;
     sp.n_chunks = pl.n_chunks;
     sp.tiles_per_chunk = pl.tiles_per_chunk;
     sp.n_tiles = pl.n_tiles;
     sp.static_tiles = pl.static_tiles;
     sp.tail_g = pl.tail_g;
     sp.tail_blocks = pl.tail_blocks;
-    sp.tail_ctr = (int *)(ws + pl.tailctr_off);
-    // (the sample pass never reads it; a plan without a sample has a seed only when the caller brings one)
-    sp.hist = pl.refresh && (pl.sample || caller_seed) ? (unsigned *)(ws + pl.hist_off) : nullptr;
-    sp.dmax = dmax_norm;
-    sp.cand = (SCand *)(ws + pl.cand_off);
-    sp.pcnt = (int *)(ws + pl.pcnt_off);
-    sp.flag = fallback_flag;
-    sp.max_val = nullptr;
-    sp.top_val = nullptr;
-    sp.thr0 = nullptr;
-    sp.thr0_stride = k;
+    sp.dmax = c.dmax_norm;
+    sp.flag = c.fallback_flag;
+    sp.thr0_stride = c.k; // (read with thr0 only: main_pass)
     sp.qimg = (const h8 *)(ws + pl.qimg_off);
     sp.qnorm = (const float *)(ws + pl.qnorm_off);
-    sp.dbg_thr = nullptr;
-    sp.keep = keep;
-    const bool masked = keep != nullptr;
-    if (caller_seed) {
-        sp.thr0 = seed;
-        sp.thr0_stride = 1;
-    } else {
-        hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
-                           (float *)(ws + pl.qnorm_off), fallback_flag, (B + 31) / 32, (int *)(ws + pl.tailctr_off),
-                           pl.n_qgroups, pl.hist_off ? (unsigned *)(ws + pl.hist_off) : nullptr);
-        TT_LAUNCH_CHECK();
-        if (pl.sample) {
-            ScreenParams ss = sp;
-            ss.N = (int)pl.s_docs;
-            ss.n_tiles = pl.s_tiles;
-            ss.n_chunks = pl.s_chunks;
-            ss.tiles_per_chunk = pl.s_tiles_per_chunk;
-            ss.static_tiles = pl.s_tiles;
-            ss.tail_blocks = 0;
-            float *const s_val = (float *)(ws + pl.smax_val_off); // [rows][s_vals]
-            (pl.s_onchip ? ss.top_val : ss.max_val) = s_val;
-            // (masked: the sample is the first s_docs rows, its words the first s_tiles of the mask)
-            TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, true, ss, pl.n_qgroups * pl.s_chunks, st, bf16, masked));
-            if (phase == Phase::SeedList)
-                TT_RC_CHECK(tt_k_largest_list(s_val, B, pl.s_vals, k_seed, seed, st));
-            else
-                TT_RC_CHECK(tt_kth_largest(s_val, B, pl.s_vals, k_thr, thr_out, st));
-            sp.thr0 = (const float *)(ws + pl.sthr_val_off);
-            sp.thr0_stride = 1;
-        } else if (seed_only) {
-            const int n = phase == Phase::SeedList ? B * k_seed : B;
-            hipLaunchKernelGGL(seed_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seed, n);
-            TT_LAUNCH_CHECK();
-        }
-    }
-    if (seed_only)
-        return TT_OK;
-    if (prof_events)
-        TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[0], st));
-    TT_RC_CHECK(launch_screen(pl.stream, pl.q_per_block, pl.nset, false, sp, pl.n_qgroups * pl.n_chunks, st, bf16, masked));
-    if (prof_events)
-        TT_HIP_CHECK(hipEventRecord((hipEvent_t)prof_events[1], st));
+    sp.keep = c.keep;
+    return sp;
+}
 
+// ... and the buffers of a search: candidates and their counts, the pool counters, the ladders
+ScreenParams search_params(const ScreenedCall &c, const SPlan &pl)
+{
+    char *ws = (char *)c.workspace;
+    ScreenParams sp = screen_params(c, pl);
+    sp.tail_ctr = (int *)(ws + pl.tailctr_off);
+    // (the sample pass never reads it; a plan without a sample has a seed only when the caller brings one)
+    sp.hist = pl.refresh && (pl.sample || c.phase == Phase::Seeded) ? (unsigned *)(ws + pl.hist_off) : nullptr;
+    sp.cand = (SCand *)(ws + pl.cand_off);
+    sp.pcnt = (int *)(ws + pl.pcnt_off);
+    return sp;
+}
+
+// Query image and norms; resets the fallback flags, the pool counters and the ladders.
+// (the flags are initialised by a kernel, not hipMemsetAsync: a 16-byte-multiple memset node captured in a HIP graph came back
+//  with garbage from the second replay on; ROCm 7.2, found with GraphedSearch at B=128)
+int query_image(const ScreenedCall &c, const SPlan &pl)
+{
+    char *ws = (char *)c.workspace;
+    hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, c.stream, c.Q, c.B, (h8 *)(ws + pl.qimg_off),
+                       (float *)(ws + pl.qnorm_off), c.fallback_flag, (c.B + 31) / 32, (int *)(ws + pl.tailctr_off),
+                       pl.n_qgroups, pl.hist_off ? (unsigned *)(ws + pl.hist_off) : nullptr);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+float *sample_values(const ScreenedCall &c, const SPlan &pl) { return (float *)((char *)c.workspace + pl.smax_val_off); } // [rows][s_vals]
+
+// The sample pass's launch: the search's over the first s_docs rows (masked: the first s_tiles words of the mask), everything
+// static, maxima into s_val instead of candidates
+ScreenParams sample_params(ScreenParams ss, const SPlan &pl, float *s_val)
+{
+    ss.N = (int)pl.s_docs;
+    ss.n_tiles = pl.s_tiles;
+    ss.n_chunks = pl.s_chunks;
+    ss.tiles_per_chunk = pl.s_tiles_per_chunk;
+    ss.static_tiles = pl.s_tiles;
+    ss.tail_blocks = 0;
+    (pl.s_onchip ? ss.top_val : ss.max_val) = s_val;
+    return ss;
+}
+
+int sample_pass(const ScreenedCall &c, const SPlan &pl, const ScreenParams &sp)
+{
+    return launch_screen(pl, sample_params(sp, pl, sample_values(c, pl)), c.bf16, c.stream);
+}
+
+// From the sample maxima: the k-th largest per query into the workspace (Whole) or the k_seed-th largest into seed[]
+// (SeedThreshold), or the k_seed largest into seed[] (SeedList).  A plan without a sample has nothing to select from: the
+// seed phases fill seed[] with the floor, the whole search runs without thresholds.
+int select_thresholds(const ScreenedCall &c, const SPlan &pl)
+{
+    const bool list = c.phase == Phase::SeedList;
+    if (!pl.sample) {
+        if (c.phase == Phase::Whole)
+            return TT_OK;
+        const int n = list ? c.B * c.k_seed : c.B;
+        hipLaunchKernelGGL(seed_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, c.stream, c.seed, n);
+        TT_LAUNCH_CHECK();
+        return TT_OK;
+    }
+    if (list)
+        return tt_k_largest_list(sample_values(c, pl), c.B, pl.s_vals, c.k_seed, c.seed, c.stream);
+    float *thr = c.phase == Phase::SeedThreshold ? c.seed : (float *)((char *)c.workspace + pl.sthr_val_off);
+    return tt_kth_largest(sample_values(c, pl), c.B, pl.s_vals, c.phase == Phase::SeedThreshold ? c.k_seed : c.k, thr, c.stream);
+}
+
+// The main pass between the two profiling events, under the caller's seed (Seeded), the sample's thresholds, or none
+int main_pass(const ScreenedCall &c, const SPlan &pl, ScreenParams sp)
+{
+    if (c.phase == Phase::Seeded || pl.sample) {
+        sp.thr0 = c.phase == Phase::Seeded ? c.seed : (const float *)((char *)c.workspace + pl.sthr_val_off);
+        sp.thr0_stride = 1;
+    }
+    if (c.prof_events)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)c.prof_events[0], c.stream));
+    TT_RC_CHECK(launch_screen(pl, sp, c.bf16, c.stream));
+    if (c.prof_events)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)c.prof_events[1], c.stream));
+    return TT_OK;
+}
+
+// FinishParams is filled here and nowhere else.
+int finish(const ScreenedCall &c, const SPlan &pl)
+{
+    char *ws = (char *)c.workspace;
     FinishParams fp;
-    fp.Q = Q;
-    fp.D32 = bf16 ? nullptr : (const float *)D32;
-    fp.Dbf = bf16 ? (const unsigned *)D32 : nullptr;
-    fp.B = B;
-    fp.N = (int)N;
-    fp.k = k;
+    fp.Q = c.Q;
+    fp.D32 = c.bf16 ? nullptr : (const float *)c.D32;
+    fp.Dbf = c.bf16 ? (const unsigned *)c.D32 : nullptr;
+    fp.B = c.B;
+    fp.N = (int)c.N;
+    fp.k = c.k;
     fp.n_chunks = pl.n_chunks;
     fp.q_per_block = pl.q_per_block;
-    fp.dmax = dmax_norm;
-    fp.cand = sp.cand;
-    fp.pcnt = sp.pcnt;
-    fp.flag = fallback_flag;
-    fp.idx_offset = idx_offset;
-    fp.out_val = out_val;
-    fp.out_idx = out_idx;
+    fp.dmax = c.dmax_norm;
+    fp.cand = (const SCand *)(ws + pl.cand_off);
+    fp.pcnt = (const int *)(ws + pl.pcnt_off);
+    fp.flag = c.fallback_flag;
+    fp.idx_offset = c.idx_offset;
+    fp.out_val = c.out_val;
+    fp.out_idx = c.out_idx;
     fp.stats = (int *)(ws + pl.stats_off);
-    hipLaunchKernelGGL(screen_finish_kernel, dim3(B), dim3(256), (size_t)(2 * pl.n_chunks + 1) * sizeof(int), st, fp);
+    hipLaunchKernelGGL(screen_finish_kernel, dim3(c.B), dim3(256), (size_t)(2 * pl.n_chunks + 1) * sizeof(int), c.stream, fp);
     TT_LAUNCH_CHECK();
-    // exact kernel, a no-op unless a workgroup raised the flag; then it rewrites every output row
-    if (masked) // ... of the flagged tiles with the MASKED exact answer
-        return tt_score_topk_masked_pred(Q, B, d, D32, bf16, N, keep, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
-                                         workspace_bytes - pl.ws_bytes, fallback_flag, st);
-    if (bf16)
-        return tt_score_topk_bf16_pred(Q, B, d, D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
-                                       workspace_bytes - pl.ws_bytes, fallback_flag, st);
-    return tt_score_topk_f32_pred(Q, B, d, (const float *)D32, N, k, idx_offset, out_val, out_idx, ws + pl.ws_bytes,
-                                  workspace_bytes - pl.ws_bytes, fallback_flag, st);
+    return TT_OK;
+}
+
+// The exact k <= 64 search (masked under c.keep) in the workspace behind the screen's, predicated on the fallback flags: a
+// no-op unless a workgroup raised one; then it rewrites every output row of the flagged 32-query tiles.  Its refusals carry
+// the name of the public entry it stands for.
+int fallback(const ScreenedCall &c, const SPlan &pl)
+{
+    const char *who = c.keep ? (c.bf16 ? "tt_score_topk_masked_bf16" : "tt_score_topk_masked_f32")
+                             : (c.bf16 ? "tt_score_topk_bf16" : "tt_score_topk_f32");
+    return exact_small(ExactCall{c.Q, c.B, c.d, c.D32, c.bf16, c.N, c.k, c.idx_offset, c.keep, c.out_val, c.out_idx,
+                                 (char *)c.workspace + pl.ws_bytes, c.workspace_bytes - pl.ws_bytes, c.stream, who},
+                       c.fallback_flag);
+}
+
+// One screened call: the Phase table above, step by step.
+int screened(const ScreenedCall &c)
+{
+    SPlan pl;
+    TT_RC_CHECK(screened_validate(c, &pl));
+    const ScreenParams sp = search_params(c, pl);
+    if (c.phase != Phase::Seeded) { // (Seeded: the workspace holds the seed phase's query image, the thresholds are seed[])
+        TT_RC_CHECK(query_image(c, pl));
+        if (pl.sample)
+            TT_RC_CHECK(sample_pass(c, pl, sp));
+        TT_RC_CHECK(select_thresholds(c, pl));
+    }
+    if (c.phase == Phase::SeedThreshold || c.phase == Phase::SeedList)
+        return TT_OK;
+    TT_RC_CHECK(main_pass(c, pl, sp));
+    TT_RC_CHECK(finish(c, pl));
+    return fallback(c, pl);
+}
+
+// The entries of one phase differ in their name, their rows and their mask only.
+int whole_call(const char *who, const QueryArgs &q, const RowArgs &rows, const OutArgs &out, const ScratchArgs &s)
+{
+    return screened(ScreenedCall{q, rows, out, s, who, Phase::Whole, q.k, nullptr});
+}
+
+int seed_list_call(const char *who, const QueryArgs &q, const RowArgs &rows, int k_seed, float *list, const ScratchArgs &s)
+{
+    return screened(ScreenedCall{q, rows, OutArgs{}, s, who, Phase::SeedList, k_seed, list});
+}
+
+int seeded_call(const char *who, const QueryArgs &q, const RowArgs &rows, const OutArgs &out, const float *seed, const ScratchArgs &s)
+{
+    return screened(ScreenedCall{q, rows, out, s, who, Phase::Seeded, q.k, (float *)seed});
 }
 } // namespace
-
-// ---- the same over a bf16 corpus kept as bf16: D_bf16 replaces D32 + D16 (include/tt.h)
-TT_EXPORT size_t tt_score_topk_screened_bf16_workspace_bytes(int B, int64_t N, int d, int k)
-{
-    if (B <= 0 || N <= 0)
-        return 0;
-    return make_splan(B, N, k).ws_bytes + tt_score_topk_bf16_workspace_bytes(B, N, d, k);
-}
 
 TT_EXPORT int tt_index_stats_bf16(const void *D_bf16, int64_t N, int d, float *stats, int reset_stats, tt_stream_t stream)
 {
@@ -1873,57 +1979,31 @@ TT_EXPORT int tt_index_stats_bf16(const void *D_bf16, int64_t N, int d, float *s
     return TT_OK;
 }
 
-TT_EXPORT int tt_score_topk_screened_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, float dmax_norm,
-                                          int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
-                                          void *workspace, size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
-{
-    return screened_impl("tt_score_topk_screened_bf16", Phase::Whole, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm, idx_offset,
-                         out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream,
-                         true);
-}
-
-TT_EXPORT int tt_score_topk_screened_seed_list_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
-                                                    int k_seed, float dmax_norm, int32_t *fallback_flag, float *seed_list,
-                                                    void *workspace, size_t workspace_bytes, tt_stream_t stream)
-{
-    return screened_impl("tt_score_topk_screened_seed_list_bf16", Phase::SeedList, Q, B, d, nullptr, D_bf16, N, k, k_seed,
-                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
-                         (hipStream_t)stream, true);
-}
-
-TT_EXPORT int tt_score_topk_screened_seeded_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
-                                                 float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
-                                                 int32_t *fallback_flag, const float *seed, void *workspace,
-                                                 size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
-{
-    return screened_impl("tt_score_topk_screened_seeded_bf16", Phase::Seeded, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
-                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
-                         (hipStream_t)stream, true);
-}
-
+// ---- over fp32 rows and their fp16 shadow
 TT_EXPORT int tt_score_topk_screened_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
                                          int k, float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
                                          int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
                                          void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_f32", Phase::Whole, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val, out_idx,
-                         fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream);
+    return whole_call("tt_score_topk_screened_f32", {Q, B, d, k, dmax_norm}, f32_rows(D32, D16, N, nullptr),
+                 {idx_offset, out_val, out_idx, prof_events}, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seed_f32(const float *Q, int B, int d, const void *D16, int64_t N, int k, int k_seed,
                                               float dmax_norm, int32_t *fallback_flag, float *seed, void *workspace,
                                               size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_f32", Phase::SeedThreshold, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr, nullptr,
-                         fallback_flag, seed, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+    return screened(ScreenedCall{{Q, B, d, k, dmax_norm}, f32_rows(nullptr, D16, N, nullptr), OutArgs{},
+                                 {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream},
+                                 "tt_score_topk_screened_seed_f32", Phase::SeedThreshold, k_seed, seed});
 }
 
 TT_EXPORT int tt_score_topk_screened_seed_list_f32(const float *Q, int B, int d, const void *D16, int64_t N, int k, int k_seed,
                                                    float dmax_norm, int32_t *fallback_flag, float *seed_list, void *workspace,
                                                    size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_list_f32", Phase::SeedList, Q, B, d, nullptr, D16, N, k, k_seed, dmax_norm, 0, nullptr,
-                         nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+    return seed_list_call("tt_score_topk_screened_seed_list_f32", {Q, B, d, k, dmax_norm}, f32_rows(nullptr, D16, N, nullptr), k_seed,
+                       seed_list, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
@@ -1931,24 +2011,44 @@ TT_EXPORT int tt_score_topk_screened_seeded_f32(const float *Q, int B, int d, co
                                                 int32_t *fallback_flag, const float *seed, void *workspace,
                                                 size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seeded_f32", Phase::Seeded, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset, out_val,
-                         out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events, (hipStream_t)stream);
+    return seeded_call("tt_score_topk_screened_seeded_f32", {Q, B, d, k, dmax_norm}, f32_rows(D32, D16, N, nullptr),
+                  {idx_offset, out_val, out_idx, prof_events}, seed, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
+}
+
+// ---- the same over a bf16 corpus kept as bf16: D_bf16 replaces D32 + D16 (include/tt.h)
+TT_EXPORT int tt_score_topk_screened_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k, float dmax_norm,
+                                          int64_t idx_offset, float *out_val, int64_t *out_idx, int32_t *fallback_flag,
+                                          void *workspace, size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
+{
+    return whole_call("tt_score_topk_screened_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, nullptr),
+                 {idx_offset, out_val, out_idx, prof_events}, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
+}
+
+TT_EXPORT int tt_score_topk_screened_seed_list_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                                                    int k_seed, float dmax_norm, int32_t *fallback_flag, float *seed_list,
+                                                    void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return seed_list_call("tt_score_topk_screened_seed_list_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, nullptr), k_seed,
+                       seed_list, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
+}
+
+TT_EXPORT int tt_score_topk_screened_seeded_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, int k,
+                                                 float dmax_norm, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                                 int32_t *fallback_flag, const float *seed, void *workspace,
+                                                 size_t workspace_bytes, void *const *prof_events, tt_stream_t stream)
+{
+    return seeded_call("tt_score_topk_screened_seeded_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, nullptr),
+                  {idx_offset, out_val, out_idx, prof_events}, seed, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 // ---- the same six calls under a keep-bitmask (include/tt.h "Masked screened search"); keep == NULL is the unmasked call
-TT_EXPORT size_t tt_score_topk_screened_masked_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
-{
-    return bf16 ? tt_score_topk_screened_bf16_workspace_bytes(B, N, d, k) : tt_score_topk_screened_workspace_bytes(B, N, d, k);
-}
-
 TT_EXPORT int tt_score_topk_screened_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
                                                 const uint32_t *keep, int k, float dmax_norm, int64_t idx_offset, float *out_val,
                                                 int64_t *out_idx, int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
                                                 void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_masked_f32", Phase::Whole, Q, B, d, D32, D16, N, k, k, dmax_norm, idx_offset,
-                         out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events, (hipStream_t)stream,
-                         false, keep);
+    return whole_call("tt_score_topk_screened_masked_f32", {Q, B, d, k, dmax_norm}, f32_rows(D32, D16, N, keep),
+                 {idx_offset, out_val, out_idx, prof_events}, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *keep,
@@ -1956,9 +2056,8 @@ TT_EXPORT int tt_score_topk_screened_masked_bf16(const float *Q, int B, int d, c
                                                  int32_t *fallback_flag, void *workspace, size_t workspace_bytes,
                                                  void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_masked_bf16", Phase::Whole, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
-                         idx_offset, out_val, out_idx, fallback_flag, nullptr, workspace, workspace_bytes, prof_events,
-                         (hipStream_t)stream, true, keep);
+    return whole_call("tt_score_topk_screened_masked_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, keep),
+                 {idx_offset, out_val, out_idx, prof_events}, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seed_list_masked_f32(const float *Q, int B, int d, const void *D16, int64_t N,
@@ -1966,9 +2065,8 @@ TT_EXPORT int tt_score_topk_screened_seed_list_masked_f32(const float *Q, int B,
                                                           int32_t *fallback_flag, float *seed_list, void *workspace,
                                                           size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_list_masked_f32", Phase::SeedList, Q, B, d, nullptr, D16, N, k, k_seed,
-                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
-                         (hipStream_t)stream, false, keep);
+    return seed_list_call("tt_score_topk_screened_seed_list_masked_f32", {Q, B, d, k, dmax_norm}, f32_rows(nullptr, D16, N, keep), k_seed,
+                       seed_list, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seed_list_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
@@ -1976,9 +2074,8 @@ TT_EXPORT int tt_score_topk_screened_seed_list_masked_bf16(const float *Q, int B
                                                            int32_t *fallback_flag, float *seed_list, void *workspace,
                                                            size_t workspace_bytes, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seed_list_masked_bf16", Phase::SeedList, Q, B, d, nullptr, D_bf16, N, k, k_seed,
-                         dmax_norm, 0, nullptr, nullptr, fallback_flag, seed_list, workspace, workspace_bytes, nullptr,
-                         (hipStream_t)stream, true, keep);
+    return seed_list_call("tt_score_topk_screened_seed_list_masked_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, keep), k_seed,
+                       seed_list, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seeded_masked_f32(const float *Q, int B, int d, const float *D32, const void *D16, int64_t N,
@@ -1987,9 +2084,8 @@ TT_EXPORT int tt_score_topk_screened_seeded_masked_f32(const float *Q, int B, in
                                                        void *workspace, size_t workspace_bytes, void *const *prof_events,
                                                        tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seeded_masked_f32", Phase::Seeded, Q, B, d, D32, D16, N, k, k, dmax_norm,
-                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
-                         (hipStream_t)stream, false, keep);
+    return seeded_call("tt_score_topk_screened_seeded_masked_f32", {Q, B, d, k, dmax_norm}, f32_rows(D32, D16, N, keep),
+                  {idx_offset, out_val, out_idx, prof_events}, seed, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 TT_EXPORT int tt_score_topk_screened_seeded_masked_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N,
@@ -1998,9 +2094,8 @@ TT_EXPORT int tt_score_topk_screened_seeded_masked_bf16(const float *Q, int B, i
                                                         const float *seed, void *workspace, size_t workspace_bytes,
                                                         void *const *prof_events, tt_stream_t stream)
 {
-    return screened_impl("tt_score_topk_screened_seeded_masked_bf16", Phase::Seeded, Q, B, d, D_bf16, D_bf16, N, k, k, dmax_norm,
-                         idx_offset, out_val, out_idx, fallback_flag, (float *)seed, workspace, workspace_bytes, prof_events,
-                         (hipStream_t)stream, true, keep);
+    return seeded_call("tt_score_topk_screened_seeded_masked_bf16", {Q, B, d, k, dmax_norm}, bf16_rows(D_bf16, N, keep),
+                  {idx_offset, out_val, out_idx, prof_events}, seed, {fallback_flag, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 // ------------------------------------------------------------------ test-only: observe the screen's raw scores
@@ -2010,94 +2105,77 @@ TT_EXPORT int tt_score_topk_screened_seeded_masked_bf16(const float *Q, int B, i
 // t = fl(sum - thr[query]) (accumulators start at -thr, the main pass's arithmetic).  A test that fills every tile
 // with 32 copies of one document reads that document's value.  Not bound by the Python package.
 namespace {
-struct DbgPlan {
-    int q_per_block, n_qgroups, rows_pad, n_tiles, n_chunks, tiles_per_chunk;
-    size_t qimg_off, qnorm_off, flag_off, total;
-};
+// An SPlan with the caller's form in place of make_splan's choice, and a workspace of its own: query image, norms, flags.
 // form 0: streaming, 32 queries per wave; form 1, 2, 4: shared-tile with that many query sets per wave.  The chunks are
-// make_splan's without its finish-pool bound (there is no finish kernel here) and without the tail pool.
-bool make_dbg_plan(int B, int64_t N, int form, DbgPlan &pl)
+// make_splan's without its finish-pool bound (there is no finish kernel here) and without the tail pool; what a search alone
+// needs stays zero.  False: no such plan (the size query answers 0).
+struct DbgPlan {
+    SPlan s;
+    size_t flag_off;
+};
+bool make_dbg_plan(int B, int64_t N, int form, DbgPlan *dp)
 {
-    if (form != 0 && form != 1 && form != 2 && form != 4)
+    if (B <= 0 || N <= 0 || (form != 0 && form != 1 && form != 2 && form != 4))
         return false;
+    SPlan pl = {};
+    pl.stream = form == 0;
+    pl.nset = form;
     pl.q_per_block = form == 0 ? 32 : SW * 16 * form;
     pl.n_qgroups = (B + pl.q_per_block - 1) / pl.q_per_block;
     pl.rows_pad = pl.n_qgroups * pl.q_per_block;
     pl.n_tiles = (int)((N + 31) / 32);
-    const TTChunks c = tt_chunks(pl.n_tiles, one_round(form == 0, pl.n_qgroups), INT_MAX);
+    const TTChunks c = tt_chunks(pl.n_tiles, one_round(pl.stream, pl.n_qgroups), INT_MAX);
     pl.tiles_per_chunk = c.tiles_per_chunk;
     pl.n_chunks = c.n_chunks;
+    pl.static_tiles = pl.n_tiles; // everything static
+    pl.tail_g = 1;
     TTWorkspace ws;
     pl.qimg_off = ws.take((size_t)pl.rows_pad * 256 * sizeof(_Float16));
     pl.qnorm_off = ws.take((size_t)pl.rows_pad * sizeof(float));
-    pl.flag_off = ws.take((size_t)(pl.rows_pad / 32 + 1) * sizeof(int));
-    pl.total = ws.off;
+    dp->flag_off = ws.take((size_t)(pl.rows_pad / 32 + 1) * sizeof(int));
+    pl.ws_bytes = ws.off;
+    dp->s = pl;
     return true;
+}
+
+// (both entries answer under the first one's name)
+int debug_screen(const QueryArgs &q, const RowArgs &rows, const ScratchArgs &s, const float *thr, int form, float *out_t)
+{
+    DbgPlan dp;
+    if (rows.N >= (int64_t)INT_MAX - 64 || !make_dbg_plan(q.B, rows.N, form, &dp))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_debug_screen_s16: B=%d N=%lld form=%d", q.B, (long long)rows.N, form);
+    if (!q.Q || !rows.D16 || !out_t)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_debug_screen_s16: null pointer");
+    if (!s.workspace || s.workspace_bytes < dp.s.ws_bytes || ((uintptr_t)s.workspace & 255))
+        return tt_fail(TT_ERR_WORKSPACE, "tt_debug_screen_s16: workspace %zu < %zu bytes", s.workspace_bytes, dp.s.ws_bytes);
+    char *ws = (char *)s.workspace;
+    ScreenParams sp = screen_params(ScreenedCall{q, rows, OutArgs{}, s, "tt_debug_screen_s16", Phase::Whole, q.k, nullptr}, dp.s);
+    sp.flag = (int *)(ws + dp.flag_off);
+    sp.max_val = out_t; // [B][n_tiles]
+    sp.dbg_thr = thr;
+    hipLaunchKernelGGL(q_image_kernel, dim3(dp.s.rows_pad / 32), dim3(128), 0, s.stream, q.Q, q.B, (h8 *)(ws + dp.s.qimg_off),
+                       (float *)(ws + dp.s.qnorm_off), sp.flag, dp.s.rows_pad / 32, (int *)nullptr, 0, (unsigned *)nullptr);
+    TT_LAUNCH_CHECK();
+    return launch_screen(dp.s, sp, rows.bf16, s.stream);
 }
 } // namespace
 
 TT_EXPORT size_t tt_debug_screen_s16_workspace_bytes(int B, int64_t N, int form)
 {
-    DbgPlan pl;
-    if (B <= 0 || N <= 0 || !make_dbg_plan(B, N, form, pl))
-        return 0;
-    return pl.total;
+    DbgPlan dp;
+    return make_dbg_plan(B, N, form, &dp) ? dp.s.ws_bytes : 0;
 }
-
-namespace {
-int debug_screen(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr, int form, float *out_t,
-                 void *workspace, size_t workspace_bytes, tt_stream_t stream, bool bf16)
-{
-    hipStream_t st = (hipStream_t)stream;
-    DbgPlan pl;
-    if (B <= 0 || N <= 0 || N >= (int64_t)INT_MAX - 64 || !make_dbg_plan(B, N, form, pl))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_debug_screen_s16: B=%d N=%lld form=%d", B, (long long)N, form);
-    if (!Q || !D16 || !out_t)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_debug_screen_s16: null pointer");
-    if (!workspace || workspace_bytes < pl.total || ((uintptr_t)workspace & 255))
-        return tt_fail(TT_ERR_WORKSPACE, "tt_debug_screen_s16: workspace %zu < %zu bytes", workspace_bytes, pl.total);
-    char *ws = (char *)workspace;
-    ScreenParams sp;
-    sp.Q = Q;
-    sp.D16 = (const _Float16 *)D16;
-    sp.B = B;
-    sp.N = (int)N;
-    sp.k = 1;
-    sp.n_chunks = pl.n_chunks;
-    sp.tiles_per_chunk = pl.tiles_per_chunk;
-    sp.n_tiles = pl.n_tiles;
-    sp.static_tiles = pl.n_tiles;
-    sp.tail_g = 1;
-    sp.tail_blocks = 0;
-    sp.tail_ctr = nullptr;
-    sp.hist = nullptr;
-    sp.dmax = dmax_norm;
-    sp.cand = nullptr;
-    sp.pcnt = nullptr;
-    sp.flag = (int *)(ws + pl.flag_off);
-    sp.max_val = out_t; // [B][n_tiles]
-    sp.top_val = nullptr;
-    sp.thr0 = nullptr;
-    sp.thr0_stride = 1;
-    sp.qimg = (const h8 *)(ws + pl.qimg_off);
-    sp.qnorm = (const float *)(ws + pl.qnorm_off);
-    sp.dbg_thr = thr;
-    sp.keep = nullptr;
-    hipLaunchKernelGGL(q_image_kernel, dim3(pl.rows_pad / 32), dim3(128), 0, st, Q, B, (h8 *)(ws + pl.qimg_off),
-                       (float *)(ws + pl.qnorm_off), sp.flag, pl.rows_pad / 32, (int *)nullptr, 0, (unsigned *)nullptr);
-    TT_LAUNCH_CHECK();
-    return launch_screen(form == 0, pl.q_per_block, form, true, sp, pl.n_qgroups * pl.n_chunks, st, bf16);
-}
-} // namespace
 
 TT_EXPORT int tt_debug_screen_s16(const float *Q, int B, const void *D16, int64_t N, float dmax_norm, const float *thr,
                                   int form, float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream)
 {
-    return debug_screen(Q, B, D16, N, dmax_norm, thr, form, out_t, workspace, workspace_bytes, stream, false);
+    return debug_screen({Q, B, 256, 1, dmax_norm}, {D16, nullptr, false, N, nullptr},
+                        {nullptr, workspace, workspace_bytes, (hipStream_t)stream}, thr, form, out_t);
 }
 
 TT_EXPORT int tt_debug_screen_s16_bf16(const float *Q, int B, const void *D_bf16, int64_t N, float dmax_norm, const float *thr,
                                        int form, float *out_t, void *workspace, size_t workspace_bytes, tt_stream_t stream)
 {
-    return debug_screen(Q, B, D_bf16, N, dmax_norm, thr, form, out_t, workspace, workspace_bytes, stream, true);
+    return debug_screen({Q, B, 256, 1, dmax_norm}, {D_bf16, nullptr, true, N, nullptr},
+                        {nullptr, workspace, workspace_bytes, (hipStream_t)stream}, thr, form, out_t);
 }
