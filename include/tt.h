@@ -13,7 +13,10 @@
  *    the parameter comment says "host".  All matrices are row-major, dense.
  *  - the library never allocates or frees user-visible memory and keeps no
  *    reference past return: outputs and workspace are caller-owned; workspace
- *    size comes from the matching *_workspace_bytes() query.
+ *    size comes from the matching *_workspace_bytes() query.  A workspace and
+ *    every output may hold anything on entry (another call's leftovers, NaN
+ *    bits): a call writes each word before it reads it, except where a
+ *    parameter comment names it an input (accumulate, the seeded calls).
  *  - every call is asynchronous on `stream` (a hipStream_t; NULL = the null
  *    stream), issues no hipDeviceSynchronize and may be captured in a hipGraph.
  *  - every call returns an int status (TT_OK = 0) and never throws;
