@@ -645,6 +645,24 @@ int tt_triplet_loss_f32(const float *q, const float *p, const float *n, int B, i
                         float *dq, float *dp, float *dn, float *scratch_rows, tt_stream_t stream);
 
 /*
+ * In-batch negatives: the softmax contrastive loss over the batch's positives and its explicit negatives (DPR's loss), with
+ * its gradient.  q, p, n [B,H] f32; D = [p; n] (2B rows); eps = 1e-8:
+ *   qh_i = q_i / max(||q_i||, eps)        Dh_j = D_j / max(||D_j||, eps)
+ *   s_ij = (qh_i . Dh_j) / temperature    i < B, j < 2B
+ *   loss = mean_i (logsumexp_j s_ij - s_ii)                    (the positive of query i is D_i = p_i)
+ * loss [1]; dq/dp/dn [B,H] = d loss / d{q,p,n}, through the norms (all three or none, nullable; without them only the loss is
+ * written, the same bits as with them).  A row shorter than eps is divided by eps, as the formula states.
+ * Any 1 <= H <= 512, 1 <= B <= 2^24; temperature finite and > 0.  Exact f32 products (f32-input MFMA), running maximum
+ * inside the softmax ([B,2B] is never stored; logits of +-1/temperature do not overflow).  Deterministic: no atomics, every
+ * reduction in one fixed order, so two calls on the same inputs give the same bits, whatever the workspace held on entry.
+ * workspace: tt_in_batch_loss_workspace_bytes(B, H) bytes (0 for a shape the call refuses), 16-byte aligned, caller-owned;
+ * asynchronous on `stream`; capture-clean.  Refusals are TT_ERR_BAD_SHAPE.
+ */
+size_t tt_in_batch_loss_workspace_bytes(int B, int H);
+int tt_in_batch_loss_f32(const float *q, const float *p, const float *n, int B, int H, float temperature, float *loss,
+                         float *dq, float *dp, float *dn, void *workspace, size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

@@ -5,13 +5,13 @@ from . import collective, evaluators, hybrid, model, query_inferencer, tokenizer
 from .index import (BruteForceIndex, GraphedSearch, PendingSearch, ShardedIndex, StreamedIndex, pack_keep_mask, score_all, score_count, score_ids, score_rank, score_topk,
                     shard_bounds, topk_cut_below, topk_exclude, topk_merge)
 from .hybrid import HybridSearcher, SimpleHybridRetriever
-from .model import RNNEncoder, TwoTowerModel, triplet_loss_cosine
+from .model import RNNEncoder, TwoTowerModel, in_batch_softmax_loss, triplet_loss_cosine
 from .query_inferencer import QueryInferencer
 from .tokenizer import PretrainedTokenizer
 from .trainer import DataParallelTrainer, FusedClipAdam, GraphedTrainStep, train_step
 
 __all__ = ["BruteForceIndex", "GraphedSearch", "ShardedIndex", "PendingSearch", "StreamedIndex", "score_topk", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "shard_bounds", "pack_keep_mask", "score_count", "topk_cut_below",
-           "RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "QueryInferencer", "PretrainedTokenizer", "HybridSearcher", "SimpleHybridRetriever",
+           "RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "QueryInferencer", "PretrainedTokenizer", "HybridSearcher", "SimpleHybridRetriever",
            "FusedClipAdam", "DataParallelTrainer", "train_step", "GraphedTrainStep", "model", "trainer", "tokenizer", "query_inferencer",
            "evaluators", "hybrid", "collective"]
 __version__ = "0.1.0"

@@ -1,0 +1,494 @@
+// K9 in-batch softmax contrastive loss (forward + gradient) on the f32-input MFMA (gfx950).
+//
+//   qh_i = q_i / max(||q_i||, eps)     Dh_j = D_j / max(||D_j||, eps)     D = [p; n] (2B rows), eps = 1e-8
+//   s_ij = (qh_i . Dh_j) / temperature                       loss = mean_i (logsumexp_j s_ij - s_ii)
+//
+// Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
+//   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
+//   2 ib_stats_kernel    a workgroup per (32 queries, slice of the documents): S^T tiles on v_mfma_f32_32x32x2_f32, online
+//                        (max, sum exp) per lane, fixed-order combine -> the slice's (max, sum exp) per query
+//   3 ib_lse_kernel      a thread per query: the slices' partials in ascending order -> lse_i, row loss_i
+//   4 ib_sum_kernel      fixed-order mean of the row losses
+//   5 ib_grad_kernel     a workgroup per (32 queries, slice of the documents): recomputes S^T, G = (exp(s - lse) - onehot) /
+//                        (B temperature) through LDS, partial dqh = G Dh; and, in the same launch with the roles swapped, a
+//                        workgroup per (32 documents, slice of the queries): partial dDh = G^T qh
+//   6 ib_project_kernel  one wave per row: the slices' partials in ascending order, back-projection through the norm
+//                        -> dq, dp, dn
+// [B,2B] never reaches memory.  Every sum has one fixed order (the MFMA's k order, chunks of 128 rows ascending, slices
+// ascending, xor trees), and the slicing depends on (B, H) alone, so the result is bit-reproducible and independent of what
+// the workspace held.
+#include <float.h>
+
+#include "tt_common.h"
+
+namespace {
+
+constexpr int IB_TILE = 32;    // rows a workgroup owns (query-tile height / document-tile width): one MFMA tile
+constexpr int IB_CHUNK = 128;  // rows of the other side per iteration: one 32-row tile per wave
+constexpr int IB_MAX_H = 512;
+constexpr float IB_EPS = 1e-8f;
+constexpr int IB_WANT_WGS = 256;  // workgroups a pass aims at (a constant, not the device's CU count: same bits everywhere)
+constexpr int IB_MAX_SLICES = 8;
+constexpr int IB_KB = 8;  // MFMA k-steps (of 2 rows) per prefetched batch of the gradient product
+
+// The rows a pass walks, cut into slices of whole chunks: n_slices slices of `per` chunks, none empty.
+struct IBSlices {
+    int per, n;
+};
+IBSlices ib_slices(int walked_rows, int owner_rows)
+{
+    const int chunks = (walked_rows + IB_CHUNK - 1) / IB_CHUNK, tiles = (owner_rows + IB_TILE - 1) / IB_TILE;
+    int want = IB_WANT_WGS / tiles;
+    want = want > IB_MAX_SLICES ? IB_MAX_SLICES : (want < 1 ? 1 : want);
+    want = want > chunks ? chunks : want;
+    const int per = (chunks + want - 1) / want;
+    return {per, (chunks + per - 1) / per};
+}
+
+struct IBPlan {
+    int Hp, Bq, Dp;   // image width (H up to a multiple of 32), image heights (B, 2B up to multiples of IB_CHUNK)
+    IBSlices sq, sd;  // slices of the documents a query tile walks / of the queries a document tile walks
+    size_t qh, dh, den, flag, lse, rows, pm, pl, pos, part_q, part_d, total;
+};
+
+IBPlan ib_plan(int B, int H)
+{
+    IBPlan P;
+    P.Hp = (H + 31) / 32 * 32;
+    P.Bq = (B + IB_CHUNK - 1) / IB_CHUNK * IB_CHUNK;
+    P.Dp = (2 * B + IB_CHUNK - 1) / IB_CHUNK * IB_CHUNK;
+    TTWorkspace w;
+    P.qh = w.take(sizeof(float) * (size_t)P.Bq * P.Hp);
+    P.dh = w.take(sizeof(float) * (size_t)P.Dp * P.Hp);
+    P.den = w.take(sizeof(float) * (size_t)(P.Bq + P.Dp));   // max(norm, eps): queries, then documents
+    P.flag = w.take(sizeof(float) * (size_t)(P.Bq + P.Dp));  // 1 where norm >= eps (the clamp passes gradient), else 0
+    P.lse = w.take(sizeof(float) * (size_t)P.Bq);
+    P.rows = w.take(sizeof(float) * (size_t)P.Bq);
+    P.sq = ib_slices(2 * B, B);
+    P.sd = ib_slices(B, 2 * B);
+    P.pm = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);  // per (slice, query): running maximum, sum of exponentials
+    P.pl = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);
+    P.pos = w.take(sizeof(float) * (size_t)P.Bq);          // s_ii
+    P.part_q = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq * P.Hp);  // per slice: partial dqh [Bq][Hp], dDh [Dp][Hp]
+    P.part_d = w.take(sizeof(float) * (size_t)P.sd.n * P.Dp * P.Hp);
+    P.total = w.off;
+    return P;
+}
+
+// ------------------------------------------------------------------ 1: norms and images
+// Row r of [queries (Bq rows); documents (Dp rows)]; rows past B / 2B and columns past H are written as zeros.
+__global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ q, const float *__restrict__ p,
+                                                      const float *__restrict__ n, int B, int H, int Hp, int Bq, int Dp,
+                                                      float *__restrict__ qh, float *__restrict__ dh,
+                                                      float *__restrict__ den, float *__restrict__ flag)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= Bq + Dp)
+        return;
+    const float *src = nullptr;
+    float *dst;
+    if (r < Bq) {
+        src = r < B ? q + (size_t)r * H : nullptr;
+        dst = qh + (size_t)r * Hp;
+    } else {
+        const int j = r - Bq;
+        src = j < B ? p + (size_t)j * H : (j < 2 * B ? n + (size_t)(j - B) * H : nullptr);
+        dst = dh + (size_t)j * Hp;
+    }
+    float ss = 0.0f;
+    if (src)
+        for (int u = lane; u < H; u += 64)
+            ss += src[u] * src[u];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        ss += __shfl_xor(ss, off);
+    const float norm = sqrtf(ss);
+    const float d = fmaxf(norm, IB_EPS);
+    for (int u = lane; u < Hp; u += 64)
+        dst[u] = (src && u < H) ? src[u] / d : 0.0f;
+    if (lane == 0) {
+        den[r] = d;
+        flag[r] = norm >= IB_EPS ? 1.0f : 0.0f;
+    }
+}
+
+// S^T tile on the matrix pipe: acc[reg] = A_row(a0 + rho(reg) + 4 * (lane >> 5)) . B_row(b0 + (lane & 31)), rho(reg) =
+// (reg & 3) + 8 * (reg >> 2).  Both images are [rows][Hp] with Hp % 32 == 0; each lane loads 4 consecutive k of its row for
+// four MFMA steps (the k order inside a group of 8 is permuted identically for both operands).  Two accumulators (even and odd
+// groups of 8) are added at the end.  One wave per SIMD has nobody to hide a load behind, so the loop is software-pipelined:
+// the 32 columns of the next step are in flight while the 16 MFMAs (1024 cycles) of this one issue.
+struct IBFrag {
+    f32x4 a[4], b[4];
+};
+__device__ __forceinline__ IBFrag ib_frag(const float *__restrict__ ap, const float *__restrict__ bp, int k)
+{
+    IBFrag f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        f.a[g] = *(const f32x4 *)(ap + k + 8 * g);
+        f.b[g] = *(const f32x4 *)(bp + k + 8 * g);
+    }
+    return f;
+}
+__device__ __forceinline__ f32x16 ib_scores(const float *__restrict__ A, int a0, const float *__restrict__ Bm, int b0,
+                                            int Hp, int lane)
+{
+    const float *ap = A + (size_t)(a0 + (lane & 31)) * Hp + 4 * (lane >> 5);
+    const float *bp = Bm + (size_t)(b0 + (lane & 31)) * Hp + 4 * (lane >> 5);
+    f32x16 acc0 = {}, acc1 = {};
+    IBFrag cur = ib_frag(ap, bp, 0);
+    for (int k = 0; k < Hp; k += 32) {  // Hp % 32 == 0
+        IBFrag nxt = cur;
+        if (k + 32 < Hp)
+            nxt = ib_frag(ap, bp, k + 32);
+#pragma unroll
+        for (int g = 0; g < 4; g += 2)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[g][e], cur.b[g][e], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[g + 1][e], cur.b[g + 1][e], acc1, 0, 0, 0);
+            }
+        cur = nxt;
+    }
+    return acc0 + acc1;
+}
+
+__device__ __forceinline__ int ib_rho(int reg) { return (reg & 3) + 8 * (reg >> 2); }
+
+// ------------------------------------------------------------------ 2: row statistics
+// Workgroup = 32 queries (on the lanes) x slice blockIdx.y of the documents; wave w takes the 32-document tiles w, w + 4, ... of
+// the slice.  Each lane keeps a running maximum and a sum of exponentials over the documents it sees; the 8 partials of a
+// query (4 waves x 2 lane halves) are combined in a fixed order into the slice's pair.  (A slice holds a valid document
+// for every query: slices are whole chunks, none empty.)
+__global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh, int B,
+                                                       int Hp, int Bq, int tiles_per_slice, float temperature,
+                                                       float *__restrict__ pm, float *__restrict__ pl,
+                                                       float *__restrict__ pos)
+{
+    __shared__ float part_m[8][IB_TILE], part_l[8][IB_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5;
+    const int i0 = blockIdx.x * IB_TILE, i = i0 + (lane & 31);
+    const int ND = 2 * B;
+    const int t_begin = blockIdx.y * tiles_per_slice;
+    const int t_all = (ND + IB_TILE - 1) / IB_TILE, n_tiles = t_begin + tiles_per_slice < t_all ? t_begin + tiles_per_slice : t_all;
+    float m = -INFINITY, l = 0.0f;
+    for (int t = t_begin + wave; t < n_tiles; t += 4) {
+        const int j0 = t * IB_TILE;
+        const f32x16 acc = ib_scores(dh, j0, qh, i0, Hp, lane);
+        float x[16], tm = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = j0 + ib_rho(r) + 4 * half;
+            x[r] = acc[r] / temperature;
+            if (j < ND)
+                tm = fmaxf(tm, x[r]);
+            if (j == i && i < B)
+                pos[i] = x[r];  // (one lane of one wave of one slice, once)
+        }
+        if (tm > -INFINITY) {  // (some document of the tile is valid for this lane half)
+            const float mn = fmaxf(m, tm);
+            float s = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (j0 + ib_rho(r) + 4 * half < ND)
+                    s += expf(x[r] - mn);
+            l = l * expf(m - mn) + s;  // (m = -inf: l = 0 and exp(-inf) = 0)
+            m = mn;
+        }
+    }
+    part_m[wave * 2 + half][lane & 31] = m;
+    part_l[wave * 2 + half][lane & 31] = l;
+    __syncthreads();
+    if (threadIdx.x < IB_TILE && i0 + (int)threadIdx.x < B) {
+        const int c = threadIdx.x;
+        float M = -INFINITY;
+        for (int k = 0; k < 8; ++k)
+            M = fmaxf(M, part_m[k][c]);
+        float L = 0.0f;
+        for (int k = 0; k < 8; ++k)
+            if (part_l[k][c] > 0.0f)
+                L += part_l[k][c] * expf(part_m[k][c] - M);
+        pm[(size_t)blockIdx.y * Bq + i0 + c] = M;
+        pl[(size_t)blockIdx.y * Bq + i0 + c] = L;
+    }
+}
+
+// The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_ii.
+__global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ pm, const float *__restrict__ pl,
+                                                     const float *__restrict__ pos, int B, int Bq, int n_slices,
+                                                     float *__restrict__ lse, float *__restrict__ row_loss)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B)
+        return;
+    float m[IB_MAX_SLICES], l[IB_MAX_SLICES];  // (all slices asked for at once, combined in ascending order)
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s) {
+        m[s] = s < n_slices ? pm[(size_t)s * Bq + i] : -INFINITY;
+        l[s] = s < n_slices ? pl[(size_t)s * Bq + i] : 0.0f;
+    }
+    float M = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s)
+        M = fmaxf(M, m[s]);
+    float L = 0.0f;
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s)
+        if (s < n_slices)
+            L += l[s] * expf(m[s] - M);
+    const float v = M + logf(L);
+    lse[i] = v;
+    row_loss[i] = v - pos[i];
+}
+
+// ------------------------------------------------------------------ 5: gradients of the images
+// QOWN: the workgroup owns 32 queries and walks a slice of the documents (dqh = G Dh); else it owns 32 documents and walks a
+// slice of the queries (dDh = G^T qh).  Per chunk of 128 rows of the other side: each wave recomputes one S^T tile
+// [other 32][owner 32], turns it into G and stores it to LDS [128][32]; then wave w accumulates the 32-column slices w, w + 4, ...
+// of the owner rows' gradient, dXh^T [h 32][owner 32] += Other^T [h][128] G [128][owner] (A operand straight from the image,
+// coalesced; B operand from LDS).  A chunk's product starts from zero and is added to the running total (blocked summation).
+// The epilogue turns the [h][owner] accumulators into rows through LDS and stores the slice's partial [32][Hp] coalesced.
+template <bool QOWN>
+__device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restrict__ qh, const float *__restrict__ dh,
+                                             const float *__restrict__ lse, int B, int Hp, float temperature, int tile,
+                                             int chunk_begin, int chunk_end, float *__restrict__ part)
+{
+    // (the wave index as a scalar: the compiler then branches on it instead of masking lanes)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5, col = lane & 31;
+    const float *own = QOWN ? qh : dh, *oth = QOWN ? dh : qh;
+    const int n_oth = QOWN ? 2 * B : B;
+    const int own0 = tile * IB_TILE, o = own0 + col;
+    const int NT = Hp / 32;
+    const float scale = 1.0f / ((float)B * temperature);
+    const float lse_own = (QOWN && o < B) ? lse[o] : 0.0f;
+    f32x16 tot[4] = {};
+    for (int ch = chunk_begin; ch < chunk_end; ++ch) {
+        const int c0 = ch * IB_CHUNK, y0 = c0 + IB_TILE * wave;
+        f32x16 g = {};
+        if (y0 < n_oth) {  // (wave-uniform; a tile wholly past the end stores zeros)
+            // the walked queries' lse, asked for before the products so that they arrive behind them (entries past B hold
+            // anything and are not used; the array is padded like the images)
+            float ls_y[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                ls_y[r] = QOWN ? lse_own : lse[y0 + ib_rho(r) + 4 * half];
+            const f32x16 acc = ib_scores(oth, y0, own, own0, Hp, lane);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int y = y0 + ib_rho(r) + 4 * half;
+                const int iq = QOWN ? o : y, jd = QOWN ? y : o;
+                float v = 0.0f;
+                if (iq < B && jd < 2 * B) {
+                    const float ls = ls_y[r];
+                    v = (expf(acc[r] / temperature - ls) - (jd == iq ? 1.0f : 0.0f)) * scale;
+                }
+                g[r] = v;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            ib_lds[(IB_TILE * wave + ib_rho(r) + 4 * half) * IB_TILE + col] = g[r];
+        __syncthreads();
+        f32x16 acc[4] = {};
+        // (rows < Bq / Dp: the images are padded to whole chunks.)  Software-pipelined like ib_scores: the A operands of the next
+        // 8 k-steps (16 rows of the chunk) are in flight while this batch's MFMAs issue.
+        const float *ap = oth + (size_t)(c0 + half) * Hp + 32 * wave + col;
+        float cur[IB_KB][4], nxt[IB_KB][4];
+#pragma unroll
+        for (int s = 0; s < IB_KB; ++s)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                cur[s][t] = wave + 4 * t < NT ? ap[(size_t)(2 * s) * Hp + 128 * t] : 0.0f;
+        for (int k = 0; k < IB_CHUNK; k += 2 * IB_KB) {
+#pragma unroll
+            for (int s = 0; s < IB_KB; ++s)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    nxt[s][t] = (k + 2 * IB_KB < IB_CHUNK && wave + 4 * t < NT) ? ap[(size_t)(k + 2 * IB_KB + 2 * s) * Hp + 128 * t] : 0.0f;
+#pragma unroll
+            for (int s = 0; s < IB_KB; ++s) {
+                const float b = ib_lds[(k + 2 * s + half) * IB_TILE + col];
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (wave + 4 * t < NT)
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur[s][t], b, acc[t], 0, 0, 0);
+            }
+#pragma unroll
+            for (int s = 0; s < IB_KB; ++s)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    cur[s][t] = nxt[s][t];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            tot[t] += acc[t];
+        __syncthreads();  // (the next chunk, or the epilogue, overwrites G)
+    }
+    // gradient tile [owner 32][Hp], the columns of row c rotated by c so that the 32 lanes of a store hit 32 banks
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (wave + 4 * t < NT)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int u = 32 * (wave + 4 * t) + ib_rho(r) + 4 * half + col;
+                u = u >= Hp ? u - Hp : u;
+                ib_lds[col * Hp + u] = tot[t][r];
+            }
+    __syncthreads();
+    // (all 32 rows: the partial buffers are padded to whole chunks like the images; rows past the end hold zeros)
+    for (int c = wave * 8; c < wave * 8 + 8; ++c) {
+        const float *gt = ib_lds + c * Hp;
+        float *out = part + (size_t)(own0 + c) * Hp;
+        for (int u = lane; u < Hp; u += 64)
+            out[u] = gt[u + c >= Hp ? u + c - Hp : u + c];
+    }
+}
+
+// Blocks [0, tiles_q * slices_q): query tiles (block = slice * tiles_q + tile); the rest: document tiles, the same way.
+__global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                      const float *__restrict__ lse, int B, int Hp, int Bq, int Dp,
+                                                      float temperature, int tiles_q, int slices_q, int per_q, int tiles_d,
+                                                      int per_d, float *__restrict__ part_q, float *__restrict__ part_d)
+{
+    extern __shared__ __attribute__((aligned(16))) float ib_lds[];  // G [128][32], later the gradient tile [32][Hp]
+    int b = blockIdx.x;
+    if (b < tiles_q * slices_q) {
+        const int slice = b / tiles_q, chunks = (2 * B + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
+        ib_grad_body<true>(ib_lds, qh, dh, lse, B, Hp, temperature, b % tiles_q, slice * per_q, end,
+                           part_q + (size_t)slice * Bq * Hp);
+    } else {
+        b -= tiles_q * slices_q;
+        const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
+        ib_grad_body<false>(ib_lds, qh, dh, lse, B, Hp, temperature, b % tiles_d, slice * per_d, end,
+                            part_d + (size_t)slice * Dp * Hp);
+    }
+}
+
+// ------------------------------------------------------------------ 6: through the norms
+// One wave per row of [q; p; n]: the slices' partials in ascending order -> dxh, then
+// dx = (dxh - xh (xh . dxh)) / ||x||, or dxh / eps for a row shorter than eps: (dxh - flag xh (xh . dxh)) / max(||x||, eps).
+__global__ __launch_bounds__(256) void ib_project_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                         const float *__restrict__ den, const float *__restrict__ flag,
+                                                         const float *__restrict__ part_q, const float *__restrict__ part_d,
+                                                         int B, int H, int Hp, int Bq, int Dp, int slices_q, int slices_d,
+                                                         float *__restrict__ dq, float *__restrict__ dp, float *__restrict__ dn)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= 3 * B)
+        return;
+    const bool is_q = r < B;
+    const int row = is_q ? r : r - B;  // row of the image
+    const float *xh = (is_q ? qh : dh) + (size_t)row * Hp;
+    const float *part = (is_q ? part_q : part_d) + (size_t)row * Hp;
+    const size_t stride = (size_t)(is_q ? Bq : Dp) * Hp;
+    const int ns = is_q ? slices_q : slices_d, nr = is_q ? row : Bq + row;
+    float gv[IB_MAX_H / 64], dot = 0.0f;
+#pragma unroll
+    for (int e = 0; e < IB_MAX_H / 64; ++e) {
+        const int u = lane + 64 * e;
+        float g = 0.0f;
+        if (u < Hp) {
+            float v[IB_MAX_SLICES];  // (all slices asked for at once, added in ascending order)
+#pragma unroll
+            for (int s = 0; s < IB_MAX_SLICES; ++s)
+                v[s] = s < ns ? part[s * stride + u] : 0.0f;
+            g = v[0];
+#pragma unroll
+            for (int s = 1; s < IB_MAX_SLICES; ++s)
+                if (s < ns)
+                    g += v[s];
+            dot += xh[u] * g;
+        }
+        gv[e] = g;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        dot += __shfl_xor(dot, off);
+    const float d = den[nr], f = flag[nr] * dot;
+    float *out = is_q ? dq + (size_t)row * H : (row < B ? dp + (size_t)row * H : dn + (size_t)(row - B) * H);
+#pragma unroll
+    for (int e = 0; e < IB_MAX_H / 64; ++e) {
+        const int u = lane + 64 * e;
+        if (u < H)
+            out[u] = (gv[e] - f * xh[u]) / d;
+    }
+}
+
+// Fixed-order sum of x[0..n) by one block -> out[0] * scale.
+__global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ x, int n, float scale, float *__restrict__ out)
+{
+    __shared__ float red[16];
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 1024)
+        s += x[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+        for (int w = 0; w < 16; ++w)
+            t += red[w];
+        out[0] = t * scale;
+    }
+}
+
+} // namespace
+
+TT_EXPORT size_t tt_in_batch_loss_workspace_bytes(int B, int H)
+{
+    if (B < 1 || H < 1 || H > IB_MAX_H || B > (1 << 24))
+        return 0;
+    return ib_plan(B, H).total;
+}
+
+TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *n, int B, int H, float temperature,
+                                   float *loss, float *dq, float *dp, float *dn, void *workspace, size_t workspace_bytes,
+                                   tt_stream_t stream)
+{
+    if (B < 1 || B > (1 << 24) || H < 1 || H > IB_MAX_H)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: B=%d H=%d (B >= 1, 1 <= H <= %d)", B, H, IB_MAX_H);
+    if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: temperature=%g must be finite and > 0", (double)temperature);
+    if (!q || !p || !n || !loss || !workspace)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: null pointer");
+    if ((dq || dp || dn) && !(dq && dp && dn))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: dq, dp, dn must be all null or all non-null");
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: the workspace must be 16-byte aligned");
+    const IBPlan P = ib_plan(B, H);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
+    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
+    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, p, n, B, H, P.Hp, P.Bq, P.Dp, qh, dh,
+                       den, flag);
+    float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
+    float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
+    const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (2 * B + IB_TILE - 1) / IB_TILE;
+    hipLaunchKernelGGL(ib_stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, B, P.Hp,
+                       P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
+    hipLaunchKernelGGL(ib_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
+                       (const float *)pos, B, P.Bq, P.sq.n, lse, rows);
+    hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
+    if (dq) {
+        const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
+        const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
+        hipLaunchKernelGGL(ib_grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh,
+                           (const float *)dh, (const float *)lse, B, P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per,
+                           tiles_d, P.sd.per, part_q, part_d);
+        hipLaunchKernelGGL(ib_project_kernel, dim3((3 * B + 3) / 4), dim3(256), 0, st, (const float *)qh, (const float *)dh,
+                           (const float *)den, (const float *)flag, (const float *)part_q, (const float *)part_d, B, H, P.Hp,
+                           P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dp, dn);
+    }
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}

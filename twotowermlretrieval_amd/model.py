@@ -5,12 +5,13 @@
     RNNEncoder.forward(LongTensor[B,T]) -> FloatTensor[B,H]                              model.py:48-75
     TwoTowerModel(config, pretrained_embeddings).encode_query / encode_document / forward model.py:78-106
     triplet_loss_cosine((q, p, n), margin=0.2) -> 0-d tensor                             model.py:109-114
+    in_batch_softmax_loss((q, p, n), temperature=0.05) -> 0-d tensor                     (not in the reference: in-batch negatives)
 
 Same constructor arguments, attribute names (`query_encoder.embedding.embedding_dim` is read by
 backend/main.py:104) and state_dict keys ({query,doc}_encoder.{embedding.weight,
 rnn.weight_ih_l0[_reverse], ..., projection.weight/bias}), so a model.pth written by either side
 loads in the other.  The nn.Module objects here only OWN the parameters; every forward/backward
-runs in hand-written HIP kernels (csrc/encoder*.hip, gru16.hip, train.hip).  There is no PyTorch fallback:
+runs in hand-written HIP kernels (csrc/encoder*.hip, gru16.hip, train.hip, in_batch_loss.hip).  There is no PyTorch fallback:
 CPU tensors raise.  RNN_TYPE GRU, LSTM and RNN (tanh) are the three the reference's getattr(nn, ...) accepts.
 """
 from __future__ import annotations
@@ -26,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "SplitRecurrenceTimeout"]
+__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "SplitRecurrenceTimeout"]
 
 
 class SplitRecurrenceTimeout(RuntimeError):
@@ -523,3 +524,49 @@ def triplet_loss_cosine(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
             raise ValueError("triplet_loss_cosine wants three float32 [B,H] tensors of one shape")
     return _TripletFn.apply(query, pos_doc, neg_doc, margin)
+
+
+def in_batch_workspace(B: int, H: int, device) -> torch.Tensor:
+    """An uninitialised workspace for tt_in_batch_loss_f32 at [B,H] (the call rewrites all of it that it reads)."""
+    need = _lib.lib().tt_in_batch_loss_workspace_bytes(B, H)
+    if need == 0:
+        raise ValueError(f"in_batch_softmax_loss: B={B} H={H} (B >= 1, 1 <= H <= 512)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+class _InBatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, p, n, temperature: float):
+        L = _lib.lib()
+        q, p, n = q.contiguous(), p.contiguous(), n.contiguous()
+        B, H = q.shape
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        dq, dp, dn = torch.empty_like(q), torch.empty_like(p), torch.empty_like(n)
+        ws = in_batch_workspace(B, H, q.device)
+        with torch.cuda.device(q.device):
+            _lib.check(L.tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(temperature),
+                                              loss.data_ptr(), dq.data_ptr(), dp.data_ptr(), dn.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream(q.device)))
+        ctx.save_for_backward(dq, dp, dn)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, dp, dn = ctx.saved_tensors
+        return g * dq, g * dp, g * dn, None
+
+
+def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], temperature: float = 0.05) -> torch.Tensor:
+    """In-batch negatives: mean_i(logsumexp_j s_ij - s_ii), s_ij = cos(q_i, D_j) / temperature over D = [p; n] -- every query
+    is scored against all 2B passages of the batch (its own positive, the other queries' positives, all explicit negatives)
+    instead of one hinge against one negative.  Cosine with eps 1e-8 per norm, as triplet_loss_cosine.  Differentiable (fused
+    forward + gradient kernels on the f32 matrix pipe, deterministic).
+    The negatives are rank-local: under DataParallelTrainer each rank's softmax runs over its own 2B passages and the gradient
+    is averaged over the ranks like any other; passages of other ranks are not gathered."""
+    query, pos_doc, neg_doc = triplet
+    for t in (query, pos_doc, neg_doc):
+        if not t.is_cuda:
+            raise RuntimeError("in_batch_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
+            raise ValueError("in_batch_softmax_loss wants three float32 [B,H] tensors of one shape")
+    return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)

@@ -23,7 +23,7 @@ from typing import Callable, Iterable, Optional, Tuple
 import torch
 
 from . import _lib
-from .model import TwoTowerModel, deferred_input_checks, triplet_loss_cosine
+from .model import TwoTowerModel, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, triplet_loss_cosine
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -437,7 +437,7 @@ class _towers_in_flight:
 
 def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_docs, margin: float, phase: str = "all",
                        join_on_caller: bool = False, both: Optional[torch.Tensor] = None, plan: Optional[_towers_in_flight] = None,
-                       seed_words: Optional[dict] = None):
+                       seed_words: Optional[dict] = None, negatives: str = "paired", temperature: float = 0.05):
     """The same step without the autograd engine: tower forwards (train mode), the fused loss + gradient kernel, tower backwards
     written STRAIGHT into the optimizer's flat gradient buffer, optimizer step.  Every parameter receives its gradient exactly
     once (query tower once; positives and negatives as one 2B-row document-tower call), so nothing has to be zeroed or
@@ -456,7 +456,8 @@ def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_d
     plan: the step's _towers_in_flight; when the two towers' split recurrences do not fit the device together their recurrence
     launches are ordered with events (query tower's first in the forward, last in the backward).
     seed_words: {id(encoder): device int64[1]} -- the towers' dropout seeds as device words the kernels read when they run
-    (TT_ENC_SEED_ON_DEVICE: GraphedTrainStep writes a fresh seed there before every replay); default: drawn here, passed by value."""
+    (TT_ENC_SEED_ON_DEVICE: GraphedTrainStep writes a fresh seed there before every replay); default: drawn here, passed by value.
+    negatives / temperature: see train_step; "in_batch" swaps the one loss call (same q, pn, dq, dpn buffers), nothing else."""
     if not isinstance(optimizer, _FlatClipAdam) or not torch.is_grad_enabled():
         return None
     encs = (model.doc_encoder, model.query_encoder)
@@ -553,13 +554,18 @@ def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_d
             loss = torch.empty((), dtype=torch.float32, device=dev)
             dq = torch.empty_like(q)
             dpn = torch.empty_like(pn)
-            rows = torch.empty(B, dtype=torch.float32, device=dev)
+            rows = in_batch_workspace(B, H, dev) if negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
             for t in (q, pn, loss, dq, dpn, rows):
                 t.record_stream(s_main)
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().tt_triplet_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(margin), loss.data_ptr(),
-                                                          dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(), rows.data_ptr(),
-                                                          s_main.cuda_stream))
+                if negatives == "in_batch":
+                    _lib.check(_lib.lib().tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(temperature),
+                                                               loss.data_ptr(), dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(),
+                                                               rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+                else:
+                    _lib.check(_lib.lib().tt_triplet_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(margin), loss.data_ptr(),
+                                                              dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(), rows.data_ptr(),
+                                                              s_main.cuda_stream))
         fork()
         for enc, ids, s, f, d_out, grads in zip(encs, ids_of, streams, fw, (dpn, dq), into):
             with torch.cuda.stream(s):
@@ -609,9 +615,16 @@ def _draw_dropout_seeds(model: TwoTowerModel) -> dict:
             for enc in (model.query_encoder, model.doc_encoder)}
 
 
-def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan=None):
+def _check_negatives(negatives: str) -> None:
+    if negatives not in ("paired", "in_batch"):
+        raise ValueError(f'negatives must be "paired" or "in_batch", got {negatives!r}')
+
+
+def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan=None,
+                     negatives="paired", temperature=0.05):
     if direct and concurrent_towers and queries.is_cuda and neg_docs.shape[0] == pos_docs.shape[0] == queries.shape[0]:
-        loss = _train_step_direct(model, optimizer, queries, pos_docs, neg_docs, margin, plan=plan)
+        loss = _train_step_direct(model, optimizer, queries, pos_docs, neg_docs, margin, plan=plan, negatives=negatives,
+                                  temperature=temperature)
         if loss is not None:
             return loss
     if plan is not None:
@@ -655,7 +668,10 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
         q = model.encode_query(queries)
         p = model.encode_document(pos_docs)
         n = model.encode_document(neg_docs)
-    loss = triplet_loss_cosine((q, p, n), margin=margin)
+    if negatives == "in_batch":
+        loss = in_batch_softmax_loss((q, p, n), temperature=temperature)
+    else:
+        loss = triplet_loss_cosine((q, p, n), margin=margin)
     loss.backward()
     optimizer.step()
     return loss.detach()
@@ -663,7 +679,7 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
 
 def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Tensor, pos_docs: torch.Tensor,
                neg_docs: torch.Tensor, margin: float = 0.2, concurrent_towers: bool = True, direct: bool = True,
-               defer_check: bool = False) -> torch.Tensor:
+               defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05) -> torch.Tensor:
     """One step of backend/main.py:244-259 on this rank's (equal-sized) share of the global batch.
     Returns the local loss as a 0-d device tensor (no .item(): the reference's per-step sync is dropped).
 
@@ -680,16 +696,24 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     back: the words are copied to pinned memory behind the step and looked at inside the NEXT call (or optimizer.settle()), after
     that step has been enqueued, so the host runs ahead of the GPU and the ~0.1 ms the GPU idles per step while the host
     enqueues the next 40 launches is gone.  A bad batch's exception then comes out one call late; its step was not applied
-    (the device decided that), the step behind it is an ordinary step on the same weights."""
+    (the device decided that), the step behind it is an ordinary step on the same weights.
+
+    negatives: "paired" (default) = the reference's triplet loss, one hinge per row against its own negative.  "in_batch" = the
+    softmax contrastive loss over all 2B passages of the batch (model.in_batch_softmax_loss) at `temperature`; `margin` is
+    ignored; needs as many negatives as positives as queries.  The negatives are rank-local: under data parallelism each rank's
+    softmax runs over its own 2B passages and the gradients are averaged over the ranks as always -- no embeddings are gathered."""
     from .model import SplitRecurrenceTimeout
+    _check_negatives(negatives)
     if defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda:
         keep, optimizer.check = optimizer.check, False
         try:
-            loss = train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct)
+            loss = train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
+                              negatives=negatives, temperature=temperature)
         finally:
             optimizer.check = keep
         if keep:
-            optimizer.snapshot_gate(redo=lambda: train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct))
+            optimizer.snapshot_gate(redo=lambda: train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
+                                                            negatives=negatives, temperature=temperature))
         return loss
     encs = (model.query_encoder, model.doc_encoder)
     n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
@@ -698,12 +722,14 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     rng = torch.get_rng_state() if any(e.dropout > 0.0 and e.training for e in encs) else None
     try:
         with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
-            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan)
+            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
+                                    negatives, temperature)
     except SplitRecurrenceTimeout:
         if rng is not None:
             torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
         with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
-            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan)
+            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
+                                    negatives, temperature)
 
 
 class DataParallelTrainer:
@@ -713,12 +739,17 @@ class DataParallelTrainer:
     widths rounded up to `width_step` columns, the `max_graphs` most recently used buckets kept (a graph owns its workspaces:
     ~0.3 GB at 512 triplets x 128 columns).  A batch that does not fit the rules of GraphedTrainStep (unchecked inputs,
     non-int64 ids, a trainable table) takes the eager train_step; results are the eager step's on ids padded to the bucket's widths.
-    defer_check: see GraphedTrainStep (exceptions one call late; call flush() after the last step)."""
+    defer_check: see GraphedTrainStep (exceptions one call late; call flush() after the last step).
+    negatives / temperature: see train_step.  "in_batch" negatives are rank-local (each rank's softmax over its own 2B passages,
+    gradients averaged over the ranks as for the triplet loss; no all-gather of embeddings)."""
 
     def __init__(self, model: TwoTowerModel, lr: float = 1e-4, margin: float = 0.2, max_norm: float = 1.0, group=None,
-                 graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False):
+                 graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False,
+                 negatives: str = "paired", temperature: float = 0.05):
+        _check_negatives(negatives)
         self.model = model
         self.margin = margin
+        self.negatives, self.temperature = negatives, float(temperature)
         self.optimizer = FusedClipAdam(model.parameters(), lr=lr, max_norm=max_norm, group=group)
         self.optimizer.watch(model)  # (a hand-written loop over self.model / self.optimizer fails collectively too)
         self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
@@ -742,7 +773,8 @@ class DataParallelTrainer:
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
                 self._graphs.pop(next(iter(self._graphs)))
-            g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], self.margin, defer_check=self.defer_check)
+            g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], self.margin, defer_check=self.defer_check,
+                                 negatives=self.negatives, temperature=self.temperature)
         self._graphs[key] = g                                      # (re-inserted: most recently used last)
         return g
 
@@ -756,7 +788,8 @@ class DataParallelTrainer:
             g = self._graph_for(queries, pos_docs, neg_docs)
             if g is not None:
                 return g(queries, pos_docs, neg_docs)
-        return train_step(self.model, self.optimizer, queries, pos_docs, neg_docs, self.margin, defer_check=self.defer_check)
+        return train_step(self.model, self.optimizer, queries, pos_docs, neg_docs, self.margin, defer_check=self.defer_check,
+                          negatives=self.negatives, temperature=self.temperature)
 
 
 def _stage_ids(out: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> None:
@@ -798,13 +831,15 @@ class GraphedTrainStep:
     eager step would have computed with the generator in the same state."""
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
-                 defer_check: bool = False):
+                 defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05):
+        _check_negatives(negatives)
         encs = (model.query_encoder, model.doc_encoder)
         if not isinstance(optimizer, _FlatClipAdam) or optimizer._gated_step_fn is None:
             raise TypeError("GraphedTrainStep needs a FusedClipAdam")
         if not all(e.check_inputs for e in encs):
             raise ValueError("GraphedTrainStep: input checking must be on (the gate is what keeps a bad batch from being applied)")
         self.model, self.optimizer, self.margin = model, optimizer, float(margin)
+        self.negatives, self.temperature = negatives, float(temperature)   # (arguments of the captured loss launches)
         self.B, self.q_width, self.doc_width = int(batch), int(q_width), int(doc_width)
         self.defer_check = bool(defer_check)
         dev = optimizer.flat_params.device
@@ -848,7 +883,8 @@ class GraphedTrainStep:
             words = {id(self.model.query_encoder): self._seed_words[0:1], id(self.model.doc_encoder): self._seed_words[1:2]}
         with _towers_in_flight(self.model, self.optimizer, rows) as plan:
             return _train_step_direct(self.model, self.optimizer, self.q, None, None, self.margin, phase=self._phase,
-                                      join_on_caller=True, both=self.both, plan=plan, seed_words=words)
+                                      join_on_caller=True, both=self.both, plan=plan, seed_words=words,
+                                      negatives=self.negatives, temperature=self.temperature)
 
     def flush(self):
         """defer_check: settle the optimizer's pending check (raises that step's exception, if any)."""
@@ -882,7 +918,8 @@ class GraphedTrainStep:
         if not opt.check:
             return self.loss
         # (the eager redo takes the one-workgroup retry itself if it must)
-        opt.snapshot_gate(redo=lambda: train_step(self.model, opt, queries, pos_docs, neg_docs, self.margin))
+        opt.snapshot_gate(redo=lambda: train_step(self.model, opt, queries, pos_docs, neg_docs, self.margin,
+                                                  negatives=self.negatives, temperature=self.temperature))
         if not self.defer_check:
             redone = opt.settle()            # the step's one host synchronisation
             if redone is not None:
