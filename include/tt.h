@@ -457,6 +457,54 @@ int tt_score_ids_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t 
                       const int64_t *ids /*[B][C]*/, int C, int64_t idx_offset, float *out_val /*[B][C]*/,
                       int64_t *out_idx /*[B][C], nullable*/, tt_stream_t stream);
 
+/*
+ * Lexical search: sparse TF-IDF rows times a sparse query, exact top-k, no [B,N] matrix -- the lexical half of the hybrid
+ * search on the device.  Replaces the whole-corpus TF-IDF cosine and the sort of every document behind it:
+ *   cosine_similarity(query_tfidf, doc_tfidf_matrix) ; argsort ; score > 1e-5        frontend/main.py:119-147
+ *   tfidf_scores ; alpha * dense + (1 - alpha) * tfidf ; argsort()[::-1][:top_k]      backend/simple_hybrid.py:44-60
+ * Corpus: CSR on the device.  indptr int64 [N+1] (8-byte aligned), cols int32 [nnz], vals f32 [nnz] (4-byte aligned); row n
+ * owns entries indptr[n] .. indptr[n+1], indptr non-decreasing, columns strictly ascending within a row (sklearn's rows
+ * after sort_indices()).  cols and vals are BASES: a caller scores rows [r0, r1) of a corpus by passing indptr + r0 and
+ * N = r1 - r0, nothing is copied.  F = number of columns, 1 <= F <= TT_LEXICAL_FMAX (above: TT_ERR_UNSUPPORTED).
+ * Queries: CSR as well, q_indptr int64 [B+1], q_cols int32, q_vals f32, columns distinct within a query.
+ * Score contract:  s(b,n) = ((0 + p_1) + p_2) + ...,  p_i = fl32(vals[i] * q_b[cols[i]])  over the row's entries in stored
+ * order, q_b = the query as a dense vector: every product rounded to fp32, then added in fp32, no FMA contraction.  An entry
+ * whose query weight is zero adds +-0.  A column outside [0,F), in a row or in a query, contributes nothing and is never used
+ * as an address.  Rows may be empty and of any length.  The score of a document depends on its own row and the query alone
+ * -- not on where the row lies in the nnz stream, on N, on B, or on how the corpus is split over workgroups, slices or ranks
+ * -- so numpy reproduces it bit for bit and a sharded caller gets the single-device bits.
+ * tt_lexical_score_topk_f32: ranked value v(b,n) = s(b,n) when base == NULL (the weights are ignored), otherwise
+ *   fl32(fl32(w_base * base[b][n]) + fl32(w_lex * s(b,n)))       base [B][base_stride] f32, base_stride >= N
+ * which is simple_hybrid's alpha * dense + (1 - alpha) * tfidf over every document with base from tt_score_all_f32.  Document
+ * n is a candidate iff it is kept (keep: tt_score_topk_masked_f32's words, ceil(N/32), or NULL = all) and v >= min_score[b]
+ * (min_score [B] device f32, NULL = no threshold); a NaN value is never selected.  out_val / out_idx [B,k]: the best k
+ * candidates, (value desc, index asc) -- tie groups of any size resolve by lowest index: duplicate passages and zero scores
+ * make them normal --, out_idx = idx_offset + row, tail (-inf, -1).  A zero value is returned as +0.
+ * 1 <= k <= TT_TOPK_LARGE_KMAX (k <= 0: TT_ERR_BAD_SHAPE, above: TT_ERR_UNSUPPORTED), N < 2^31 - 64 per call and
+ * B <= 65535 (TT_ERR_UNSUPPORTED), TT_ERR_BAD_SHAPE for negative sizes, null or misaligned pointers, base_stride < N,
+ * TT_ERR_WORKSPACE for a NULL, misaligned (8 bytes) or short workspace (tt_lexical_workspace_bytes; 0 for shapes the call
+ * refuses).  Every check runs before any HIP call.  B = 0 does nothing; N = 0 writes the tail.
+ * One workgroup per query and chunk of tt_lexical_chunk_docs() documents: the query's dense image sits in LDS (4 F bytes of
+ * the CU's 160 KiB), the chunk's entries are streamed once (8 bytes per entry + 8 per row), and the chunk's exact top-k goes
+ * to the workspace in tt_score_topk_partials_f32's form; tt_topk_merge / tt_topk_merge_large finish.  A batch costs B passes
+ * over the CSR stream (queries share no pass): serving is B = 1.  Asynchronous, capturable, no host synchronisation, no
+ * atomics in the scoring and selection pass; the result depends only on the inputs, not on what the workspace or the outputs
+ * held.
+ * tt_lexical_score_all_f32: S [B][N] f32 = s(b,n), the same chain, for callers that want every score (tests, small corpora).
+ */
+#define TT_LEXICAL_FMAX 20480
+int tt_lexical_chunk_docs(void); /* documents per chunk: tests size N from it */
+size_t tt_lexical_workspace_bytes(int B, int64_t N, int k);
+int tt_lexical_score_topk_f32(const int64_t *indptr, const int32_t *cols, const float *vals, int64_t N, int F,
+                              const int64_t *q_indptr, const int32_t *q_cols, const float *q_vals, int B,
+                              const uint32_t *keep /*nullable*/, const float *min_score /*[B], nullable*/,
+                              const float *base /*[B][base_stride] f32, nullable*/, int64_t base_stride, float w_base,
+                              float w_lex, int k, int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+int tt_lexical_score_all_f32(const int64_t *indptr, const int32_t *cols, const float *vals, int64_t N, int F,
+                             const int64_t *q_indptr, const int32_t *q_cols, const float *q_vals, int B, float *S /*[B][N]*/,
+                             tt_stream_t stream);
+
 /* ------------------------------------------------------------------ */
 /* Encoder tower (GloVe gather -> GRU -> L2-normalise)                 */
 /* ------------------------------------------------------------------ */

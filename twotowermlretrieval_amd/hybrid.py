@@ -12,7 +12,13 @@ Dense score definition.  The reference stores embeddings in a Chroma collection 
 score (frontend/main.py:162); for unit vectors that is 2*cos - 1, not the cosine.  `dense_score="cosine"`
 (default) uses the cosine itself; `dense_score="chroma_l2"` reproduces the reference's 2*cos - 1 so the
 blend weights match its behaviour exactly.  alpha == 0 is the reference's pure keyword search over the
-whole corpus (frontend/main.py:119-147) and never touches the GPU.
+whole corpus (frontend/main.py:119-147) and, by default, never touches the GPU.
+
+Lexical half on the GPU (opt-in, lexical="gpu").  The whole-corpus TF-IDF steps -- the alpha == 0 keyword search, the
+lexical_candidates, SimpleHybridRetriever's blend over every document -- are one LexicalIndex.search (lexical.py) instead
+of sklearn's cosine_similarity + argsort on the host.  The GPU lexical score is the fp32 dot product of the f32-ROUNDED
+TF-IDF rows; sklearn renormalises in float64, so the two agree within (m + 3) * 2^-24 for a query of m terms and are not
+bit-identical: near-ties may swap, which is why the default, lexical="sklearn", stays the code it always was.
 """
 from __future__ import annotations
 
@@ -22,20 +28,33 @@ import numpy as np
 import torch
 
 from .index import BruteForceIndex, score_all
+from .lexical import LexicalIndex
+
+# the smallest float32 above 1e-5: `score >= LEXICAL_MIN_SCORE` in fp32 mirrors the reference's `score > 1e-5`
+LEXICAL_MIN_SCORE = float(np.nextafter(np.float32(1e-5), np.float32(1.0)))
+
+
+def _lexical_mode(lexical: str) -> str:
+    if lexical not in ("sklearn", "gpu"):
+        raise ValueError("lexical must be 'sklearn' or 'gpu'")
+    return lexical
 
 
 class HybridSearcher:
     def __init__(self, inferencer, documents: Sequence[str], doc_embeddings: torch.Tensor = None, tfidf_vectorizer=None,
                  doc_tfidf_matrix=None, n_candidates: int = 50, dense_score: str = "cosine", index: BruteForceIndex = None,
-                 lexical_candidates: int = 0):
+                 lexical_candidates: int = 0, lexical: str = "sklearn"):
         """documents: documents.pkl's list (row i of the embeddings <-> documents[i]); any object with __len__ and __getitem__
         is used as it is (a corpus too large for a Python list: an mmap-backed or generated sequence), other iterables are
         listed.  index: an existing BruteForceIndex over the embedding matrix instead of doc_embeddings (one is built otherwise).
         lexical_candidates: 0 (the default) blends over the dense top-`n_candidates` only, as the reference does -- the best
         lexical match is lost when it ranks below them by cosine.  n > 0 adds the query's n best TF-IDF matches over the
-        whole corpus (similarity > 1e-5) to the candidates; their dense scores come from index.score_ids."""
+        whole corpus (similarity > 1e-5) to the candidates; their dense scores come from index.score_ids.
+        lexical: "sklearn" (the default) computes the whole-corpus TF-IDF steps on the host as the reference does; "gpu"
+        uploads doc_tfidf_matrix once as a LexicalIndex and answers them with one search each (module docstring)."""
         if dense_score not in ("cosine", "chroma_l2"):
             raise ValueError("dense_score must be 'cosine' or 'chroma_l2'")
+        self.lexical = _lexical_mode(lexical)
         if (index is None) == (doc_embeddings is None):
             raise ValueError("HybridSearcher wants doc_embeddings or index (exactly one)")
         self.inferencer = inferencer
@@ -56,9 +75,26 @@ class HybridSearcher:
             doc_tfidf_matrix = tfidf_vectorizer.fit_transform(self.documents)
         self.tfidf = tfidf_vectorizer
         self.doc_tfidf = doc_tfidf_matrix
+        self.lexical_index = (LexicalIndex(doc_tfidf_matrix, self.index.device, self.index.idx_offset)
+                              if self.lexical == "gpu" else None)
+
+    def _lexical_top(self, q_tfidf, n: int):
+        """lexical="gpu": the n best TF-IDF matches of the whole corpus with score > 1e-5, not removed from the dense index:
+        (row numbers, scores), best first."""
+        n = min(n, self.index.ntotal)
+        if n <= 0:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
+        vals, idx = self.lexical_index.search(q_tfidf, n, min_score=LEXICAL_MIN_SCORE, keep=self.index.keep_mask)
+        vals, idx = vals[0].cpu().numpy(), idx[0].cpu().numpy()
+        live = idx >= 0
+        return idx[live] - self.index.idx_offset, vals[live]
 
     def search(self, query: str, alpha: float = 0.5, n_results: int = 10) -> List[Dict]:
         from sklearn.metrics.pairwise import cosine_similarity
+        if alpha == 0.0 and self.lexical == "gpu":
+            rows, sims = self._lexical_top(self.tfidf.transform([query]), n_results)
+            return [{"doc": self.documents[int(i)], "index": int(i), "score": float(s), "dense_score": 0.0,
+                     "tfidf_score": float(s)} for i, s in zip(rows, sims)]
         if alpha == 0.0:
             sims = cosine_similarity(self.tfidf.transform([query]), self.doc_tfidf).flatten()
             order = np.argsort(-sims, kind="stable")[:n_results]
@@ -72,9 +108,12 @@ class HybridSearcher:
         q_tfidf = self.tfidf.transform([query])
         if self.lexical_candidates > 0 and q_tfidf.nnz > 0:
             # the best lexical matches of the whole corpus join the dense top-k, with their exact dense scores
-            sims = cosine_similarity(q_tfidf, self.doc_tfidf).flatten()
             have = set(cand)
-            extra = [int(i) for i in np.argsort(-sims, kind="stable")[:self.lexical_candidates] if sims[i] > 1e-5 and int(i) not in have]
+            if self.lexical == "gpu":
+                extra = [int(i) for i in self._lexical_top(q_tfidf, self.lexical_candidates)[0] if int(i) not in have]
+            else:
+                sims = cosine_similarity(q_tfidf, self.doc_tfidf).flatten()
+                extra = [int(i) for i in np.argsort(-sims, kind="stable")[:self.lexical_candidates] if sims[i] > 1e-5 and int(i) not in have]
             if extra:
                 s = self.index.score_ids(q, torch.tensor(extra, dtype=torch.int64, device=q.device)).cpu().numpy()
                 live = np.isfinite(s)  # (a removed document scores -inf: it is no candidate)
@@ -101,8 +140,13 @@ class SimpleHybridRetriever:
     sklearn `cosine_similarity` only for unit rows, i.e. with NORMALIZE_OUTPUT = true (the reference's default and the
     only configuration G11 pins); with NORMALIZE_OUTPUT = false the blend differs from the reference's."""
 
-    def __init__(self, artifacts_path: str, alpha: float = 0.5, device=None):
+    def __init__(self, artifacts_path: str, alpha: float = 0.5, device=None, lexical: str = "sklearn"):
+        """lexical: "sklearn" (the default) is the reference's host blend over every document; "gpu" keeps the TF-IDF matrix
+        on the device as a LexicalIndex and makes the blend and the top_k selection one search over it, with the dense scores
+        as its base: no N-sized array goes to the host (hybrid.py's docstring has the numerics)."""
         from sklearn.feature_extraction.text import TfidfVectorizer
+        self.lexical = _lexical_mode(lexical)
+        self.lexical_index = None
         from .query_inferencer import QueryInferencer
         self.dense_retriever = QueryInferencer(artifacts_path, device=device)
         self.alpha = alpha
@@ -115,8 +159,16 @@ class SimpleHybridRetriever:
         self.tfidf_matrix = self.tfidf.fit_transform(self.documents)
         # one batched call of the query tower instead of the reference's per-document loop: same rows
         self.doc_embeddings = self.dense_retriever.get_query_embeddings(self.documents)
+        if self.lexical == "gpu":
+            self.lexical_index = LexicalIndex(self.tfidf_matrix, self.doc_embeddings.device)
 
     def search(self, query: str, top_k: int = 10):
+        if self.lexical == "gpu":
+            q = torch.from_numpy(self.dense_retriever.get_query_embedding(query)).to(self.doc_embeddings.device)
+            dense = score_all(q.unsqueeze(0), self.doc_embeddings)
+            vals, idx = self.lexical_index.search(self.tfidf.transform([query]), min(top_k, max(len(self.documents), 1)),
+                                                  base=dense, w_base=self.alpha, w_lex=1 - self.alpha)
+            return [(self.documents[i], float(v)) for v, i in zip(vals[0].tolist(), idx[0].tolist()) if i >= 0]
         from sklearn.metrics.pairwise import cosine_similarity
         tfidf_scores = cosine_similarity(self.tfidf.transform([query]), self.tfidf_matrix)[0]
         q = torch.from_numpy(self.dense_retriever.get_query_embedding(query)).to(self.doc_embeddings.device)
