@@ -10,6 +10,12 @@ enum { CELL_GRU = 0, CELL_LSTM = 1, CELL_RNN = 2 };
 static inline int enc_gates(int cell) { return cell == CELL_LSTM ? 4 : (cell == CELL_RNN ? 1 : 3); }
 constexpr int ENC_RB = 16; // batch rows per recurrence block (one 16x16x4 MFMA M-tile)
 
+// What every entry point is told about the model and the batch (V, the vocabulary, travels beside it: the layouts do not
+// depend on it).  cell: CELL_*; bidirectional: 0 / non-zero as the caller gave it.
+struct EncShape {
+    int B, T, E, H, L, bidirectional, cell;
+};
+
 // All offsets are bytes from the start of the caller's workspace.  Token-indexed buffers use
 // the PACKED token order: row b's position t lives at tok_off[b] + t (t < len[b]); their
 // capacity is the upper bound MT = B*T because the valid count is only known on the device.
@@ -43,11 +49,20 @@ struct EncLayout {
     size_t total;
 };
 
-// Word of the 256-byte status block (EncLayout::flag) that holds the bit pattern of max |x| over the embedding vectors of
-// the call's valid tokens: written by the training forward (K1's fill, or tt_absmax_rows), read by the backward as the X
-// scale of dW_ih = dGi^T X.  (Other words: 0 error flags, 16.. max|W_hh| forward, 32.. backward, 40.. max|W_ih|, 48..63
-// max|dGi| / max|dGh|.)
+// The 256-byte status block (EncLayout::flag), 64 words.  The training forward fills it, the backward of the same
+// workspace reads it and adds its own maxima; every maximum is the bit pattern of a max |x|, raised with atomicMax.
+//    0          error flags of the prep (1: a zero-length row, 2: an id outside [0, V))
+//    8          max |x| over the embedding vectors of the call's valid tokens (K1's fill, or tt_absmax_rows): the X scale
+//               of the backward's dW_ih = dGi^T X
+//   16 + 2l + d max |W_hh| of layer l, direction d (the forward's pack; the backward's transposed pack reads it)
+//   40 + 2l + d max |W_ih| (the forward's pack; the scale of W_ih in the backward's input-gradient product)
+//   48 + 2(2l + d), + 1   max |dGi|, max |dGh| (backward: the recurrence kernel or the column sums); these 16 words are
+//               the ones the backward's head kernel clears
 constexpr int ENC_FLAG_XMAX = 8;
+constexpr int ENC_FLAG_DG = 48, ENC_FLAG_DG_WORDS = 16; // (head_bwd_kernel clears exactly ENC_FLAG_DG_WORDS words)
+static inline int enc_flag_whh_max(int l, int d) { return 16 + 2 * l + d; }
+static inline int enc_flag_wih_max(int l, int d) { return 40 + 2 * l + d; }
+static inline int enc_flag_dgi_max(int l, int d) { return ENC_FLAG_DG + 2 * (2 * l + d); } // max |dGh|: the word behind it
 
 #ifndef TT_ENC_SPLITK
 #define TT_ENC_SPLITK 64
@@ -77,11 +92,19 @@ bool gru16x4_usable(int B, int H, int ndir); // this device has a CU for every m
 int gru16x4_launches(int B, int H, int ndir); // 1: both directions in one grid, 2: one launch per direction, 0: does not fit
 bool gru16x4_bwd_usable(int B, int H, int ndir);
 
+// Capacity of the split-K scratch (EncLayout::slabs) in floats: ENC_SPLITK partial products of the largest weight gradient.
+// The backward also parks the recurrence kernel's per-row-group bias sums there when they fit (EncRoute::fused_bias).
+static inline size_t enc_slab_floats(int E, int H, int ndir, int ng)
+{
+    const size_t in_max = (size_t)(E > ndir * H ? E : ndir * H);
+    return (size_t)ENC_SPLITK * (ng < 3 ? 3 : ng) * H * (in_max > (size_t)H ? in_max : (size_t)H);
+}
+
 // projected: an inference call whose layer 0 reads its input projections from the projected table (encoder.hip): a
 // one-layer model then needs no [tokens][3H] scratch at all (11 GB at 32 768 passages)
-static inline EncLayout enc_layout(int B, int T, int E, int H, int L, int bidir, int train, int dropout = 0,
-                                   int cell = CELL_GRU, bool projected = false)
+static inline EncLayout enc_layout(const EncShape &s, int train, int dropout, bool projected)
 {
+    const int B = s.B, T = s.T, E = s.E, H = s.H, L = s.L, bidir = s.bidirectional, cell = s.cell;
     EncLayout lo;
     lo.B = B; lo.T = T; lo.E = E; lo.H = H; lo.L = L; lo.ndir = bidir ? 2 : 1; lo.train = train;
     const int ng = enc_gates(cell);
@@ -148,8 +171,7 @@ static inline EncLayout enc_layout(int B, int T, int E, int H, int L, int bidir,
             const size_t xb = cell == CELL_GRU ? gru16x4_bwd_xch_bytes(B, H, lo.ndir) : 0;
             lo.xchb = xb ? take(xb) : 0;
         }
-        const size_t in_max = (size_t)(E > lo.ndir * H ? E : lo.ndir * H);
-        lo.slabs = take(sizeof(float) * ENC_SPLITK * (ng < 3 ? 3 : ng) * H * (in_max > (size_t)H ? in_max : (size_t)H));
+        lo.slabs = take(sizeof(float) * enc_slab_floats(E, H, lo.ndir, ng));
     }
     // last, so that the layouts of train == 1 and train == 2 agree on everything before it
     lo.dx0 = train == 2 ? take(sizeof(float) * lo.MT * E) : 0;
@@ -266,3 +288,81 @@ int gru16_bwd_launch(const GruBwdParams &bp, int ndir, hipStream_t st);
 int gru16x4_launch(const GruParams &gp, int ndir, void *xch, int32_t *status, hipStream_t st, bool xch_zeroed = false);
 // the reverse-time recurrence on four CUs per row group (reduction split; deterministic, not bit-identical to gru16_bwd_launch)
 int gru16x4_bwd_launch(const GruBwdParams &bp, int ndir, void *xch, int32_t *status, hipStream_t st);
+
+// ------------------------------------------------------------------ one encoder call, as the host code passes it on
+// The train word of tt_encoder_forward_f32 / the opts word of the other entries, taken apart once (include/tt.h has the bits).
+enum { ENC_PHASE_WHOLE = 0, ENC_PHASE_BEGIN = 1, ENC_PHASE_FINISH = 2 };
+// every product of a call on the fp32-MFMA kernels (TT_ENC_F32; the comparison build's TT_GRU_F32): the one spelling both passes use
+static inline bool enc_force_f32(int word) { return (word & TT_ENC_F32) != 0 || TT_AB_SWITCH(TT_GRU_F32, 0) != 0; }
+struct EncOpts {
+    int word;                 // as received: enc_validate refuses the words an entry does not take, with the entry's message
+    int train_mode;           // 0 inference, 1 training, 2 training with a trainable table (the backward: 2 when g_table is given)
+    bool one_wg;              // TT_ENC_ONE_WORKGROUP: the caller keeps the recurrences off the column-split kernels
+    bool force_f32;           // enc_force_f32(word): the backward must be told what the forward that filled the workspace was
+    int phase;                // ENC_PHASE_*: the call in two halves (BEGIN = everything in front of the first recurrence launch)
+    uint64_t seed;            // the dropout seed by value (0 when it is on the device)
+    const uint64_t *seed_dev; // TT_ENC_SEED_ON_DEVICE: the kernels read it from here when they run; null otherwise
+};
+static inline EncOpts enc_opts(int word, int train_mode, uint64_t dropout_seed)
+{
+    const bool on_dev = (word & TT_ENC_SEED_ON_DEVICE) != 0;
+    return {word, train_mode, (word & TT_ENC_ONE_WORKGROUP) != 0, enc_force_f32(word),
+            (word & TT_ENC_PHASE_BEGIN) ? ENC_PHASE_BEGIN : ((word & TT_ENC_PHASE_FINISH) ? ENC_PHASE_FINISH : ENC_PHASE_WHOLE),
+            on_dev ? 0ull : dropout_seed, on_dev ? (const uint64_t *)(uintptr_t)dropout_seed : nullptr};
+}
+
+// the backward's own arguments, beside the record of the forward call it undoes
+struct EncBwd {
+    const float *d_out;
+    float *const *grads;
+    float *g_proj_w, *g_proj_b, *g_table; // g_table nullable: the table is frozen
+};
+
+struct EncCall : EncShape {
+    const char *who; // the entry point's name, for tt_last_error()
+    int64_t V;
+    const int64_t *ids;
+    const float *table;
+    const float *const *weights; // [L][ndir][4]: W_ih, W_hh, b_ih, b_hh
+    const float *proj_w, *proj_b;
+    const void *prepared, *projected; // tt_encoder_prepare_f32's / tt_encoder_project_table_f32's buffers (null: not given)
+    EncOpts o;
+    float dropout_p;
+    int normalize;
+    float *out;
+    void *workspace;
+    size_t workspace_bytes;
+    int32_t *status;
+    const tt_enc_sync_t *sync;
+    hipStream_t st;
+    const EncBwd *bwd; // null: a forward call
+};
+
+// inter-layer dropout is live: the workspace has the xd buffers
+static inline bool enc_drops(const EncCall &c) { return c.o.train_mode && c.dropout_p > 0.0f && c.L > 1; }
+static inline bool enc_use16(int cell, int H, bool force_f32) { return cell == CELL_GRU && gru16_supported(H) && !force_f32; }
+// the forward recurrence column-split over four CUs: the shape has hand-off slots and this device a CU for every team member
+static inline bool enc_split_fwd(int B, int H, int ndir, bool use16, bool one_wg)
+{
+    return use16 && !one_wg && gru16x4_xch_bytes(B, H, ndir) != 0 && gru16x4_usable(B, H, ndir);
+}
+
+// Which kernels a call runs: every decision in one place, for encoder_forward, tt_encoder_backward_f32 and (through the
+// predicates above) tt_encoder_split_workgroups.  The two per-layer decisions, rows16 or tiled K1 and the fused pack, depend
+// on the layer's input width: enc_rows16 and enc_fused_pack (encoder.hip), which tt_encoder_prepare_f32 asks as well.
+struct EncRoute {
+    bool drop;         // enc_drops
+    bool use16;        // the GRU recurrence of H = 128 / 256 on the f16 matrix pipes (gru16.hip), else the fp32-MFMA kernels
+    bool use_prepared; // forward: the weights in kernel form come from c.prepared, else they are packed into the workspace
+                       // (force_f32 too: the prepared images are the f16-split kernels')
+    bool fused_prep;   // forward: the whole prep in one workgroup, else the four-kernel prep
+    bool split_fwd;    // forward: the recurrence column-split over four CUs (gru16x4.hip), else one workgroup per row group
+    bool head_gemm;    // forward: Linear(2H, H) as two GEMMs in front of a head kernel that only normalises
+    bool fused_bias;   // backward: the f16-split recurrence leaves the bias sums and operand maxima, else column-sum passes
+    bool split_bwd;    // backward: the reverse-time recurrence on four CUs per row group
+};
+
+// encoder.hip
+int enc_check_shape(const char *who, const EncShape &s, int64_t V);
+int enc_validate(const EncCall &c, EncLayout &lo); // every refusal of the forward entries and the backward; fills the layout
+EncRoute enc_route(const EncCall &c, const EncLayout &lo);

@@ -514,17 +514,17 @@ __global__ __launch_bounds__(256) void head_kernel(const float *__restrict__ hfi
 
 } // namespace
 
-int enc_check_shape(const char *who, int B, int T, int E, int H, int L, int64_t V)
+int enc_check_shape(const char *who, const EncShape &s, int64_t V)
 {
-    if (B <= 0 || T <= 0)
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: Cannot pack empty tensors (B=%d T=%d)", who, B, T);
-    if (H < 32 || H > 512 || (H & 31))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: HIDDEN_DIM=%d (supported: multiples of 32 in [32,512])", who, H);
-    if (E < 4 || (E & 3))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: EMBED_DIM=%d must be a multiple of 4", who, E);
-    if (L < 1 || L > ENC_MAX_LAYERS)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: NUM_LAYERS=%d (supported: 1..%d)", who, L, ENC_MAX_LAYERS);
-    if ((int64_t)B * T >= INT_MAX / 4 || V <= 0 || V >= INT_MAX)
+    if (s.B <= 0 || s.T <= 0)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: Cannot pack empty tensors (B=%d T=%d)", who, s.B, s.T);
+    if (s.H < 32 || s.H > 512 || (s.H & 31))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: HIDDEN_DIM=%d (supported: multiples of 32 in [32,512])", who, s.H);
+    if (s.E < 4 || (s.E & 3))
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: EMBED_DIM=%d must be a multiple of 4", who, s.E);
+    if (s.L < 1 || s.L > ENC_MAX_LAYERS)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: NUM_LAYERS=%d (supported: 1..%d)", who, s.L, ENC_MAX_LAYERS);
+    if ((int64_t)s.B * s.T >= INT_MAX / 4 || V <= 0 || V >= INT_MAX)
         return tt_fail(TT_ERR_UNSUPPORTED, "%s: B*T or V too large for 32-bit token indices", who);
     return TT_OK;
 }
@@ -536,25 +536,49 @@ TT_EXPORT size_t tt_encoder_workspace_bytes(int B, int T, int E, int H, int num_
         return 0;
     const bool projected = train > 0 && (train & TT_ENC_PROJECTED) != 0;
     train = train < 0 ? 0 : (train & TT_ENC_TRAIN_MASK); // (the other option bits above the mask do not change the layout)
-    return enc_layout(B, T, E, H, num_layers, bidirectional, train > 2 ? 2 : train, dropout, rnn_type, projected && train == 0).total;
+    return enc_layout({B, T, E, H, num_layers, bidirectional, rnn_type}, train > 2 ? 2 : train, dropout, projected && train == 0).total;
 }
 
+// ------------------------------------------------------------------ weights in kernel form
 // H = 128 / 256: the recurrence runs on the f16 matrix pipes with both operands split into fp16 hi + lo parts
-// (gru16.hip; fp32-grade accuracy at 3/16 of the fp32 MFMA time).  The option bit TT_ENC_F32 of a call (include/tt.h) keeps
-// every product of that call on the fp32-MFMA kernels instead: the reference's own arithmetic (nn.GRU in fp32, model.py:31-37).
-static bool enc_force_f32(int flags = 0)
-{
-    return (flags & TT_ENC_F32) != 0 || TT_AB_SWITCH(TT_GRU_F32, 0) != 0;
-}
+// (gru16.hip; fp32-grade accuracy at 3/16 of the fp32 MFMA time: enc_use16).  The option bit TT_ENC_F32 of a call (include/tt.h)
+// keeps every product of that call on the fp32-MFMA kernels instead: the reference's own arithmetic (nn.GRU in fp32, model.py:31-37).
 static bool enc_tiled_k1() // A/B switch: the tiled f16 GEMM instead of the token-stationary one
 {
     return TT_AB_SWITCH(TT_K1_TILED, 0) != 0;
 }
+// K1 of a layer with NGH gate rows and input width I: token-stationary (gemm_rows16.hip), else the tiled f16 GEMM
 static bool enc_rows16(int NGH, int I) { return !enc_tiled_k1() && tt_gemm_rows16_supported(NGH, I, I, NGH); }
 
-// One layer and direction's weights into the forms the forward kernels read.  wih_max / wmax: zeroed words that receive
-// the bit patterns of max |W_ih| / max |W_hh|; w16: W_ih split into fp16 hi/lo parts (scaled by the power of two its
-// maximum implies) as gemm_rows16's fragment stream or the tiled GEMM's [rows][Kp] images; wp: W_hh in packed order.
+// One layer and direction's weights in the forms the forward kernels read.  wih_max / wmax: words that receive the bit
+// patterns of max |W_ih| / max |W_hh| (zeroed before the pack); w16: W_ih split into fp16 hi/lo parts (scaled by the power of
+// two its maximum implies) as gemm_rows16's fragment stream or the tiled GEMM's [rows][Kp] images; wp: W_hh in packed order.
+struct EncW {
+    unsigned *wih_max, *wmax;
+    char *w16, *wp;
+};
+static EncW enc_prepared_weights(char *pb, const EncPrepared &pl, int l, int d) // (header words: EncPrepared, encoder.h)
+{
+    unsigned *words = (unsigned *)pb + 2 * (2 * l + d);
+    return {words, words + 1, pb + pl.wih[l][d], pb + pl.wp[l][d]};
+}
+static EncW enc_workspace_weights(char *ws, const EncLayout &lo, int l, int d) // (the maxima in the status block)
+{
+    unsigned *flag = (unsigned *)(ws + lo.flag);
+    return {flag + enc_flag_wih_max(l, d), flag + enc_flag_whh_max(l, d), ws + lo.wih16[d], ws + lo.wp[d]};
+}
+
+// what a pack depends on: the layer's input width, H, the cell, and whether the call stays on the fp32-MFMA kernels
+struct EncPack {
+    int I, H, cell;
+    bool f32;
+};
+// the north-star shape: two launches instead of four (both maxima, then both conversions)
+static bool enc_fused_pack(const EncPack &k)
+{
+    return enc_use16(k.cell, k.H, k.f32) && enc_rows16(enc_gates(k.cell) * k.H, k.I) && (k.I + 15) / 16 <= 19;
+}
+
 namespace {
 // both conversions of a GRU layer in one launch (pack16.h): blockIdx.y = 0: W_ih -> fragment stream, 1: W_hh -> packed order
 __global__ __launch_bounds__(256) void pack2_kernel(const float *__restrict__ Wih, int N, int K, int nks, int waves, int ctn,
@@ -569,37 +593,71 @@ __global__ __launch_bounds__(256) void pack2_kernel(const float *__restrict__ Wi
 }
 } // namespace
 
-static int enc_pack_weights(int I, int H, int rnn_type, const float *const *w, unsigned *wih_max, unsigned *wmax, char *w16,
-                            char *wp, hipStream_t st, bool f32 = false)
+static int enc_pack_weights(const EncPack &k, const float *const *w, const EncW &o, hipStream_t st)
 {
-    const int NGH = enc_gates(rnn_type) * H;
-    f32 = f32 || enc_force_f32();
-    if (!f32 && rnn_type == CELL_GRU && gru16_supported(H) && enc_rows16(NGH, I) && (I + 15) / 16 <= 19) {
-        // the north-star shape: two launches instead of four (both maxima, then both conversions)
-        TT_RC_CHECK(tt_absmax2(w[0], (int64_t)NGH * I, wih_max, w[1], (int64_t)3 * H * H, wmax, st));
+    const int I = k.I, H = k.H, NGH = enc_gates(k.cell) * H;
+    if (enc_fused_pack(k)) {
+        TT_RC_CHECK(tt_absmax2(w[0], (int64_t)NGH * I, o.wih_max, w[1], (int64_t)3 * H * H, o.wmax, st));
         const int nks = (I + 15) / 16;
-        hipLaunchKernelGGL(pack2_kernel, dim3(96, 2), dim3(256), 0, st, w[0], NGH, I, nks, 4, 2, (const unsigned *)wih_max,
-                           (_Float16 *)w16, w[1], H, (const unsigned *)wmax, (_Float16 *)wp);
+        hipLaunchKernelGGL(pack2_kernel, dim3(96, 2), dim3(256), 0, st, w[0], NGH, I, nks, 4, 2, (const unsigned *)o.wih_max,
+                           (_Float16 *)o.w16, w[1], H, (const unsigned *)o.wmax, (_Float16 *)o.wp);
         TT_LAUNCH_CHECK();
         return TT_OK;
     }
-    if (!f32) {
-        TT_RC_CHECK(tt_absmax(w[0], (int64_t)NGH * I, wih_max, st));
+    if (!k.f32) {
+        TT_RC_CHECK(tt_absmax(w[0], (int64_t)NGH * I, o.wih_max, st));
         if (enc_rows16(NGH, I)) {
-            TT_RC_CHECK(tt_pack_frag16(w[0], NGH, I, wih_max, w16, st));
+            TT_RC_CHECK(tt_pack_frag16(w[0], NGH, I, o.wih_max, o.w16, st));
         } else {
             // (every 128-token workgroup would otherwise convert the tiles of W_ih it touches)
             const int Kp = (I + 31) / 32 * 32;
-            TT_RC_CHECK(tt_pack_rows16(w[0], NGH, I, wih_max, w16, w16 + (size_t)NGH * Kp * sizeof(uint16_t), st));
+            TT_RC_CHECK(tt_pack_rows16(w[0], NGH, I, o.wih_max, o.w16, o.w16 + (size_t)NGH * Kp * sizeof(uint16_t), st));
         }
     }
-    if (rnn_type == CELL_GRU && gru16_supported(H) && !f32) {
-        TT_RC_CHECK(gru16_pack(w[1], H, wmax, wp, st));
+    if (enc_use16(k.cell, H, k.f32)) {
+        TT_RC_CHECK(gru16_pack(w[1], H, o.wmax, o.wp, st));
     } else {
-        hipLaunchKernelGGL(pack_whh_kernel, dim3(96), dim3(256), 0, st, w[1], H, enc_gates(rnn_type), (float *)wp);
+        hipLaunchKernelGGL(pack_whh_kernel, dim3(96), dim3(256), 0, st, w[1], H, enc_gates(k.cell), (float *)o.wp);
         TT_LAUNCH_CHECK();
     }
     return TT_OK;
+}
+
+// ------------------------------------------------------------------ K1: the input projection of one layer and direction
+// Gi = A W_ih^T + b_ih for a layer of input width I.  Everything the weights decide is filled here; the caller adds what its
+// rows are: A, a_map, M, m_dyn, C (and a_absmax_out).  On the f16 pipes (fp16 hi/lo split, fp32-grade; sgemm.h) W_ih is scaled by
+// the power of two that puts its largest element in [2^13, 2^14); deeper layers' A rows are hidden states in (-1, 1) (times
+// 1/(1-p) under dropout): 2^6; layer 0's are embedding vectors of ANY magnitude: the token-stationary kernel scales every
+// row by its own power of two (the tiled kernel, for the shapes that one does not take, takes them as they are: fp32-grade
+// for |x|max in ~[0.1, 6e4]).  The forward's layer 0 and the projected table are this one descriptor, launched by enc_k1_launch.
+static SgemmParams enc_k1(int l, int I, int NGH, const float *const *w, const EncW &k, bool f32)
+{
+    SgemmParams g;
+    g.B = w[0];
+    g.bias = w[2];
+    g.N = NGH;
+    g.K = I;
+    g.lda = g.ldb = I;
+    g.ldc = NGH;
+    if (f32)
+        return g;
+    g.a_exp = l == 0 ? 0 : 6;
+    g.b_absmax = k.wih_max;
+    g.b_hi16 = k.w16;
+    if (enc_rows16(NGH, I)) { // W_ih as a fragment stream
+        g.a_row_scale = l == 0;
+    } else {
+        const int Kp = (I + 31) / 32 * 32;
+        g.b_lo16 = k.w16 + (size_t)NGH * Kp * sizeof(uint16_t);
+        g.ldb16 = Kp;
+    }
+    return g;
+}
+static int enc_k1_launch(const SgemmParams &g, bool f32, hipStream_t st)
+{
+    if (f32)
+        return tt_sgemm(g, false, false, 1, st);
+    return enc_rows16(g.N, g.K) ? tt_gemm_rows16(g, st) : tt_sgemm16(g, false, false, 1, st);
 }
 
 namespace {
@@ -647,9 +705,7 @@ TT_EXPORT int tt_encoder_prepare_f32(int E, int H, int num_layers, int bidirecti
                                      const float *const *weights, void *prepared, size_t prepared_bytes, tt_stream_t stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    int rc = enc_check_shape("tt_encoder_prepare_f32", 1, 1, E, H, num_layers, 1);
-    if (rc != TT_OK)
-        return rc;
+    TT_RC_CHECK(enc_check_shape("tt_encoder_prepare_f32", {1, 1, E, H, num_layers, bidirectional, rnn_type}, 1));
     if (rnn_type < CELL_GRU || rnn_type > CELL_RNN)
         return tt_fail(TT_ERR_UNSUPPORTED, "tt_encoder_prepare_f32: rnn_type=%d (0 GRU, 1 LSTM, 2 RNN)", rnn_type);
     const EncPrepared pl = enc_prepared_layout(E, H, num_layers, bidirectional, rnn_type);
@@ -660,318 +716,24 @@ TT_EXPORT int tt_encoder_prepare_f32(int E, int H, int num_layers, int bidirecti
     const int ndir = bidirectional ? 2 : 1;
     TT_RC_CHECK(tt_zero_async(pb, 256, st));
     for (int l = 0; l < num_layers; ++l)
-        for (int d = 0; d < ndir; ++d) {
-            unsigned *words = (unsigned *)pb + 2 * (2 * l + d);
-            TT_RC_CHECK(enc_pack_weights(l == 0 ? E : ndir * H, H, rnn_type, weights + ((size_t)l * ndir + d) * 4, words,
-                                         words + 1, pb + pl.wih[l][d], pb + pl.wp[l][d], st));
-        }
+        for (int d = 0; d < ndir; ++d)
+            TT_RC_CHECK(enc_pack_weights({l == 0 ? E : ndir * H, H, rnn_type, enc_force_f32(0)}, weights + ((size_t)l * ndir + d) * 4,
+                                         enc_prepared_weights(pb, pl, l, d), st));
     return TT_OK;
 }
-
 
 // ------------------------------------------------------------------ the projected table (inference)
 // With GloVe loaded the table is frozen (backend/model.py:25-27) and at inference W_ih is fixed too, so layer 0's input
 // projection of a token depends on its id alone: P[v] = table[v] W_ih^T + b_ih for every vocabulary row v, V x 3H floats per
 // direction (400 003 x 768 x 4 B = 1.23 GB for the north-star tower).  It is built by the launch the forward itself would make
-// (same kernel, same weight images and scale words, rows taken in order instead of through the packed ids; the token-stationary
-// kernel scales every row by its own power of two), so row v holds the bits K1 writes for a token with id v, and the
-// recurrence kernels gather their step's rows from it (GruParams::gi_ids): K1 -- half the index build's GPU time, and a
-// [tokens][3H] buffer written and read back -- is gone from inference.
-static bool enc_projected_supported(int H, int rnn_type)
-{
-    return rnn_type == CELL_GRU && gru16_supported(H) && !enc_force_f32();
-}
+// (enc_k1: same kernel, same weight images and scale words, rows taken in order instead of through the packed ids; the
+// token-stationary kernel scales every row by its own power of two), so row v holds the bits K1 writes for a token with id v,
+// and the recurrence kernels gather their step's rows from it (GruParams::gi_ids): K1 -- half the index build's GPU time, and
+// a [tokens][3H] buffer written and read back -- is gone from inference.
+static bool enc_projected_supported(int H, int rnn_type) { return enc_use16(rnn_type, H, enc_force_f32(0)); }
 static size_t enc_projected_dir_bytes(int64_t V, int H, int rnn_type)
 {
     return tt_align_up(sizeof(float) * (size_t)V * enc_gates(rnn_type) * H, 256);
-}
-
-static int encoder_forward(const char *who, const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
-                           int num_layers, int bidirectional, int rnn_type, const float *const *weights,
-                           const void *prepared, const float *proj_w, const float *proj_b, int normalize, int train,
-                           float dropout_p, uint64_t dropout_seed, float *out, void *workspace, size_t workspace_bytes,
-                           int32_t *status, hipStream_t st, const tt_enc_sync_t *sync = nullptr, const void *projected = nullptr)
-{
-    int rc = enc_check_shape(who, B, T, E, H, num_layers, V);
-    if (rc != TT_OK)
-        return rc;
-    if (train < 0 || (train & ~(TT_ENC_TRAIN_MASK | TT_ENC_ONE_WORKGROUP | TT_ENC_PHASE_BEGIN | TT_ENC_PHASE_FINISH | TT_ENC_SEED_ON_DEVICE | TT_ENC_F32)) ||
-        (train & TT_ENC_TRAIN_MASK) > 2 || ((train & TT_ENC_PHASE_BEGIN) && (train & TT_ENC_PHASE_FINISH)))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: train=0x%x (0, 1 or 2, optionally | TT_ENC_ONE_WORKGROUP | one TT_ENC_PHASE_* | TT_ENC_F32)", who, train);
-    const bool force_f32 = enc_force_f32(train); // every product of this call on the fp32-MFMA kernels
-    if (force_f32)
-        prepared = nullptr; // (the prepared images are the f16-split kernels'; this path derives its own in the workspace)
-    const bool one_wg = (train & TT_ENC_ONE_WORKGROUP) != 0; // the caller keeps the recurrences off the column-split kernels
-    // the call in two halves (include/tt.h): BEGIN = everything in front of the first recurrence launch, FINISH = the rest
-    const bool ph_begin = (train & TT_ENC_PHASE_BEGIN) != 0, ph_finish = (train & TT_ENC_PHASE_FINISH) != 0;
-    // the dropout seed as the address of a device word the kernels read when they run (a captured step replays with new masks)
-    const uint64_t *seed_dev = (train & TT_ENC_SEED_ON_DEVICE) ? (const uint64_t *)(uintptr_t)dropout_seed : nullptr;
-    train &= TT_ENC_TRAIN_MASK;
-    if (!ids || (!table && !projected) || !weights || !out || (bidirectional && (!proj_w || !proj_b)))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
-    if (projected && (train || ph_begin || ph_finish || force_f32 || !enc_projected_supported(H, rnn_type)))
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: a projected table serves inference calls of the f16-split GRU (H = 128, 256) only", who);
-    if (!(dropout_p >= 0.0f && dropout_p < 1.0f))
-        return tt_fail(TT_ERR_BAD_SHAPE, "%s: dropout_p=%g", who, dropout_p);
-    if (rnn_type < CELL_GRU || rnn_type > CELL_RNN)
-        return tt_fail(TT_ERR_UNSUPPORTED, "%s: rnn_type=%d (0 GRU, 1 LSTM, 2 RNN)", who, rnn_type);
-    const int NGH = enc_gates(rnn_type) * H;
-    const bool drop = train && dropout_p > 0.0f && num_layers > 1;
-    const EncLayout lo = enc_layout(B, T, E, H, num_layers, bidirectional, train, drop, rnn_type, projected != nullptr);
-    if (!workspace || workspace_bytes < lo.total || ((uintptr_t)workspace & 255))
-        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (or not 256-B aligned)", who, workspace_bytes,
-                       lo.total);
-    char *ws = (char *)workspace;
-    int32_t *len = (int32_t *)(ws + lo.len), *tok_off = (int32_t *)(ws + lo.tok_off);
-    int32_t *perm = (int32_t *)(ws + lo.perm), *idsp = (int32_t *)(ws + lo.ids), *flag = (int32_t *)(ws + lo.flag);
-    const int ndir = lo.ndir;
-
-    // (training: the backward's "previous token" maps are made here -- they depend on the lengths only)
-    int32_t *pm_fwd = train ? (int32_t *)(ws + lo.prevmap[0]) : nullptr;
-    int32_t *pm_rev = (train && ndir == 2) ? (int32_t *)(ws + lo.prevmap[1]) : nullptr;
-    // Layer 0's zero fills ride on ONE launch in front of the prep kernels (each was its own ~5 us launch on the call's chain):
-    // the status flags (when the prep kernels do not clear them themselves), the all-zero row behind layer 0's output
-    // (training) and the split recurrence's hand-off slots.
-    const bool use16_early = rnn_type == CELL_GRU && gru16_supported(H) && !force_f32;
-    const bool split0 = use16_early && lo.xch && !one_wg && gru16x4_usable(B, H, ndir);
-    const bool fused_prep = B <= 1024 && (int64_t)B * T <= PREP_FUSED_MAX_IDS;
-    if (!ph_finish) {
-        float *x1 = (num_layers == 1 && !train) ? nullptr : (float *)(ws + lo.x[1]);
-        TT_RC_CHECK(tt_zero3_async(fused_prep ? nullptr : (void *)flag, fused_prep ? 0 : 256,
-                                   train ? (void *)(x1 + (size_t)lo.MT * ndir * H) : nullptr, train ? sizeof(float) * ndir * H : 0,
-                                   split0 ? (void *)(ws + lo.xch) : nullptr, split0 ? gru16x4_xch_bytes(B, H, ndir) : 0, st));
-    }
-    if (ph_finish) {
-        // (the BEGIN half made lengths, packed ids, maps and layer 0's projections in this workspace)
-    } else if (fused_prep) {
-        hipLaunchKernelGGL(prep_fused_kernel, dim3(1), dim3(1024), 0, st, ids, B, T, V, len, flag, tok_off, perm, idsp, status,
-                           pm_fwd, pm_rev, (int)lo.MT);
-        TT_LAUNCH_CHECK();
-    } else {
-        hipLaunchKernelGGL(prep_len_kernel, dim3((B + 3) / 4), dim3(256), 0, st, ids, B, T, V, len, flag);
-        hipLaunchKernelGGL(prep_scan_sort_kernel, dim3(1), dim3(1024), 0, st, len, B, T, tok_off, perm);
-        hipLaunchKernelGGL(prep_pack_ids_kernel, dim3(B), dim3(256), 0, st, ids, B, T, len, tok_off, V, idsp, flag, status,
-                           pm_fwd, pm_rev, (int)lo.MT);
-        TT_LAUNCH_CHECK();
-    }
-
-    const size_t lds = sizeof(float) * 2 * ENC_RB * (H + 4);
-    const bool use16 = rnn_type == CELL_GRU && gru16_supported(H) && !force_f32;
-    const EncPrepared pl = enc_prepared_layout(E, H, num_layers, bidirectional, rnn_type);
-    const char *pb = (const char *)prepared;
-    for (int l = 0; l < num_layers; ++l) {
-        const int I = l == 0 ? E : ndir * H;
-        GruParams gp;
-        gp.len = len;
-        gp.tok_off = tok_off;
-        gp.perm = perm;
-        gp.B = B;
-        gp.H = H;
-        gp.out_ld = ndir * H;
-        gp.slots = 2 * tt_device_cus();
-        const bool last = l == num_layers - 1;
-        float *xout = (last && !train) ? nullptr : (float *)(ws + lo.x[l + 1]);
-        if (train && l > 0) // the all-zero row that stands for "h before the first step" in the backward GEMMs (layer 0: above)
-            TT_RC_CHECK(tt_zero_async(xout + (size_t)lo.MT * ndir * H, sizeof(float) * ndir * H, st));
-        for (int d = 0; d < ndir; ++d) {
-            const float *const *w = weights + ((size_t)l * ndir + d) * 4;
-            SgemmParams g;
-            g.A = l == 0 ? table : (const float *)(ws + ((drop && l > 0) ? lo.xd[l] : lo.x[l]));
-            g.a_map = l == 0 ? idsp : nullptr;
-            g.B = w[0];
-            g.b_map = nullptr;
-            g.C = (float *)(ws + lo.gi[d]);
-            g.bias = w[2];
-            g.m_dyn = tok_off + B;
-            g.k_dyn = nullptr;
-            g.M = (int)lo.MT;
-            g.N = NGH;
-            g.K = I;
-            g.lda = I;
-            g.ldb = I;
-            g.ldc = NGH;
-            g.slab_stride = 0;
-            g.accumulate = 0;
-            // the weights in kernel form: from the caller's prepared buffer, or derived here into the workspace
-            unsigned *wih_max, *wmax;
-            char *w16, *wp;
-            if (pb) {
-                wih_max = (unsigned *)pb + 2 * (2 * l + d);
-                wmax = wih_max + 1;
-                w16 = (char *)pb + pl.wih[l][d];
-                wp = (char *)pb + pl.wp[l][d];
-            } else {
-                wih_max = (unsigned *)flag + 40 + 2 * l + d; // in the status block cleared above
-                wmax = (unsigned *)flag + 16 + 2 * l + d;
-                w16 = ws + lo.wih16[d];
-                wp = ws + lo.wp[d];
-                if (!(ph_finish && l == 0)) {
-                    rc = enc_pack_weights(I, H, rnn_type, w, wih_max, wmax, w16, wp, st, force_f32);
-                    if (rc != TT_OK)
-                        return rc;
-                }
-            }
-            if (ph_finish && l == 0) {
-                rc = TT_OK; // (layer 0's projection was launched by the BEGIN half)
-            } else if (projected && l == 0) {
-                rc = TT_OK; // (every vocabulary row's projection is in the table: the recurrence gathers them by token id)
-            } else if (!force_f32) {
-                // K1 on the f16 pipes (fp16 hi/lo split, fp32-grade; sgemm.h): W_ih is scaled by the power of two
-                // that puts its largest element in [2^13, 2^14); deeper layers' A rows are hidden states in (-1, 1) (times
-                // 1/(1-p) under dropout): 2^6; layer 0's are embedding vectors of ANY magnitude: the token-stationary
-                // kernel scales every row by its own power of two (the tiled kernel, for the shapes that one does not take,
-                // takes them as they are: fp32-grade for |x|max in ~[0.1, 6e4])
-                g.a_absmax = nullptr;
-                g.a_exp = l == 0 ? 0 : 6;
-                g.b_absmax = wih_max;
-                g.b_exp = 0;
-                g.b_hi16 = w16;
-                unsigned *xmax = (train && l == 0) ? (unsigned *)flag + ENC_FLAG_XMAX : nullptr; // for the backward's dW_ih
-                if (enc_rows16(NGH, I)) { // token-stationary form (gemm_rows16.hip): W_ih as a fragment stream
-                    g.b_lo16 = nullptr;
-                    g.ldb16 = 0;
-                    g.a_row_scale = l == 0;
-                    g.a_absmax_out = d == 0 ? xmax : nullptr;
-                    rc = tt_gemm_rows16(g, st);
-                } else {
-                    if (xmax && d == 0)
-                        TT_RC_CHECK(tt_absmax_rows(table, E, E, idsp, (int)lo.MT, tok_off + B, xmax, st));
-                    const int Kp = (I + 31) / 32 * 32;
-                    g.b_lo16 = w16 + (size_t)NGH * Kp * sizeof(uint16_t);
-                    g.ldb16 = Kp;
-                    rc = tt_sgemm16(g, false, false, 1, st);
-                }
-            } else {
-                rc = tt_sgemm(g, false, false, 1, st);
-            }
-            if (rc != TT_OK)
-                return rc;
-            gp.dir[d].gi = (const float *)(ws + lo.gi[d]);
-            if (projected && l == 0) {
-                gp.dir[d].gi = (const float *)((const char *)projected + (size_t)d * enc_projected_dir_bytes(V, H, rnn_type));
-                gp.gi_ids = idsp;
-                gp.gi_rows = (unsigned)V;
-            }
-            gp.dir[d].wp = (const float *)wp;
-            gp.dir[d].wmax = wmax;
-            gp.dir[d].b_hh = w[3];
-            gp.dir[d].out_seq = xout;
-            gp.dir[d].gates = (train && rnn_type != CELL_RNN) ? (float *)(ws + lo.gates[l][d]) : nullptr;
-            gp.dir[d].cseq = nullptr;
-            if (train && rnn_type == CELL_LSTM) { // c before the first step: the all-zero row at index MT
-                gp.dir[d].cseq = (float *)(ws + lo.cseq[l][d]);
-                TT_RC_CHECK(tt_zero_async(gp.dir[d].cseq + (size_t)lo.MT * H, sizeof(float) * H, st));
-            }
-            // only the last layer's final hidden state is used (model.py:65-71)
-            gp.dir[d].h_final = (float *)(ws + lo.hfin) + (size_t)d * B * H;
-            gp.dir[d].out_col0 = d * H;
-            gp.dir[d].reverse = d;
-        }
-        if (ndir == 1)
-            gp.dir[1] = gp.dir[0];
-        if (ph_begin) { // everything in front of the first recurrence launch is in the queue
-            TT_LAUNCH_CHECK();
-            return TT_OK;
-        }
-        if (l == 0 && sync && sync->wait_before_recurrence) // (include/tt.h: the host orders this call's recurrences behind another call's)
-            TT_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)sync->wait_before_recurrence, 0));
-        if (use16 && lo.xch && !one_wg && gru16x4_usable(B, H, ndir)) {
-            // a row group's gate columns on four CUs (gru16x4.hip): same bits out, ~half the time per step
-            rc = gru16x4_launch(gp, ndir, ws + lo.xch, status, st, /*xch_zeroed=*/l == 0 && split0);
-            if (rc != TT_OK)
-                return rc;
-        } else if (use16) {
-            rc = gru16_launch(gp, ndir, st);
-            if (rc != TT_OK)
-                return rc;
-        } else {
-            rc = rnn_type == CELL_LSTM ? launch_seq<CELL_LSTM>(gp, B, H, ndir, lds, st)
-                                       : (rnn_type == CELL_RNN ? launch_seq<CELL_RNN>(gp, B, H, ndir, lds, st)
-                                                               : launch_seq<CELL_GRU>(gp, B, H, ndir, lds, st));
-            if (rc != TT_OK)
-                return rc;
-        }
-        TT_LAUNCH_CHECK();
-        if (last && sync && sync->record_after_recurrence)
-            TT_HIP_CHECK(hipEventRecord((hipEvent_t)sync->record_after_recurrence, st));
-        if (drop && !last) { // nn.GRU's dropout sits on the outputs of every layer but the last
-            hipLaunchKernelGGL(dropout_apply_kernel, dim3(B, B >= 2048 ? 1 : (B >= 512 ? 4 : 16)), dim3(256), 0, st, (const float *)xout,
-                               (float *)(ws + lo.xd[l + 1]), len, tok_off, T, ndir * H, l, dropout_p, seed_dev ? 0ull : dropout_seed,
-                               seed_dev);
-            TT_RC_CHECK(tt_zero_async((float *)(ws + lo.xd[l + 1]) + (size_t)lo.MT * ndir * H, sizeof(float) * ndir * H, st));
-            TT_LAUNCH_CHECK();
-        }
-    }
-    if (ndir == 2 && B >= 2048) { // (below that the two launches cost what the per-row loop does: ~50 us at B = 512 .. 1024)
-        // Linear(2H, H) on cat(h_fwd, h_bwd) (model.py:65-69) as two accumulating GEMMs over the two halves of the weight
-        // (the head kernel's per-row scalar loop read all of proj_w once per batch row: 0.6 ms at B = 8192), then the head
-        // kernel only normalises
-        float *hid = (float *)(ws + lo.hid);
-        for (int d = 0; d < 2; ++d) {
-            SgemmParams g;
-            g.A = (const float *)(ws + lo.hfin) + (size_t)d * B * H;
-            g.B = proj_w + (size_t)d * H;
-            g.C = hid;
-            g.bias = d == 0 ? proj_b : nullptr;
-            g.a_map = g.b_map = nullptr;
-            g.m_dyn = g.k_dyn = nullptr;
-            g.M = B;
-            g.N = H;
-            g.K = H;
-            g.lda = H;
-            g.ldb = 2 * H;
-            g.ldc = H;
-            g.slab_stride = 0;
-            g.accumulate = d;
-            rc = tt_sgemm(g, false, false, 1, st);
-            if (rc != TT_OK)
-                return rc;
-        }
-        hipLaunchKernelGGL(head_kernel, dim3(B), dim3(256), 0, st, (const float *)hid, B, H, 1, proj_w, proj_b, normalize,
-                           (float *)nullptr, out);
-    } else {
-        hipLaunchKernelGGL(head_kernel, dim3(B), dim3(256), 0, st, (const float *)(ws + lo.hfin), B, H, ndir, proj_w,
-                           proj_b, normalize, train ? (float *)(ws + lo.hid) : (float *)nullptr, out);
-    }
-    TT_LAUNCH_CHECK();
-    return TT_OK;
-}
-
-// Workgroups (= CUs: one each) the column-split recurrence of a call of this shape occupies, 0 when the call runs the
-// one-workgroup kernels anyway.  For hosts that keep several encoder calls in flight (include/tt.h).
-TT_EXPORT int tt_encoder_split_workgroups(int B, int H, int bidirectional, int rnn_type)
-{
-    const int ndir = bidirectional ? 2 : 1;
-    if (rnn_type != CELL_GRU || !gru16_supported(H) || enc_force_f32() || gru16x4_xch_bytes(B, H, ndir) == 0 ||
-        !gru16x4_usable(B, H, ndir))
-        return 0;
-    return ((B + ENC_RB - 1) / ENC_RB + 7) / 8 * 32 * (gru16x4_launches(B, H, ndir) == 2 ? 1 : ndir); // (per launch)
-}
-
-TT_EXPORT int tt_encoder_forward_f32(const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
-                                     int num_layers, int bidirectional, int rnn_type, const float *const *weights,
-                                     const float *proj_w, const float *proj_b, int normalize, int train,
-                                     float dropout_p, uint64_t dropout_seed, float *out, void *workspace,
-                                     size_t workspace_bytes, int32_t *status, const tt_enc_sync_t *sync, tt_stream_t stream)
-{
-    return encoder_forward("tt_encoder_forward_f32", ids, B, T, table, V, E, H, num_layers, bidirectional, rnn_type, weights,
-                           nullptr, proj_w, proj_b, normalize, train, dropout_p, dropout_seed, out, workspace,
-                           workspace_bytes, status, (hipStream_t)stream, sync);
-}
-
-TT_EXPORT int tt_encoder_forward_prepared_f32(const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
-                                              int num_layers, int bidirectional, int rnn_type,
-                                              const float *const *weights, const void *prepared, const float *proj_w,
-                                              const float *proj_b, int normalize, int opts, float *out, void *workspace,
-                                              size_t workspace_bytes, int32_t *status, tt_stream_t stream)
-{
-    if (!prepared || ((uintptr_t)prepared & 255))
-        return tt_fail(TT_ERR_WORKSPACE, "tt_encoder_forward_prepared_f32: prepared buffer null or not 256-B aligned");
-    if (opts & ~(TT_ENC_ONE_WORKGROUP | TT_ENC_F32))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_forward_prepared_f32: opts=0x%x (0, TT_ENC_ONE_WORKGROUP, TT_ENC_F32)", opts);
-    return encoder_forward("tt_encoder_forward_prepared_f32", ids, B, T, table, V, E, H, num_layers, bidirectional, rnn_type,
-                           weights, prepared, proj_w, proj_b, normalize, /*train=*/0 | opts, 0.0f, 0, out, workspace,
-                           workspace_bytes, status, (hipStream_t)stream);
 }
 
 TT_EXPORT size_t tt_encoder_projected_bytes(int64_t V, int E, int H, int bidirectional, int rnn_type)
@@ -985,13 +747,11 @@ TT_EXPORT int tt_encoder_project_table_f32(const float *table, int64_t V, int E,
                                            int rnn_type, const float *const *weights, const void *prepared, void *projected,
                                            size_t projected_bytes, tt_stream_t stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = enc_check_shape("tt_encoder_project_table_f32", 1, 1, E, H, num_layers, V);
-    if (rc != TT_OK)
-        return rc;
+    TT_RC_CHECK(enc_check_shape("tt_encoder_project_table_f32", {1, 1, E, H, num_layers, bidirectional, rnn_type}, V));
     const size_t need = tt_encoder_projected_bytes(V, E, H, bidirectional, rnn_type);
     if (need == 0)
         return tt_fail(TT_ERR_UNSUPPORTED, "tt_encoder_project_table_f32: rnn_type=%d H=%d has no projected table (f16-split GRU: H = 128, 256)", rnn_type, H);
+    // (a misaligned `prepared` is TT_ERR_BAD_SHAPE here and TT_ERR_WORKSPACE in the forward entries that read the same buffer)
     if (!table || !weights || !prepared || ((uintptr_t)prepared & 255))
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_project_table_f32: null pointer (or prepared not 256-B aligned)");
     if (!projected || projected_bytes < need || ((uintptr_t)projected & 255))
@@ -999,47 +759,347 @@ TT_EXPORT int tt_encoder_project_table_f32(const float *table, int64_t V, int E,
                        projected_bytes, need);
     const int ndir = bidirectional ? 2 : 1, NGH = enc_gates(rnn_type) * H;
     const EncPrepared pl = enc_prepared_layout(E, H, num_layers, bidirectional, rnn_type);
-    const char *pb = (const char *)prepared;
     for (int d = 0; d < ndir; ++d) {
-        const float *const *w = weights + (size_t)d * 4; // layer 0
-        SgemmParams g;
+        // layer 0 of direction d; rows in order (no a_map): row v of the result is what a token with id v gets
+        SgemmParams g = enc_k1(0, E, NGH, weights + (size_t)d * 4, enc_prepared_weights((char *)prepared, pl, 0, d), false);
         g.A = table;
-        g.a_map = nullptr; // rows in order: row v of the result is what a token with id v gets
-        g.B = w[0];
-        g.b_map = nullptr;
-        g.C = (float *)((char *)projected + (size_t)d * enc_projected_dir_bytes(V, H, rnn_type));
-        g.bias = w[2];
-        g.m_dyn = nullptr;
-        g.k_dyn = nullptr;
         g.M = (int)V;
-        g.N = NGH;
-        g.K = E;
-        g.lda = E;
-        g.ldb = E;
-        g.ldc = NGH;
-        g.slab_stride = 0;
-        g.accumulate = 0;
-        g.a_absmax = nullptr;
-        g.a_exp = 0;
-        g.b_absmax = (const unsigned *)pb + 2 * d; // layer 0, direction d: max |W_ih| (tt_encoder_prepare_f32)
-        g.b_exp = 0;
-        g.b_hi16 = pb + pl.wih[0][d];
-        if (enc_rows16(NGH, E)) {
-            g.b_lo16 = nullptr;
-            g.ldb16 = 0;
-            g.a_row_scale = 1;
-            g.a_absmax_out = nullptr;
-            rc = tt_gemm_rows16(g, st);
-        } else {
-            const int Kp = (E + 31) / 32 * 32;
-            g.b_lo16 = pb + pl.wih[0][d] + (size_t)NGH * Kp * sizeof(uint16_t);
-            g.ldb16 = Kp;
-            rc = tt_sgemm16(g, false, false, 1, st);
-        }
-        if (rc != TT_OK)
-            return rc;
+        g.C = (float *)((char *)projected + (size_t)d * enc_projected_dir_bytes(V, H, rnn_type));
+        TT_RC_CHECK(enc_k1_launch(g, false, (hipStream_t)stream));
     }
     return TT_OK;
+}
+
+// ------------------------------------------------------------------ one call: refusals, route, steps
+// The refusals of the three forward entries and of the backward, in the order and with the words each had when it checked
+// for itself.  Where the two passes differ it is marked; tests/test_encoder_args_cpu.py pins every answer.
+int enc_validate(const EncCall &c, EncLayout &lo)
+{
+    const char *who = c.who;
+    const int word = c.o.word;
+    TT_RC_CHECK(enc_check_shape(who, c, c.V));
+    if (c.bwd) {
+        if (word & ~(TT_ENC_ONE_WORKGROUP | TT_ENC_SEED_ON_DEVICE | TT_ENC_F32))
+            return tt_fail(TT_ERR_BAD_SHAPE, "%s: opts=0x%x (0, TT_ENC_ONE_WORKGROUP, TT_ENC_SEED_ON_DEVICE, TT_ENC_F32)", who, word);
+        // (the backward reads neither ids nor proj_b, and never looks at dropout_p: the forward it follows did)
+        if (!c.table || !c.weights || !c.bwd->d_out || !c.bwd->grads ||
+            (c.bidirectional && (!c.proj_w || !c.bwd->g_proj_w || !c.bwd->g_proj_b)))
+            return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    } else {
+        // (the prepared and projected entries have refused the bits they do not take before they come here, with their own words)
+        if (word < 0 || (word & ~(TT_ENC_TRAIN_MASK | TT_ENC_ONE_WORKGROUP | TT_ENC_PHASE_BEGIN | TT_ENC_PHASE_FINISH | TT_ENC_SEED_ON_DEVICE | TT_ENC_F32)) ||
+            (word & TT_ENC_TRAIN_MASK) > 2 || ((word & TT_ENC_PHASE_BEGIN) && (word & TT_ENC_PHASE_FINISH)))
+            return tt_fail(TT_ERR_BAD_SHAPE, "%s: train=0x%x (0, 1 or 2, optionally | TT_ENC_ONE_WORKGROUP | one TT_ENC_PHASE_* | TT_ENC_F32)", who, word);
+        if (!c.ids || (!c.table && !c.projected) || !c.weights || !c.out || (c.bidirectional && (!c.proj_w || !c.proj_b)))
+            return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+        // (in front of the rnn_type check: an unknown cell on the projected entry gets this refusal, not that one)
+        if (c.projected && (c.o.train_mode || c.o.phase != ENC_PHASE_WHOLE || c.o.force_f32 || !enc_projected_supported(c.H, c.cell)))
+            return tt_fail(TT_ERR_UNSUPPORTED, "%s: a projected table serves inference calls of the f16-split GRU (H = 128, 256) only", who);
+        if (!(c.dropout_p >= 0.0f && c.dropout_p < 1.0f))
+            return tt_fail(TT_ERR_BAD_SHAPE, "%s: dropout_p=%g", who, c.dropout_p);
+    }
+    if (c.cell < CELL_GRU || c.cell > CELL_RNN)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: rnn_type=%d (0 GRU, 1 LSTM, 2 RNN)", who, c.cell);
+    lo = enc_layout(c, c.o.train_mode, enc_drops(c), c.projected != nullptr);
+    if (!c.workspace || c.workspace_bytes < lo.total || ((uintptr_t)c.workspace & 255)) {
+        if (c.bwd) // (its own words: the buffer is the one a training forward filled)
+            return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes: pass the buffer the forward call (train=%d) filled", who,
+                           c.workspace_bytes, lo.total, c.o.train_mode);
+        return tt_fail(TT_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (or not 256-B aligned)", who, c.workspace_bytes, lo.total);
+    }
+    return TT_OK;
+}
+
+EncRoute enc_route(const EncCall &c, const EncLayout &lo)
+{
+    EncRoute r = {};
+    r.drop = enc_drops(c);
+    r.use16 = enc_use16(c.cell, c.H, c.o.force_f32);
+    if (!c.bwd) {
+        r.use_prepared = c.prepared && !c.o.force_f32;
+        r.fused_prep = c.B <= 1024 && lo.MT <= PREP_FUSED_MAX_IDS;
+        r.split_fwd = enc_split_fwd(c.B, c.H, lo.ndir, r.use16, c.o.one_wg);
+        // (below 2048 rows the two GEMM launches cost what the head kernel's per-row loop does: ~50 us at B = 512 .. 1024)
+        r.head_gemm = lo.ndir == 2 && c.B >= 2048;
+    } else {
+        // the recurrence kernel's bias partial sums live in the split-K scratch (free while it runs): they must fit
+        const size_t n_rowgroups = (c.B + ENC_RB - 1) / ENC_RB;
+        r.fused_bias = r.use16 && n_rowgroups * 2 * lo.ng * c.H * lo.ndir <= enc_slab_floats(c.E, c.H, lo.ndir, lo.ng);
+        r.split_bwd = r.fused_bias && lo.xchb && !c.o.one_wg && gru16x4_bwd_usable(c.B, c.H, lo.ndir);
+    }
+    return r;
+}
+
+// typed views of the workspace's int32 metadata
+struct EncMeta {
+    char *ws;
+    int32_t *len, *tok_off, *perm, *idsp, *flag;
+};
+static EncMeta enc_meta(const EncCall &c, const EncLayout &lo)
+{
+    char *ws = (char *)c.workspace;
+    return {ws, (int32_t *)(ws + lo.len), (int32_t *)(ws + lo.tok_off), (int32_t *)(ws + lo.perm), (int32_t *)(ws + lo.ids),
+            (int32_t *)(ws + lo.flag)};
+}
+
+// prep: lengths, input flags, token offsets, row order, packed ids (training: the backward's "previous token" maps too --
+// they depend on the lengths only).  Layer 0's zero fills ride on ONE launch in front of the prep kernels (each was its own
+// ~5 us launch on the call's chain): the status flags (when the prep kernels do not clear them themselves), the all-zero
+// row behind layer 0's output (training) and the split recurrence's hand-off slots.
+static int enc_prep(const EncCall &c, const EncLayout &lo, const EncRoute &r)
+{
+    const EncMeta m = enc_meta(c, lo);
+    const int B = c.B, T = c.T, ndir = lo.ndir;
+    const bool train = c.o.train_mode != 0;
+    hipStream_t st = c.st;
+    int32_t *pm_fwd = train ? (int32_t *)(m.ws + lo.prevmap[0]) : nullptr;
+    int32_t *pm_rev = (train && ndir == 2) ? (int32_t *)(m.ws + lo.prevmap[1]) : nullptr;
+    float *x1 = (c.L == 1 && !train) ? nullptr : (float *)(m.ws + lo.x[1]);
+    TT_RC_CHECK(tt_zero3_async(r.fused_prep ? nullptr : (void *)m.flag, r.fused_prep ? 0 : 256,
+                               train ? (void *)(x1 + (size_t)lo.MT * ndir * c.H) : nullptr, train ? sizeof(float) * ndir * c.H : 0,
+                               r.split_fwd ? (void *)(m.ws + lo.xch) : nullptr, r.split_fwd ? gru16x4_xch_bytes(B, c.H, ndir) : 0, st));
+    if (r.fused_prep) {
+        hipLaunchKernelGGL(prep_fused_kernel, dim3(1), dim3(1024), 0, st, c.ids, B, T, c.V, m.len, m.flag, m.tok_off, m.perm, m.idsp,
+                           c.status, pm_fwd, pm_rev, (int)lo.MT);
+    } else {
+        hipLaunchKernelGGL(prep_len_kernel, dim3((B + 3) / 4), dim3(256), 0, st, c.ids, B, T, c.V, m.len, m.flag);
+        hipLaunchKernelGGL(prep_scan_sort_kernel, dim3(1), dim3(1024), 0, st, m.len, B, T, m.tok_off, m.perm);
+        hipLaunchKernelGGL(prep_pack_ids_kernel, dim3(B), dim3(256), 0, st, c.ids, B, T, m.len, m.tok_off, c.V, m.idsp, m.flag,
+                           c.status, pm_fwd, pm_rev, (int)lo.MT);
+    }
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+// the output sequence of layer l: nothing for the last layer of an inference call (only its final hidden state is used)
+static float *enc_layer_out(const EncCall &c, const EncLayout &lo, int l)
+{
+    return (l == c.L - 1 && !c.o.train_mode) ? nullptr : (float *)((char *)c.workspace + lo.x[l + 1]);
+}
+
+// what the two directions of layer l's recurrence share (training, l > 0: also the all-zero row behind the layer's output that
+// stands for "h before the first step" in the backward GEMMs; layer 0's is zeroed by the prep)
+static int enc_layer_open(const EncCall &c, const EncLayout &lo, int l, GruParams &gp)
+{
+    const EncMeta m = enc_meta(c, lo);
+    gp.len = m.len;
+    gp.tok_off = m.tok_off;
+    gp.perm = m.perm;
+    gp.B = c.B;
+    gp.H = c.H;
+    gp.out_ld = lo.ndir * c.H;
+    gp.slots = 2 * tt_device_cus();
+    if (c.o.train_mode && l > 0)
+        TT_RC_CHECK(tt_zero_async(enc_layer_out(c, lo, l) + (size_t)lo.MT * lo.ndir * c.H, sizeof(float) * lo.ndir * c.H, c.st));
+    return TT_OK;
+}
+
+// per-layer weights in kernel form: in the caller's prepared buffer, or in the workspace, where enc_pack_layer puts them
+static EncW enc_layer_weights(const EncCall &c, const EncLayout &lo, const EncRoute &r, int l, int d)
+{
+    if (r.use_prepared)
+        return enc_prepared_weights((char *)c.prepared, enc_prepared_layout(c.E, c.H, c.L, c.bidirectional, c.cell), l, d);
+    return enc_workspace_weights((char *)c.workspace, lo, l, d);
+}
+static int enc_pack_layer(const EncCall &c, const EncLayout &lo, int l, int d, const EncW &k)
+{
+    return enc_pack_weights({l == 0 ? c.E : lo.ndir * c.H, c.H, c.cell, c.o.force_f32}, c.weights + ((size_t)l * lo.ndir + d) * 4, k, c.st);
+}
+
+// input projection of layer l, direction d, over all valid tokens: layer 0 gathers its rows from the table through the packed ids
+static int enc_input_projection(const EncCall &c, const EncLayout &lo, const EncRoute &r, int l, int d, const EncW &k)
+{
+    const EncMeta m = enc_meta(c, lo);
+    const int I = l == 0 ? c.E : lo.ndir * c.H, NGH = lo.ng * c.H;
+    const bool f32 = c.o.force_f32;
+    SgemmParams g = enc_k1(l, I, NGH, c.weights + ((size_t)l * lo.ndir + d) * 4, k, f32);
+    g.A = l == 0 ? c.table : (const float *)(m.ws + (r.drop ? lo.xd[l] : lo.x[l]));
+    g.a_map = l == 0 ? m.idsp : nullptr;
+    g.C = (float *)(m.ws + lo.gi[d]);
+    g.m_dyn = m.tok_off + c.B;
+    g.M = (int)lo.MT;
+    // training, layer 0: max |x| over the call's embedding vectors, the X scale of the backward's dW_ih (once: direction 0)
+    unsigned *xmax = (!f32 && c.o.train_mode && l == 0 && d == 0) ? (unsigned *)m.flag + ENC_FLAG_XMAX : nullptr;
+    if (xmax && enc_rows16(NGH, I))
+        g.a_absmax_out = xmax; // (K1 finds it while it fills its rows)
+    else if (xmax)
+        TT_RC_CHECK(tt_absmax_rows(c.table, c.E, c.E, m.idsp, (int)lo.MT, m.tok_off + c.B, xmax, c.st));
+    return enc_k1_launch(g, f32, c.st);
+}
+
+// one direction of layer l's recurrence (LSTM training: also zeroes the row that stands for c before the first step)
+static int enc_recurrence_dir(const EncCall &c, const EncLayout &lo, int l, int d, const EncW &k, GruParams &gp)
+{
+    char *ws = (char *)c.workspace;
+    const bool train = c.o.train_mode != 0;
+    const float *const *w = c.weights + ((size_t)l * lo.ndir + d) * 4;
+    GruDir &gd = gp.dir[d];
+    gd.gi = (const float *)(ws + lo.gi[d]);
+    if (c.projected && l == 0) { // every vocabulary row's projection is in the table: the recurrence gathers them by token id
+        gd.gi = (const float *)((const char *)c.projected + (size_t)d * enc_projected_dir_bytes(c.V, c.H, c.cell));
+        gp.gi_ids = (const int32_t *)(ws + lo.ids);
+        gp.gi_rows = (unsigned)c.V;
+    }
+    gd.wp = (const float *)k.wp;
+    gd.wmax = k.wmax;
+    gd.b_hh = w[3];
+    gd.out_seq = enc_layer_out(c, lo, l);
+    gd.gates = (train && c.cell != CELL_RNN) ? (float *)(ws + lo.gates[l][d]) : nullptr;
+    gd.cseq = nullptr;
+    if (train && c.cell == CELL_LSTM) { // c before the first step: the all-zero row at index MT
+        gd.cseq = (float *)(ws + lo.cseq[l][d]);
+        TT_RC_CHECK(tt_zero_async(gd.cseq + (size_t)lo.MT * c.H, sizeof(float) * c.H, c.st));
+    }
+    // only the last layer's final hidden state is used (model.py:65-71)
+    gd.h_final = (float *)(ws + lo.hfin) + (size_t)d * c.B * c.H;
+    gd.out_col0 = d * c.H;
+    gd.reverse = d;
+    return TT_OK;
+}
+
+// the recurrence of layer l, both directions; tt_enc_sync_t (include/tt.h): the host orders this call's recurrences behind
+// another call's -- wait in front of the first, record behind the last
+static int enc_recurrence(const EncCall &c, const EncLayout &lo, const EncRoute &r, int l, const GruParams &gp)
+{
+    const int B = c.B, H = c.H, ndir = lo.ndir;
+    hipStream_t st = c.st;
+    if (l == 0 && c.sync && c.sync->wait_before_recurrence)
+        TT_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)c.sync->wait_before_recurrence, 0));
+    if (r.split_fwd) {
+        // a row group's gate columns on four CUs (gru16x4.hip): same bits out, ~half the time per step
+        // (layer 0's hand-off slots were zeroed in front of the prep)
+        TT_RC_CHECK(gru16x4_launch(gp, ndir, (char *)c.workspace + lo.xch, c.status, st, /*xch_zeroed=*/l == 0));
+    } else if (r.use16) {
+        TT_RC_CHECK(gru16_launch(gp, ndir, st));
+    } else {
+        const size_t lds = sizeof(float) * 2 * ENC_RB * (H + 4);
+        TT_RC_CHECK(c.cell == CELL_LSTM ? launch_seq<CELL_LSTM>(gp, B, H, ndir, lds, st)
+                                        : (c.cell == CELL_RNN ? launch_seq<CELL_RNN>(gp, B, H, ndir, lds, st)
+                                                              : launch_seq<CELL_GRU>(gp, B, H, ndir, lds, st)));
+    }
+    TT_LAUNCH_CHECK();
+    if (l == c.L - 1 && c.sync && c.sync->record_after_recurrence)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)c.sync->record_after_recurrence, st));
+    return TT_OK;
+}
+
+// nn.GRU's dropout sits on the outputs of every layer but the last: xd[l + 1] = x[l + 1] * mask / (1 - p)
+static int enc_dropout(const EncCall &c, const EncLayout &lo, int l)
+{
+    const EncMeta m = enc_meta(c, lo);
+    const int B = c.B, ld = lo.ndir * c.H;
+    float *xd = (float *)(m.ws + lo.xd[l + 1]);
+    hipLaunchKernelGGL(dropout_apply_kernel, dim3(B, B >= 2048 ? 1 : (B >= 512 ? 4 : 16)), dim3(256), 0, c.st,
+                       (const float *)enc_layer_out(c, lo, l), xd, m.len, m.tok_off, c.T, ld, l, c.dropout_p, c.o.seed, c.o.seed_dev);
+    TT_RC_CHECK(tt_zero_async(xd + (size_t)lo.MT * ld, sizeof(float) * ld, c.st));
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+// K3: (bidirectional) cat + Linear(2H, H), F.normalize
+static int enc_head(const EncCall &c, const EncLayout &lo, const EncRoute &r)
+{
+    char *ws = (char *)c.workspace;
+    const int B = c.B, H = c.H;
+    const float *hfin = (const float *)(ws + lo.hfin);
+    float *hid = (float *)(ws + lo.hid);
+    if (r.head_gemm) {
+        // Linear(2H, H) on cat(h_fwd, h_bwd) (model.py:65-69) as two accumulating GEMMs over the two halves of the weight
+        // (the head kernel's per-row scalar loop read all of proj_w once per batch row: 0.6 ms at B = 8192), then the head
+        // kernel only normalises
+        for (int d = 0; d < 2; ++d) {
+            SgemmParams g;
+            g.A = hfin + (size_t)d * B * H;
+            g.B = c.proj_w + (size_t)d * H;
+            g.C = hid;
+            g.bias = d == 0 ? c.proj_b : nullptr;
+            g.M = B;
+            g.N = g.K = H;
+            g.lda = g.ldc = H;
+            g.ldb = 2 * H;
+            g.accumulate = d;
+            TT_RC_CHECK(tt_sgemm(g, false, false, 1, c.st));
+        }
+        hipLaunchKernelGGL(head_kernel, dim3(B), dim3(256), 0, c.st, (const float *)hid, B, H, 1, c.proj_w, c.proj_b, c.normalize,
+                           (float *)nullptr, c.out);
+    } else {
+        hipLaunchKernelGGL(head_kernel, dim3(B), dim3(256), 0, c.st, hfin, B, H, lo.ndir, c.proj_w, c.proj_b, c.normalize,
+                           c.o.train_mode ? hid : (float *)nullptr, c.out);
+    }
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+static int encoder_forward(const EncCall &c)
+{
+    EncLayout lo;
+    TT_RC_CHECK(enc_validate(c, lo));
+    const EncRoute r = enc_route(c, lo);
+    // the call in two halves (include/tt.h): BEGIN = everything in front of the first recurrence launch, FINISH = the rest
+    const bool begin = c.o.phase == ENC_PHASE_BEGIN, finish = c.o.phase == ENC_PHASE_FINISH;
+    if (!finish) // (FINISH: the BEGIN half made lengths, packed ids and maps in this workspace ...)
+        TT_RC_CHECK(enc_prep(c, lo, r));
+    for (int l = 0; l < c.L; ++l) {
+        const bool made = finish && l == 0; // (... and packed layer 0's weights and launched its projections)
+        GruParams gp;
+        TT_RC_CHECK(enc_layer_open(c, lo, l, gp));
+        for (int d = 0; d < lo.ndir; ++d) {
+            const EncW k = enc_layer_weights(c, lo, r, l, d);
+            if (!made && !r.use_prepared)
+                TT_RC_CHECK(enc_pack_layer(c, lo, l, d, k));
+            if (!made && !(c.projected && l == 0)) // (a projected table holds layer 0's projection of every vocabulary row)
+                TT_RC_CHECK(enc_input_projection(c, lo, r, l, d, k));
+            TT_RC_CHECK(enc_recurrence_dir(c, lo, l, d, k, gp));
+        }
+        if (lo.ndir == 1)
+            gp.dir[1] = gp.dir[0];
+        if (begin) { // everything in front of the first recurrence launch is in the queue
+            TT_LAUNCH_CHECK();
+            return TT_OK;
+        }
+        TT_RC_CHECK(enc_recurrence(c, lo, r, l, gp));
+        if (r.drop && l + 1 < c.L)
+            TT_RC_CHECK(enc_dropout(c, lo, l));
+    }
+    return enc_head(c, lo, r);
+}
+
+// Workgroups (= CUs: one each) the column-split recurrence of a call of this shape occupies, 0 when the call runs the
+// one-workgroup kernels anyway.  For hosts that keep several encoder calls in flight (include/tt.h).
+TT_EXPORT int tt_encoder_split_workgroups(int B, int H, int bidirectional, int rnn_type)
+{
+    const int ndir = bidirectional ? 2 : 1;
+    if (!enc_split_fwd(B, H, ndir, enc_use16(rnn_type, H, enc_force_f32(0)), /*one_wg=*/false))
+        return 0;
+    return ((B + ENC_RB - 1) / ENC_RB + 7) / 8 * 32 * (gru16x4_launches(B, H, ndir) == 2 ? 1 : ndir); // (per launch)
+}
+
+TT_EXPORT int tt_encoder_forward_f32(const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
+                                     int num_layers, int bidirectional, int rnn_type, const float *const *weights,
+                                     const float *proj_w, const float *proj_b, int normalize, int train,
+                                     float dropout_p, uint64_t dropout_seed, float *out, void *workspace,
+                                     size_t workspace_bytes, int32_t *status, const tt_enc_sync_t *sync, tt_stream_t stream)
+{
+    return encoder_forward({{B, T, E, H, num_layers, bidirectional, rnn_type}, "tt_encoder_forward_f32", V, ids, table, weights,
+                            proj_w, proj_b, /*prepared=*/nullptr, /*projected=*/nullptr,
+                            enc_opts(train, train & TT_ENC_TRAIN_MASK, dropout_seed), dropout_p, normalize, out, workspace,
+                            workspace_bytes, status, sync, (hipStream_t)stream, /*bwd=*/nullptr});
+}
+
+TT_EXPORT int tt_encoder_forward_prepared_f32(const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
+                                              int num_layers, int bidirectional, int rnn_type,
+                                              const float *const *weights, const void *prepared, const float *proj_w,
+                                              const float *proj_b, int normalize, int opts, float *out, void *workspace,
+                                              size_t workspace_bytes, int32_t *status, tt_stream_t stream)
+{
+    if (!prepared || ((uintptr_t)prepared & 255))
+        return tt_fail(TT_ERR_WORKSPACE, "tt_encoder_forward_prepared_f32: prepared buffer null or not 256-B aligned");
+    if (opts & ~(TT_ENC_ONE_WORKGROUP | TT_ENC_F32))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_forward_prepared_f32: opts=0x%x (0, TT_ENC_ONE_WORKGROUP, TT_ENC_F32)", opts);
+    return encoder_forward({{B, T, E, H, num_layers, bidirectional, rnn_type}, "tt_encoder_forward_prepared_f32", V, ids, table,
+                            weights, proj_w, proj_b, prepared, /*projected=*/nullptr, enc_opts(opts, /*train_mode=*/0, 0),
+                            /*dropout_p=*/0.0f, normalize, out, workspace, workspace_bytes, status, /*sync=*/nullptr,
+                            (hipStream_t)stream, /*bwd=*/nullptr});
 }
 
 TT_EXPORT int tt_encoder_forward_projected_f32(const int64_t *ids, int B, int T, const void *projected, int64_t V, int E, int H,
@@ -1052,7 +1112,9 @@ TT_EXPORT int tt_encoder_forward_projected_f32(const int64_t *ids, int B, int T,
         return tt_fail(TT_ERR_WORKSPACE, "tt_encoder_forward_projected_f32: prepared / projected buffer null or not 256-B aligned");
     if (opts & ~TT_ENC_ONE_WORKGROUP)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_forward_projected_f32: opts=0x%x (0 or TT_ENC_ONE_WORKGROUP)", opts);
-    return encoder_forward("tt_encoder_forward_projected_f32", ids, B, T, nullptr, V, E, H, num_layers, bidirectional, rnn_type,
-                           weights, prepared, proj_w, proj_b, normalize, /*train=*/0 | opts, 0.0f, 0, out, workspace,
-                           workspace_bytes, status, (hipStream_t)stream, nullptr, projected);
+    return encoder_forward({{B, T, E, H, num_layers, bidirectional, rnn_type}, "tt_encoder_forward_projected_f32", V, ids,
+                            /*table=*/nullptr, weights, proj_w, proj_b, prepared, projected, enc_opts(opts, /*train_mode=*/0, 0),
+                            /*dropout_p=*/0.0f, normalize, out, workspace, workspace_bytes, status, /*sync=*/nullptr,
+                            (hipStream_t)stream, /*bwd=*/nullptr});
 }
+

@@ -15,8 +15,6 @@
 
 #include <stdlib.h>
 
-int enc_check_shape(const char *who, int B, int T, int E, int H, int L, int64_t V);
-
 namespace {
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -362,59 +360,314 @@ __global__ __launch_bounds__(256) void bias_reduce_kernel(const float *__restric
 
 constexpr int COLSUM_SLICES = 256; // N <= 3H <= 1536 columns: 256 x N floats fit the split-K slab buffer
 
-int colsum(const float *X, int64_t ld, int N, int M, const int *m_dyn, float *slabs, float *out, hipStream_t st,
-           unsigned *absmax = nullptr)
+// out[n] = column sums of X[M][N] (row pitch N; rows clipped by *m_dyn when given); absmax (nullable): see colsum_kernel
+struct ColSum {
+    const float *X;
+    int N, M;
+    const int *m_dyn;
+    float *out;
+    unsigned *absmax;
+};
+int colsum(const ColSum &s, float *slabs, hipStream_t st)
 {
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256, COLSUM_SLICES), dim3(256), 0, st, X, ld, N, M, m_dyn, slabs,
-                       absmax);
+    hipLaunchKernelGGL(colsum_kernel, dim3((s.N + 255) / 256, COLSUM_SLICES), dim3(256), 0, st, s.X, (int64_t)s.N, s.N, s.M, s.m_dyn,
+                       slabs, s.absmax);
     TT_LAUNCH_CHECK();
-    return tt_slab_reduce(slabs, COLSUM_SLICES, N, out, 0, st);
+    return tt_slab_reduce(slabs, COLSUM_SLICES, s.N, s.out, 0, st);
 }
 
-// C[Mo][No] = A[:, a0:a0+Mo]^T * Bsrc (both summed over tokens), split-K + deterministic reduce.
+// what the reductions over all tokens of a call share: the split-K scratch, the bound MT of the token count and the device
+// word that holds the count itself
+struct SplitK {
+    float *slabs;
+    int MT;
+    const int *m_valid;
+    hipStream_t st;
+};
+
+// out[Mo][No] = A^T * B, both summed over the tokens, split-K + deterministic reduce.
 // a_absmax != nullptr: on the f16 pipes (fp16 hi/lo split of both operands, sgemm.h): A = gradients, scaled by the
-// power of two that *a_absmax (max |A|, from the colsum pass over the same matrix) implies; B scaled by 2^b_exp.
-// b_rows: an upper bound of Bsrc's row count (the 256-row-tile kernel addresses B with 32-bit offsets and checks it).
-int gemm_tn(const float *A, int64_t lda, int Mo, const float *Bsrc, int64_t ldb, const int32_t *b_map, int64_t b_rows, int No,
-            int Ktok, const int *k_dyn, float *slabs, float *out, hipStream_t st, const unsigned *a_absmax = nullptr,
-            int b_exp = 0, const unsigned *b_absmax = nullptr)
+// power of two that *a_absmax (max |A|, from the recurrence kernel or the colsum pass over the same matrix) implies; B scaled
+// by the power of two of *b_absmax when given, else by 2^b_exp.
+// b_rows: an upper bound of B's row count (the 256-row-tile kernel addresses B with 32-bit offsets and checks it).
+struct GemmTn {
+    const float *A; // [tokens][lda]
+    int64_t lda;
+    int Mo;
+    const float *B; // [b_rows][ldb], the row of token k: b_map ? b_map[k] : k
+    int64_t ldb;
+    const int32_t *b_map;
+    int64_t b_rows;
+    int No;
+    const unsigned *a_absmax;
+    int b_exp;
+    const unsigned *b_absmax;
+    float *out;
+};
+int gemm_tn(const GemmTn &t, const SplitK &k)
 {
     SgemmParams g;
-    g.A = A;
-    g.B = Bsrc;
-    g.C = slabs;
-    g.bias = nullptr;
-    g.a_map = nullptr;
-    g.b_map = b_map;
-    g.m_dyn = nullptr;
-    g.k_dyn = k_dyn;
-    g.M = Mo;
-    g.N = No;
-    g.K = Ktok;
-    g.lda = lda;
-    g.ldb = ldb;
-    g.ldc = No;
-    g.slab_stride = (int64_t)Mo * No;
-    g.accumulate = 0;
-    g.a_absmax = a_absmax;
-    g.b_absmax = a_absmax ? b_absmax : nullptr;
-    g.a_exp = 0;
-    g.b_exp = b_exp;
-    g.b_hi16 = g.b_lo16 = nullptr;
-    g.ldb16 = 0;
-    if (a_absmax && tt_wgrad16_supported(Mo, No, lda, ldb, b_rows) && !((uintptr_t)A & 15) && !((uintptr_t)Bsrc & 15)) {
+    g.A = t.A;
+    g.B = t.B;
+    g.C = k.slabs;
+    g.b_map = t.b_map;
+    g.k_dyn = k.m_valid;
+    g.M = t.Mo;
+    g.N = t.No;
+    g.K = k.MT;
+    g.lda = t.lda;
+    g.ldb = t.ldb;
+    g.ldc = t.No;
+    g.slab_stride = (int64_t)t.Mo * t.No;
+    g.a_absmax = t.a_absmax;
+    g.b_absmax = t.a_absmax ? t.b_absmax : nullptr;
+    g.b_exp = t.b_exp;
+    if (t.a_absmax && tt_wgrad16_supported(t.Mo, t.No, t.lda, t.ldb, t.b_rows) && !((uintptr_t)t.A & 15) && !((uintptr_t)t.B & 15)) {
         // 256-row output tiles with the whole K slab in one workgroup per CU (wgrad16.hip)
-        const int ns = tt_wgrad16_slabs(Mo, No, tt_device_cus(), ENC_SPLITK);
-        TT_RC_CHECK(tt_wgrad16(g, ns, st));
-        return tt_slab_reduce(slabs, ns, (int64_t)Mo * No, out, 0, st);
+        const int ns = tt_wgrad16_slabs(t.Mo, t.No, tt_device_cus(), ENC_SPLITK);
+        TT_RC_CHECK(tt_wgrad16(g, ns, k.st));
+        return tt_slab_reduce(k.slabs, ns, (int64_t)t.Mo * t.No, t.out, 0, k.st);
     }
-    int rc = a_absmax ? tt_sgemm16(g, true, true, ENC_SPLITK, st) : tt_sgemm(g, true, true, ENC_SPLITK, st);
-    if (rc != TT_OK)
-        return rc;
-    return tt_slab_reduce(slabs, ENC_SPLITK, (int64_t)Mo * No, out, 0, st);
+    TT_RC_CHECK(t.a_absmax ? tt_sgemm16(g, true, true, ENC_SPLITK, k.st) : tt_sgemm(g, true, true, ENC_SPLITK, k.st));
+    return tt_slab_reduce(k.slabs, ENC_SPLITK, (int64_t)t.Mo * t.No, t.out, 0, k.st);
 }
 
 } // namespace
+
+// ------------------------------------------------------------------ the steps of one backward call
+// (lengths, token offsets, row order, packed ids and the "previous token" maps are the training forward's: csrc/encoder.hip)
+static SplitK bwd_splitk(const EncCall &c, const EncLayout &lo)
+{
+    char *ws = (char *)c.workspace;
+    return {(float *)(ws + lo.slabs), (int)lo.MT, (const int32_t *)(ws + lo.tok_off) + c.B, c.st};
+}
+static unsigned *bwd_flag(const EncCall &c, const EncLayout &lo) { return (unsigned *)((char *)c.workspace + lo.flag); }
+// the scale words of layer l, direction d's weight-gradient products (max |dGi|; max |dGh| behind it): null on the fp32-MFMA path
+static unsigned *bwd_dg_max(const EncCall &c, const EncLayout &lo, int l, int d)
+{
+    return c.o.force_f32 ? nullptr : bwd_flag(c, lo) + enc_flag_dgi_max(l, d);
+}
+
+// head: F.normalize backward (the kernel also clears the ENC_FLAG_DG_WORDS maxima that the kernels behind it raise), then
+// (bidirectional) the Linear(2H, H) backward
+static int bwd_head(const EncCall &c, const EncLayout &lo)
+{
+    char *ws = (char *)c.workspace;
+    const int B = c.B, H = c.H;
+    hipStream_t st = c.st;
+    float *slabs = (float *)(ws + lo.slabs);
+    float *d_hfin = (float *)(ws + lo.d_hfin), *d_hid = (float *)(ws + lo.d_hid);
+    const float *hfin = (const float *)(ws + lo.hfin);
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(256), 0, st, (const float *)(ws + lo.hid), c.bwd->d_out, H, c.normalize,
+                       c.bidirectional ? d_hid : d_hfin, bwd_flag(c, lo) + ENC_FLAG_DG);
+    TT_LAUNCH_CHECK();
+    if (!c.bidirectional)
+        return TT_OK;
+    TT_RC_CHECK(colsum({d_hid, H, B, nullptr, c.bwd->g_proj_b, nullptr}, slabs, st));
+    for (int d = 0; d < 2; ++d) {
+        // g_proj_w[:, dH:(d+1)H] = d_hid^T * hfin[d]
+        SgemmParams g;
+        g.A = d_hid;
+        g.B = hfin + (size_t)d * B * H;
+        g.M = g.N = H;
+        g.K = B;
+        g.lda = g.ldb = H;
+        // The product sums over the B batch rows: with one k-range a 256 x 256 output is 4 workgroups walking B / 32
+        // tiles each (160 us at B = 1024).  Split it over 16 k-ranges into contiguous slabs, reduce in fixed order,
+        // then place the H x H block into its half of g_proj_w (row pitch 2H).
+        const int psplit = B >= 256 ? 16 : 1;
+        if (psplit > 1) {
+            float *ptmp = slabs + (size_t)psplit * H * H; // behind the slabs, inside the split-K scratch
+            g.C = slabs;
+            g.ldc = H;
+            g.slab_stride = (int64_t)H * H;
+            TT_RC_CHECK(tt_sgemm(g, true, true, psplit, st));
+            TT_RC_CHECK(tt_slab_reduce(slabs, psplit, (int64_t)H * H, ptmp, 0, st));
+            TT_HIP_CHECK(hipMemcpy2DAsync(c.bwd->g_proj_w + (size_t)d * H, sizeof(float) * 2 * H, ptmp, sizeof(float) * H,
+                                          sizeof(float) * H, H, hipMemcpyDeviceToDevice, st));
+        } else {
+            g.C = c.bwd->g_proj_w + (size_t)d * H;
+            g.ldc = 2 * H;
+            TT_RC_CHECK(tt_sgemm(g, true, true, 1, st));
+        }
+        // d_hfin[d] = d_hid * proj_w[:, dH:(d+1)H]
+        SgemmParams h;
+        h.A = d_hid;
+        h.B = c.proj_w + (size_t)d * H;
+        h.C = d_hfin + (size_t)d * B * H;
+        h.M = B;
+        h.N = h.K = H;
+        h.lda = h.ldc = H;
+        h.ldb = 2 * H;
+        TT_RC_CHECK(tt_sgemm(h, false, true, 1, st));
+    }
+    return TT_OK;
+}
+
+// the reverse-time recurrence of layer l, both directions, behind the transposed pack of W_hh; tt_enc_sync_t as in the
+// forward: wait in front of the call's first recurrence launch (the top layer's), record behind its last (layer 0's)
+static int bwd_recurrence(const EncCall &c, const EncLayout &lo, const EncRoute &r, int l)
+{
+    char *ws = (char *)c.workspace;
+    const int B = c.B, H = c.H, ndir = lo.ndir, NG = lo.ng, H3 = NG * H; // H3: gate rows (3H for the GRU)
+    hipStream_t st = c.st;
+    const bool top = l == c.L - 1;
+    const int n_rowgroups = (B + ENC_RB - 1) / ENC_RB;
+    float *slabs = (float *)(ws + lo.slabs);
+    GruBwdParams bp;
+    bp.len = (const int32_t *)(ws + lo.len);
+    bp.tok_off = (const int32_t *)(ws + lo.tok_off);
+    bp.perm = (const int32_t *)(ws + lo.perm);
+    bp.B = B;
+    bp.H = H;
+    bp.ld = ndir * H;
+    bp.drop_p = (r.drop && !top) ? c.dropout_p : 0.0f;
+    bp.drop_seed = c.o.seed;
+    bp.drop_seed_ptr = c.o.seed_dev;
+    bp.drop_layer = l;
+    bp.T = c.T;
+    for (int d = 0; d < ndir; ++d) {
+        const float *const *w = c.weights + ((size_t)l * ndir + d) * 4;
+        // max |W_hh| of this layer and direction: the training forward left it in its status block (encoder.hip)
+        const unsigned *wmax = bwd_flag(c, lo) + enc_flag_whh_max(l, d);
+        if (r.use16) {
+            TT_RC_CHECK(gru16_pack_t(w[1], H, wmax, ws + lo.wtp[d], st));
+        } else {
+            hipLaunchKernelGGL(pack_whh_t_kernel, dim3(96), dim3(256), 0, st, w[1], H, NG, (float *)(ws + lo.wtp[d]));
+        }
+        GruBwdDir &bd = bp.dir[d];
+        bd.wmax = wmax;
+        bd.gates = (const float *)(ws + lo.gates[l][d]);
+        bd.cseq = c.cell == CELL_LSTM ? (const float *)(ws + lo.cseq[l][d]) : nullptr;
+        bd.hseq = (const float *)(ws + lo.x[l + 1]);
+        bd.d_seq = top ? nullptr : (const float *)(ws + lo.dx[(l + 1) & 1]);
+        bd.d_hfin = top ? (float *)(ws + lo.d_hfin) + (size_t)d * B * H : nullptr;
+        bd.wtp = (const float *)(ws + lo.wtp[d]);
+        bd.dgi = (float *)(ws + lo.dgi[d]);
+        bd.dghn = (float *)(ws + lo.dghn[d]);
+        bd.col0 = d * H;
+        bd.reverse = d;
+        // f16-split recurrence: bias sums per row group and the operand maxima come out of the kernel itself
+        bd.bias_slab = r.fused_bias ? slabs + (size_t)d * n_rowgroups * 2 * H3 : nullptr;
+        bd.mx_dgi = bwd_flag(c, lo) + enc_flag_dgi_max(l, d);
+        bd.mx_dghn = bd.mx_dgi + 1;
+    }
+    if (ndir == 1)
+        bp.dir[1] = bp.dir[0];
+    if (top && c.sync && c.sync->wait_before_recurrence)
+        TT_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)c.sync->wait_before_recurrence, 0));
+    if (r.split_bwd) {
+        // a row group's reduction over the gate columns on four CUs (gru16x4.hip); a time-out ORs bit 2 into `status`
+        TT_RC_CHECK(gru16x4_bwd_launch(bp, ndir, ws + lo.xchb, c.status, st));
+    } else if (r.use16) {
+        TT_RC_CHECK(gru16_bwd_launch(bp, ndir, st));
+    } else {
+        const size_t lds = sizeof(float) * ENC_RB * (H3 + 4);
+        TT_RC_CHECK(c.cell == CELL_LSTM ? launch_bwd_seq<CELL_LSTM>(bp, B, H, ndir, lds, st)
+                                        : (c.cell == CELL_RNN ? launch_bwd_seq<CELL_RNN>(bp, B, H, ndir, lds, st)
+                                                              : launch_bwd_seq<CELL_GRU>(bp, B, H, ndir, lds, st)));
+    }
+    if (l == 0 && c.sync && c.sync->record_after_recurrence)
+        TT_HIP_CHECK(hipEventRecord((hipEvent_t)c.sync->record_after_recurrence, st));
+    return TT_OK;
+}
+
+// bias sums, fused form: the recurrence kernel left one partial sum per row group in the split-K scratch: reduce them
+// (row-group order: deterministic) for BOTH directions before the first weight-gradient product reuses that scratch
+static int bwd_bias_reduce(const EncCall &c, const EncLayout &lo, int l)
+{
+    const int ndir = lo.ndir, H3 = lo.ng * c.H, n_rowgroups = (c.B + ENC_RB - 1) / ENC_RB;
+    const float *slabs = (const float *)((char *)c.workspace + lo.slabs);
+    for (int d = 0; d < ndir; ++d) {
+        float *const *g = c.bwd->grads + ((size_t)l * ndir + d) * 4;
+        hipLaunchKernelGGL(bias_reduce_kernel, dim3((2 * H3 + 31) / 32), dim3(256), 0, c.st, slabs + (size_t)d * n_rowgroups * 2 * H3,
+                           n_rowgroups, H3, g[2], g[3]);
+    }
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+// bias sums of one direction as column-sum passes: b_ih <- colsum(dGi); b_hh <- colsum(dGh) (GRU: the n gate's hidden-side
+// pre-activation is scaled by r) or the same sums (LSTM / RNN: one pre-activation per gate).  The passes also find the maxima
+// that scale the f16-split products behind them.
+static int bwd_bias_colsums(const EncCall &c, const EncLayout &lo, int l, int d)
+{
+    char *ws = (char *)c.workspace;
+    const SplitK k = bwd_splitk(c, lo);
+    const int H3 = lo.ng * c.H;
+    float *const *g = c.bwd->grads + ((size_t)l * lo.ndir + d) * 4;
+    unsigned *mx = bwd_dg_max(c, lo, l, d);
+    TT_RC_CHECK(colsum({(const float *)(ws + lo.dgi[d]), H3, k.MT, k.m_valid, g[2], mx}, k.slabs, k.st));
+    if (c.cell == CELL_GRU)
+        return colsum({(const float *)(ws + lo.dghn[d]), H3, k.MT, k.m_valid, g[3], mx ? mx + 1 : nullptr}, k.slabs, k.st);
+    TT_HIP_CHECK(hipMemcpyAsync(g[3], g[2], sizeof(float) * H3, hipMemcpyDeviceToDevice, k.st));
+    return TT_OK;
+}
+
+// the two weight-gradient products of layer l, direction d
+static int bwd_weight_grads(const EncCall &c, const EncLayout &lo, const EncRoute &r, int l, int d)
+{
+    char *ws = (char *)c.workspace;
+    const SplitK k = bwd_splitk(c, lo);
+    const int H = c.H, ndir = lo.ndir, H3 = lo.ng * H, I = l == 0 ? c.E : ndir * H;
+    const bool gru = c.cell == CELL_GRU;
+    float *const *g = c.bwd->grads + ((size_t)l * ndir + d) * 4;
+    const float *dgi = (const float *)(ws + lo.dgi[d]), *dghn = (const float *)(ws + lo.dghn[d]);
+    const unsigned *mx_dgi = bwd_dg_max(c, lo, l, d), *mx_dghn = mx_dgi ? mx_dgi + 1 : nullptr;
+    // W_ih <- dGi^T X   (X = gathered table rows for layer 0, the layer below's output above)
+    // (f16-split products: embedding rows scaled by the power of two of the batch's largest |x|, which the training
+    //  forward left in the status block; hidden states (|h| < 1, times 1/(1-p) when dropped) 2^6)
+    if (l == 0)
+        TT_RC_CHECK(gemm_tn({dgi, H3, H3, c.table, c.E, (const int32_t *)(ws + lo.ids), c.V, c.E, mx_dgi, 0,
+                             bwd_flag(c, lo) + ENC_FLAG_XMAX, g[0]}, k));
+    else
+        TT_RC_CHECK(gemm_tn({dgi, H3, H3, (const float *)(ws + (r.drop ? lo.xd[l] : lo.x[l])), I, nullptr, k.MT, I, mx_dgi, 6, nullptr,
+                             g[0]}, k));
+    // W_hh <- dGh^T H_prev, H_prev rows through the previous-token map into this layer's own output
+    // (GRU: the hidden-side gradients dGh = [dr_pre, dz_pre, dn_pre r]; LSTM / RNN: the same matrix as dGi)
+    const float *hseq = (const float *)(ws + lo.x[l + 1]);
+    return gemm_tn({gru ? dghn : dgi, H3, H3, hseq + (size_t)d * H, ndir * H, (const int32_t *)(ws + lo.prevmap[d]), (int64_t)k.MT + 1, H,
+                    gru ? mx_dghn : mx_dgi, 10, nullptr, g[1]}, k);
+}
+
+// gradient w.r.t. layer l's input sequence, accumulated over the directions (below layer 0: w.r.t. the gathered vectors)
+static int bwd_input_grad(const EncCall &c, const EncLayout &lo, int l, int d)
+{
+    char *ws = (char *)c.workspace;
+    const SplitK k = bwd_splitk(c, lo);
+    const int H3 = lo.ng * c.H, I = l == 0 ? c.E : lo.ndir * c.H;
+    SgemmParams x;
+    x.A = (const float *)(ws + lo.dgi[d]);
+    x.B = c.weights[((size_t)l * lo.ndir + d) * 4];
+    x.C = l > 0 ? (float *)(ws + lo.dx[l & 1]) : (float *)(ws + lo.dx0);
+    x.m_dyn = k.m_valid;
+    x.M = k.MT;
+    x.N = I;
+    x.K = H3;
+    x.lda = H3;
+    x.ldb = x.ldc = I;
+    x.accumulate = d;
+    if (c.o.force_f32)
+        return tt_sgemm(x, false, true, 1, k.st);
+    // on the f16 pipes like every other product of the step: dGi scaled by its maximum (the recurrence kernel or the
+    // column-sum pass found it), W_ih by the power of two the forward pass derived
+    x.a_absmax = bwd_dg_max(c, lo, l, d);
+    x.b_absmax = bwd_flag(c, lo) + enc_flag_wih_max(l, d);
+    return tt_sgemm16(x, false, true, 1, k.st);
+}
+
+// nn.Embedding backward (model.py:23-27 without GloVe vectors): row id accumulates the input gradients of the positions
+// that hold it; padding_idx = 0 gets none.  Dense [V,E] gradient, as torch's.
+static int bwd_table_scatter(const EncCall &c, const EncLayout &lo)
+{
+    char *ws = (char *)c.workspace;
+    const SplitK k = bwd_splitk(c, lo);
+    TT_RC_CHECK(tt_zero_async(c.bwd->g_table, sizeof(float) * (size_t)c.V * c.E, k.st));
+    hipLaunchKernelGGL(table_scatter_kernel, dim3(2048), dim3(256), 0, k.st, (const float *)(ws + lo.dx0),
+                       (const int32_t *)(ws + lo.ids), k.m_valid, k.MT, c.E, c.bwd->g_table);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
 
 TT_EXPORT int tt_encoder_backward_f32(const int64_t *ids, int B, int T, const float *table, int64_t V, int E, int H,
                                       int num_layers, int bidirectional, int rnn_type, const float *const *weights,
@@ -424,264 +677,28 @@ TT_EXPORT int tt_encoder_backward_f32(const int64_t *ids, int B, int T, const fl
                                       size_t workspace_bytes, int opts, int32_t *status, const tt_enc_sync_t *sync,
                                       tt_stream_t stream)
 {
-    (void)ids;
-    (void)proj_b;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = enc_check_shape("tt_encoder_backward_f32", B, T, E, H, num_layers, V);
-    if (rc != TT_OK)
-        return rc;
-    if (opts & ~(TT_ENC_ONE_WORKGROUP | TT_ENC_SEED_ON_DEVICE | TT_ENC_F32))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_backward_f32: opts=0x%x (0, TT_ENC_ONE_WORKGROUP, TT_ENC_SEED_ON_DEVICE, TT_ENC_F32)", opts);
-    const bool one_wg = (opts & TT_ENC_ONE_WORKGROUP) != 0;
-    if (!table || !weights || !d_out || !grads || (bidirectional && (!proj_w || !g_proj_w || !g_proj_b)))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_encoder_backward_f32: null pointer");
-    if (rnn_type < CELL_GRU || rnn_type > CELL_RNN)
-        return tt_fail(TT_ERR_UNSUPPORTED, "tt_encoder_backward_f32: rnn_type=%d (0 GRU, 1 LSTM, 2 RNN)", rnn_type);
-    const bool drop = dropout_p > 0.0f && num_layers > 1;
-    const EncLayout lo = enc_layout(B, T, E, H, num_layers, bidirectional, g_table ? 2 : 1, drop, rnn_type);
-    if (!workspace || workspace_bytes < lo.total || ((uintptr_t)workspace & 255))
-        return tt_fail(TT_ERR_WORKSPACE, "tt_encoder_backward_f32: workspace %zu < %zu bytes: pass the buffer the "
-                                         "forward call (train=%d) filled", workspace_bytes, lo.total, g_table ? 2 : 1);
-    char *ws = (char *)workspace;
-    const int ndir = lo.ndir, NG = lo.ng, H3 = NG * H; // H3: gate rows (3H for the GRU)
-    const int32_t *len = (const int32_t *)(ws + lo.len), *tok_off = (const int32_t *)(ws + lo.tok_off);
-    const int32_t *perm = (const int32_t *)(ws + lo.perm), *idsp = (const int32_t *)(ws + lo.ids);
-    const int *m_valid = tok_off + B;
-    float *slabs = (float *)(ws + lo.slabs);
-    float *d_hfin = (float *)(ws + lo.d_hfin), *d_hid = (float *)(ws + lo.d_hid);
-    const float *hfin = (const float *)(ws + lo.hfin);
-    const int MT = (int)lo.MT;
-
-    // scale words of the f16-split weight-gradient products (max |dGi|, max |dGh_n| per layer and direction), written
-    // by the colsum passes: words 48..63 of the forward's status block
-
-    // ---- head ------------------------------------------------------------------
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(256), 0, st, (const float *)(ws + lo.hid), d_out, H, normalize,
-                       bidirectional ? d_hid : d_hfin, (unsigned *)(ws + lo.flag) + 48);
-    TT_LAUNCH_CHECK();
-    if (bidirectional) {
-        rc = colsum(d_hid, H, H, B, nullptr, slabs, g_proj_b, st);
-        if (rc != TT_OK)
-            return rc;
-        for (int d = 0; d < 2; ++d) {
-            // g_proj_w[:, dH:(d+1)H] = d_hid^T * hfin[d]
-            SgemmParams g;
-            g.A = d_hid;
-            g.B = hfin + (size_t)d * B * H;
-            g.C = g_proj_w + (size_t)d * H;
-            g.bias = nullptr;
-            g.a_map = g.b_map = nullptr;
-            g.m_dyn = g.k_dyn = nullptr;
-            g.M = H;
-            g.N = H;
-            g.K = B;
-            g.lda = H;
-            g.ldb = H;
-            g.ldc = 2 * H;
-            g.slab_stride = 0;
-            g.accumulate = 0;
-            // The product sums over the B batch rows: with one k-range a 256 x 256 output is 4 workgroups walking B / 32
-            // tiles each (160 us at B = 1024).  Split it over 16 k-ranges into contiguous slabs, reduce in fixed order,
-            // then place the H x H block into its half of g_proj_w (row pitch 2H).
-            const int psplit = B >= 256 ? 16 : 1;
-            if (psplit > 1) {
-                float *ptmp = slabs + (size_t)psplit * H * H; // behind the slabs, inside the split-K scratch
-                g.C = slabs;
-                g.ldc = H;
-                g.slab_stride = (int64_t)H * H;
-                rc = tt_sgemm(g, true, true, psplit, st);
-                if (rc != TT_OK)
-                    return rc;
-                rc = tt_slab_reduce(slabs, psplit, (int64_t)H * H, ptmp, 0, st);
-                if (rc != TT_OK)
-                    return rc;
-                TT_HIP_CHECK(hipMemcpy2DAsync(g_proj_w + (size_t)d * H, sizeof(float) * 2 * H, ptmp, sizeof(float) * H,
-                                              sizeof(float) * H, H, hipMemcpyDeviceToDevice, st));
-                g.slab_stride = 0;
-            } else {
-                rc = tt_sgemm(g, true, true, 1, st);
-                if (rc != TT_OK)
-                    return rc;
-            }
-            // d_hfin[d] = d_hid * proj_w[:, dH:(d+1)H]
-            g.A = d_hid;
-            g.B = proj_w + (size_t)d * H;
-            g.C = d_hfin + (size_t)d * B * H;
-            g.M = B;
-            g.N = H;
-            g.K = H;
-            g.lda = H;
-            g.ldb = 2 * H;
-            g.ldc = H;
-            rc = tt_sgemm(g, false, true, 1, st);
-            if (rc != TT_OK)
-                return rc;
+    const EncBwd b = {d_out, grads, g_proj_w, g_proj_b, g_table};
+    // the record of the forward call that filled the workspace (train = 2 when the table is trained): opts must repeat its
+    // TT_ENC_F32 and TT_ENC_SEED_ON_DEVICE, so that the route and the dropout masks are that call's
+    const EncCall c = {{B, T, E, H, num_layers, bidirectional, rnn_type}, "tt_encoder_backward_f32", V, ids, table, weights, proj_w,
+                       proj_b, /*prepared=*/nullptr, /*projected=*/nullptr, enc_opts(opts, g_table ? 2 : 1, dropout_seed),
+                       dropout_p, normalize, /*out=*/nullptr, workspace, workspace_bytes, status, sync, (hipStream_t)stream, &b};
+    EncLayout lo;
+    TT_RC_CHECK(enc_validate(c, lo));
+    const EncRoute r = enc_route(c, lo);
+    TT_RC_CHECK(bwd_head(c, lo));
+    for (int l = c.L - 1; l >= 0; --l) {
+        TT_RC_CHECK(bwd_recurrence(c, lo, r, l));
+        if (r.fused_bias)
+            TT_RC_CHECK(bwd_bias_reduce(c, lo, l));
+        for (int d = 0; d < lo.ndir; ++d) {
+            if (!r.fused_bias)
+                TT_RC_CHECK(bwd_bias_colsums(c, lo, l, d));
+            TT_RC_CHECK(bwd_weight_grads(c, lo, r, l, d));
+            if (l > 0 || g_table) // (below layer 0 only when the table is trained)
+                TT_RC_CHECK(bwd_input_grad(c, lo, l, d));
         }
     }
-
-    // (the "previous token" maps were made by the training forward's prep: csrc/encoder.hip)
-
-    const size_t lds = sizeof(float) * ENC_RB * (H3 + 4);
-    const bool force_f32 = (opts & TT_ENC_F32) != 0 || TT_AB_SWITCH(TT_GRU_F32, 0) != 0; // as the forward that filled the workspace
-    const bool use16 = rnn_type == CELL_GRU && gru16_supported(H) && !force_f32; // (gru16.hip)
-    const int n_rowgroups = (B + ENC_RB - 1) / ENC_RB;
-    // the recurrence kernel's bias partial sums live in the split-K scratch (free while it runs): they must fit
-    const size_t slab_floats = (size_t)ENC_SPLITK * (NG < 3 ? 3 : NG) * H * (size_t)((E > ndir * H ? E : ndir * H) > H ? (E > ndir * H ? E : ndir * H) : H);
-    const bool fused_bias = use16 && (size_t)n_rowgroups * 2 * H3 * ndir <= slab_floats;
-    for (int l = num_layers - 1; l >= 0; --l) {
-        const int I = l == 0 ? E : ndir * H;
-        const bool top = l == num_layers - 1;
-        const float *hseq = (const float *)(ws + lo.x[l + 1]);
-        const float *d_seq = top ? nullptr : (const float *)(ws + lo.dx[(l + 1) & 1]);
-        GruBwdParams bp;
-        bp.len = len;
-        bp.tok_off = tok_off;
-        bp.perm = perm;
-        bp.B = B;
-        bp.H = H;
-        bp.ld = ndir * H;
-        bp.drop_p = (drop && !top) ? dropout_p : 0.0f;
-        bp.drop_seed = (opts & TT_ENC_SEED_ON_DEVICE) ? 0ull : dropout_seed;
-        bp.drop_seed_ptr = (opts & TT_ENC_SEED_ON_DEVICE) ? (const uint64_t *)(uintptr_t)dropout_seed : nullptr;
-        bp.drop_layer = l;
-        bp.T = T;
-        for (int d = 0; d < ndir; ++d) {
-            const float *const *w = weights + ((size_t)l * ndir + d) * 4;
-            // max |W_hh| of this layer and direction: the training forward left it in its status block (encoder.hip)
-            const unsigned *wmax = (const unsigned *)(ws + lo.flag) + 16 + 2 * l + d;
-            if (use16) {
-                rc = gru16_pack_t(w[1], H, wmax, ws + lo.wtp[d], st);
-                if (rc != TT_OK)
-                    return rc;
-            } else {
-                hipLaunchKernelGGL(pack_whh_t_kernel, dim3(96), dim3(256), 0, st, w[1], H, NG, (float *)(ws + lo.wtp[d]));
-            }
-            bp.dir[d].wmax = wmax;
-            bp.dir[d].gates = (const float *)(ws + lo.gates[l][d]);
-            bp.dir[d].cseq = rnn_type == CELL_LSTM ? (const float *)(ws + lo.cseq[l][d]) : nullptr;
-            bp.dir[d].hseq = hseq;
-            bp.dir[d].d_seq = d_seq;
-            bp.dir[d].d_hfin = top ? d_hfin + (size_t)d * B * H : nullptr;
-            bp.dir[d].wtp = (const float *)(ws + lo.wtp[d]);
-            bp.dir[d].dgi = (float *)(ws + lo.dgi[d]);
-            bp.dir[d].dghn = (float *)(ws + lo.dghn[d]);
-            bp.dir[d].col0 = d * H;
-            bp.dir[d].reverse = d;
-            // f16-split recurrence: bias sums per row group and the operand maxima come out of the kernel itself
-            bp.dir[d].bias_slab = fused_bias ? slabs + (size_t)d * n_rowgroups * 2 * H3 : nullptr;
-            bp.dir[d].mx_dgi = (unsigned *)(ws + lo.flag) + 48 + 2 * (2 * l + d);
-            bp.dir[d].mx_dghn = bp.dir[d].mx_dgi + 1;
-        }
-        if (ndir == 1)
-            bp.dir[1] = bp.dir[0];
-        if (l == num_layers - 1 && sync && sync->wait_before_recurrence) // (the first recurrence launch of the call)
-            TT_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)sync->wait_before_recurrence, 0));
-        if (use16 && fused_bias && lo.xchb && !one_wg && gru16x4_bwd_usable(B, H, ndir)) {
-            // a row group's reduction over the gate columns on four CUs (gru16x4.hip); a time-out ORs bit 2 into `status`
-            rc = gru16x4_bwd_launch(bp, ndir, ws + lo.xchb, status, st);
-        } else if (use16) {
-            rc = gru16_bwd_launch(bp, ndir, st);
-        } else {
-            rc = rnn_type == CELL_LSTM ? launch_bwd_seq<CELL_LSTM>(bp, B, H, ndir, lds, st)
-                                       : (rnn_type == CELL_RNN ? launch_bwd_seq<CELL_RNN>(bp, B, H, ndir, lds, st)
-                                                               : launch_bwd_seq<CELL_GRU>(bp, B, H, ndir, lds, st));
-        }
-        if (rc != TT_OK)
-            return rc;
-        if (l == 0 && sync && sync->record_after_recurrence) // (the last recurrence launch of the call)
-            TT_HIP_CHECK(hipEventRecord((hipEvent_t)sync->record_after_recurrence, st));
-        if (fused_bias) {
-            // the recurrence kernel left one partial sum per row group in the split-K scratch: reduce them (row-group order:
-            // deterministic) for BOTH directions before the first weight-gradient product reuses that scratch
-            for (int d = 0; d < ndir; ++d) {
-                float *const *g = grads + ((size_t)l * ndir + d) * 4;
-                hipLaunchKernelGGL(bias_reduce_kernel, dim3((2 * H3 + 31) / 32), dim3(256), 0, st,
-                                   (const float *)(slabs + (size_t)d * n_rowgroups * 2 * H3), n_rowgroups, H3, g[2], g[3]);
-            }
-            TT_LAUNCH_CHECK();
-        }
-
-        for (int d = 0; d < ndir; ++d) {
-            const float *const *w = weights + ((size_t)l * ndir + d) * 4;
-            float *const *g = grads + ((size_t)l * ndir + d) * 4;
-            const float *dgi = (const float *)(ws + lo.dgi[d]);
-            const float *dghn = (const float *)(ws + lo.dghn[d]);
-            // biases: b_ih <- colsum(dGi); b_hh <- colsum(dGh) (GRU: the n gate's hidden-side pre-activation is scaled by r)
-            // or the same sums (LSTM / RNN: one pre-activation per gate)
-            unsigned *mx_dgi = force_f32 ? nullptr : (unsigned *)(ws + lo.flag) + 48 + 2 * (2 * l + d);
-            unsigned *mx_dghn = force_f32 ? nullptr : mx_dgi + 1;
-            if (!fused_bias) {
-                rc = colsum(dgi, H3, H3, MT, m_valid, slabs, g[2], st, mx_dgi);
-                if (rc != TT_OK)
-                    return rc;
-            }
-            if (fused_bias) {
-            } else if (rnn_type == CELL_GRU) {
-                rc = colsum(dghn, H3, H3, MT, m_valid, slabs, g[3], st, mx_dghn);
-                if (rc != TT_OK)
-                    return rc;
-            } else {
-                TT_HIP_CHECK(hipMemcpyAsync(g[3], g[2], sizeof(float) * H3, hipMemcpyDeviceToDevice, st));
-            }
-            // W_ih <- dGi^T X   (X = gathered table rows for layer 0, the layer below's output above)
-            // (f16-split products: embedding rows scaled by the power of two of the batch's largest |x|, which the training
-            //  forward left in the status block; hidden states (|h| < 1, times 1/(1-p) when dropped) 2^6)
-            if (l == 0)
-                rc = gemm_tn(dgi, H3, H3, table, E, idsp, V, E, MT, m_valid, slabs, g[0], st, mx_dgi, 0,
-                             (const unsigned *)(ws + lo.flag) + ENC_FLAG_XMAX);
-            else
-                rc = gemm_tn(dgi, H3, H3, (const float *)(ws + (drop ? lo.xd[l] : lo.x[l])), I, nullptr, MT, I, MT, m_valid,
-                             slabs, g[0], st, mx_dgi, 6);
-            if (rc != TT_OK)
-                return rc;
-            // W_hh <- dGh^T H_prev, H_prev rows through the previous-token map into this layer's own output
-            const int32_t *pm = (const int32_t *)(ws + lo.prevmap[d]);
-            // (GRU: the hidden-side gradients dGh = [dr_pre, dz_pre, dn_pre r]; LSTM / RNN: the same matrix as dGi)
-            rc = gemm_tn(rnn_type == CELL_GRU ? dghn : dgi, H3, H3, hseq + (size_t)d * H, ndir * H, pm, (int64_t)MT + 1, H, MT, m_valid, slabs, g[1],
-                         st, rnn_type == CELL_GRU ? mx_dghn : mx_dgi, 10);
-            if (rc != TT_OK)
-                return rc;
-            // gradient w.r.t. this layer's input sequence (below layer 0 only when the table is trained)
-            if (l > 0 || g_table) {
-                SgemmParams x;
-                x.A = dgi;
-                x.B = w[0];
-                x.C = l > 0 ? (float *)(ws + lo.dx[l & 1]) : (float *)(ws + lo.dx0);
-                x.bias = nullptr;
-                x.a_map = x.b_map = nullptr;
-                x.m_dyn = m_valid;
-                x.k_dyn = nullptr;
-                x.M = MT;
-                x.N = I;
-                x.K = H3;
-                x.lda = H3;
-                x.ldb = I;
-                x.ldc = I;
-                x.slab_stride = 0;
-                x.accumulate = d;
-                if (!force_f32) {
-                    // on the f16 pipes like every other product of the step: dGi scaled by its maximum (the column-sum
-                    // pass found it), W_ih by the power of two the forward pass derived (status word 40 + 2 l + d)
-                    x.a_absmax = mx_dgi;
-                    x.b_absmax = (const unsigned *)(ws + lo.flag) + 40 + 2 * l + d;
-                    x.a_exp = x.b_exp = 0;
-                    x.b_hi16 = x.b_lo16 = nullptr;
-                    x.ldb16 = 0;
-                    rc = tt_sgemm16(x, false, true, 1, st);
-                } else
-                    rc = tt_sgemm(x, false, true, 1, st);
-                if (rc != TT_OK)
-                    return rc;
-            }
-        }
-    }
-    if (g_table) {
-        // nn.Embedding backward (model.py:23-27 without GloVe vectors): row id accumulates the input gradients of the
-        // positions that hold it; padding_idx = 0 gets none.  Dense [V,E] gradient, as torch's.
-        TT_RC_CHECK(tt_zero_async(g_table, sizeof(float) * (size_t)V * E, st));
-        hipLaunchKernelGGL(table_scatter_kernel, dim3(2048), dim3(256), 0, st, (const float *)(ws + lo.dx0), idsp, m_valid, MT,
-                           E, g_table);
-        TT_LAUNCH_CHECK();
-    }
-    return TT_OK;
+    return g_table ? bwd_table_scatter(c, lo) : TT_OK;
 }
+

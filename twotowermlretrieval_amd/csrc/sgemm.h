@@ -5,6 +5,7 @@
 #pragma once
 #include "tt_common.h"
 
+// Every member has a default (null, 0): a call site names only what its product needs.
 struct SgemmParams {
     // C[M,N] (+ bias[N]) (+= when accumulate) = opA(A) * opB(B)
     //   A_T == false: A is [M,K] row-major (lda), row m read from source row a_map ? a_map[m] : m
@@ -12,27 +13,27 @@ struct SgemmParams {
     //                 reduction index k is a_map ? a_map[k] : k
     //   B_T == false: B is [N,K] row-major (ldb)  ("weights" layout: C = A * B^T)
     //   B_T == true : B is [K,N] row-major (ldb), source row of k is b_map ? b_map[k] : k
-    const float *A;
-    const float *B;
-    float *C;
-    const float *bias;
-    const int32_t *a_map;
-    const int32_t *b_map;
-    const int *m_dyn; // optional device scalar: effective M = min(M, *m_dyn)
-    const int *k_dyn; // optional device scalar: effective K = min(K, *k_dyn)
-    int M, N, K;
-    int64_t lda, ldb, ldc;
-    int64_t slab_stride; // split-K: slice z writes C + z*slab_stride (0 when gridDim.z == 1)
-    int accumulate;      // C += result (gridDim.z must be 1)
+    const float *A = nullptr;
+    const float *B = nullptr;
+    float *C = nullptr;
+    const float *bias = nullptr;
+    const int32_t *a_map = nullptr;
+    const int32_t *b_map = nullptr;
+    const int *m_dyn = nullptr; // optional device scalar: effective M = min(M, *m_dyn)
+    const int *k_dyn = nullptr; // optional device scalar: effective K = min(K, *k_dyn)
+    int M = 0, N = 0, K = 0;
+    int64_t lda = 0, ldb = 0, ldc = 0;
+    int64_t slab_stride = 0; // split-K: slice z writes C + z*slab_stride (0 when gridDim.z == 1)
+    int accumulate = 0;  // C += result (gridDim.z must be 1)
     // tt_sgemm16 only: power-of-two operand scales applied before the fp16 hi/lo split (exact; undone on the fp32
     // accumulator).  exponent = *_absmax ? tt_pow2_exponent(*_absmax) (largest element -> [2^13, 2^14)) : *_exp
-    const unsigned *a_absmax, *b_absmax; // device: bit pattern of max |element| (nullable)
-    int a_exp, b_exp;
+    const unsigned *a_absmax = nullptr, *b_absmax = nullptr; // device: bit pattern of max |element| (nullable)
+    int a_exp = 0, b_exp = 0;
     // tt_sgemm16 with B_T == false only: B given ALREADY split (tt_pack_rows16: [N][ldb16] fp16 hi and lo images, k padded
     // with zeros to a multiple of 32, scaled by *b_absmax's power of two).  A weight matrix is then converted once per
     // call instead of once per workgroup that touches a tile of it.  Null: B is split on the fly like A.
-    const void *b_hi16, *b_lo16;
-    int64_t ldb16;
+    const void *b_hi16 = nullptr, *b_lo16 = nullptr;
+    int64_t ldb16 = 0;
     // tt_gemm_rows16 only.  a_row_scale != 0: every A row (an embedding vector gathered through a_map) is scaled by ITS OWN
     // power of two (row maximum -> [2^13, 2^14)) before the split, undone on that row's accumulators: fp32-grade for tables of
     // any magnitude, and -- unlike a batch-wide scale -- a row's result does not depend on which other rows share the launch.
