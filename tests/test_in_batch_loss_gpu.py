@@ -8,6 +8,19 @@ tiles and chunks both ways, ragged); H = 20 (< 32, not a multiple of 4), 32, 96,
 The walked side is cut into slices of whole chunks, one workgroup each, whose partial results are added in ascending order:
 one slice up to B = 64, two (of the documents) at B = 65, six uneven ones of the documents and three of the queries at B = 1025.
 
+The slice classes (ib_slices: up to IB_MAX_SLICES = 8 partial results per side, combined in fixed order by ib_lse_kernel and
+ib_project_kernel).  Q = slices x chunks each of the documents a query tile walks, D = the same of the queries a document tile
+walks:
+     B     H    Q                      D
+   129    20    3 x 1                  2 x 1     the first multi-slice document side
+   257    96    5 x 1                  3 x 1
+   449    32    8 x 1                  4 x 1     the smallest B with all 8 slices, ragged last chunk
+   512   256    8 x 1                  4 x 1     the product's train batch
+   513    32    5 x 2 (last: 1 chunk)  5 x 1     uneven last slice
+   641    20    6 x 2 (last: 1 chunk)  6 x 1     the most document-side slices any B gives
+  1024    32    8 x 2                  4 x 2     all 8 slices, two chunks each
+  4096    32    2 x 32                 1 x 32    32 chunks folded by one workgroup through the online softmax
+
 Bound per result (loss, dq, dp, dn): 4 x the error of the helper itself evaluated in float32 at that very shape, plus
 4 * 2^-24 * max|want| -- room for another summation order over 2B * H terms, none for a half-precision product."""
 import numpy as np
@@ -61,7 +74,11 @@ def check(q, p, n, temperature):
 # every B once, every H at least once; scale: rows of non-unit norm (the cosine divides it out, the gradients do not)
 @pytest.mark.parametrize("B,H,temperature,scale", [(1, 20, 1.0, 1.0), (3, 32, 0.05, 1.0), (17, 96, 1.0, 30.0), (31, 256, 0.05, 1.0),
                                                    (32, 512, 1.0, 1.0e-3), (33, 20, 0.05, 30.0), (65, 96, 0.05, 1.0e-3),
-                                                   (1025, 256, 0.05, 1.0)])
+                                                   (1025, 256, 0.05, 1.0),
+                                                   # the slice classes of the module docstring
+                                                   (129, 20, 0.05, 1.0), (257, 96, 0.05, 30.0), (449, 32, 0.05, 1.0e-3),
+                                                   (512, 256, 0.05, 1.0), (513, 32, 0.05, 30.0), (641, 20, 0.05, 1.0e-3),
+                                                   (1024, 32, 0.05, 1.0), (4096, 32, 0.05, 30.0)])
 def test_loss_and_gradients_vs_float64(B, H, temperature, scale):
     q, p, n = ((synth.unit_rows(11 * B + s, B, H) * np.float32(scale)).astype(np.float32) for s in range(3))
     check(q, p, n, temperature)
@@ -72,6 +89,18 @@ def test_logits_of_100_do_not_overflow():
     running maximum inside the softmax keeps the sums finite."""
     B, H = 33, 96
     q, p, n = (synth.unit_rows(70 + s, B, H).copy() for s in range(3))
+    p[::3] = q[::3]
+    got, _ = check(q, p, n, 0.01)
+    assert np.isfinite(got[0])
+
+
+@pytest.mark.parametrize("B", [449, 4096])
+def test_logits_of_100_across_slices_and_chunks(B):
+    """The same construction at B = 449 (8 slices of one chunk: the maximum of 100 sits in another slice than most of a row's
+    logits, and ib_lse_kernel rescales across slices) and B = 4096 (one workgroup folds 32 chunks: the running maximum jumps
+    to 100 in whichever chunk holds p_i)."""
+    H = 32
+    q, p, n = (synth.unit_rows(170 + B + s, B, H).copy() for s in range(3))
     p[::3] = q[::3]
     got, _ = check(q, p, n, 0.01)
     assert np.isfinite(got[0])

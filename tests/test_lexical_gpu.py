@@ -22,8 +22,8 @@ import poison
 
 pytestmark = pytest.mark.gpu
 
-F = 257
-TIE_COLS = np.array([3, 17, 40, 41, 77, 101, 130, 131, 200, 222, 240, 255], dtype=np.int32)
+F = ref.MAIN_F
+TIE_COLS = ref.TIE_COLS
 
 
 def _dev(a):
@@ -44,25 +44,6 @@ class Corpus:
         return ref.ref_scores32(self.indptr, self.cols, self.vals, ref.dense_query(q_cols, q_vals, self.F))
 
 
-def _replace_rows(indptr, cols, vals, new_rows):
-    """CSR with the rows in new_rows {row: (cols, vals)} replaced."""
-    N = indptr.size - 1
-    lens = np.diff(indptr)
-    for r, (c, _) in new_rows.items():
-        lens[r] = len(c)
-    out_ip = np.zeros(N + 1, dtype=np.int64)
-    np.cumsum(lens, out=out_ip[1:])
-    out_c = np.empty(int(out_ip[-1]), dtype=np.int32)
-    out_v = np.empty(int(out_ip[-1]), dtype=np.float32)
-    for n in range(N):
-        if n in new_rows:
-            out_c[out_ip[n]:out_ip[n + 1]], out_v[out_ip[n]:out_ip[n + 1]] = new_rows[n]
-        else:
-            out_c[out_ip[n]:out_ip[n + 1]] = cols[indptr[n]:indptr[n + 1]]
-            out_v[out_ip[n]:out_ip[n + 1]] = vals[indptr[n]:indptr[n + 1]]
-    return out_ip, out_c, out_v
-
-
 @pytest.fixture(scope="module")
 def env():
     import twotowermlretrieval_amd as tt
@@ -70,36 +51,18 @@ def env():
     from twotowermlretrieval_amd.lexical import TT_LEXICAL_FMAX
     lib = _lib.lib()
     C = lib.tt_lexical_chunk_docs()
-    rng = np.random.default_rng(11)
 
     class E:
         pass
     e = E()
     e.tt, e.lib, e.C, e.FMAX = tt, lib, C, TT_LEXICAL_FMAX
 
-    # main
-    N = 3 * C + 17
-    e.long_rows = (2 * C, 2 * C - 1, C // 2 + 7)
-    e.tie_rows = (1, C - 1, C, 2 * C + 3, N - 1)
-    ip, cols, vals = ref.random_corpus(1, N, F, long_rows=e.long_rows, cols_below=F - 1)
-    for r in e.long_rows:
-        vals[ip[r]:ip[r + 1]] *= np.float32(1.0 / 64)
-    e.tie_vals = rng.uniform(0.5, 1.0, size=TIE_COLS.size).astype(np.float32)
-    ip, cols, vals = _replace_rows(ip, cols, vals, {r: (TIE_COLS, e.tie_vals) for r in e.tie_rows})
-    e.main = Corpus(ip, cols, vals, F)
-    assert int(np.diff(ip).max()) == 3000 and int(np.diff(ip).min()) == 0 and int(cols.max()) == F - 2
-
-    # the queries of the main corpus and their reference scores, computed once
-    qa = rng.choice(F - 1, size=20, replace=False)
-    e.queries = {
-        "random": (qa, rng.uniform(0.05, 1.0, size=20).astype(np.float32)),
-        "every": (rng.permutation(F), rng.uniform(0.05, 1.0, size=F).astype(np.float32)),
-        "one": (np.array([17]), np.array([0.75], dtype=np.float32)),
-        "empty": (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)),
-        "nothing": (np.array([F - 1]), np.array([1.0], dtype=np.float32)),      # the column no document uses
-        "tie": (TIE_COLS, e.tie_vals),
-    }
-    e.S = {name: e.main.scores32(*q) for name, q in e.queries.items()}
+    # main (built in lexical_ref: test_lexical_big_gpu.py places the same corpus at high offsets of the nnz stream)
+    m = ref.MainCorpus(C)
+    rng = m.rng
+    e.long_rows, e.tie_rows, e.tie_vals = m.long_rows, m.tie_rows, m.tie_vals
+    e.main = Corpus(m.indptr, m.cols, m.vals, F)
+    e.queries, e.S = m.queries, m.S
     e.batch = ("random", "every", "one")
 
     # wide

@@ -9,6 +9,7 @@ For each query, over B in {1, 64, 65, 1024}, the k and d its entry allows and bo
     it holds (int32 words: 4-byte aligned), or is (size_t)-1 where the header says the shape has none."""
 import ctypes
 import itertools
+import math
 
 import pytest
 
@@ -101,3 +102,54 @@ def test_screened_stats_offset(libtt):  # noqa: F811
                       libtt.tt_score_topk_screened_masked_workspace_bytes(B, N, 256, k, 0),
                       libtt.tt_score_topk_screened_masked_workspace_bytes(B, N, 256, k, 1)):
             _inside(off, 2 * B, total, ("stats", B, N, k))
+
+
+# ---- lexical search and the in-batch loss --------------------------------------------------------------------------------------
+LEX_BS = (1, 64, 65, 1024, 65535)
+LEX_CHUNK = 4096
+
+
+def test_lexical_workspace_grows_with_the_corpus(libtt):  # noqa: F811
+    """tt_lexical_workspace_bytes(B, N, k): one float and one int64 per entry of every chunk's partial list at least (12 B k
+    ceil(N / 4096) bytes), positive, non-decreasing in N, not wrapped; 0 for the shapes the call refuses.
+    "Not wrapped" is below 2^48 wherever the lower bound itself is (at B = 65535, k = 1024, N = 2^31 - 65 the lists alone are
+    12 x 65535 x 1024 x 524288 = 4.2e14 bytes > 2^48 = 2.8e14: no size can satisfy both), and everywhere at most what the plan
+    can need: above 64 chunks the lists are padded to groups of per = ceil(sqrt(chunks)) -- fewer than chunks + per lists --
+    and the first merge writes one list per group, at most per + 1: 12 B k (chunks + 2 per + 1) bytes plus alignment."""
+    size = libtt.tt_lexical_workspace_bytes
+    assert libtt.tt_lexical_chunk_docs() == LEX_CHUNK
+    for B, k in itertools.product(LEX_BS, K_LARGE):
+        got = [size(B, N, k) for N in NS]
+        print("tt_lexical_workspace_bytes", "B", B, "k", k, got)
+        assert all(a <= b for a, b in zip(got, got[1:])), (B, k, got)
+        for N, g in zip(NS, got):
+            chunks = -(-N // LEX_CHUNK)
+            per = math.isqrt(chunks - 1) + 1
+            least = 12 * B * k * chunks
+            assert 0 < least <= g <= 12 * B * k * (chunks + 2 * per + 1) + 4096, (B, N, k, g)
+            assert g < 2 ** 48 or least >= 2 ** 48, (B, N, k, g)
+        assert size(B, 2 ** 31 - 64, k) == 0 and size(B, 2 ** 31 - 65, k) == got[3]
+    for B in LEX_BS:
+        assert size(B, NS[1], 0) == 0 and size(B, NS[1], 1025) == 0 and size(B, NS[1], 1024) > 0
+    for k in K_LARGE:
+        assert size(0, NS[1], k) == 0
+
+
+def test_in_batch_loss_workspace_grows_with_the_batch(libtt):  # noqa: F811
+    """tt_in_batch_loss_workspace_bytes(B, H): at least the two images, 4 (Bq + Dp) Hp bytes with Hp = H up to a multiple of 32
+    and Bq / Dp = B / 2 B up to multiples of 128 (ib_plan), positive, non-decreasing in B and in H; 0 beyond B = 2^24 or
+    H = 512."""
+    size = libtt.tt_in_batch_loss_workspace_bytes
+    BS_IB, HS = (1, 512, 1025, 65536, 2 ** 24), (1, 20, 512)
+    got = {(B, H): size(B, H) for B in BS_IB for H in HS}
+    print("tt_in_batch_loss_workspace_bytes", got)
+    for (B, H), g in got.items():
+        Hp, Bq, Dp = -(-H // 32) * 32, -(-B // 128) * 128, -(-2 * B // 128) * 128
+        assert 4 * (Bq + Dp) * Hp <= g < 2 ** 48, (B, H, g)
+    for H in HS:
+        col = [got[B, H] for B in BS_IB]
+        assert all(a <= b for a, b in zip(col, col[1:])), (H, col)
+    for B in BS_IB:
+        row = [got[B, H] for H in HS]
+        assert all(a <= b for a, b in zip(row, row[1:])), (B, row)
+    assert size(2 ** 24 + 1, 20) == 0 and size(512, 513) == 0 and size(0, 20) == 0 and size(512, 0) == 0

@@ -995,3 +995,149 @@ def test_screened_search_on_one_workspace_through_the_c_abi(tt, L, oracle):
         ev, ei = tt.score_topk(q, Dt, k)
         assert torch.equal(i, ei) and torch.equal(v, ev), B
         assert not flags[:(B + 31) // 32].any(), (B, flags)            # this call's tiles; the words behind them are the last call's
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# lexical search and the in-batch loss
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def lexical_corpora(L):
+    """The `main` corpus of test_lexical_gpu.py (3 C + 17 rows: the direct merge) and a corpus of 65 C + 3 short rows (more than 64
+    chunks: the two-step merge), with two queries each and their reference scores; N = 5 and N = 0 are prefixes of main."""
+    def make():
+        import lexical_ref as ref
+        C_ = L.tt_lexical_chunk_docs()
+        m = ref.MainCorpus(C_)
+        rng = np.random.default_rng(41)
+        N = 65 * C_ + 3
+        lens = rng.integers(0, 9, size=N)
+        allc = np.cumsum(rng.integers(1, 31, size=(N, 8)), axis=1) - 1
+        ip = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(lens, out=ip[1:])
+        cols = allc[np.arange(8)[None, :] < lens[:, None]].astype(np.int32)
+        vals = (rng.integers(1, 9, size=cols.size) / 8.0).astype(np.float32)         # few distinct values: large tie groups
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        big_q = [(rng.permutation(241)[:40], (rng.integers(1, 5, size=40) / 4.0).astype(np.float32)) for _ in range(3)]
+        out = {"C": C_, "F": ref.MAIN_F, "ref": ref,
+               "main": ((dev(m.indptr), dev(m.cols), dev(m.vals)), [m.queries[n] for n in ("random", "every", "tie")],
+                        [m.S[n] for n in ("random", "every", "tie")]),
+               "big": ((dev(ip), dev(cols), dev(vals)), big_q,
+                       [ref.ref_scores32(ip, cols, vals, ref.dense_query(*q, ref.MAIN_F)) for q in big_q])}
+        return out
+    return corpus("lexical", make)
+
+
+def lexical_abi(L, t, N, F, q, k, ws):
+    """tt_lexical_score_topk_f32 over the first N rows of the corpus t on the caller's workspace -> (vals, idx) as numpy."""
+    from twotowermlretrieval_amd import _lib
+    qi, qc, qv = q
+    B = qi.numel() - 1
+    ov = torch.full((B, k), float("nan"), dtype=torch.float32, device="cuda")
+    oi = torch.full((B, k), -7, dtype=torch.int64, device="cuda")
+    _lib.check(L.tt_lexical_score_topk_f32(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), N, F, qi.data_ptr(), qc.data_ptr(),
+                                           qv.data_ptr(), B, None, None, None, 0, 0.0, 1.0, k, 0, ov.data_ptr(), oi.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return host(ov), host(oi)
+
+
+def test_lexical_search_on_one_workspace_through_the_c_abi(L):
+    """ONE workspace sized for the largest call, filled once with -1 words and never cleared, through (B, N, k) = (3, 65 C + 3,
+    1024), (1, 5, 100), (2, 3 C + 17, 10), (3, 65 C + 3, 64), (1, 0, 7): two-step and direct merge in turn, each plan's lists
+    laid over the previous call's lists of another k.  Every answer is ref_topk's, and bit for bit the answer of the same call
+    on a fresh zeroed workspace."""
+    lx = lexical_corpora(L)
+    ref, C_, F = lx["ref"], lx["C"], lx["F"]
+    calls = [("big", 3, 65 * C_ + 3, 1024), ("main", 1, 5, 100), ("main", 2, 3 * C_ + 17, 10), ("big", 3, 65 * C_ + 3, 64),
+             ("main", 1, 0, 7)]
+    need = max(L.tt_lexical_workspace_bytes(B, N, k) for _, B, N, k in calls)
+    assert L.tt_lexical_workspace_bytes(3, 65 * C_ + 3, 1024) > 3 * 1024 * 12 * 65 + 3 * 1024 * 12      # (it holds the first merge's lists)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    ws.view(torch.int32).fill_(-1)                                     # never cleared from here on
+    for which, B, N, k in calls:
+        t, queries_, S = lx[which]
+        q = tuple(torch.from_numpy(a).cuda() for a in ref.queries_csr(queries_[:B]))
+        v, i = lexical_abi(L, t, N, F, q, k, ws)
+        fresh = torch.zeros(max(L.tt_lexical_workspace_bytes(B, N, k), 16), dtype=torch.uint8, device="cuda")
+        fv, fi = lexical_abi(L, t, N, F, q, k, fresh)
+        assert same_bits(v, fv) and np.array_equal(i, fi), (which, B, N, k)
+        for b in range(B):
+            wv, wi = ref.ref_topk(S[b][:N], k)
+            assert np.array_equal(i[b], wi) and same_bits(v[b], wv), (which, B, N, k, b)
+
+
+def test_lexical_forms_under_every_pattern(tt, L):
+    """lexical_score_topk (its workspace and outputs are torch.empty) at k = 10 and 100 on the direct merge, k = 10 and 1024 on
+    the two-step merge, under a keep-bitmask; lexical_score_all's output; a LexicalIndex search after remove_ids."""
+    lx = lexical_corpora(L)
+    ref, C_, F = lx["ref"], lx["C"], lx["F"]
+    t, queries_, S = lx["main"]
+    tb, big_q, big_S = lx["big"]
+    N, Nb = 3 * C_ + 17, 65 * C_ + 3
+    q = tuple(torch.from_numpy(a).cuda() for a in ref.queries_csr(queries_))
+    qb = tuple(torch.from_numpy(a).cuda() for a in ref.queries_csr(big_q[:2]))
+    keep_host = np.arange(N) % 3 != 0
+    keep = tt.pack_keep_mask(torch.from_numpy(keep_host).cuda())
+    gone = [int(ref.ref_topk(big_S[0], 1)[1][0]), 0, Nb - 1]
+    kept_b = np.ones(Nb, dtype=bool)
+    kept_b[gone] = False
+    ix = tt.LexicalIndex((*tb, F), idx_offset=9)
+    ix.remove_ids([g + 9 for g in gone])
+
+    def run():
+        out = {"all": tt.lexical_score_all(t, F, q)}
+        for k in (10, 100):
+            out[f"v{k}"], out[f"i{k}"] = tt.lexical_score_topk(t, F, q, k, keep=keep)
+        for k in (10, 1024):
+            out[f"bv{k}"], out[f"bi{k}"] = tt.lexical_score_topk(tb, F, qb, k)
+        out["xv"], out["xi"] = ix.search(qb, 100)
+        return out
+
+    def check(got, word):
+        w = pattern_id(word)
+        for b in range(3):
+            assert same_bits(got["all"][b], S[b]), w
+            for k in (10, 100):
+                wv, wi = ref.ref_topk(S[b], k, keep=keep_host)
+                assert np.array_equal(got[f"i{k}"][b], wi) and same_bits(got[f"v{k}"][b], wv), (w, k, b)
+        for b in range(2):
+            for k in (10, 1024):
+                wv, wi = ref.ref_topk(big_S[b], k)
+                assert np.array_equal(got[f"bi{k}"][b], wi) and same_bits(got[f"bv{k}"][b], wv), (w, k, b)
+            wv, wi = ref.ref_topk(big_S[b], 100, keep=kept_b, idx_offset=9)
+            assert np.array_equal(got["xi"][b], wi) and same_bits(got["xv"][b], wv), (w, b)
+
+    every_pattern(run, check)
+
+
+def test_in_batch_loss_on_one_workspace_through_the_c_abi(L):
+    """ONE workspace sized for B = 1025, H = 512, filled once with 0xFF bytes and never cleared, through (B, H) = (1025, 256),
+    (65, 96), (449, 32), (3, 32), (513, 20), (1025, 256): images, partial maxima and sums and the per-slice gradient partials of
+    each plan (3 to 8 slices, other paddings) lie over the previous call's.  Every result is finite and bit for bit that of the
+    same call on a zeroed workspace; the first and the last call agree bit for bit."""
+    from twotowermlretrieval_amd import _lib
+    shapes = [(1025, 256), (65, 96), (449, 32), (3, 32), (513, 20), (1025, 256)]
+    need = L.tt_in_batch_loss_workspace_bytes(1025, 512)
+    assert need >= max(L.tt_in_batch_loss_workspace_bytes(B, H) for B, H in shapes)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    ws.fill_(0xFF)                                                     # never cleared from here on
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(t, B, H, work):
+        loss = torch.full((1,), float("nan"), device="cuda")
+        g = [torch.full_like(x, float("nan")) for x in t]
+        _lib.check(L.tt_in_batch_loss_f32(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), B, H, 0.05, loss.data_ptr(),
+                                          g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), work.data_ptr(), work.numel(), st))
+        torch.cuda.synchronize()
+        return [host(loss)] + [host(x) for x in g]
+
+    results = []
+    for B, H in shapes:
+        t = [torch.from_numpy(synth.unit_rows(300 + B + s, B, H)).cuda() for s in range(3)]
+        got = call(t, B, H, ws)
+        want = call(t, B, H, torch.zeros(L.tt_in_batch_loss_workspace_bytes(B, H), dtype=torch.uint8, device="cuda"))
+        for name, x, y in zip(("loss", "dq", "dp", "dn"), got, want):
+            assert np.isfinite(x).all(), (B, H, name)
+            assert same_bits(x, y), (B, H, name)
+        results.append(got)
+    assert all(same_bits(x, y) for x, y in zip(results[0], results[-1]))
