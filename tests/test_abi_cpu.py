@@ -47,6 +47,76 @@ def test_binding_table_matches_header():
     assert sorted(_lib.SIGNATURES) == _declared()
 
 
+_PTR = ("pointer", ctypes.sizeof(ctypes.c_void_p), None)
+# what a by-value C type of the header is to the calling convention: (kind, bytes, signed -- None where there is no sign)
+_C_VALUE_TYPES = {"int": ("int", 4, True), "int32_t": ("int", 4, True), "uint32_t": ("int", 4, False),
+                  "int64_t": ("int", 8, True), "uint64_t": ("int", 8, False), "size_t": ("int", ctypes.sizeof(ctypes.c_size_t), False),
+                  "float": ("float", 4, None), "char": ("char", 1, None), "tt_stream_t": _PTR}
+
+
+def _c_shape(decl, named):
+    """(kind, bytes, signed) of one C parameter declaration (`named`: it ends in the parameter's name) or return type."""
+    if "*" in decl:
+        return _PTR
+    words = [w for w in decl.split() if w != "const"]
+    if named:
+        assert len(words) == 2, f"cannot read the parameter {decl!r}"
+        words = words[:1]
+    assert len(words) == 1 and words[0] in _C_VALUE_TYPES, f"a type this test does not know: {decl!r}"
+    return _C_VALUE_TYPES[words[0]]
+
+
+def _ctypes_shape(t):
+    """The same triple of a ctypes type of the binding table."""
+    code = t._type_
+    if code in "Pz":                                             # c_void_p, c_char_p
+        return _PTR
+    if code == "f":
+        return ("float", ctypes.sizeof(t), None)
+    if code == "c":
+        return ("char", ctypes.sizeof(t), None)
+    assert code in "bhilqBHILQ", f"a ctypes type this test does not know: {t}"
+    return ("int", ctypes.sizeof(t), code.islower())
+
+
+def _prototypes(header="tt.h"):
+    """name -> (return shape or None for void, [argument shapes]) of every function the header declares."""
+    text = (ROOT / "include" / header).read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(tt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        ret, args = " ".join(ret.split()), [" ".join(a.split()) for a in args.split(",")]
+        assert name not in out, f"{name} is declared twice"
+        out[name] = (None if ret == "void" else _c_shape(ret, False), [] if args == ["void"] else [_c_shape(a, True) for a in args])
+    return out
+
+
+def test_binding_table_matches_header_prototypes():
+    """Every argument of every prototype: the table's ctypes type has the kind (pointer, integer, float, char), the size
+    and the signedness of the header's C type, and so has the return type.  An `int` in the table where the header says
+    int64_t truncates a row count or an offset only past 2^31, where no small test would see it."""
+    from twotowermlretrieval_amd import _lib
+    protos = _prototypes()
+    assert sorted(protos) == _declared() == sorted(_lib.SIGNATURES)
+    for name, (c_res, c_args) in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        assert (None if res is None else _ctypes_shape(res)) == c_res, f"{name}: return type"
+        assert len(args) == len(c_args), f"{name}: {len(args)} arguments bound, {len(c_args)} declared"
+        for n, (a, c) in enumerate(zip(args, c_args)):
+            assert _ctypes_shape(a) == c, f"{name}: argument {n} is bound as {a.__name__}, the header says {c}"
+
+
+def test_prototype_reader_tells_the_types_apart():
+    """The reader itself: the shapes it gives to the declarations a wrong table entry would be confused with."""
+    assert _c_shape("int64_t N", True) != _c_shape("int N", True) and _c_shape("size_t n", True) != _c_shape("int64_t n", True)
+    assert _c_shape("uint64_t seed", True) == _c_shape("size_t n", True) == _ctypes_shape(ctypes.c_uint64)
+    assert _c_shape("const float *const *w", True) == _c_shape("tt_stream_t stream", True) == _ctypes_shape(ctypes.c_void_p)
+    assert _ctypes_shape(ctypes.c_int) == _c_shape("int", False) != _ctypes_shape(ctypes.c_int64) == _c_shape("int64_t", False)
+    assert _c_shape("float margin", True) == _ctypes_shape(ctypes.c_float) and _c_shape("char sep", True) == _ctypes_shape(ctypes.c_char)
+    assert _c_shape("const char *", False) == _ctypes_shape(ctypes.c_char_p)
+
+
 def test_version_and_error_strings(libtt):
     assert b"gfx950" in libtt.tt_version()
     assert isinstance(libtt.tt_last_error(), bytes)

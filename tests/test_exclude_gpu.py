@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import synth
+from index_model import filter_ref, idiom, own_top  # (stated once, with the rest of the index model)
 from test_masked_gpu import host_f32, queries, rows_on_device
 from test_search_aux_gpu import par_rows
 
@@ -47,17 +48,6 @@ def same(got, want):
 
 
 # ---- the filter alone --------------------------------------------------------------------------------------------------------
-
-def filter_ref(v, i, ex, k):
-    """The first k entries of each row whose index is >= 0 and not listed, in input order, then (-inf, -1)."""
-    B = v.shape[0]
-    ov = np.full((B, k), -np.inf, dtype=np.float32)
-    oi = np.full((B, k), -1, dtype=np.int64)
-    for b in range(B):
-        sel = np.flatnonzero((i[b] >= 0) & ~np.isin(i[b], ex[b]))[:k]
-        ov[b, :len(sel)], oi[b, :len(sel)] = v[b, sel], i[b, sel]
-    return ov, oi
-
 
 def sorted_rows(seed, B, M, n_pad=0):
     """[B,M] rows as a search writes them: scores descending with runs of equal scores (index ascending inside a run),
@@ -133,35 +123,6 @@ def test_filter_writes_into_out_and_depends_only_on_its_inputs(tt):
 
 
 # ---- the reference idiom -----------------------------------------------------------------------------------------------------
-
-def idiom(S, ex, k, idx_offset=0, mask=None):
-    """scores[b, exclude[b]] = -inf (and the masked columns) ; sort by (score desc, index asc) ; first k.  S [B,N] is left
-    unchanged (it is shared among the cases)."""
-    B, N = S.shape
-    ov = np.full((B, k), -np.inf, dtype=np.float32)
-    oi = np.full((B, k), -1, dtype=np.int64)
-    for b in range(B):
-        s = S[b].copy()
-        loc = ex[b] - idx_offset
-        s[loc[(loc >= 0) & (loc < N) & (ex[b] >= 0)]] = -np.inf
-        if mask is not None:
-            s[~mask] = -np.inf
-        order = np.lexsort((np.arange(N), -s))[:k]
-        order = order[~np.isneginf(s[order])]
-        ov[b, :len(order)], oi[b, :len(order)] = s[order], order + idx_offset
-    return ov, oi
-
-
-def own_top(S, E, rs, n_random, idx_offset=0, mask=None):
-    """exclude [B,E]: each query's own true top-(E - n_random) (of the kept documents), then n_random random ids."""
-    B, N = S.shape
-    ex = np.empty((B, E), dtype=np.int64)
-    for b in range(B):
-        s = S[b] if mask is None else np.where(mask, S[b], -np.inf)
-        top = np.lexsort((np.arange(N), -s))[:E - n_random]
-        ex[b] = np.concatenate([top, rs.randint(0, N, size=E - len(top))]) + idx_offset
-    return ex
-
 
 @pytest.fixture(scope="module")
 def small(tt, oracle):

@@ -154,10 +154,15 @@ def test_shard_lists_seeded_for_the_final_k_give_the_same_top_k():
             sv, si = sx.search(Q, 10)
             ev, ei = tt.score_topk(Q, D, 10, 5)
             assert torch.equal(sv, ev) and torch.equal(si, ei)
-            pend = [sx.submit(Q, 10) for _ in range(3)]
-            for p_ in pend:
+            pend = [sx.submit(Q, 10) for _ in range(2)]
+            v_, i_ = pend[0].result()                               # (valid until the second further submit of its shape)
+            assert torch.equal(v_, ev) and torch.equal(i_, ei)
+            pend.append(sx.submit(Q, 10))
+            for p_ in pend[1:]:
                 v_, i_ = p_.result()
                 assert torch.equal(v_, ev) and torch.equal(i_, ei)
+            with pytest.raises(RuntimeError, match="two more submits of the same shape"):
+                pend[0].result()                                    # its slot is the third step's now
             # the shard list itself: its first 10 entries are the shard's exact top-10, the rest are real documents or padding
             ix = tt.BruteForceIndex(D, idx_offset=5, screen=True)
             lv, li = ix.search(Q, 50, _seed_union=_index._local_seed, _k_seed=10)

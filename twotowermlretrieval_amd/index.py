@@ -892,9 +892,9 @@ def _local_seed(lst: torch.Tensor) -> torch.Tensor:
 
 
 class _Slot:
-    """One set of exchange buffers of a ShardedIndex (three per shape: two that submit() alternates between -- a step's
-    all-gather + merge overlaps the next step's search -- and one of search()'s own): send block [vals f32 [B,kp] |
-    idx int64 [B,kp]], receive buffer of `world` such blocks, outputs."""
+    """One set of exchange buffers of a ShardedIndex (three per shape: two that submit() alternates between, per shape
+    (_SlotTurns) -- a step's all-gather + merge overlaps the next step's search -- and one of search()'s own): send block
+    [vals f32 [B,kp] | idx int64 [B,kp]], receive buffer of `world` such blocks, outputs."""
 
     def __init__(self, B: int, kp: int, k: int, world: int, dev):
         self.nv = (B * kp * 4 + 7) // 8 * 8           # idx block 8-byte aligned
@@ -913,22 +913,56 @@ class _Slot:
         return (self.send, self.recv, self.out_v, self.out_i)
 
 
+class _SlotTurns:
+    """Whose turn it is in submit()'s two slots, kept PER SHAPE, on the host alone (no tensors: the CPU tests drive it).
+    The n-th submit of a shape (n = 0, 1, ...: the step's generation) takes slot n % 2 of that shape's set, so a step's
+    buffers are written again by the second further submit OF THE SAME SHAPE and by nothing else, whatever other shapes
+    are submitted in between.  (One parity over all shapes -- what this replaces -- sent A, B, A to A's slot 0 twice: the
+    first A's rows were overwritten after ONE further submit of its shape.)  The counts outlive a retired slot set (an int
+    per shape ever seen), so the rule does not depend on which sets are resident."""
+
+    def __init__(self):
+        self._submitted = {}  # shape -> submits so far
+
+    def take(self, shape) -> Tuple[int, int]:
+        """(slot 0 / 1, generation) of the next submit of `shape`; the step that held the slot (generation - 2) expires."""
+        n = self._submitted.get(shape, 0)
+        self._submitted[shape] = n + 1
+        return n % 2, n
+
+    def holds(self, shape, generation: int) -> bool:
+        """Whether the step of that generation still owns its slot: fewer than two submits of the shape have followed it."""
+        return self._submitted.get(shape, 0) - generation <= 2
+
+
 class PendingSearch:
     """Result of ShardedIndex.submit(): result() makes the CURRENT stream wait for the exchange + merge (no host
-    synchronisation) and returns (values, indices) views valid until two more submits of the same shape on the same
-    index (search() has a slot of its own and never overwrites them)."""
+    synchronisation) and returns (values, indices) views valid until two more submits of the same shape -- the same
+    (B, max(k + E, shard_k), k + E) -- on the same index.  Submits of other shapes in between do not count: the two slots
+    alternate per shape (_SlotTurns), and search() has a slot of its own and never overwrites them.  Once the second further
+    submit of the shape has been made the slot holds (or is being written with) that step's rows: result() then raises
+    RuntimeError instead of returning them.  (A step submitted with exclude= that has been collected once keeps its filtered
+    rows, which are its own tensors.)"""
 
-    def __init__(self, slot: _Slot, index: "ShardedIndex", exclude: Optional[torch.Tensor] = None, k: int = 0):
+    def __init__(self, slot: _Slot, index: "ShardedIndex", exclude: Optional[torch.Tensor] = None, k: int = 0,
+                 shape=None, generation: int = 0):
         self._slot, self._index = slot, index
         self._exclude, self._k, self._filtered = exclude, k, None  # submit(exclude=): the filter runs in result(), once
+        self._shape, self._generation = shape, generation          # the slot's generation when this step took it
 
     def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(A COLLECTIVE when this step's exchange has not been issued yet -- it normally goes out inside the NEXT submit():
         every rank must then call result() at the same point of its sequence of submit / search / result calls.)
         A step submitted with exclude= is filtered here, on the current stream, from the merged k + E rows into tensors of
-        its own: the list must stay as it was until then."""
+        its own: the list must stay as it was until then.
+        RuntimeError: two more submits of this step's shape have been made since, and its slot is another step's now."""
         if self._filtered is not None:
             return self._filtered
+        if not self._index._turns.holds(self._shape, self._generation):
+            B, kp, k = self._shape[:3]
+            raise RuntimeError(f"PendingSearch.result(): this step's slot has been taken -- a result stays valid until two more "
+                               f"submits of the same shape on the same index, and (B, k', k) = ({B}, {kp}, {k}) has been "
+                               "submitted twice since; collect a step before the second further submit of its shape")
         self._index._flush(self._slot)
         torch.cuda.current_stream(self._slot.out_v.device).wait_event(self._slot.merged)
         if self._exclude is not None:
@@ -998,7 +1032,7 @@ class ShardedIndex:
         self._dev = self._index.device
         self._coll = Collective(group, self._dev, comm=comm)
         self._slots = {}
-        self._n_submitted = 0
+        self._turns = _SlotTurns()  # which of a shape's two submit() slots is next, and the generation it then holds
         self._xs: Optional[torch.cuda.Stream] = None
         self._deferred = None  # (slot, B, kp, k) of the last submit(): its list exchange goes out behind the next seed gather
         # a resident d = 256 shard that screens its smallest screened batch
@@ -1241,7 +1275,10 @@ class ShardedIndex:
         merge go out on this index's second stream inside the NEXT submit() (behind that step's seed gather), or when
         .result() / search() asks for them.  Call .result() when the answer is needed.  keep: as in search() (all ranks or
         none).  exclude: as in search(); the step runs for k + E and .result() filters the merged rows.  candidates: as in
-        search(): the step's local search is the candidate search."""
+        search(): the step's local search is the candidate search.
+        Slots: the step writes one of two slots of its shape (B, max(k + E, shard_k), k + E), taken in turn per shape, so
+        its result is valid until two more submits of THAT shape, however many other shapes are submitted in between; after
+        that its .result() raises RuntimeError.  The collectives issued, and their order, do not depend on the slot."""
         if q.dim() != 2:
             raise ValueError("submit wants a [B,d] batch")
         k_out = k
@@ -1251,8 +1288,9 @@ class ShardedIndex:
             candidates = _check_ids(candidates, q.shape[0], self._dev, "candidates")
         kp = max(k, self.shard_k)
         B = q.shape[0]
-        sl = self._slot(B, kp, k, self._n_submitted % 2)
-        self._n_submitted += 1
+        shape = (B, kp, k, self._coll.world)
+        which, generation = self._turns.take(shape)
+        sl = self._slot(B, kp, k, which)
         dev = sl.send.device
         if self._xs is None:
             self._xs = torch.cuda.Stream(device=dev)
@@ -1263,7 +1301,7 @@ class ShardedIndex:
         self._flush()                        # (a local search without a seed exchange has not issued the previous step's yet)
         sl.searched.record(cur)
         self._deferred = (sl, B, kp, k)
-        return PendingSearch(sl, self, exclude, k_out)
+        return PendingSearch(sl, self, exclude, k_out, shape, generation)
 
 
 class StreamedIndex:
