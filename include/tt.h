@@ -711,6 +711,29 @@ int tt_in_batch_loss_f32(const float *q, const float *p, const float *n, int B, 
                          float *dq, float *dp, float *dn, void *workspace, size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The same loss over a POOL of documents: B queries against M >= B documents in one contiguous array, the positive of query i
+ * in row pos_offset + i (the passages gathered from all ranks of a data-parallel job: M = world * 2B, pos_offset = rank * 2B;
+ * or several explicit negatives per query on one GPU).  q [B,H], docs [M,H] f32; eps = 1e-8:
+ *   qh_i = q_i / max(||q_i||, eps)        Dh_j = docs_j / max(||docs_j||, eps)
+ *   s_ij = (qh_i . Dh_j) / temperature    i < B, j < M
+ *   loss = mean_{i<B} (logsumexp_{j<M} s_ij - s_{i, pos_offset+i})
+ * loss [1]; dq [B,H], ddocs [M,H] = d loss / d{q,docs}, through the norms, all M rows (both or none, nullable; without them
+ * only the loss is written, the same bits as with them).  A row shorter than eps is divided by eps, as the formula states.
+ * 1 <= B <= 2^24, B <= M <= 2^25, 0 <= pos_offset <= M - B, 1 <= H <= 512; temperature finite and > 0.
+ * tt_in_batch_loss_f32 is the case M = 2B, pos_offset = 0 of the same kernels: on docs = [p; n] this call returns its bits.
+ * Exact f32 products (f32-input MFMA), running maximum inside the softmax ([B,M] is never stored).  Deterministic: no atomics,
+ * every reduction in one fixed order that depends on (B, M, H) alone, whatever the workspace held on entry.
+ * workspace: tt_contrastive_loss_workspace_bytes(B, M, H) bytes (0 for a shape the call refuses), 16-byte aligned,
+ * caller-owned; the plan's exact need, equal to tt_in_batch_loss_workspace_bytes(B, H) at M = 2B and NOT monotone in M (the
+ * number of slices is not): size it for the shape it is used at.  Asynchronous on `stream`; capture-clean.  Refusals are
+ * TT_ERR_BAD_SHAPE.
+ */
+size_t tt_contrastive_loss_workspace_bytes(int B, int M, int H);
+int tt_contrastive_loss_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H, int pos_offset,
+                            float temperature, float *loss /*[1]*/, float *dq /*[B,H]*/, float *ddocs /*[M,H]*/,
+                            void *workspace, size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

@@ -6,14 +6,14 @@ from .index import (BruteForceIndex, GraphedSearch, PendingSearch, ShardedIndex,
                     shard_bounds, topk_cut_below, topk_exclude, topk_merge)
 from .lexical import LexicalIndex, lexical_score_all, lexical_score_topk
 from .hybrid import HybridSearcher, SimpleHybridRetriever
-from .model import RNNEncoder, TwoTowerModel, in_batch_softmax_loss, triplet_loss_cosine
+from .model import RNNEncoder, TwoTowerModel, contrastive_softmax_loss, in_batch_softmax_loss, triplet_loss_cosine
 from .query_inferencer import QueryInferencer
 from .tokenizer import PretrainedTokenizer
 from .trainer import DataParallelTrainer, FusedClipAdam, GraphedTrainStep, train_step
 
 __all__ = ["BruteForceIndex", "GraphedSearch", "ShardedIndex", "PendingSearch", "StreamedIndex", "score_topk", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "shard_bounds", "pack_keep_mask", "score_count", "topk_cut_below",
            "LexicalIndex", "lexical_score_topk", "lexical_score_all", "lexical",
-           "RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "QueryInferencer", "PretrainedTokenizer", "HybridSearcher", "SimpleHybridRetriever",
+           "RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "QueryInferencer", "PretrainedTokenizer", "HybridSearcher", "SimpleHybridRetriever",
            "FusedClipAdam", "DataParallelTrainer", "train_step", "GraphedTrainStep", "model", "trainer", "tokenizer", "query_inferencer",
            "evaluators", "hybrid", "collective"]
 __version__ = "0.1.0"

@@ -1,7 +1,10 @@
-// K9 in-batch softmax contrastive loss (forward + gradient) on the f32-input MFMA (gfx950).
+// K9 softmax contrastive loss of B queries over a pool of M >= B documents (forward + gradient) on the f32-input MFMA (gfx950).
 //
-//   qh_i = q_i / max(||q_i||, eps)     Dh_j = D_j / max(||D_j||, eps)     D = [p; n] (2B rows), eps = 1e-8
-//   s_ij = (qh_i . Dh_j) / temperature                       loss = mean_i (logsumexp_j s_ij - s_ii)
+//   qh_i = q_i / max(||q_i||, eps)     Dh_j = D_j / max(||D_j||, eps)     eps = 1e-8
+//   s_ij = (qh_i . Dh_j) / temperature      loss = mean_i (logsumexp_j s_ij - s_{i, pos_offset + i})       i < B, j < M
+//
+// Two entries on the same kernels: tt_contrastive_loss_f32 (one contiguous pool `docs` [M,H]: the passages gathered from all
+// ranks, or several negatives per query) and tt_in_batch_loss_f32 (D = [p; n] as two pointers: M = 2B, pos_offset = 0).
 //
 // Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
 //   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
@@ -13,9 +16,9 @@
 //                        (B temperature) through LDS, partial dqh = G Dh; and, in the same launch with the roles swapped, a
 //                        workgroup per (32 documents, slice of the queries): partial dDh = G^T qh
 //   6 ib_project_kernel  one wave per row: the slices' partials in ascending order, back-projection through the norm
-//                        -> dq, dp, dn
-// [B,2B] never reaches memory.  Every sum has one fixed order (the MFMA's k order, chunks of 128 rows ascending, slices
-// ascending, xor trees), and the slicing depends on (B, H) alone, so the result is bit-reproducible and independent of what
+//                        -> dq, ddocs (dp, dn)
+// [B,M] never reaches memory.  Every sum has one fixed order (the MFMA's k order, chunks of 128 rows ascending, slices
+// ascending, xor trees), and the slicing depends on (B, M, H) alone, so the result is bit-reproducible and independent of what
 // the workspace held.
 #include <float.h>
 
@@ -46,17 +49,17 @@ IBSlices ib_slices(int walked_rows, int owner_rows)
 }
 
 struct IBPlan {
-    int Hp, Bq, Dp;   // image width (H up to a multiple of 32), image heights (B, 2B up to multiples of IB_CHUNK)
+    int Hp, Bq, Dp;   // image width (H up to a multiple of 32), image heights (B, M up to multiples of IB_CHUNK)
     IBSlices sq, sd;  // slices of the documents a query tile walks / of the queries a document tile walks
     size_t qh, dh, den, flag, lse, rows, pm, pl, pos, part_q, part_d, total;
 };
 
-IBPlan ib_plan(int B, int H)
+IBPlan ib_plan(int B, int M, int H)
 {
     IBPlan P;
     P.Hp = (H + 31) / 32 * 32;
     P.Bq = (B + IB_CHUNK - 1) / IB_CHUNK * IB_CHUNK;
-    P.Dp = (2 * B + IB_CHUNK - 1) / IB_CHUNK * IB_CHUNK;
+    P.Dp = (M + IB_CHUNK - 1) / IB_CHUNK * IB_CHUNK;
     TTWorkspace w;
     P.qh = w.take(sizeof(float) * (size_t)P.Bq * P.Hp);
     P.dh = w.take(sizeof(float) * (size_t)P.Dp * P.Hp);
@@ -64,11 +67,11 @@ IBPlan ib_plan(int B, int H)
     P.flag = w.take(sizeof(float) * (size_t)(P.Bq + P.Dp));  // 1 where norm >= eps (the clamp passes gradient), else 0
     P.lse = w.take(sizeof(float) * (size_t)P.Bq);
     P.rows = w.take(sizeof(float) * (size_t)P.Bq);
-    P.sq = ib_slices(2 * B, B);
-    P.sd = ib_slices(B, 2 * B);
+    P.sq = ib_slices(M, B);
+    P.sd = ib_slices(B, M);
     P.pm = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);  // per (slice, query): running maximum, sum of exponentials
     P.pl = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);
-    P.pos = w.take(sizeof(float) * (size_t)P.Bq);          // s_ii
+    P.pos = w.take(sizeof(float) * (size_t)P.Bq);          // s_{i, pos_offset + i}
     P.part_q = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq * P.Hp);  // per slice: partial dqh [Bq][Hp], dDh [Dp][Hp]
     P.part_d = w.take(sizeof(float) * (size_t)P.sd.n * P.Dp * P.Hp);
     P.total = w.off;
@@ -76,9 +79,19 @@ IBPlan ib_plan(int B, int H)
 }
 
 // ------------------------------------------------------------------ 1: norms and images
-// Row r of [queries (Bq rows); documents (Dp rows)]; rows past B / 2B and columns past H are written as zeros.
-__global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ q, const float *__restrict__ p,
-                                                      const float *__restrict__ n, int B, int H, int Hp, int Bq, int Dp,
+// The documents as the caller holds them: rows [0, split) at `lo`, rows [split, M) at `hi` (one contiguous pool: split = M).
+struct IBDocs {
+    const float *lo, *hi;
+    int split;
+};
+struct IBDocGrads {
+    float *lo, *hi;
+    int split;
+};
+
+// Row r of [queries (Bq rows); documents (Dp rows)]; rows past B / M and columns past H are written as zeros.
+__global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ q, IBDocs docs, int B, int M, int H, int Hp,
+                                                      int Bq, int Dp,
                                                       float *__restrict__ qh, float *__restrict__ dh,
                                                       float *__restrict__ den, float *__restrict__ flag)
 {
@@ -93,7 +106,7 @@ __global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ 
         dst = qh + (size_t)r * Hp;
     } else {
         const int j = r - Bq;
-        src = j < B ? p + (size_t)j * H : (j < 2 * B ? n + (size_t)(j - B) * H : nullptr);
+        src = j < docs.split ? docs.lo + (size_t)j * H : (j < M ? docs.hi + (size_t)(j - docs.split) * H : nullptr);
         dst = dh + (size_t)j * Hp;
     }
     float ss = 0.0f;
@@ -161,15 +174,15 @@ __device__ __forceinline__ int ib_rho(int reg) { return (reg & 3) + 8 * (reg >> 
 // the slice.  Each lane keeps a running maximum and a sum of exponentials over the documents it sees; the 8 partials of a
 // query (4 waves x 2 lane halves) are combined in a fixed order into the slice's pair.  (A slice holds a valid document
 // for every query: slices are whole chunks, none empty.)
-__global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh, int B,
-                                                       int Hp, int Bq, int tiles_per_slice, float temperature,
+__global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh, int B, int M,
+                                                       int pos_offset, int Hp, int Bq, int tiles_per_slice, float temperature,
                                                        float *__restrict__ pm, float *__restrict__ pl,
                                                        float *__restrict__ pos)
 {
     __shared__ float part_m[8][IB_TILE], part_l[8][IB_TILE];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5;
     const int i0 = blockIdx.x * IB_TILE, i = i0 + (lane & 31);
-    const int ND = 2 * B;
+    const int ND = M;
     const int t_begin = blockIdx.y * tiles_per_slice;
     const int t_all = (ND + IB_TILE - 1) / IB_TILE, n_tiles = t_begin + tiles_per_slice < t_all ? t_begin + tiles_per_slice : t_all;
     float m = -INFINITY, l = 0.0f;
@@ -183,7 +196,7 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
             x[r] = acc[r] / temperature;
             if (j < ND)
                 tm = fmaxf(tm, x[r]);
-            if (j == i && i < B)
+            if (j == i + pos_offset && i < B)
                 pos[i] = x[r];  // (one lane of one wave of one slice, once)
         }
         if (tm > -INFINITY) {  // (some document of the tile is valid for this lane half)
@@ -214,7 +227,7 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     }
 }
 
-// The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_ii.
+// The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.
 __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ pm, const float *__restrict__ pl,
                                                      const float *__restrict__ pos, int B, int Bq, int n_slices,
                                                      float *__restrict__ lse, float *__restrict__ row_loss)
@@ -251,13 +264,14 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
 // The epilogue turns the [h][owner] accumulators into rows through LDS and stores the slice's partial [32][Hp] coalesced.
 template <bool QOWN>
 __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restrict__ qh, const float *__restrict__ dh,
-                                             const float *__restrict__ lse, int B, int Hp, float temperature, int tile,
-                                             int chunk_begin, int chunk_end, float *__restrict__ part)
+                                             const float *__restrict__ lse, int B, int M, int pos_offset, int Hp,
+                                             float temperature, int tile, int chunk_begin, int chunk_end,
+                                             float *__restrict__ part)
 {
     // (the wave index as a scalar: the compiler then branches on it instead of masking lanes)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5, col = lane & 31;
     const float *own = QOWN ? qh : dh, *oth = QOWN ? dh : qh;
-    const int n_oth = QOWN ? 2 * B : B;
+    const int n_oth = QOWN ? M : B;
     const int own0 = tile * IB_TILE, o = own0 + col;
     const int NT = Hp / 32;
     const float scale = 1.0f / ((float)B * temperature);
@@ -279,9 +293,9 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
                 const int y = y0 + ib_rho(r) + 4 * half;
                 const int iq = QOWN ? o : y, jd = QOWN ? y : o;
                 float v = 0.0f;
-                if (iq < B && jd < 2 * B) {
+                if (iq < B && jd < M) {
                     const float ls = ls_y[r];
-                    v = (expf(acc[r] / temperature - ls) - (jd == iq ? 1.0f : 0.0f)) * scale;
+                    v = (expf(acc[r] / temperature - ls) - (jd == iq + pos_offset ? 1.0f : 0.0f)) * scale;
                 }
                 g[r] = v;
             }
@@ -347,38 +361,38 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
 
 // Blocks [0, tiles_q * slices_q): query tiles (block = slice * tiles_q + tile); the rest: document tiles, the same way.
 __global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
-                                                      const float *__restrict__ lse, int B, int Hp, int Bq, int Dp,
-                                                      float temperature, int tiles_q, int slices_q, int per_q, int tiles_d,
+                                                      const float *__restrict__ lse, int B, int M, int pos_offset, int Hp,
+                                                      int Bq, int Dp, float temperature, int tiles_q, int slices_q, int per_q, int tiles_d,
                                                       int per_d, float *__restrict__ part_q, float *__restrict__ part_d)
 {
     extern __shared__ __attribute__((aligned(16))) float ib_lds[];  // G [128][32], later the gradient tile [32][Hp]
     int b = blockIdx.x;
     if (b < tiles_q * slices_q) {
-        const int slice = b / tiles_q, chunks = (2 * B + IB_CHUNK - 1) / IB_CHUNK;
+        const int slice = b / tiles_q, chunks = (M + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
-        ib_grad_body<true>(ib_lds, qh, dh, lse, B, Hp, temperature, b % tiles_q, slice * per_q, end,
+        ib_grad_body<true>(ib_lds, qh, dh, lse, B, M, pos_offset, Hp, temperature, b % tiles_q, slice * per_q, end,
                            part_q + (size_t)slice * Bq * Hp);
     } else {
         b -= tiles_q * slices_q;
         const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
-        ib_grad_body<false>(ib_lds, qh, dh, lse, B, Hp, temperature, b % tiles_d, slice * per_d, end,
+        ib_grad_body<false>(ib_lds, qh, dh, lse, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d, end,
                             part_d + (size_t)slice * Dp * Hp);
     }
 }
 
 // ------------------------------------------------------------------ 6: through the norms
-// One wave per row of [q; p; n]: the slices' partials in ascending order -> dxh, then
+// One wave per row of [q; documents]: the slices' partials in ascending order -> dxh, then
 // dx = (dxh - xh (xh . dxh)) / ||x||, or dxh / eps for a row shorter than eps: (dxh - flag xh (xh . dxh)) / max(||x||, eps).
 __global__ __launch_bounds__(256) void ib_project_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
                                                          const float *__restrict__ den, const float *__restrict__ flag,
                                                          const float *__restrict__ part_q, const float *__restrict__ part_d,
-                                                         int B, int H, int Hp, int Bq, int Dp, int slices_q, int slices_d,
-                                                         float *__restrict__ dq, float *__restrict__ dp, float *__restrict__ dn)
+                                                         int B, int M, int H, int Hp, int Bq, int Dp, int slices_q,
+                                                         int slices_d, float *__restrict__ dq, IBDocGrads dd)
 {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= 3 * B)
+    if (r >= B + M)
         return;
     const bool is_q = r < B;
     const int row = is_q ? r : r - B;  // row of the image
@@ -409,7 +423,7 @@ __global__ __launch_bounds__(256) void ib_project_kernel(const float *__restrict
     for (int off = 32; off >= 1; off >>= 1)
         dot += __shfl_xor(dot, off);
     const float d = den[nr], f = flag[nr] * dot;
-    float *out = is_q ? dq + (size_t)row * H : (row < B ? dp + (size_t)row * H : dn + (size_t)(row - B) * H);
+    float *out = is_q ? dq + (size_t)row * H : (row < dd.split ? dd.lo + (size_t)row * H : dd.hi + (size_t)(row - dd.split) * H);
 #pragma unroll
     for (int e = 0; e < IB_MAX_H / 64; ++e) {
         const int u = lane + 64 * e;
@@ -439,20 +453,53 @@ __global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ 
     }
 }
 
+// The launches of one call; both entries have refused what they refuse.  dd.lo == nullptr: the loss only.
+void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, int pos_offset, float temperature, float *loss,
+               float *dq, IBDocGrads dd, void *workspace, hipStream_t st)
+{
+    char *ws = (char *)workspace;
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
+    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
+    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, docs, B, M, H, P.Hp, P.Bq, P.Dp, qh, dh,
+                       den, flag);
+    float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
+    float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
+    const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
+    hipLaunchKernelGGL(ib_stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, B, M,
+                       pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
+    hipLaunchKernelGGL(ib_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
+                       (const float *)pos, B, P.Bq, P.sq.n, lse, rows);
+    hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
+    if (dq) {
+        const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
+        const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
+        hipLaunchKernelGGL(ib_grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh,
+                           (const float *)dh, (const float *)lse, B, M, pos_offset, P.Hp, P.Bq, P.Dp, temperature, tiles_q,
+                           P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d);
+        hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
+                           (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
+                           (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dd);
+    }
+}
+
+constexpr int IB_MAX_B = 1 << 24, IB_MAX_M = 1 << 25;
+
+bool ib_shape_ok(int B, int M, int H) { return B >= 1 && B <= IB_MAX_B && M >= B && M <= IB_MAX_M && H >= 1 && H <= IB_MAX_H; }
+
 } // namespace
 
 TT_EXPORT size_t tt_in_batch_loss_workspace_bytes(int B, int H)
 {
-    if (B < 1 || H < 1 || H > IB_MAX_H || B > (1 << 24))
+    if (B < 1 || H < 1 || H > IB_MAX_H || B > IB_MAX_B)
         return 0;
-    return ib_plan(B, H).total;
+    return ib_plan(B, 2 * B, H).total;
 }
 
 TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *n, int B, int H, float temperature,
                                    float *loss, float *dq, float *dp, float *dn, void *workspace, size_t workspace_bytes,
                                    tt_stream_t stream)
 {
-    if (B < 1 || B > (1 << 24) || H < 1 || H > IB_MAX_H)
+    if (B < 1 || B > IB_MAX_B || H < 1 || H > IB_MAX_H)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: B=%d H=%d (B >= 1, 1 <= H <= %d)", B, H, IB_MAX_H);
     if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: temperature=%g must be finite and > 0", (double)temperature);
@@ -462,33 +509,42 @@ TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: dq, dp, dn must be all null or all non-null");
     if ((uintptr_t)workspace & 15)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: the workspace must be 16-byte aligned");
-    const IBPlan P = ib_plan(B, H);
+    const IBPlan P = ib_plan(B, 2 * B, H);
     if (workspace_bytes < P.total)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
-    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
-    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, p, n, B, H, P.Hp, P.Bq, P.Dp, qh, dh,
-                       den, flag);
-    float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
-    float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
-    const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (2 * B + IB_TILE - 1) / IB_TILE;
-    hipLaunchKernelGGL(ib_stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, B, P.Hp,
-                       P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
-    hipLaunchKernelGGL(ib_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
-                       (const float *)pos, B, P.Bq, P.sq.n, lse, rows);
-    hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
-    if (dq) {
-        const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
-        const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
-        hipLaunchKernelGGL(ib_grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh,
-                           (const float *)dh, (const float *)lse, B, P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per,
-                           tiles_d, P.sd.per, part_q, part_d);
-        hipLaunchKernelGGL(ib_project_kernel, dim3((3 * B + 3) / 4), dim3(256), 0, st, (const float *)qh, (const float *)dh,
-                           (const float *)den, (const float *)flag, (const float *)part_q, (const float *)part_d, B, H, P.Hp,
-                           P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dp, dn);
-    }
+    // D = [p; n]: the pool of M = 2B documents in two pieces, the positive of query i in row i
+    ib_launch(P, q, IBDocs{p, n, B}, B, 2 * B, H, 0, temperature, loss, dq, IBDocGrads{dp, dn, B}, workspace, (hipStream_t)stream);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+TT_EXPORT size_t tt_contrastive_loss_workspace_bytes(int B, int M, int H)
+{
+    return ib_shape_ok(B, M, H) ? ib_plan(B, M, H).total : 0;
+}
+
+TT_EXPORT int tt_contrastive_loss_f32(const float *q, int B, const float *docs, int M, int H, int pos_offset, float temperature,
+                                      float *loss, float *dq, float *ddocs, void *workspace, size_t workspace_bytes,
+                                      tt_stream_t stream)
+{
+    if (!ib_shape_ok(B, M, H))
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", B, M,
+                       H, IB_MAX_B, IB_MAX_M, IB_MAX_H);
+    if (pos_offset < 0 || pos_offset > M - B)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: pos_offset=%d outside [0, M - B = %d]", pos_offset, M - B);
+    if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: temperature=%g must be finite and > 0", (double)temperature);
+    if (!q || !docs || !loss || !workspace)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: null pointer");
+    if (!dq != !ddocs)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: dq, ddocs must be both null or both non-null");
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: the workspace must be 16-byte aligned");
+    const IBPlan P = ib_plan(B, M, H);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
+    ib_launch(P, q, IBDocs{docs, nullptr, M}, B, M, H, pos_offset, temperature, loss, dq, IBDocGrads{ddocs, nullptr, M}, workspace,
+              (hipStream_t)stream);
     TT_LAUNCH_CHECK();
     return TT_OK;
 }

@@ -6,6 +6,7 @@
     TwoTowerModel(config, pretrained_embeddings).encode_query / encode_document / forward model.py:78-106
     triplet_loss_cosine((q, p, n), margin=0.2) -> 0-d tensor                             model.py:109-114
     in_batch_softmax_loss((q, p, n), temperature=0.05) -> 0-d tensor                     (not in the reference: in-batch negatives)
+    contrastive_softmax_loss(q, docs, pos_offset=0, temperature=0.05) -> 0-d tensor      (the same over any pool of documents)
 
 Same constructor arguments, attribute names (`query_encoder.embedding.embedding_dim` is read by
 backend/main.py:104) and state_dict keys ({query,doc}_encoder.{embedding.weight,
@@ -27,7 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "SplitRecurrenceTimeout"]
+__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "SplitRecurrenceTimeout"]
 
 
 class SplitRecurrenceTimeout(RuntimeError):
@@ -561,8 +562,8 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
     is scored against all 2B passages of the batch (its own positive, the other queries' positives, all explicit negatives)
     instead of one hinge against one negative.  Cosine with eps 1e-8 per norm, as triplet_loss_cosine.  Differentiable (fused
     forward + gradient kernels on the f32 matrix pipe, deterministic).
-    The negatives are rank-local: under DataParallelTrainer each rank's softmax runs over its own 2B passages and the gradient
-    is averaged over the ranks like any other; passages of other ranks are not gathered."""
+    The pool is the triplet's own 2B passages; contrastive_softmax_loss takes any pool (the trainers gather the passages of all
+    ranks into one with gather_negatives=True)."""
     query, pos_doc, neg_doc = triplet
     for t in (query, pos_doc, neg_doc):
         if not t.is_cuda:
@@ -570,3 +571,56 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
             raise ValueError("in_batch_softmax_loss wants three float32 [B,H] tensors of one shape")
     return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)
+
+
+def contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
+    """An uninitialised workspace for tt_contrastive_loss_f32 at q [B,H], docs [M,H] (the call rewrites all of it that it reads)."""
+    need = _lib.lib().tt_contrastive_loss_workspace_bytes(B, M, H)
+    if need == 0:
+        raise ValueError(f"contrastive_softmax_loss: B={B} M={M} H={H} (1 <= B <= M <= 2^25, B <= 2^24, 1 <= H <= 512)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+class _ContrastiveFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, docs, pos_offset: int, temperature: float):
+        L = _lib.lib()
+        q, docs = q.contiguous(), docs.contiguous()
+        (B, H), M = q.shape, docs.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        dq, ddocs = torch.empty_like(q), torch.empty_like(docs)
+        ws = contrastive_workspace(B, M, H, q.device)
+        with torch.cuda.device(q.device):
+            _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), float(temperature),
+                                                 loss.data_ptr(), dq.data_ptr(), ddocs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _stream(q.device)))
+        ctx.save_for_backward(dq, ddocs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, ddocs = ctx.saved_tensors
+        return g * dq, g * ddocs, None, None
+
+
+def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05) -> torch.Tensor:
+    """The softmax contrastive loss of B queries over a pool of M >= B documents:
+    mean_i(logsumexp_j s_ij - s_{i, pos_offset+i}), s_ij = cos(q_i, docs_j) / temperature -- the positive of query i is row
+    pos_offset + i of `docs`, every other row is a negative (the passages gathered from all ranks; or several explicit negatives
+    per query).  in_batch_softmax_loss((q, p, n)) is contrastive_softmax_loss(q, cat(p, n)), bit for bit.  Cosine with eps 1e-8
+    per norm.  Differentiable in q and docs (fused forward + gradient kernels on the f32 matrix pipe, deterministic)."""
+    for t in (q, docs):
+        if not t.is_cuda:
+            raise RuntimeError("contrastive_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError("contrastive_softmax_loss wants float32 q [B,H] and docs [M,H]")
+    (B, H), M = q.shape, docs.shape[0]
+    if docs.shape[1] != H:
+        raise ValueError(f"contrastive_softmax_loss: q has H={H}, docs has H={docs.shape[1]}")
+    if M < B:
+        raise ValueError(f"contrastive_softmax_loss: M={M} documents for B={B} queries (every query needs its positive: M >= B)")
+    if not 0 <= pos_offset <= M - B:
+        raise ValueError(f"contrastive_softmax_loss: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
+    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
+        raise ValueError(f"contrastive_softmax_loss: temperature={temperature!r} must be finite and > 0")
+    return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature))

@@ -23,7 +23,8 @@ from typing import Callable, Iterable, Optional, Tuple
 import torch
 
 from . import _lib
-from .model import TwoTowerModel, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, triplet_loss_cosine
+from .model import (TwoTowerModel, contrastive_softmax_loss, contrastive_workspace, deferred_input_checks, in_batch_softmax_loss,
+                    in_batch_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -437,7 +438,8 @@ class _towers_in_flight:
 
 def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_docs, margin: float, phase: str = "all",
                        join_on_caller: bool = False, both: Optional[torch.Tensor] = None, plan: Optional[_towers_in_flight] = None,
-                       seed_words: Optional[dict] = None, negatives: str = "paired", temperature: float = 0.05):
+                       seed_words: Optional[dict] = None, negatives: str = "paired", temperature: float = 0.05,
+                       gather_negatives: bool = False):
     """The same step without the autograd engine: tower forwards (train mode), the fused loss + gradient kernel, tower backwards
     written STRAIGHT into the optimizer's flat gradient buffer, optimizer step.  Every parameter receives its gradient exactly
     once (query tower once; positives and negatives as one 2B-row document-tower call), so nothing has to be zeroed or
@@ -457,9 +459,15 @@ def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_d
     launches are ordered with events (query tower's first in the forward, last in the backward).
     seed_words: {id(encoder): device int64[1]} -- the towers' dropout seeds as device words the kernels read when they run
     (TT_ENC_SEED_ON_DEVICE: GraphedTrainStep writes a fresh seed there before every replay); default: drawn here, passed by value.
-    negatives / temperature: see train_step; "in_batch" swaps the one loss call (same q, pn, dq, dpn buffers), nothing else."""
+    negatives / temperature: see train_step; "in_batch" swaps the one loss call (same q, pn, dq, dpn buffers), nothing else.
+    gather_negatives: the loss runs over the passages of ALL ranks, on the stream where the towers meet: all-gather of pn into the
+    pool G [world * 2B, H] (rank order), tt_contrastive_loss_f32(q, G, pos_offset = rank * 2B) -> loss, dq, dG, summing
+    all-reduce of dG, dpn = this rank's 2B rows of it.  Both collectives go out whatever the towers' status words say, in front
+    of the query tower's reduce_prefix: every rank issues gather, reduce, (prefix,) bucket in that order."""
     if not isinstance(optimizer, _FlatClipAdam) or not torch.is_grad_enabled():
         return None
+    if gather_negatives and (join_on_caller or getattr(optimizer, "_coll", None) is None):
+        return None  # (no exchange inside a capture; no Collective to exchange with)
     encs = (model.doc_encoder, model.query_encoder)
     views = {id(p): gv for p, gv in zip(optimizer.params, optimizer._views)}
     into = []
@@ -553,12 +561,26 @@ def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_d
         with torch.cuda.stream(s_main):
             loss = torch.empty((), dtype=torch.float32, device=dev)
             dq = torch.empty_like(q)
-            dpn = torch.empty_like(pn)
-            rows = in_batch_workspace(B, H, dev) if negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
+            if gather_negatives:
+                coll = optimizer._coll
+                pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
+                d_pool = torch.empty_like(pool)
+                dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
+                rows = contrastive_workspace(B, pool.shape[0], H, dev)
+            else:
+                dpn = torch.empty_like(pn)
+                rows = in_batch_workspace(B, H, dev) if negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
             for t in (q, pn, loss, dq, dpn, rows):
                 t.record_stream(s_main)
             with torch.cuda.device(dev):
-                if negatives == "in_batch":
+                if gather_negatives:
+                    coll.all_gather_blocks(pn, pool)
+                    _lib.check(_lib.lib().tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
+                                                                  float(temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
+                                                                  rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+                    # (no scale: a summed row is sum_r d loss_r / d D_j, and the optimizer's 1 / world makes it the mean's)
+                    coll.all_reduce_sum(d_pool.view(-1))
+                elif negatives == "in_batch":
                     _lib.check(_lib.lib().tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(temperature),
                                                                loss.data_ptr(), dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(),
                                                                rows.data_ptr(), rows.numel(), s_main.cuda_stream))
@@ -615,22 +637,57 @@ def _draw_dropout_seeds(model: TwoTowerModel) -> dict:
             for enc in (model.query_encoder, model.doc_encoder)}
 
 
-def _check_negatives(negatives: str) -> None:
+def _check_negatives(negatives: str, gather_negatives: bool = False, graphs: bool = False) -> None:
     if negatives not in ("paired", "in_batch"):
         raise ValueError(f'negatives must be "paired" or "in_batch", got {negatives!r}')
+    if gather_negatives and negatives != "in_batch":
+        raise ValueError(f'gather_negatives=True needs negatives="in_batch", got negatives={negatives!r}')
+    if gather_negatives and graphs:
+        raise ValueError("gather_negatives=True is not available with graphs=True (the exchange of the passages sits between the "
+                         "captured forward and backward)")
+
+
+class _GatherPoolFn(torch.autograd.Function):
+    """This rank's passages pn [2B,H] -> the pool of all ranks [world * 2B, H], rank order (Collective.all_gather_blocks).
+    Backward: summing all-reduce of the pool's gradient -- every rank's loss has a gradient for every row -- and this rank's rows."""
+
+    @staticmethod
+    def forward(ctx, pn, coll):
+        pn = pn.contiguous()
+        pool = torch.empty((coll.world * pn.shape[0], pn.shape[1]), dtype=pn.dtype, device=pn.device)
+        coll.all_gather_blocks(pn, pool)
+        ctx.coll, ctx.rows = coll, pn.shape[0]
+        return pool
+
+    @staticmethod
+    def backward(ctx, d_pool):
+        d_pool = d_pool.contiguous().clone()  # (reduced in place: not the engine's tensor)
+        ctx.coll.all_reduce_sum(d_pool.view(-1))
+        return d_pool[ctx.coll.rank * ctx.rows:(ctx.coll.rank + 1) * ctx.rows], None
+
+
+def _gathered_loss(optimizer, q, p, n, pn, temperature):
+    """The autograd form of the gathered step: the loss of this rank's queries over the passages of all ranks."""
+    coll = getattr(optimizer, "_coll", None)
+    if coll is None:
+        raise ValueError("gather_negatives=True needs a FusedClipAdam (the passages travel through its Collective)")
+    if pn is None:
+        pn = torch.cat((p, n))
+    return contrastive_softmax_loss(q, _GatherPoolFn.apply(pn, coll), pos_offset=coll.rank * pn.shape[0], temperature=temperature)
 
 
 def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan=None,
-                     negatives="paired", temperature=0.05):
+                     negatives="paired", temperature=0.05, gather_negatives=False):
     if direct and concurrent_towers and queries.is_cuda and neg_docs.shape[0] == pos_docs.shape[0] == queries.shape[0]:
         loss = _train_step_direct(model, optimizer, queries, pos_docs, neg_docs, margin, plan=plan, negatives=negatives,
-                                  temperature=temperature)
+                                  temperature=temperature, gather_negatives=gather_negatives)
         if loss is not None:
             return loss
     if plan is not None:
         plan.use_one_workgroup()   # (autograd calls cannot carry the ordering events)
     optimizer.zero_grad()
     watched = isinstance(optimizer, _FlatClipAdam)
+    pn = None   # (the 2B passages as one tensor, when the document tower ran once)
     if concurrent_towers and queries.is_cuda:
         cur = torch.cuda.current_stream(queries.device)
         B = pos_docs.shape[0]
@@ -662,13 +719,16 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
                 launch()
         if len(outs) == 2:
             q, p, n = outs[0], outs[1][:B], outs[1][B:]
+            pn = outs[1]
         else:
             q, p, n = outs
     else:
         q = model.encode_query(queries)
         p = model.encode_document(pos_docs)
         n = model.encode_document(neg_docs)
-    if negatives == "in_batch":
+    if gather_negatives:
+        loss = _gathered_loss(optimizer, q, p, n, pn, temperature)
+    elif negatives == "in_batch":
         loss = in_batch_softmax_loss((q, p, n), temperature=temperature)
     else:
         loss = triplet_loss_cosine((q, p, n), margin=margin)
@@ -679,7 +739,8 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
 
 def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Tensor, pos_docs: torch.Tensor,
                neg_docs: torch.Tensor, margin: float = 0.2, concurrent_towers: bool = True, direct: bool = True,
-               defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05) -> torch.Tensor:
+               defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05,
+               gather_negatives: bool = False) -> torch.Tensor:
     """One step of backend/main.py:244-259 on this rank's (equal-sized) share of the global batch.
     Returns the local loss as a 0-d device tensor (no .item(): the reference's per-step sync is dropped).
 
@@ -700,20 +761,32 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
 
     negatives: "paired" (default) = the reference's triplet loss, one hinge per row against its own negative.  "in_batch" = the
     softmax contrastive loss over all 2B passages of the batch (model.in_batch_softmax_loss) at `temperature`; `margin` is
-    ignored; needs as many negatives as positives as queries.  The negatives are rank-local: under data parallelism each rank's
-    softmax runs over its own 2B passages and the gradients are averaged over the ranks as always -- no embeddings are gathered."""
+    ignored; needs as many negatives as positives as queries.  The negatives are rank-local (each rank's softmax runs over its
+    own 2B passages, the gradients are averaged over the ranks as always) unless gather_negatives=True.
+
+    gather_negatives (negatives="in_batch" only): every query is scored against the passages of ALL ranks -- world * 2B - 1
+    negatives instead of 2B - 1.  Two collectives of the optimizer's Collective per step, between the towers' forwards and
+    backwards: an all-gather of the rank's 2B passage embeddings into a pool [world * 2B, H], and a summing all-reduce of the
+    pool's gradient (every rank's loss has a gradient for every passage), of which the rank keeps its own 2B rows.  With the
+    optimizer's 1/world the update is the gradient of the mean of the ranks' losses, which is the loss of the global batch.
+    Every rank must bring the same B.  Returns the rank's own loss: the mean over its B queries against the global pool.
+    Both collectives are issued whatever the batch holds, so failure stays collective (above); a redo after a recurrence
+    time-out repeats them on all ranks.  One process without a group: the same bits as without the flag."""
     from .model import SplitRecurrenceTimeout
-    _check_negatives(negatives)
+    _check_negatives(negatives, gather_negatives)
+    if gather_negatives and not queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]:
+        raise ValueError("gather_negatives=True needs as many negatives as positives as queries")
     if defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda:
         keep, optimizer.check = optimizer.check, False
         try:
             loss = train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
-                              negatives=negatives, temperature=temperature)
+                              negatives=negatives, temperature=temperature, gather_negatives=gather_negatives)
         finally:
             optimizer.check = keep
         if keep:
             optimizer.snapshot_gate(redo=lambda: train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
-                                                            negatives=negatives, temperature=temperature))
+                                                            negatives=negatives, temperature=temperature,
+                                                            gather_negatives=gather_negatives))
         return loss
     encs = (model.query_encoder, model.doc_encoder)
     n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
@@ -723,13 +796,13 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     try:
         with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
             return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
-                                    negatives, temperature)
+                                    negatives, temperature, gather_negatives)
     except SplitRecurrenceTimeout:
         if rng is not None:
             torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
         with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
             return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
-                                    negatives, temperature)
+                                    negatives, temperature, gather_negatives)
 
 
 class DataParallelTrainer:
@@ -740,16 +813,18 @@ class DataParallelTrainer:
     ~0.3 GB at 512 triplets x 128 columns).  A batch that does not fit the rules of GraphedTrainStep (unchecked inputs,
     non-int64 ids, a trainable table) takes the eager train_step; results are the eager step's on ids padded to the bucket's widths.
     defer_check: see GraphedTrainStep (exceptions one call late; call flush() after the last step).
-    negatives / temperature: see train_step.  "in_batch" negatives are rank-local (each rank's softmax over its own 2B passages,
-    gradients averaged over the ranks as for the triplet loss; no all-gather of embeddings)."""
+    negatives / temperature / gather_negatives: see train_step.  "in_batch" negatives are rank-local (each rank's softmax over
+    its own 2B passages, gradients averaged over the ranks as for the triplet loss) unless gather_negatives=True: then the
+    passages of all ranks are gathered and every query sees world * 2B - 1 negatives (every rank must bring the same B; two
+    more collectives per step, same order on every rank).  Not with graphs=True."""
 
     def __init__(self, model: TwoTowerModel, lr: float = 1e-4, margin: float = 0.2, max_norm: float = 1.0, group=None,
                  graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False,
-                 negatives: str = "paired", temperature: float = 0.05):
-        _check_negatives(negatives)
+                 negatives: str = "paired", temperature: float = 0.05, gather_negatives: bool = False):
+        _check_negatives(negatives, gather_negatives, graphs)
         self.model = model
         self.margin = margin
-        self.negatives, self.temperature = negatives, float(temperature)
+        self.negatives, self.temperature, self.gather_negatives = negatives, float(temperature), bool(gather_negatives)
         self.optimizer = FusedClipAdam(model.parameters(), lr=lr, max_norm=max_norm, group=group)
         self.optimizer.watch(model)  # (a hand-written loop over self.model / self.optimizer fails collectively too)
         self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
@@ -789,7 +864,7 @@ class DataParallelTrainer:
             if g is not None:
                 return g(queries, pos_docs, neg_docs)
         return train_step(self.model, self.optimizer, queries, pos_docs, neg_docs, self.margin, defer_check=self.defer_check,
-                          negatives=self.negatives, temperature=self.temperature)
+                          negatives=self.negatives, temperature=self.temperature, gather_negatives=self.gather_negatives)
 
 
 def _stage_ids(out: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> None:
