@@ -611,12 +611,13 @@ def test_k1_tail_split_writes_the_same_bits(B, T):
 def test_train_step_keeps_the_split_recurrences_within_the_cus():
     """The train step launches the query tower and the 2B-row document tower on two streams.  Both column-split would be 32 + 64
     teams = 384 one-per-CU workgroups for 256 CUs: members of some teams would wait for a CU while their partners already sweep
-    for them, and progress would rest on dispatch order.  trainer._towers_in_flight makes co-residency a matter of construction:
+    for them, and progress would rest on dispatch order.  trainer._towers_in_flight makes co-residency a matter of construction
+    (the decision is trainer._plan_towers, pinned without a GPU in tests/test_train_plan_cpu.py):
     the direct step ORDERS the two towers' forward recurrence launches with an event inside the calls (tt_enc_sync_t: the query
     tower's first; the document tower's call goes out in two halves around the query tower's, TT_ENC_PHASE_BEGIN / _FINISH, so
-    that its projection is not delayed) and gives the smaller tower the one-workgroup BACKWARD recurrence; the autograd path and
-    graph capture give the smaller tower the one-workgroup recurrences in both directions.  Checked here on what the tower calls
-    really got.  Three steps: with the split forward alone
+    that its projection is not delayed: trainer._forward_sequence) and gives the smaller tower the one-workgroup BACKWARD
+    recurrence; the autograd path and graph capture give the smaller tower the one-workgroup recurrences in both directions.
+    Checked here on what the tower calls really got.  Three steps: with the split forward alone
     the parameters are the all-one-workgroup run's bit for bit; with the backwards split too the run repeats itself bit for bit
     and its last gradient agrees with the one-workgroup run's to the gradient tolerance; direct and autograd paths agree."""
     import copy

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Interleaved A/B of the train step's forward ordering (trainer._FWD_ORDER) on one box: eager step time per mode, three rounds;
+"""Interleaved A/B of the train step's forward ordering (trainer._FWD_ORDER, the keys of trainer._FORWARD_SEQUENCES) on one box: eager
+step time per mode, three rounds;
 the parameters after the steps must be the same bits in every mode (the recurrence kernels are bit-identical).
 With a mode name as argument: six steps of that mode only (for tools/train_timeline.sh-style kernel traces)."""
 import json, sys, time, copy
@@ -16,7 +17,7 @@ def main():
     inp = bench.make_encoder_inputs(dev, with_index_batch=False)
     m0 = inp["model"].train()
     q, p, n = (inp[k].to(dev) for k in "qpn")
-    modes = sys.argv[1:] or ["query_first", "doc_first", "query_one_wg"]
+    modes = sys.argv[1:] or ["query_first", "query_first_whole", "doc_first", "query_one_wg"]
     res, params = {k: [] for k in modes}, {}
     for rep in range(3 if len(modes) > 1 else 1):
         for mode in modes:

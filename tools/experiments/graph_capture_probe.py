@@ -28,6 +28,7 @@ def one(variant):
         m.query_encoder.one_workgroup = True
         variant = variant[:-5]
     rows = {m.query_encoder: B, m.doc_encoder: 2 * B}
+    spec = T._StepSpec(0.5, "paired", 0.05, False, True, True).checked(graphs=False)
     if variant == "two_norecord":
         torch.Tensor.record_stream = lambda self, s: None
 
@@ -48,7 +49,9 @@ def one(variant):
                     cur.wait_stream(s)
                 opt._pending_status.clear()
                 return outs[0]
-            return T._train_step_direct(m, opt, q, p, n, 0.5, join_on_caller=(variant != "eager2"), plan=plan)
+            # (a capture joins the towers on the caller's stream: trainer._Capture; the batch is concatenated inside, seeds by value)
+            capture = None if variant == "eager2" else T._Capture("all", None, None)
+            return T._train_step_direct(m, opt, (q, p, n), spec, plan, capture)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):

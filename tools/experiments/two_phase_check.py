@@ -14,8 +14,9 @@ torch.manual_seed(5)
 m0 = tt.TwoTowerModel({"VOCAB_SIZE": V, "EMBED_DIM": E, "HIDDEN_DIM": H}, synth.make_table(4, V, E)).cuda().train()
 ids = [torch.from_numpy(synth.make_ids(60 + s, B, Tn, V)).cuda() for s, Tn in enumerate((9, 60, 70))]
 res = {}
-for name, two, direct in (("two_phase", True, True), ("query_first", False, True), ("autograd", True, False), ("two_phase_again", True, True)):
-    T._TWO_PHASE = two
+for name, order, direct in (("two_phase", "query_first", True), ("query_first", "query_first_whole", True),
+                            ("autograd", "query_first", False), ("two_phase_again", "query_first", True)):
+    T._FWD_ORDER = order   # ("query_first": the document tower's call in two halves; "query_first_whole": whole calls)
     m = copy.deepcopy(m0)
     o = tt.FusedClipAdam(m.parameters(), lr=1e-5, max_norm=1.0)
     loss = tt.train_step(m, o, *ids, margin=0.5, direct=direct)
@@ -30,8 +31,8 @@ for name, r in res.items():
     print(name, "loss", r[0], "grads differ at", int((dg > 0).sum()), "max", float(dg.max()), "per tensor max", parts,
           "params differ at", int((r[2] != base[2]).sum()), flush=True)
 # what did the optimizer do in each?
-for name, two, direct in (("direct", True, True), ("autograd", True, False)):
-    T._TWO_PHASE = two
+T._FWD_ORDER = "query_first"
+for name, direct in (("direct", True), ("autograd", False)):
     m = copy.deepcopy(m0)
     o = tt.FusedClipAdam(m.parameters(), lr=1e-5, max_norm=1.0)
     before = o.flat_params.clone()

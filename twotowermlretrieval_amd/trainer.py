@@ -18,13 +18,15 @@ are ordinary tensors); the fused optimizer is the MI355X-native path.
 """
 from __future__ import annotations
 
-from typing import Callable, Iterable, Optional, Tuple
+import ctypes as C
+from typing import Callable, Iterable, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib
-from .model import (TwoTowerModel, contrastive_softmax_loss, contrastive_workspace, deferred_input_checks, in_batch_softmax_loss,
-                    in_batch_workspace, triplet_loss_cosine)
+from .collective import Collective
+from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _raise_status, contrastive_softmax_loss,
+                    contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -50,7 +52,6 @@ def _hip_clip_adam_gated(flat_p, flat_g, m, v, step_dev, lr, betas, eps, max_nor
 
 def _hip_step_gate(status_words, gate):
     """gate[b] = how many of the status words have bit b set (one launch, no host read)."""
-    import ctypes as C
     cur = torch.cuda.current_stream(gate.device)
     arr = (C.c_void_p * len(status_words))()
     for i, st in enumerate(status_words):
@@ -144,14 +145,12 @@ class _FlatClipAdam:
         gradient accumulation) decide the next step() together.  Forwards that belong to no step -- validation -- must run under
         torch.no_grad() (as the reference's evaluators do, backend/evaluators.py:31), or their bad batch vetoes the next training
         step instead of raising where it happened; unwatch() ends the hand-over."""
-        from .model import RNNEncoder
         for mod in modules:
             for enc in mod.modules():
                 if isinstance(enc, RNNEncoder):
                     enc._status_sink = self._pending_status
 
     def unwatch(self, *modules) -> None:
-        from .model import RNNEncoder
         for mod in modules:
             for enc in mod.modules():
                 if isinstance(enc, RNNEncoder) and enc._status_sink is self._pending_status:
@@ -236,7 +235,6 @@ class _FlatClipAdam:
 
     @staticmethod
     def raise_for_gate(words) -> None:
-        from .model import _raise_status
         _raise_status(sum(1 << b for b in range(3) if words[b] != 0))
 
     # ---- the gate read, one step late (train_step(defer_check=True), GraphedTrainStep(defer_check=True)) --------------------
@@ -268,7 +266,6 @@ class _FlatClipAdam:
         return self._settle_one(pending)
 
     def _settle_one(self, pending):
-        from .model import SplitRecurrenceTimeout
         if pending is None:
             return None
         slot, redo = pending
@@ -298,7 +295,6 @@ class FusedClipAdam(_FlatClipAdam):
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, max_norm: float = 1.0, group=None, comm=None):
-        from .collective import Collective
         params = [p for p in params if p.requires_grad]
         if params and params[0].device.type != "cuda":
             raise RuntimeError("FusedClipAdam runs only on an AMD GPU via libtt.so (no CPU fallback)")
@@ -306,6 +302,28 @@ class FusedClipAdam(_FlatClipAdam):
         self._coll = Collective(group, params[0].device if params else None, comm=comm)
         super().__init__(params, _hip_clip_adam, self._coll.all_reduce_sum, self._coll.world, lr, betas, eps, max_norm,
                          _lib.lib().tt_clip_adam_scratch_bytes(), gate_fn=_hip_step_gate, gated_step_fn=_hip_clip_adam_gated)
+
+
+class _StepSpec(NamedTuple):
+    """What one train step is asked to do, apart from its batch (the arguments are train_step's: see there).  Built and checked
+    once at the public entries -- train_step, DataParallelTrainer, GraphedTrainStep --; everything below them takes the record."""
+    margin: float
+    negatives: str
+    temperature: float
+    gather_negatives: bool
+    concurrent_towers: bool
+    direct: bool
+
+    def checked(self, graphs: bool) -> "_StepSpec":
+        """This record, or the ValueError of a combination no step can run: raised before anything is launched."""
+        if self.negatives not in ("paired", "in_batch"):
+            raise ValueError(f'negatives must be "paired" or "in_batch", got {self.negatives!r}')
+        if self.gather_negatives and self.negatives != "in_batch":
+            raise ValueError(f'gather_negatives=True needs negatives="in_batch", got negatives={self.negatives!r}')
+        if self.gather_negatives and graphs:
+            raise ValueError("gather_negatives=True is not available with graphs=True (the exchange of the passages sits between "
+                             "the captured forward and backward)")
+        return self
 
 
 _TOWER_STREAMS = {}
@@ -321,42 +339,60 @@ def _tower_streams(device):
     return _TOWER_STREAMS[key]
 
 
+def _stage_ids(out: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor]) -> None:
+    """out [Ba + Bb, T] <- rows of a, then rows of b (None: no rows), zero-padded to out's width: ONE launch (tt_concat_ids_i64)
+    on the current stream, into an existing buffer (GraphedTrainStep's static inputs)."""
+    a = a.contiguous()
+    b = b.contiguous() if b is not None else None
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().tt_concat_ids_i64(a.data_ptr(), a.shape[0], a.shape[1], b.data_ptr() if b is not None else None,
+                                                b.shape[0] if b is not None else 0, b.shape[1] if b is not None else 0,
+                                                out.data_ptr(), out.shape[1], torch.cuda.current_stream(out.device).cuda_stream))
+
+
 def _concat_ids(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """[a; b] padded to the longer T with id 0, on the CURRENT stream: one launch (tt_concat_ids_i64) instead of torch's zero
-    fill + two slice copies -- the document tower's whole chain waits for it."""
-    from . import _lib
-    T = max(a.shape[1], b.shape[1])
-    a, b = a.contiguous(), b.contiguous()
-    out = torch.empty((a.shape[0] + b.shape[0], T), dtype=torch.int64, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.lib().tt_concat_ids_i64(a.data_ptr(), a.shape[0], a.shape[1], b.data_ptr(), b.shape[0], b.shape[1],
-                                                out.data_ptr(), T, torch.cuda.current_stream(a.device).cuda_stream))
+    """[a; b] padded to the longer T with id 0, on the CURRENT stream: one launch (_stage_ids) instead of torch's zero fill + two
+    slice copies -- the document tower's whole chain waits for it."""
+    out = torch.empty((a.shape[0] + b.shape[0], max(a.shape[1], b.shape[1])), dtype=torch.int64, device=a.device)
+    _stage_ids(out, a, b)
     return out
 
 
-_ORDER_EVENTS = {}
-_TWO_PHASE = True   # (tools/experiments: False issues the query tower first instead of splitting the document tower's call)
-# How the two towers' FORWARD recurrences share the CUs when both column-split would not fit (tools/experiments/fwd_order_ab.py):
-#   "query_first"  the query tower's recurrence first, the document tower's waits for it (event inside the calls); default
-#   "doc_first"    the document tower's first, the query tower's waits (it has slack at the END of the step, none here: the
-#                  loss needs its output)
-#   "query_one_wg" no ordering: the query tower on the one-workgroup recurrence beside the document tower's split one
-_FWD_ORDER = "query_first"
+# ---- which tower runs which recurrence ---------------------------------------------------------------------------------------
+class _TowerPlan(NamedTuple):
+    one_workgroup: tuple        # towers that run the one-workgroup recurrences, forward and backward
+    one_workgroup_bwd: tuple    # towers that run the one-workgroup recurrence in the backward alone
+    ordered: bool               # the towers' forward recurrence launches are to be ordered by events inside the calls
 
 
-def _order_events(device):
-    """Two hipEvents per device (tt_event_create: plain HIP events the C calls record / wait on, include/tt.h tt_enc_sync_t)."""
-    import ctypes as C
-    key = (device.type, device.index)
-    if key not in _ORDER_EVENTS:
-        evs = []
-        with torch.cuda.device(device):
-            for _ in range(2):
-                e = C.c_void_p()
-                _lib.check(_lib.lib().tt_event_create(C.byref(e)))
-                evs.append(e.value)
-        _ORDER_EVENTS[key] = tuple(evs)
-    return _ORDER_EVENTS[key]
+def _plan_towers(need, rows, cus, stacked, mode) -> _TowerPlan:
+    """Which towers leave the column-split recurrences so that what is in flight together fits the device: the smallest towers
+    first (fewest rows among equals) until the sum of the others fits.  Arithmetic only: no device, no library call.
+    need: {tower: workgroups its split recurrence occupies; 0: it runs the one-workgroup kernels already}; rows: {tower: rows of
+    its call}; cus: the device's CU count; stacked: a tower has more than one layer.  mode:
+      "ordered"    the direct step, whose calls carry events: the towers stay split in the FORWARD and their recurrences are
+                   ordered; the towers picked take the one-workgroup BACKWARD.  Stacked layers: as "no_events" (the ordering
+                   event is recorded behind a call's LAST recurrence launch, i.e. behind ALL the layers of the smaller tower -- the
+                   document tower's first layer would wait for the whole query tower: 207 us of a 5.5 ms step at the reference's
+                   default shape, profiles/r04_z_config1_train_timeline.txt; the smaller tower's few short sequences on one
+                   workgroup cost it ~90 us off the critical path)
+      "no_events"  calls that cannot carry events (the autograd path, a graph capture): the towers picked take the one-workgroup
+                   recurrences in both directions
+      "forced"     the redo after a recurrence time-out: every tower of `need`, both directions."""
+    if mode == "forced":
+        return _TowerPlan(tuple(need), (), False)
+    left, picked = dict(need), []
+    for t in sorted(left, key=lambda t: (left[t], rows.get(t, 0))):
+        if sum(left.values()) <= cus:
+            break
+        if left[t]:
+            picked.append(t)
+            left[t] = 0
+    if not picked:
+        return _TowerPlan((), (), False)
+    if mode == "ordered" and not stacked:
+        return _TowerPlan((), tuple(picked), True)
+    return _TowerPlan(tuple(picked), (), False)
 
 
 class _towers_in_flight:
@@ -365,12 +401,11 @@ class _towers_in_flight:
     never have more column-split workgroups in flight than the device has CUs.  A split launch needs every member of every
     team resident at once (one workgroup per CU), which ONE launch guarantees against the CU count and two launches on two
     streams do not (query tower 128 + document tower 256 on 256 CUs: round 3 rested on in-order dispatch).  Two ways out, both
-    co-residency BY CONSTRUCTION:
+    co-residency BY CONSTRUCTION (_plan_towers decides; this class gathers its inputs, sets the encoders' flags and puts them back):
       * ordered (the direct step), FORWARD: the towers' recurrence launches are ordered by an event inside the calls
         (tt_enc_sync_t): the query tower's recurrence first, the document tower's behind it, everything else of the two towers
-        still overlaps; the document tower's call goes out in two halves around the query tower's (TT_ENC_PHASE_BEGIN / _FINISH),
-        so that the record is issued before the wait without the document tower's projection waiting for the host.  BACKWARD: the smaller tower runs the
-        one-workgroup recurrence (its workgroups wait for nobody).  Ordering the backwards too was measured and dropped: the query
+        still overlaps (_forward_sequence).  BACKWARD: the smaller tower runs the one-workgroup recurrence (its workgroups wait
+        for nobody).  Ordering the backwards too was measured and dropped: the query
         tower's split recurrence behind the document tower's lands under the document tower's weight-gradient kernels, whose
         one-per-CU workgroups keep it off the CUs until they end (graph replay 1.146 -> 1.207 ms), and in front of it it would
         add its ~100 us to the critical path;
@@ -389,43 +424,27 @@ class _towers_in_flight:
         self._saved = [(e, e.one_workgroup, e.one_workgroup_bwd, e._status_sink) for e in encs]
         if isinstance(self.optimizer, _FlatClipAdam):
             self.optimizer.watch(*encs)
-        self._need = {}
+        self._need, self._cus, self._stacked = {}, 0, any(e.num_layers > 1 for e in encs)
         if self.force:
-            for e in encs:
-                e.one_workgroup, e.one_workgroup_bwd = True, None
+            self._apply(_plan_towers(dict.fromkeys(encs, 0), {}, 0, self._stacked, "forced"))
         elif self.rows and encs[0].embedding.weight.is_cuda:
-            L = _lib.lib()
-            cus = torch.cuda.get_device_properties(encs[0].embedding.weight.device).multi_processor_count
+            self._cus = torch.cuda.get_device_properties(encs[0].embedding.weight.device).multi_processor_count
             self._need = {e: (0 if (e.one_workgroup and e.one_workgroup_bwd is not False) else e.split_workgroups(B))
                           for e, B in self.rows.items()}
-            self.needs_order = sum(self._need.values()) > cus
-            if self.needs_order and any(e.num_layers > 1 for e in encs):
-                # stacked layers: the ordering event is recorded behind a call's LAST recurrence launch, i.e. behind ALL the layers
-                # of the smaller tower -- the document tower's first layer would wait for the whole query tower (207 us of a
-                # 5.5 ms step at the reference's default shape, profiles/r04_z_config1_train_timeline.txt).  The smaller tower
-                # on the one-workgroup recurrences instead: its few short sequences cost it ~90 us off the critical path.
-                self.use_one_workgroup()
-            if self.needs_order:   # the backward: the smaller towers on the one-workgroup recurrence until the sum fits
-                left = dict(self._need)
-                for e in sorted(left, key=lambda e: (left[e], self.rows.get(e, 0))):
-                    if sum(left.values()) <= cus:
-                        break
-                    if left[e]:
-                        e.one_workgroup_bwd, left[e] = True, 0
+            self._apply(_plan_towers(self._need, self.rows, self._cus, self._stacked, "ordered"))
         return self
+
+    def _apply(self, plan: _TowerPlan) -> None:
+        for e in plan.one_workgroup:
+            e.one_workgroup, e.one_workgroup_bwd = True, None
+        for e in plan.one_workgroup_bwd:
+            e.one_workgroup_bwd = True
+        self.needs_order = plan.ordered
 
     def use_one_workgroup(self) -> None:
         """The plan for calls that cannot carry events: the smaller towers on the one-workgroup recurrences until the sum fits."""
-        if not self.needs_order:
-            return
-        cus = torch.cuda.get_device_properties(self.model.query_encoder.embedding.weight.device).multi_processor_count
-        need = self._need
-        for e in sorted(need, key=lambda e: (need[e], self.rows.get(e, 0))):  # smallest first (fewest rows among equals)
-            if sum(need.values()) <= cus:
-                break
-            if need[e]:
-                e.one_workgroup, e.one_workgroup_bwd, need[e] = True, None, 0
-        self.needs_order = False
+        if self.needs_order:
+            self._apply(_plan_towers(self._need, self.rows, self._cus, self._stacked, "no_events"))
 
     def __exit__(self, exc_type, exc, tb):
         for e, one, one_bwd, sink in self._saved:
@@ -436,198 +455,318 @@ class _towers_in_flight:
         return False
 
 
-def _train_step_direct(model: TwoTowerModel, optimizer, queries, pos_docs, neg_docs, margin: float, phase: str = "all",
-                       join_on_caller: bool = False, both: Optional[torch.Tensor] = None, plan: Optional[_towers_in_flight] = None,
-                       seed_words: Optional[dict] = None, negatives: str = "paired", temperature: float = 0.05,
-                       gather_negatives: bool = False):
+# ---- the order of the towers' forward calls ------------------------------------------------------------------------------------
+_DOC, _QRY = 0, 1   # the direct step's tuples are (document tower, query tower): the document tower carries the critical path
+
+
+class _FwdIssue(NamedTuple):
+    tower: int              # _DOC / _QRY
+    phase: int              # 0 = the whole call; _lib.TT_ENC_PHASE_BEGIN / _FINISH = one half of it
+    event: Optional[str]    # "record": behind this call's recurrence; "wait": in front of it; None: the call carries no event
+    one_workgroup: bool     # this call on the one-workgroup recurrence, whatever the encoder's flags say
+
+
+# How the two towers' FORWARD recurrences share the CUs when both column-split would not fit (tools/experiments/fwd_order_ab.py,
+# two_phase_check.py).  The call that RECORDS the ordering event must be issued before the WAIT for it (include/tt.h):
+#   "query_first"        default: the query tower's recurrence first, the document tower's waits for it; the document tower's call
+#                        goes out in two halves around the query tower's -- BEGIN (prep, weight conversion, input projection:
+#                        130 us of GPU work), the query tower (records behind its recurrence), FINISH (waits, then recurrence +
+#                        head) -- so that the document tower's projection does not wait for the host to issue the query tower
+#   "query_first_whole"  the same order of recurrences with whole calls: the query tower's call is issued first
+#   "doc_first"          the document tower's first, the query tower's waits (it has slack at the END of the step, none here: the
+#                        loss needs its output)
+#   "query_one_wg"       no ordering: the query tower on the one-workgroup recurrence beside the document tower's split one
+_FWD_ORDER = "query_first"
+_FORWARD_SEQUENCES = {
+    "query_first": [_FwdIssue(_DOC, _lib.TT_ENC_PHASE_BEGIN, None, False), _FwdIssue(_QRY, 0, "record", False),
+                    _FwdIssue(_DOC, _lib.TT_ENC_PHASE_FINISH, "wait", False)],
+    "query_first_whole": [_FwdIssue(_QRY, 0, "record", False), _FwdIssue(_DOC, 0, "wait", False)],
+    "doc_first": [_FwdIssue(_DOC, 0, "record", False), _FwdIssue(_QRY, 0, "wait", False)],
+    "query_one_wg": [_FwdIssue(_DOC, 0, None, False), _FwdIssue(_QRY, 0, None, True)],
+}
+
+
+def _forward_sequence(ordered: bool, order: str) -> list:
+    """The tower calls of the direct step's forward in the order they are issued.  Not ordered (both towers' split recurrences fit
+    the device, or the plan took one off them): the document tower (2B rows of ~70 tokens: the step's critical path) FIRST, the
+    query tower's ~15 small launches then overlap it instead of delaying it by the ~0.1 ms the host needs to issue them."""
+    if order not in _FORWARD_SEQUENCES:
+        raise ValueError(f"_FWD_ORDER must be one of {sorted(_FORWARD_SEQUENCES)}, got {order!r}")
+    return _FORWARD_SEQUENCES[order] if ordered else [_FwdIssue(_DOC, 0, None, False), _FwdIssue(_QRY, 0, None, False)]
+
+
+_ORDER_EVENTS = {}
+
+
+def _order_events(device):
+    """Two hipEvents per device (tt_event_create: plain HIP events the C calls record / wait on, include/tt.h tt_enc_sync_t)."""
+    key = (device.type, device.index)
+    if key not in _ORDER_EVENTS:
+        evs = []
+        with torch.cuda.device(device):
+            for _ in range(2):
+                e = C.c_void_p()
+                _lib.check(_lib.lib().tt_event_create(C.byref(e)))
+                evs.append(e.value)
+        _ORDER_EVENTS[key] = tuple(evs)
+    return _ORDER_EVENTS[key]
+
+
+# ---- the direct step ---------------------------------------------------------------------------------------------------------
+class _Capture(NamedTuple):
+    """What only a direct step under stream capture carries (GraphedTrainStep).  Such a step joins the towers' streams on the
+    CALLER's stream (loss and optimizer run there) instead of on the document tower's.  Eagerly that would cost two hops per join
+    on the critical path (~20 us each); under capture it is free (the hops are graph edges) and it is the only form this ROCm can
+    capture: a side stream that waits for ANOTHER side stream and then goes on makes hipStreamEndCapture crash inside the runtime
+    (tools/experiments/graph_pattern_probe.py: fork / join through the origin stream is fine, side-to-side joins segfault,
+    whatever the kernels).  For the same reason it carries no ordering events (an event edge between the two tower streams is a
+    side-to-side edge; with the query tower moved onto the capturing stream it can be captured, but replays slower: 1.19-1.21 ms
+    against 1.16 with the smaller tower on the one-workgroup recurrences, profiles/r04_m_graph_probe.log)."""
+    phase: str                          # "all" = through optimizer.step(); "fold" = up to the gate words behind the gradients
+    #                                     (optimizer._fold_status): the caller reduces and applies -- with a process group the
+    #                                     all-reduce stays outside the captured graph
+    both: Optional[torch.Tensor]        # the 2B-row document batch [pos_docs; neg_docs], staged outside the graph (None: the batch's)
+    seed_words: Optional[dict]          # {id(encoder): device int64[1]}: the towers' dropout seeds as device words the kernels read
+    #                                     when they run (TT_ENC_SEED_ON_DEVICE); None: drawn in the step, passed by value
+
+
+class _TowerForward(NamedTuple):
+    """What a tower's forward leaves for its backward."""
+    out: torch.Tensor
+    ws: torch.Tensor
+    status: torch.Tensor
+    dropout_p: float
+    seed: object
+    opts_bwd: int
+
+
+class _DirectStep:
+    """One direct step in flight: what its stages -- forward towers, loss, backward towers, apply or fold -- hand to each other."""
+
+    def __init__(self, model, optimizer, spec, capture):
+        self.model, self.optimizer, self.spec, self.capture = model, optimizer, spec, capture
+        self.encs = (model.doc_encoder, model.query_encoder)
+        self.ordered = False     # the forward recurrences are ordered by events (syncs: what a call of each kind carries)
+        self.into = self.ids_of = self.streams = self.cur = self.s_main = self.syncs = None
+        self.fw = [None, None]
+        self.loss = self.d_out = None
+
+    def join(self):   # s_main waits for both towers
+        for t in reversed(self.streams):
+            if t is not self.s_main:
+                self.s_main.wait_stream(t)
+
+    def fork(self):   # both towers wait for s_main
+        for t in reversed(self.streams):
+            if t is not self.s_main:
+                t.wait_stream(self.s_main)
+
+
+def _standard_batch(batch) -> bool:
+    """Ids on the GPU, as many negatives as positives as queries, the documents int64 already (tt_concat_ids_i64 reads them as
+    they are): the batch of the direct step and of a captured one."""
+    queries, pos_docs, neg_docs = batch
+    return (queries.is_cuda and neg_docs.shape[0] == pos_docs.shape[0] == queries.shape[0]
+            and pos_docs.dtype == neg_docs.dtype == torch.int64)
+
+
+def _frozen_tables(model: TwoTowerModel) -> bool:
+    return not any(e.embedding.weight.requires_grad for e in (model.doc_encoder, model.query_encoder))
+
+
+def _direct_grad_views(model, optimizer, batch, spec, capture):
+    """Does the direct step apply -- and if so, into which of the optimizer's gradient views the towers' backwards write: [the
+    document tower's, the query tower's], one view per _flat_params() entry.  None: it does not (the step was asked not to, a
+    batch of another shape, another optimizer, a trainable embedding table, a tower in eval mode, parameters without the
+    optimizer's gradient views or views no tower call would write, an exchange of passages inside a capture or without a
+    Collective): the caller takes the autograd path, which computes the same numbers.  Looks, touches nothing."""
+    if not isinstance(optimizer, _FlatClipAdam) or not torch.is_grad_enabled():
+        return None
+    if capture is None and not (spec.direct and spec.concurrent_towers):
+        return None
+    if (capture is None or capture.both is None) and not _standard_batch(batch):
+        return None
+    if spec.gather_negatives and (capture is not None or getattr(optimizer, "_coll", None) is None):
+        return None
+    encs = (model.doc_encoder, model.query_encoder)
+    if not _frozen_tables(model) or not all(enc.training for enc in encs):
+        return None
+    views = {id(p): gv for p, gv in zip(optimizer.params, optimizer._views)}
+    params = [enc._flat_params() for enc in encs]
+    if any(id(p) not in views for ps in params for p in ps) or len({id(p) for ps in params for p in ps}) != len(optimizer.params):
+        return None
+    return [[views[id(p)] for p in ps] for ps in params]
+
+
+def _forward_towers(st: _DirectStep, batch) -> None:
+    queries, pos_docs, neg_docs = batch
+    s_doc = st.streams[_DOC]
+    both = st.capture.both if st.capture is not None else None
+    if both is None:
+        with torch.cuda.stream(s_doc):  # (on the document tower's own stream: no hop from the caller's)
+            pos_docs.record_stream(s_doc)
+            neg_docs.record_stream(s_doc)
+            both = _concat_ids(pos_docs, neg_docs)
+    st.ids_of = (both, queries)
+    # dropout seeds from torch's CPU generator in the order the autograd path draws them (query tower, then document tower)
+    seeds = st.capture.seed_words if st.capture is not None and st.capture.seed_words is not None else _draw_dropout_seeds(st.model)
+    begun = None
+    for tower, phase, event, one_workgroup in _forward_sequence(st.ordered, _FWD_ORDER):
+        enc, ids, s = st.encs[tower], st.ids_of[tower], st.streams[tower]
+        if s is not st.cur and phase != _lib.TT_ENC_PHASE_FINISH:
+            s.wait_stream(st.cur)
+        with torch.cuda.stream(s):
+            ids.record_stream(s)
+            p_drop, seed = enc.dropout, seeds[id(enc)]
+            # (the encoders are watched -- _towers_in_flight -- so the status word goes to the optimizer instead of a read here)
+            res = enc._run_forward(ids, train=True, dropout_p=p_drop, dropout_seed=seed, sync=st.syncs[event], phase=phase,
+                                   resume=begun if phase == _lib.TT_ENC_PHASE_FINISH else None,
+                                   opts=enc._opts() | _lib.TT_ENC_ONE_WORKGROUP if one_workgroup else None)
+            if phase == _lib.TT_ENC_PHASE_BEGIN:
+                begun = res
+            else:
+                st.fw[tower] = _TowerForward(*res, p_drop, seed, enc._opts_bwd())
+
+
+def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main):
+    """The fused loss + gradient launch of the step's kind on s_main (the current stream): (loss, dq, dpn) for the towers' outputs
+    q [B,H] and pn [2B,H] (positives, then negatives).  The kinds share the buffers; "in_batch" swaps the one launch, nothing else.
+    gather_negatives: the loss runs over the passages of ALL ranks: all-gather of pn into the pool G [world * 2B, H] (rank order),
+    tt_contrastive_loss_f32(q, G, pos_offset = rank * 2B) -> loss, dq, dG, summing all-reduce of dG, dpn = this rank's 2B rows of
+    it.  Both collectives go out whatever the towers' status words say, in front of the query tower's reduce_prefix: every rank
+    issues gather, reduce, (prefix,) bucket in that order."""
+    (B, H), dev = q.shape, q.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dq = torch.empty_like(q)
+    if spec.gather_negatives:
+        coll = optimizer._coll
+        pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
+        d_pool = torch.empty_like(pool)
+        dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
+        rows = contrastive_workspace(B, pool.shape[0], H, dev)
+    else:
+        dpn = torch.empty_like(pn)
+        rows = in_batch_workspace(B, H, dev) if spec.negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
+    for t in (q, pn, loss, dq, dpn, rows):
+        t.record_stream(s_main)
+    L, p, n = _lib.lib(), pn[:B], pn[B:]
+    with torch.cuda.device(dev):
+        if spec.gather_negatives:
+            coll.all_gather_blocks(pn, pool)
+            _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
+                                                 float(spec.temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
+                                                 rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+            # (no scale: a summed row is sum_r d loss_r / d D_j, and the optimizer's 1 / world makes it the mean's)
+            coll.all_reduce_sum(d_pool.view(-1))
+        elif spec.negatives == "in_batch":
+            _lib.check(L.tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(spec.temperature),
+                                              loss.data_ptr(), dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(),
+                                              rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+        else:
+            _lib.check(L.tt_triplet_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(spec.margin), loss.data_ptr(),
+                                             dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(), rows.data_ptr(),
+                                             s_main.cuda_stream))
+    return loss, dq, dpn
+
+
+def _loss_and_embedding_grads(st: _DirectStep) -> None:
+    """On the stream where the towers meet.  Eagerly that is the document tower's: it carries the step's critical path from here
+    on -- the loss, the document backward and the optimizer are enqueued on IT (a hop to the caller's stream and back cost ~20 us
+    each way on that path: event wait + launch); the query tower's stream joins for the loss and again before the optimizer."""
+    st.join()
+    with torch.cuda.stream(st.s_main):
+        st.loss, dq, dpn = _direct_loss(st.spec, st.optimizer, st.fw[_QRY].out, st.fw[_DOC].out, st.s_main)
+    st.d_out = (dpn, dq)
+
+
+def _complete_prefix(optimizer, grads) -> int:
+    """How many of the bucket's leading gradients `grads` are, when they are its prefix without a gap (0: they are not)."""
+    base = optimizer.flat_grads.data_ptr()
+    spans = sorted(((g.data_ptr() - base) // 4, g.numel()) for g in grads)
+    if spans[0][0] == 0 and all(a + n == b for (a, n), (b, _) in zip(spans, spans[1:])):
+        return spans[-1][0] + spans[-1][1]
+    return 0
+
+
+def _backward_towers(st: _DirectStep) -> None:
+    """Each tower's backward on its own stream, written STRAIGHT into the optimizer's gradient views.  No events: the plan gave
+    the smaller tower the one-workgroup recurrence (_towers_in_flight)."""
+    optimizer = st.optimizer
+    st.fork()
+    for enc, ids, s, f, d_out, grads in zip(st.encs, st.ids_of, st.streams, st.fw, st.d_out, st.into):
+        with torch.cuda.stream(s):
+            d_out.record_stream(s)
+            # (a time-out of the split backward recurrence ORs bit 2 into the forward's word, which the optimizer reads)
+            enc._run_backward(ids.contiguous(), f.ws, d_out, f.dropout_p, f.seed, into=grads, status=f.status, opts=f.opts_bwd)
+            if enc is st.model.query_encoder and optimizer.world > 1 and st.capture is None:
+                # data-parallel: the query tower's gradients are complete long before the document tower's (its backward is
+                # a tenth of the tokens) -- when they are the bucket's prefix their all-reduce goes out HERE, on the query
+                # tower's stream, and runs under the document tower's weight-gradient kernels; the rest of the bucket (with
+                # the gate words) follows in optimizer.step()
+                upto = _complete_prefix(optimizer, grads)
+                if upto:
+                    optimizer.reduce_prefix(upto)
+    st.join()
+
+
+def _apply_or_fold(st: _DirectStep) -> None:
+    optimizer = st.optimizer
+    for p_, gv in zip(optimizer.params, optimizer._views):
+        p_.grad = gv
+    with torch.cuda.stream(st.s_main):
+        # The optimizer is enqueued unconditionally: the towers' status words (zero-length rows / ids out of range raise as
+        # in the reference; a column-split recurrence that gave up) are folded into the gate behind the gradients, reduced
+        # over the ranks with them, and the device applies the step on every rank or on none.  The read of the reduced gate
+        # inside step() is the one host synchronisation of the step; for a bad batch the weights stay untouched (the
+        # gradient buffer holds garbage, which the next step overwrites).
+        for t in (optimizer.flat_params, optimizer._bucket, optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.total_norm,
+                  optimizer._scratch, optimizer._step_dev):
+            t.record_stream(st.s_main)
+        if st.capture is None or st.capture.phase == "all":
+            optimizer.step()
+        else:
+            optimizer._fold_status()
+
+
+def _train_step_direct(model: TwoTowerModel, optimizer, batch, spec: _StepSpec, plan: Optional[_towers_in_flight],
+                       capture: Optional[_Capture]):
     """The same step without the autograd engine: tower forwards (train mode), the fused loss + gradient kernel, tower backwards
     written STRAIGHT into the optimizer's flat gradient buffer, optimizer step.  Every parameter receives its gradient exactly
     once (query tower once; positives and negatives as one 2B-row document-tower call), so nothing has to be zeroed or
     accumulated: what the autograd path adds per step -- grad_output plumbing around the loss, four accumulate-adds per
     tower, the 3.4 MB zero fill -- is ~0.1 ms of small launches on the document tower's critical path.  Returns None when the
-    shortcut does not apply (another optimizer, a trainable embedding table, parameters without the optimizer's gradient
-    views): the caller then takes the autograd path, which computes the same numbers.
-    phase: "all" = through optimizer.step(); "fold" = up to the gate words behind the gradients (optimizer._fold_status), the
-    caller reduces and applies (GraphedTrainStep with a process group: the all-reduce stays outside the captured graph).
-    join_on_caller: the towers' streams meet on the CALLER's stream (loss and optimizer run there) instead of on the document
-    tower's.  Eagerly that costs two hops per join on the critical path (~20 us each); under stream capture it is free (the hops
-    are graph edges) and it is the only form this ROCm can capture: a side stream that waits for ANOTHER side stream and then
-    goes on makes hipStreamEndCapture crash inside the runtime (tools/experiments/graph_pattern_probe.py: fork / join through
-    the origin stream is fine, side-to-side joins segfault, whatever the kernels).
-    both: the 2B-row document batch [pos_docs; neg_docs] already concatenated (GraphedTrainStep stages it outside the graph).
-    plan: the step's _towers_in_flight; when the two towers' split recurrences do not fit the device together their recurrence
-    launches are ordered with events (query tower's first in the forward, last in the backward).
-    seed_words: {id(encoder): device int64[1]} -- the towers' dropout seeds as device words the kernels read when they run
-    (TT_ENC_SEED_ON_DEVICE: GraphedTrainStep writes a fresh seed there before every replay); default: drawn here, passed by value.
-    negatives / temperature: see train_step; "in_batch" swaps the one loss call (same q, pn, dq, dpn buffers), nothing else.
-    gather_negatives: the loss runs over the passages of ALL ranks, on the stream where the towers meet: all-gather of pn into the
-    pool G [world * 2B, H] (rank order), tt_contrastive_loss_f32(q, G, pos_offset = rank * 2B) -> loss, dq, dG, summing
-    all-reduce of dG, dpn = this rank's 2B rows of it.  Both collectives go out whatever the towers' status words say, in front
-    of the query tower's reduce_prefix: every rank issues gather, reduce, (prefix,) bucket in that order."""
-    if not isinstance(optimizer, _FlatClipAdam) or not torch.is_grad_enabled():
+    shortcut does not apply (_direct_grad_views): the caller then takes the autograd path.
+    batch: (queries, pos_docs, neg_docs); plan: the step's _towers_in_flight -- when the two towers' split recurrences do not fit
+    the device together their forward recurrence launches are ordered with events; capture: None for the eager step."""
+    st = _DirectStep(model, optimizer, spec, capture)
+    st.into = _direct_grad_views(model, optimizer, batch, spec, capture)
+    if st.into is None:
         return None
-    if gather_negatives and (join_on_caller or getattr(optimizer, "_coll", None) is None):
-        return None  # (no exchange inside a capture; no Collective to exchange with)
-    encs = (model.doc_encoder, model.query_encoder)
-    views = {id(p): gv for p, gv in zip(optimizer.params, optimizer._views)}
-    into = []
-    for enc in encs:
-        ps = enc._flat_params()
-        if enc.embedding.weight.requires_grad or not enc.training or any(id(p) not in views for p in ps):
-            return None
-        into.append([views[id(p)] for p in ps])
-    if len({id(p) for enc in encs for p in enc._flat_params()}) != len(optimizer.params):
-        return None  # (the optimizer holds parameters no tower call would write)
-    dev = queries.device
-    cur = torch.cuda.current_stream(dev)
-    B = queries.shape[0]
-    streams = _tower_streams(dev)[:2]
-    if both is None and (pos_docs.dtype != torch.int64 or neg_docs.dtype != torch.int64):
-        return None
-    s_doc, s_qry = streams
-    if join_on_caller and plan is not None:
-        # a capture: no ordering events (an event edge between the two tower streams is a side-to-side edge, which this ROCm
-        # cannot capture; with the query tower moved onto the capturing stream it can, but replays slower: 1.19-1.21 ms against
-        # 1.16 with the smaller tower on the one-workgroup recurrences, profiles/r04_m_graph_probe.log)
-        plan.use_one_workgroup()
-    s_main = cur if join_on_caller else s_doc     # where the towers meet: loss, optimizer
-    ordered = plan is not None and plan.needs_order
-    sync_f = sync_b = {}
-    fwd_opts = {}
-    two_phase = _TWO_PHASE
-    if ordered:
-        ev_f, ev_b = _order_events(dev)
-        q_enc, d_enc = model.query_encoder, model.doc_encoder
-        if _FWD_ORDER == "doc_first":
-            sync_f = {id(d_enc): _lib.EncSync(None, ev_f), id(q_enc): _lib.EncSync(ev_f, None)}   # document records, query waits
-            two_phase = None
-        elif _FWD_ORDER == "query_one_wg":
-            fwd_opts[id(q_enc)] = q_enc._opts() | _lib.TT_ENC_ONE_WORKGROUP
-            two_phase = None
-        else:
-            sync_f = {id(q_enc): _lib.EncSync(None, ev_f), id(d_enc): _lib.EncSync(ev_f, None)}   # query records, document waits
-        # (backward: no events -- the plan gave the smaller tower the one-workgroup recurrence, _towers_in_flight)
-
-    def join():   # s_main waits for both towers
-        for t in (s_qry, s_doc):
-            if t is not s_main:
-                s_main.wait_stream(t)
-
-    def fork():   # both towers wait for s_main
-        for t in (s_qry, s_doc):
-            if t is not s_main:
-                t.wait_stream(s_main)
+    dev = batch[0].device
+    st.cur = cur = torch.cuda.current_stream(dev)
+    st.streams = s_doc, s_qry = _tower_streams(dev)[:2]
+    if capture is not None and plan is not None:
+        plan.use_one_workgroup()      # (no ordering events in a capture: _Capture)
+    st.ordered = plan is not None and plan.needs_order
+    st.s_main = cur if capture is not None else s_doc     # where the towers meet: loss, optimizer
+    st.syncs = {None: None}
+    if st.ordered:
+        ev_f, _ = _order_events(dev)
+        st.syncs.update(record=_lib.EncSync(None, ev_f), wait=_lib.EncSync(ev_f, None))
     try:
         s_doc.wait_stream(cur)
-        if both is None:
-            with torch.cuda.stream(s_doc):  # (on the document tower's own stream: no hop from the caller's)
-                pos_docs.record_stream(s_doc)
-                neg_docs.record_stream(s_doc)
-                both = _concat_ids(pos_docs, neg_docs)
-        ids_of = (both, queries)
-        # dropout seeds from torch's CPU generator in the order the autograd path draws them (query tower, then document tower)
-        seeds = seed_words if seed_words is not None else _draw_dropout_seeds(model)
-        # Issue order: the document tower (2B rows of ~70 tokens: the step's critical path) FIRST, the query tower's ~15 small
-        # launches then overlap it instead of delaying it by the ~0.1 ms the host needs to issue them.  Ordered recurrences: the
-        # call that RECORDS the ordering event must be issued before the WAIT for it (include/tt.h), so the document tower's call
-        # goes out in two halves around the query tower's: BEGIN (prep, weight conversion, input projection: 130 us of GPU
-        # work), the query tower (records behind its recurrence), FINISH (waits, then recurrence + head).
-        fw = [None, None]
-        begun = None
-        for k, half in (((0, 0), (1, 0)) if (not ordered or two_phase is None) else
-                        (((0, _lib.TT_ENC_PHASE_BEGIN), (1, 0), (0, _lib.TT_ENC_PHASE_FINISH)) if two_phase else ((1, 0), (0, 0)))):
-            enc, ids, s = encs[k], ids_of[k], streams[k]
-            if s is not cur and half != _lib.TT_ENC_PHASE_FINISH:
-                s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                ids.record_stream(s)
-                p_drop = enc.dropout
-                seed = seeds[id(enc)]
-                # (the encoders are watched -- _towers_in_flight -- so the status word goes to the optimizer instead of a read here)
-                res = enc._run_forward(ids, train=True, dropout_p=p_drop, dropout_seed=seed, sync=sync_f.get(id(enc)) if half != _lib.TT_ENC_PHASE_BEGIN else None,
-                                       phase=half, resume=begun if half == _lib.TT_ENC_PHASE_FINISH else None, opts=fwd_opts.get(id(enc)))
-                if half == _lib.TT_ENC_PHASE_BEGIN:
-                    begun = res
-                    continue
-                out, ws, status = res
-                fw[k] = (out, ws, status, p_drop, seed, enc._opts_bwd())
-        # The document tower's stream carries the step's critical path from here on: the loss, the document backward and the
-        # optimizer are enqueued on IT (a hop to the caller's stream and back cost ~20 us each way on that path: event wait +
-        # launch); the query tower's stream joins for the loss and again before the optimizer.
-        pn, q = fw[0][0], fw[1][0]
-        p, n = pn[:B], pn[B:]
-        H = q.shape[1]
-        join()
-        with torch.cuda.stream(s_main):
-            loss = torch.empty((), dtype=torch.float32, device=dev)
-            dq = torch.empty_like(q)
-            if gather_negatives:
-                coll = optimizer._coll
-                pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
-                d_pool = torch.empty_like(pool)
-                dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
-                rows = contrastive_workspace(B, pool.shape[0], H, dev)
-            else:
-                dpn = torch.empty_like(pn)
-                rows = in_batch_workspace(B, H, dev) if negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
-            for t in (q, pn, loss, dq, dpn, rows):
-                t.record_stream(s_main)
-            with torch.cuda.device(dev):
-                if gather_negatives:
-                    coll.all_gather_blocks(pn, pool)
-                    _lib.check(_lib.lib().tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
-                                                                  float(temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
-                                                                  rows.data_ptr(), rows.numel(), s_main.cuda_stream))
-                    # (no scale: a summed row is sum_r d loss_r / d D_j, and the optimizer's 1 / world makes it the mean's)
-                    coll.all_reduce_sum(d_pool.view(-1))
-                elif negatives == "in_batch":
-                    _lib.check(_lib.lib().tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(temperature),
-                                                               loss.data_ptr(), dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(),
-                                                               rows.data_ptr(), rows.numel(), s_main.cuda_stream))
-                else:
-                    _lib.check(_lib.lib().tt_triplet_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(margin), loss.data_ptr(),
-                                                              dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(), rows.data_ptr(),
-                                                              s_main.cuda_stream))
-        fork()
-        for enc, ids, s, f, d_out, grads in zip(encs, ids_of, streams, fw, (dpn, dq), into):
-            with torch.cuda.stream(s):
-                d_out.record_stream(s)
-                # (a time-out of the split backward recurrence ORs bit 2 into the forward's word, which the optimizer reads)
-                enc._run_backward(ids.contiguous(), f[1], d_out, f[3], f[4], into=grads, status=f[2], opts=f[5],
-                                  sync=sync_b.get(id(enc)))
-                if enc is model.query_encoder and optimizer.world > 1 and not join_on_caller:
-                    # data-parallel: the query tower's gradients are complete long before the document tower's (its backward is
-                    # a tenth of the tokens) -- when they are the bucket's prefix their all-reduce goes out HERE, on the query
-                    # tower's stream, and runs under the document tower's weight-gradient kernels; the rest of the bucket (with
-                    # the gate words) follows in optimizer.step()
-                    base = optimizer.flat_grads.data_ptr()
-                    spans = sorted(((g.data_ptr() - base) // 4, g.numel()) for g in grads)
-                    if spans[0][0] == 0 and all(a + n == b for (a, n), (b, _) in zip(spans, spans[1:])):
-                        optimizer.reduce_prefix(spans[-1][0] + spans[-1][1])
-        join()
-        for p_, gv in zip(optimizer.params, optimizer._views):
-            p_.grad = gv
-        with torch.cuda.stream(s_main):
-            # The optimizer is enqueued unconditionally: the towers' status words (zero-length rows / ids out of range raise as
-            # in the reference; a column-split recurrence that gave up) are folded into the gate behind the gradients, reduced
-            # over the ranks with them, and the device applies the step on every rank or on none.  The read of the reduced gate
-            # inside step() is the one host synchronisation of the step; for a bad batch the weights stay untouched (the
-            # gradient buffer holds garbage, which the next step overwrites).
-            for t in (optimizer.flat_params, optimizer._bucket, optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.total_norm,
-                      optimizer._scratch, optimizer._step_dev):
-                t.record_stream(s_main)
-            if phase == "all":
-                optimizer.step()
-            else:
-                optimizer._fold_status()
+        _forward_towers(st, batch)
+        _loss_and_embedding_grads(st)
+        _backward_towers(st)
+        _apply_or_fold(st)
     finally:
         # (also when step() raised: the caller's stream joins the towers' streams, nothing of this step is left running
         #  behind the caller's back)
         for t in (s_qry, s_doc):
             if t is not cur:
                 cur.wait_stream(t)
-    loss.record_stream(cur)
-    return loss
+    st.loss.record_stream(cur)
+    return st.loss
 
 
 def _draw_dropout_seeds(model: TwoTowerModel) -> dict:
@@ -637,16 +776,7 @@ def _draw_dropout_seeds(model: TwoTowerModel) -> dict:
             for enc in (model.query_encoder, model.doc_encoder)}
 
 
-def _check_negatives(negatives: str, gather_negatives: bool = False, graphs: bool = False) -> None:
-    if negatives not in ("paired", "in_batch"):
-        raise ValueError(f'negatives must be "paired" or "in_batch", got {negatives!r}')
-    if gather_negatives and negatives != "in_batch":
-        raise ValueError(f'gather_negatives=True needs negatives="in_batch", got negatives={negatives!r}')
-    if gather_negatives and graphs:
-        raise ValueError("gather_negatives=True is not available with graphs=True (the exchange of the passages sits between the "
-                         "captured forward and backward)")
-
-
+# ---- the autograd step and the entries ---------------------------------------------------------------------------------------
 class _GatherPoolFn(torch.autograd.Function):
     """This rank's passages pn [2B,H] -> the pool of all ranks [world * 2B, H], rank order (Collective.all_gather_blocks).
     Backward: summing all-reduce of the pool's gradient -- every rank's loss has a gradient for every row -- and this rank's rows."""
@@ -666,29 +796,31 @@ class _GatherPoolFn(torch.autograd.Function):
         return d_pool[ctx.coll.rank * ctx.rows:(ctx.coll.rank + 1) * ctx.rows], None
 
 
-def _gathered_loss(optimizer, q, p, n, pn, temperature):
-    """The autograd form of the gathered step: the loss of this rank's queries over the passages of all ranks."""
-    coll = getattr(optimizer, "_coll", None)
-    if coll is None:
-        raise ValueError("gather_negatives=True needs a FusedClipAdam (the passages travel through its Collective)")
-    if pn is None:
-        pn = torch.cat((p, n))
-    return contrastive_softmax_loss(q, _GatherPoolFn.apply(pn, coll), pos_offset=coll.rank * pn.shape[0], temperature=temperature)
+def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn):
+    """The loss of the step's kind as an autograd graph over the towers' outputs (q, p, n); pn: the 2B passages as one tensor
+    when the document tower ran once (None: it did not).  Gathered: the loss of this rank's queries over the passages of all ranks."""
+    if spec.gather_negatives:
+        coll = getattr(optimizer, "_coll", None)
+        if coll is None:
+            raise ValueError("gather_negatives=True needs a FusedClipAdam (the passages travel through its Collective)")
+        if pn is None:
+            pn = torch.cat(embeddings[1:])
+        return contrastive_softmax_loss(embeddings[0], _GatherPoolFn.apply(pn, coll), pos_offset=coll.rank * pn.shape[0],
+                                        temperature=spec.temperature)
+    if spec.negatives == "in_batch":
+        return in_batch_softmax_loss(embeddings, temperature=spec.temperature)
+    return triplet_loss_cosine(embeddings, margin=spec.margin)
 
 
-def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan=None,
-                     negatives="paired", temperature=0.05, gather_negatives=False):
-    if direct and concurrent_towers and queries.is_cuda and neg_docs.shape[0] == pos_docs.shape[0] == queries.shape[0]:
-        loss = _train_step_direct(model, optimizer, queries, pos_docs, neg_docs, margin, plan=plan, negatives=negatives,
-                                  temperature=temperature, gather_negatives=gather_negatives)
-        if loss is not None:
-            return loss
-    if plan is not None:
-        plan.use_one_workgroup()   # (autograd calls cannot carry the ordering events)
+def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_flight):
+    loss = _train_step_direct(model, optimizer, batch, spec, plan, None)
+    if loss is not None:
+        return loss
+    plan.use_one_workgroup()   # (autograd calls cannot carry the ordering events)
+    queries, pos_docs, neg_docs = batch
     optimizer.zero_grad()
-    watched = isinstance(optimizer, _FlatClipAdam)
     pn = None   # (the 2B passages as one tensor, when the document tower ran once)
-    if concurrent_towers and queries.is_cuda:
+    if spec.concurrent_towers and queries.is_cuda:
         cur = torch.cuda.current_stream(queries.device)
         B = pos_docs.shape[0]
         if neg_docs.shape[0] == B:
@@ -709,7 +841,7 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
             for s, o in zip(_tower_streams(queries.device), outs):
                 cur.wait_stream(s)
                 o.record_stream(cur)
-        if watched:
+        if isinstance(optimizer, _FlatClipAdam):
             launch()  # (the status words go to the optimizer, which reads them -- reduced over the ranks -- in step())
         else:
             # another optimizer: input checking stays on (zero-length rows / out-of-range ids raise as in the reference), but the
@@ -726,15 +858,46 @@ def _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, conc
         q = model.encode_query(queries)
         p = model.encode_document(pos_docs)
         n = model.encode_document(neg_docs)
-    if gather_negatives:
-        loss = _gathered_loss(optimizer, q, p, n, pn, temperature)
-    elif negatives == "in_batch":
-        loss = in_batch_softmax_loss((q, p, n), temperature=temperature)
-    else:
-        loss = triplet_loss_cosine((q, p, n), margin=margin)
+    loss = _autograd_loss(spec, optimizer, (q, p, n), pn)
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+def _eager_step(model, optimizer, batch, spec: _StepSpec):
+    """One step with the read of the gate wherever optimizer.check puts it; a time-out of a column-split recurrence redoes the
+    step on the one-workgroup kernels (ordinary relaunch, same bits as the split forward)."""
+    queries, pos_docs, neg_docs = batch
+    encs = (model.query_encoder, model.doc_encoder)
+    n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (spec.concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
+        pos_docs.shape[0], neg_docs.shape[0])
+    rows = {model.query_encoder: queries.shape[0], model.doc_encoder: n_doc} if spec.concurrent_towers else {}
+    rng = torch.get_rng_state() if any(e.dropout > 0.0 and e.training for e in encs) else None
+    try:
+        with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
+            return _train_step_once(model, optimizer, batch, spec, plan)
+    except SplitRecurrenceTimeout:
+        if rng is not None:
+            torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
+        with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
+            return _train_step_once(model, optimizer, batch, spec, plan)
+
+
+def _step(model, optimizer, batch, spec: _StepSpec, defer_check: bool):
+    """train_step behind its argument list (DataParallelTrainer.step enters here with its own record)."""
+    queries, pos_docs, neg_docs = batch
+    if spec.gather_negatives and not queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]:
+        raise ValueError("gather_negatives=True needs as many negatives as positives as queries")
+    if not (defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda):
+        return _eager_step(model, optimizer, batch, spec)
+    keep, optimizer.check = optimizer.check, False
+    try:
+        loss = _eager_step(model, optimizer, batch, spec)
+    finally:
+        optimizer.check = keep
+    if keep:
+        optimizer.snapshot_gate(redo=lambda: _eager_step(model, optimizer, batch, spec))
+    return loss
 
 
 def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Tensor, pos_docs: torch.Tensor,
@@ -772,37 +935,8 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     Every rank must bring the same B.  Returns the rank's own loss: the mean over its B queries against the global pool.
     Both collectives are issued whatever the batch holds, so failure stays collective (above); a redo after a recurrence
     time-out repeats them on all ranks.  One process without a group: the same bits as without the flag."""
-    from .model import SplitRecurrenceTimeout
-    _check_negatives(negatives, gather_negatives)
-    if gather_negatives and not queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]:
-        raise ValueError("gather_negatives=True needs as many negatives as positives as queries")
-    if defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda:
-        keep, optimizer.check = optimizer.check, False
-        try:
-            loss = train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
-                              negatives=negatives, temperature=temperature, gather_negatives=gather_negatives)
-        finally:
-            optimizer.check = keep
-        if keep:
-            optimizer.snapshot_gate(redo=lambda: train_step(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct,
-                                                            negatives=negatives, temperature=temperature,
-                                                            gather_negatives=gather_negatives))
-        return loss
-    encs = (model.query_encoder, model.doc_encoder)
-    n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
-        pos_docs.shape[0], neg_docs.shape[0])
-    rows = {model.query_encoder: queries.shape[0], model.doc_encoder: n_doc} if concurrent_towers else {}
-    rng = torch.get_rng_state() if any(e.dropout > 0.0 and e.training for e in encs) else None
-    try:
-        with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
-            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
-                                    negatives, temperature, gather_negatives)
-    except SplitRecurrenceTimeout:
-        if rng is not None:
-            torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
-        with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
-            return _train_step_once(model, optimizer, queries, pos_docs, neg_docs, margin, concurrent_towers, direct, plan,
-                                    negatives, temperature, gather_negatives)
+    spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct).checked(graphs=False)
+    return _step(model, optimizer, (queries, pos_docs, neg_docs), spec, defer_check)
 
 
 class DataParallelTrainer:
@@ -821,14 +955,18 @@ class DataParallelTrainer:
     def __init__(self, model: TwoTowerModel, lr: float = 1e-4, margin: float = 0.2, max_norm: float = 1.0, group=None,
                  graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False,
                  negatives: str = "paired", temperature: float = 0.05, gather_negatives: bool = False):
-        _check_negatives(negatives, gather_negatives, graphs)
-        self.model = model
+        self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
         self.margin = margin
         self.negatives, self.temperature, self.gather_negatives = negatives, float(temperature), bool(gather_negatives)
+        self._spec()
+        self.model = model
         self.optimizer = FusedClipAdam(model.parameters(), lr=lr, max_norm=max_norm, group=group)
         self.optimizer.watch(model)  # (a hand-written loop over self.model / self.optimizer fails collectively too)
-        self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
         self._graphs: "dict" = {}
+
+    def _spec(self) -> _StepSpec:
+        """What a step does now (the attributes may be changed between steps)."""
+        return _StepSpec(self.margin, self.negatives, self.temperature, self.gather_negatives, True, True).checked(self.graphs)
 
     def broadcast_parameters(self, src: int = 0) -> None:
         import torch.distributed as dist
@@ -836,11 +974,10 @@ class DataParallelTrainer:
             dist.broadcast(self.optimizer.flat_params, src=src, group=self.optimizer.group)
         self.optimizer.mark_params_changed()  # (the broadcast wrote the flat buffer, not the parameter tensors)
 
-    def _graph_for(self, queries, pos_docs, neg_docs) -> Optional["GraphedTrainStep"]:
-        encs = (self.model.query_encoder, self.model.doc_encoder)
-        if not (queries.is_cuda and queries.dtype == pos_docs.dtype == neg_docs.dtype == torch.int64
-                and queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]
-                and all(e.check_inputs and not e.embedding.weight.requires_grad for e in encs)):
+    def _graph_for(self, batch, spec: _StepSpec) -> Optional["GraphedTrainStep"]:
+        queries, pos_docs, neg_docs = batch
+        if not (_standard_batch(batch) and queries.dtype == torch.int64 and _frozen_tables(self.model)
+                and self.model.query_encoder.check_inputs and self.model.doc_encoder.check_inputs):
             return None
         up = lambda x: max(self.width_step, -(-int(x) // self.width_step) * self.width_step)  # noqa: E731
         key = (queries.shape[0], up(queries.shape[1]), up(max(pos_docs.shape[1], neg_docs.shape[1])))
@@ -848,8 +985,8 @@ class DataParallelTrainer:
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
                 self._graphs.pop(next(iter(self._graphs)))
-            g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], self.margin, defer_check=self.defer_check,
-                                 negatives=self.negatives, temperature=self.temperature)
+            g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], spec.margin, defer_check=self.defer_check,
+                                 negatives=spec.negatives, temperature=spec.temperature)
         self._graphs[key] = g                                      # (re-inserted: most recently used last)
         return g
 
@@ -859,23 +996,34 @@ class DataParallelTrainer:
 
     def step(self, queries, pos_docs, neg_docs) -> torch.Tensor:
         self.model.train()
+        batch, spec = (queries, pos_docs, neg_docs), self._spec()
         if self.graphs:
-            g = self._graph_for(queries, pos_docs, neg_docs)
+            g = self._graph_for(batch, spec)
             if g is not None:
                 return g(queries, pos_docs, neg_docs)
-        return train_step(self.model, self.optimizer, queries, pos_docs, neg_docs, self.margin, defer_check=self.defer_check,
-                          negatives=self.negatives, temperature=self.temperature, gather_negatives=self.gather_negatives)
+        return _step(self.model, self.optimizer, batch, spec, self.defer_check)
 
 
-def _stage_ids(out: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> None:
-    """out [Ba + Bb, T] <- rows of a, then rows of b, zero-padded to out's width: ONE launch (tt_concat_ids_i64) on the current
-    stream, into an existing buffer (GraphedTrainStep's static inputs)."""
-    a = a.contiguous()
-    b = b.contiguous() if b is not None else None
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().tt_concat_ids_i64(a.data_ptr(), a.shape[0], a.shape[1], b.data_ptr() if b is not None else None,
-                                                b.shape[0] if b is not None else 0, b.shape[1] if b is not None else 0,
-                                                out.data_ptr(), out.shape[1], torch.cuda.current_stream(out.device).cuda_stream))
+class _SeedRing:
+    """The dropout seeds of a captured step: two device words (query tower, document tower) the captured kernels read when they
+    run, refilled in front of every replay from one of eight pinned host pairs -- a pair is written again only when the copy
+    that read it, eight calls ago, has finished."""
+
+    def __init__(self, device):
+        self.words = torch.zeros(2, dtype=torch.int64, device=device)
+        self._host = torch.zeros((8, 2), dtype=torch.int64).pin_memory()
+        self._events, self._n = [None] * 8, 0
+
+    def put(self, query_seed: int, doc_seed: int) -> None:
+        """Enqueue the copy of this call's seeds on the current stream."""
+        k = self._n % len(self._events)
+        self._n += 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()   # (this pinned pair was a copy's source eight calls ago: long done)
+        self._host[k, 0], self._host[k, 1] = query_seed, doc_seed
+        self.words.copy_(self._host[k], non_blocking=True)
+        self._events[k] = torch.cuda.Event()
+        self._events[k].record()
 
 
 class GraphedTrainStep:
@@ -907,25 +1055,27 @@ class GraphedTrainStep:
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
                  defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05):
-        _check_negatives(negatives)
+        # (margin, negatives and temperature are arguments of the captured loss launches)
+        self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True).checked(graphs=True)
         encs = (model.query_encoder, model.doc_encoder)
         if not isinstance(optimizer, _FlatClipAdam) or optimizer._gated_step_fn is None:
             raise TypeError("GraphedTrainStep needs a FusedClipAdam")
         if not all(e.check_inputs for e in encs):
             raise ValueError("GraphedTrainStep: input checking must be on (the gate is what keeps a bad batch from being applied)")
         self.model, self.optimizer, self.margin = model, optimizer, float(margin)
-        self.negatives, self.temperature = negatives, float(temperature)   # (arguments of the captured loss launches)
+        self.negatives, self.temperature = negatives, float(temperature)
         self.B, self.q_width, self.doc_width = int(batch), int(q_width), int(doc_width)
         self.defer_check = bool(defer_check)
         dev = optimizer.flat_params.device
         self.q = torch.zeros((self.B, self.q_width), dtype=torch.int64, device=dev)
         self.both = torch.zeros((2 * self.B, self.doc_width), dtype=torch.int64, device=dev)
         # inter-layer dropout: the seeds are device words the captured kernels read when they run (TT_ENC_SEED_ON_DEVICE); every
-        # call draws them from torch's CPU generator exactly as the eager step does and copies them here in front of the replay
-        self._seed_words = torch.zeros(2, dtype=torch.int64, device=dev) if any(e.dropout > 0.0 for e in encs) else None
-        self._seed_host = torch.zeros((8, 2), dtype=torch.int64).pin_memory() if self._seed_words is not None else None
-        self._seed_events, self._seed_step = [None] * 8, 0
+        # call draws them from torch's CPU generator exactly as the eager step does and copies them there in front of the replay
+        self._seeds = _SeedRing(dev) if any(e.dropout > 0.0 for e in encs) else None
+        words = None if self._seeds is None else {id(model.query_encoder): self._seeds.words[0:1],
+                                                  id(model.doc_encoder): self._seeds.words[1:2]}
         self._phase = "all" if optimizer.world == 1 else "fold"
+        self._capture = _Capture(self._phase, self.both, words)
         # (the optimizer's hyper-parameters are arguments of the captured launches: changing them means capturing again)
         self._hyper = (optimizer.lr, optimizer.betas, optimizer.eps, optimizer.max_norm)
         model.train()
@@ -939,7 +1089,7 @@ class GraphedTrainStep:
                 for _ in range(2):                                   # allocator pools, kernel attributes, lazy handles
                     if self._run() is None:
                         raise ValueError("GraphedTrainStep: the model / optimizer pair does not take the direct step "
-                                         "(trainer._train_step_direct)")
+                                         "(trainer._direct_grad_views)")
                     if self._phase == "fold":
                         optimizer.gate.zero_()
             torch.cuda.current_stream(dev).wait_stream(side)
@@ -953,13 +1103,8 @@ class GraphedTrainStep:
 
     def _run(self):
         rows = {self.model.query_encoder: self.B, self.model.doc_encoder: 2 * self.B}
-        words = None
-        if self._seed_words is not None:
-            words = {id(self.model.query_encoder): self._seed_words[0:1], id(self.model.doc_encoder): self._seed_words[1:2]}
         with _towers_in_flight(self.model, self.optimizer, rows) as plan:
-            return _train_step_direct(self.model, self.optimizer, self.q, None, None, self.margin, phase=self._phase,
-                                      join_on_caller=True, both=self.both, plan=plan, seed_words=words,
-                                      negatives=self.negatives, temperature=self.temperature)
+            return _train_step_direct(self.model, self.optimizer, (self.q, None, None), self._spec, plan, self._capture)
 
     def flush(self):
         """defer_check: settle the optimizer's pending check (raises that step's exception, if any)."""
@@ -974,18 +1119,11 @@ class GraphedTrainStep:
         if self._phase == "all" and (opt.lr, opt.betas, opt.eps, opt.max_norm) != self._hyper:
             raise ValueError("GraphedTrainStep: the optimizer's lr / betas / eps / max_norm changed since the capture (they are "
                              "arguments of the captured launches); build a new GraphedTrainStep")
-        _stage_ids(self.q, queries)
+        _stage_ids(self.q, queries, None)
         _stage_ids(self.both, pos_docs, neg_docs)
-        if self._seed_words is not None:
+        if self._seeds is not None:
             drawn = _draw_dropout_seeds(self.model)
-            k = self._seed_step % self._seed_host.shape[0]
-            self._seed_step += 1
-            if self._seed_events[k] is not None:
-                self._seed_events[k].synchronize()   # (this pinned pair was a copy's source eight calls ago: long done)
-            self._seed_host[k, 0], self._seed_host[k, 1] = drawn[id(self.model.query_encoder)], drawn[id(self.model.doc_encoder)]
-            self._seed_words.copy_(self._seed_host[k], non_blocking=True)
-            self._seed_events[k] = torch.cuda.Event()
-            self._seed_events[k].record()
+            self._seeds.put(drawn[id(self.model.query_encoder)], drawn[id(self.model.doc_encoder)])
         self.graph.replay()
         if self._phase == "fold":
             opt._reduce_apply(True, check=False)
@@ -993,8 +1131,7 @@ class GraphedTrainStep:
         if not opt.check:
             return self.loss
         # (the eager redo takes the one-workgroup retry itself if it must)
-        opt.snapshot_gate(redo=lambda: train_step(self.model, opt, queries, pos_docs, neg_docs, self.margin,
-                                                  negatives=self.negatives, temperature=self.temperature))
+        opt.snapshot_gate(redo=lambda: _eager_step(self.model, opt, (queries, pos_docs, neg_docs), self._spec))
         if not self.defer_check:
             redone = opt.settle()            # the step's one host synchronisation
             if redone is not None:
