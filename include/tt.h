@@ -172,6 +172,40 @@ int tt_keep_mask_clear_ids(uint32_t *keep, int64_t N, const int64_t *ids, int64_
                            tt_stream_t stream);
 
 /*
+ * Tagged search: the masked exact search with a filter PER QUERY, in one pass over the corpus -- every query of a batch
+ * searches the documents of its own tenant, language or collection.  Replaces, per query b,
+ *     scores = torch.matmul(q, D.t()) ; scores[b, ~elig[b]] = -inf ; torch.topk(scores, k)
+ * (the per-query form of backend/evaluators.py:185-186), which with the masked call takes one search -- one scan of D and one
+ * N/8-byte mask -- per distinct filter of the batch.
+ * tags: device memory, one 32-bit word per document, 32 * ceil(N/32) words (padded to whole 32-document tiles; the words at or
+ * beyond N are read and ignored, like the keep-bitmask's bits beyond N), 16-byte aligned.  match_mask, match_value: device
+ * memory, [B] words, 4-byte aligned.  Document n is eligible for query b iff
+ *     (tags[n] & match_mask[b]) == match_value[b]
+ * and, when keep is not NULL (tt_score_topk_masked_f32's format and alignment), its keep bit is set.  Equality on a whole tag is
+ * mask 0xffffffff; equality on one packed bit-field ignores the others; mask 0 with value 0 is "no filter for this query"; a
+ * value with a bit outside the mask matches nothing and needs no special case.
+ * The result for query b is the exact top-k of its eligible documents, (score desc, index asc), tail (-inf, -1): bit for bit what
+ * tt_score_topk_masked_f32 / _bf16 returns for query b alone under a keep-bitmask whose bit n is that eligibility.
+ * 1 <= k <= 64 (above: TT_ERR_UNSUPPORTED, and the size query returns 0, as it does for B = 0); d and dtype support, N's bound,
+ * the alignment of Q / D / workspace and the status codes are the masked call's.  tags, match_mask and match_value are all NULL
+ * -- the call then IS the masked call: same launches, same bits -- or all non-NULL (anything else, or a misaligned pointer:
+ * TT_ERR_BAD_SHAPE).  N = 0 writes the tail.  Asynchronous, capturable, no host synchronisation, no allocation, no global state:
+ * match_mask / match_value are read by the kernels, so a captured call follows the values they hold at replay.  The result
+ * does not depend on what the workspace (tt_score_topk_tagged_workspace_bytes: the masked call's) and the outputs held.
+ * The predicate acts where the keep-bitmask does: in the sample maxima that seed the thresholds, in the append pass and in
+ * the give-up redo.  An ineligible document is still read and scored: a selective filter pays the full scan -- once per batch.
+ */
+size_t tt_score_topk_tagged_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_tagged_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *tags,
+                             const uint32_t *match_mask, const uint32_t *match_value, const uint32_t *keep, int k,
+                             int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                             tt_stream_t stream);
+int tt_score_topk_tagged_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *tags,
+                              const uint32_t *match_mask, const uint32_t *match_value, const uint32_t *keep, int k,
+                              int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace, size_t workspace_bytes,
+                              tt_stream_t stream);
+
+/*
  * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
  * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
  * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it

@@ -58,6 +58,11 @@ struct ExactCall {
     hipStream_t stream;
     const char *who;       // the entry point's name, for messages
     bool partials = false; // tt_score_topk_partials_f32: the caller takes the lists, so there are no outputs and no empty call
+    // tagged search (tt_score_topk_tagged_f32 / _bf16): one tag per document, padded to whole 32-document tiles, and one
+    // (mask, value) pair per query; all three set, or all three nullptr
+    const unsigned *tags = nullptr;
+    const unsigned *match_mask = nullptr;
+    const unsigned *match_value = nullptr;
 };
 
 // What varies between the main passes of one call.  (The sample pass always seeds for the call's k.)

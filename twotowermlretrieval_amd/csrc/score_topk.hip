@@ -30,6 +30,7 @@
 //    sample-pass maxima and for the cross-shard merge after the RCCL all-gather).
 #include "score_topk.h"
 #include "keep_word.h"
+#include "tag_words.h"
 
 #include <limits.h>
 #include <math.h>
@@ -94,6 +95,12 @@ struct ScoreParams {
     int draw_polls;     // bound of the wait for a chunk-mate's pool draw (DRAW_POLLS; the comparison build can force a give-up)
     const unsigned *keep; // MASKED instantiations: keep-bitmask, one word per 32-document tile (bit n & 31 of word n >> 5 set ->
                           // document n of D may be returned); nullptr in every other launch
+    // TAGGED instantiations (tagged search): tags [32 * n_tiles] one word per document, match_mask / match_value [B] one pair per
+    // query -- document n is eligible for query b iff (tags[n] & match_mask[b]) == match_value[b] and, when keep is set as well,
+    // its keep bit is; all nullptr in every other launch
+    const unsigned *tags = nullptr;
+    const unsigned *match_mask = nullptr;
+    const unsigned *match_value = nullptr;
 };
 
 // The keep word of one tile (MASKED): keep_word_issue / keep_word_wait (keep_word.h, shared with screen.hip).  Here the load is
@@ -194,12 +201,20 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // moves; the epilogue counts the documents the append pass would have taken (the same predicate) in a lane-local integer and one
 // count per (query, chunk) goes out in pidx -- no candidate buffers, no compaction, no lists.  Launched on the static split only
 // (no pool draw, so no give-up); the pacing gate stays (a wait that times out loses nothing).  COUNT = false is the kernel as it was.
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false, bool COUNT = false>
+// TAGGED (with MASKED; tt_score_topk_tagged_f32 / _bf16, DESIGN.md "Tagged search"): the keep word becomes PER QUERY.  Each lane
+// forms, per tile, the 32-bit eligibility word of its own query from the tile's 32 tags (tag_words.h) and ANDs it with the tile's
+// keep word when p.keep is set (tested wave-uniformly: one instantiation serves both); that word then feeds kwh / kept(r) as the
+// keep word does under MASKED, so the sample maxima, the append pass and the give-up redo see the same predicate.  The tile skip
+// moves in front of the ballot: a tile may be dead for one query of the wave and live for another.  TAGGED = false is the kernel
+// as it was.
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false, bool COUNT = false,
+          bool TAGGED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!BF || NS % 2 == 0, "bf16 rows: d a multiple of 64");
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
+    static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
     constexpr int NST = NT ? NSTAGE_NT : NSTAGE;
     constexpr int WAVE_LDS = NST * SLAB_BYTES;
     constexpr int NSD = BF ? NS / 2 : NS; // 128-B slabs per document row
@@ -260,6 +275,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
     if (qrow < p.B)
         thr = (!MAXONLY && p.thr0) ? p.thr0[(size_t)qrow * p.thr0_stride + p.thr0_off] : -INFINITY;
     int cnt = 0;
+    // TAGGED: the query's (match_mask, match_value), read once; a padded query reads nothing and matches nothing
+    unsigned mm = 0u, mv = 1u;
+    if (TAGGED && qrow < p.B) {
+        mm = p.match_mask[qrow];
+        mv = p.match_value[qrow];
+    }
     int nmatch = 0; // COUNT: this lane's documents with score >= thr (16 of a tile's 32 per lane half)
     float runmax = -INFINITY;
     Cand *const cbase = p.cand + ((size_t)task * 32 + j) * CAP; // this lane's query buffer
@@ -354,6 +375,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 pace_gate(gb - p.pace_lag);
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             unsigned kw = 0xffffffffu; // the tile's keep word (MASKED)
+            TagWords tg;               // the tile's tags (TAGGED)
 #pragma unroll
             for (int s = 0; s < NSD; ++s) {
                 // slab (tile,s) has landed once at most (NST-2) younger slabs are pending
@@ -370,8 +392,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 #endif
                 // (MASKED: right behind the asm wait above, which already ends a scheduling region -- a statement further
                 //  down would pin dma_issue's address arithmetic in front of it instead of between the MFMAs)
+                // (TAGGED without a keep-bitmask: the word's load reads the tile's first tag instead -- any valid word, it is
+                //  replaced by all ones behind the wait -- so that the tile loop has no branch on p.keep)
+                if (TAGGED && s == NSD - 1)
+                    tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, frag[0]);
                 if (MASKED && s == NSD - 1)
-                    keep_word_issue(p.keep + tile, kw, frag[0]);
+                    keep_word_issue((!TAGGED || p.keep) ? p.keep + tile : p.tags + (size_t)tile * TILE_DOCS, kw, frag[0]);
                 dma_issue((stage + NST - 1) % NST);
                 if (BF) {
                     // chunk c holds features 8c..8c+7 of the slab; word w = features (8c+2w, 8c+2w+1) in its (low, high)
@@ -403,8 +429,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             const bool partial = tile_base + TILE_DOCS > p.N;
             // MASKED: bit (r & 3) + 8 (r >> 2) of kwh = the keep bit of the lane's document r (bits at or beyond N: the
             // doc < p.N test stays)
+            // TAGGED: the same bits of the lane's own word kwq = (eligibility word of query j) & (keep word, if any)
             unsigned kwh = 0xffffffffu;
-            if (MASKED) {
+            unsigned kwq = 0xffffffffu;
+            if (TAGGED) {
+                tag_words_wait(tg, kw, acc);
+                kwq = tag_match_word(tg, mm, mv) & (p.keep ? kw : 0xffffffffu);
+                kwh = kwq >> (4 * h);
+            } else if (MASKED) {
                 keep_word_wait(kw, acc);
                 kwh = kw >> (4 * h);
             }
@@ -432,7 +464,8 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 m = fmaxf(m, acc[r]);
             // (MASKED: m may come from a masked document -- that only costs the slow path a look; a tile with nothing kept
             //  skips it)
-            if (!COUNT && (!MASKED || kw != 0u) && __ballot(m >= thr) != 0ull) {
+            // (TAGGED: "nothing kept" is per lane -- a tile may be dead for one query of the wave and live for another)
+            if (!COUNT && (!MASKED || TAGGED || kw != 0u) && __ballot((!TAGGED || kwq != 0u) && m >= thr) != 0ull) {
                 // Append pass.  The store is inline asm on purpose: a compiler-visible global store
                 // (or the compaction's loads) inside this loop makes hipcc emit s_waitcnt vmcnt(0) at
                 // every join, which drains the LDS-DMA ring on each tile that has a candidate.
@@ -568,11 +601,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 // (tools/experiments/mfma16_order.hip), so the oracle parity carries over.  Ring, DMA, thresholds, candidate
 // buffers, compaction, partial lists and merge are K4's; the launch is bound by HBM streaming (d * 4 bytes per doc).
 // ---------------------------------------------------------------------------
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false>
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false, bool TAGGED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
+    static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
     constexpr int WAVE_LDS = NSTAGE * SLAB_BYTES;
     constexpr int ROW_BYTES = NS * 128;
     const int lane = threadIdx.x & 63;
@@ -603,6 +637,11 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
     if (qrow < p.B)
         thr = (!MAXONLY && p.thr0) ? p.thr0[(size_t)qrow * p.thr0_stride + p.thr0_off] : -INFINITY;
     int cnt = 0; // the same value in the four lanes of a query
+    unsigned mm = 0u, mv = 1u; // TAGGED: the query's (match_mask, match_value) (see score_topk_kernel)
+    if (TAGGED && qrow < p.B) {
+        mm = p.match_mask[qrow];
+        mv = p.match_value[qrow];
+    }
     int nmatch = 0; // COUNT: this lane's documents with score >= thr (8 of a tile's 32 per lane quarter)
     float runmax = -INFINITY;
     Cand *const cbase = p.cand + ((size_t)task * 16 + n) * CAP;
@@ -671,6 +710,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
         for (int tile = t0; tile < t1; ++tile) {
             f32x4 acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
             unsigned kw = 0xffffffffu; // the tile's keep word (MASKED: see score_topk_kernel)
+            TagWords tg;               // the tile's tags (TAGGED)
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_SLAB * (NSTAGE - 2)) : "memory");
@@ -683,7 +723,9 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (MASKED && s == NS - 1) {
                     float a00[2] = {a[0][0], a[1][0]}; // (both chains' first operands)
-                    keep_word_issue(p.keep + tile, kw, a00);
+                    if (TAGGED)
+                        tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, a00);
+                    keep_word_issue((!TAGGED || p.keep) ? p.keep + tile : p.tags + (size_t)tile * TILE_DOCS, kw, a00);
                     a[0][0] = a00[0];
                     a[1][0] = a00[1];
                 }
@@ -699,7 +741,10 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
             const int tile_base = tile * TILE_DOCS;
             const bool partial = tile_base + TILE_DOCS > p.N;
             unsigned kwh = 0xffffffffu; // MASKED: bit 16u + r = the keep bit of the lane's document (u, r)
-            if (MASKED) {
+            if (TAGGED) { // the lane's own word: (eligibility word of query n) & (keep word, if any)
+                tag_words_wait(tg, kw, acc[1]);
+                kwh = (tag_match_word(tg, mm, mv) & (p.keep ? kw : 0xffffffffu)) >> (4 * kq);
+            } else if (MASKED) {
                 keep_word_wait(kw, acc[1]);
                 kwh = kw >> (4 * kq);
             }
@@ -1282,40 +1327,46 @@ constexpr bool score_dim_ok(int d, bool bf16)
 enum PassKind { PASS_LISTS, PASS_MAXONLY, PASS_COUNT };
 
 struct Score32 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT, TAGGED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
 };
 struct Score32Bf16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT, TAGGED>; }
     static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false>
-    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT, TAGGED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
 };
 
-template <class K, int NS, bool MASKED>
+// (TAGGED: the tagged search's instantiations -- lists and maxima only, there is no tagged count -- one per shape, with or
+//  without a keep-bitmask, which the kernel tests itself)
+template <class K, int NS, bool MASKED, bool TAGGED = false>
 int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
     const void *fn;
     size_t smem = pl.smem;
     if (kind == PASS_MAXONLY) {
-        fn = K::template fn<NS, 64, true, false, MASKED>();
+        fn = K::template fn<NS, 64, true, false, MASKED, false, TAGGED>();
     } else if (kind == PASS_COUNT) { // (the nt form under the main pass's own rule: one query tile at d = 256)
-        if (NS == 8 && sp.n_qtiles == 1) {
+        if constexpr (TAGGED) {
+            return tt_fail(TT_ERR_UNSUPPORTED, "the counting pass takes no tags");
+        } else if (NS == 8 && sp.n_qtiles == 1) {
             fn = K::template fn<8, 64, false, true, MASKED, true>();
             smem = K::smem_nt;
         } else {
             fn = K::template fn<NS, 64, false, false, MASKED, true>();
         }
     } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
-        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED>() : K::template fn<8, 128, false, true, MASKED>();
+        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED, false, TAGGED>()
+                          : K::template fn<8, 128, false, true, MASKED, false, TAGGED>();
         smem = K::smem_nt;
     } else {
-        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED>() : K::template fn<NS, 128, false, false, MASKED>();
+        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED, false, TAGGED>()
+                          : K::template fn<NS, 128, false, false, MASKED, false, TAGGED>();
     }
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     ScoreParams args = sp;
@@ -1324,10 +1375,12 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind 
     return TT_OK;
 }
 
-// sp.keep set: the MASKED instantiation of the same kernel
+// sp.keep set: the MASKED instantiation of the same kernel; sp.tags set: the TAGGED one, with or without sp.keep
 template <class K, int NS>
 int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
+    if (sp.tags)
+        return launch_ns_m<K, NS, true, true>(sp, pl, st, kind);
     return sp.keep ? launch_ns_m<K, NS, true>(sp, pl, st, kind) : launch_ns_m<K, NS, false>(sp, pl, st, kind);
 }
 
@@ -1398,6 +1451,9 @@ ScoreParams pass_params(const Pass &ps, const ExactCall &c, int list_k, int64_t 
     sp.run_if = nullptr;
     sp.draw_polls = TT_AB_SWITCH(TT_DRAW_POLLS, DRAW_POLLS);
     sp.keep = c.keep;
+    sp.tags = c.tags;
+    sp.match_mask = c.match_mask;
+    sp.match_value = c.match_value;
     return sp;
 }
 

@@ -713,6 +713,47 @@ TT_EXPORT int tt_score_topk_masked_bf16(const float *Q, int B, int d, const void
                                       workspace_bytes, (hipStream_t)stream, "tt_score_topk_masked_bf16"});
 }
 
+// ---- Tagged search (DESIGN.md "Tagged search") -------------------------------------------------------------------------------
+// The masked call for k <= 64 with a per-query filter: the same plan, workspace and launches, on the TAGGED instantiations of the
+// main and sample passes (score_topk.hip).  tags == match_mask == match_value == NULL is the masked call itself.
+namespace {
+int score_topk_tagged(ExactCall c)
+{
+    if (c.k > MERGE_KMAX)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d (tagged search keeps the k <= 64 lists only)", c.who, c.k, MERGE_KMAX);
+    const int given = (c.tags != nullptr) + (c.match_mask != nullptr) + (c.match_value != nullptr);
+    if (given != 0 && given != 3)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: tags, match_mask and match_value must be all NULL or all non-NULL", c.who);
+    // (tags: a tile's 128 bytes are read as two 16-word scalar loads)
+    if (((uintptr_t)c.tags & 15) || (((uintptr_t)c.match_mask | (uintptr_t)c.match_value) & 3))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: tags must be 16-byte, match_mask and match_value 4-byte aligned", c.who);
+    return score_topk_large(c);
+}
+} // namespace
+
+TT_EXPORT size_t tt_score_topk_tagged_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return k > MERGE_KMAX ? 0 : tt_score_topk_large_workspace_bytes(B, N, d, k, bf16);
+}
+
+TT_EXPORT int tt_score_topk_tagged_f32(const float *Q, int B, int d, const float *D, int64_t N, const uint32_t *tags,
+                                       const uint32_t *match_mask, const uint32_t *match_value, const uint32_t *keep, int k,
+                                       int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                       size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_tagged(ExactCall{Q, B, d, D, false, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                       (hipStream_t)stream, "tt_score_topk_tagged_f32", false, tags, match_mask, match_value});
+}
+
+TT_EXPORT int tt_score_topk_tagged_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const uint32_t *tags,
+                                        const uint32_t *match_mask, const uint32_t *match_value, const uint32_t *keep, int k,
+                                        int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                                        size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_tagged(ExactCall{Q, B, d, D_bf16, true, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                       (hipStream_t)stream, "tt_score_topk_tagged_bf16", false, tags, match_mask, match_value});
+}
+
 namespace {
 // keep word w = the ballots of keep_bool[32 w .. 32 w + 31] != 0 (a wave packs two words); bits at or beyond N are zero
 __global__ __launch_bounds__(256) void keep_pack_kernel(const uint8_t *__restrict__ keep_bool, int64_t N, unsigned *__restrict__ keep)

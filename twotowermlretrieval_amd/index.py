@@ -22,7 +22,7 @@ import torch
 from . import _lib
 
 __all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
-           "shard_bounds", "seed_union", "score_count", "topk_cut_below"]
+           "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged"]
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -197,6 +197,101 @@ def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
         _lib.check(getattr(_lib.lib(), route.fn)(*route.args(q.data_ptr(), B, d, docs.data_ptr(), N,
                                                              None if keep is None else keep.data_ptr(), k, tail)))
     return vals, idx
+
+
+def _tag_words(n: int) -> int:
+    """Words of a tags buffer over n documents as the tagged kernels read it: one per document, whole 32-document tiles."""
+    return 32 * _keep_words(n)
+
+
+def _check_tags(tags: torch.Tensor, n: int, device) -> torch.Tensor:
+    """The tags of n documents on `device` as tt_score_topk_tagged_* reads them: int32 [32*ceil(n/32)], contiguous (the bit
+    pattern is read as unsigned).  A [n] tensor is padded with zeros, which the kernels ignore."""
+    if not isinstance(tags, torch.Tensor) or tags.dtype not in _KEEP_DTYPES:
+        raise TypeError(f"tags must be an int32 / uint32 tensor, one word per document, got {getattr(tags, 'dtype', type(tags))}")
+    if tags.device != device:
+        raise ValueError(f"tags on {tags.device} but the documents live on {device}")
+    if tags.dim() != 1 or tags.numel() not in (n, _tag_words(n)):
+        raise ValueError(f"tags must hold N = {n} words (or N padded to whole tiles, {_tag_words(n)}), got {tuple(tags.shape)}")
+    tags = tags if tags.dtype == torch.int32 else tags.view(torch.int32)
+    if tags.numel() != _tag_words(n):
+        padded = torch.zeros(_tag_words(n), dtype=torch.int32, device=device)
+        padded[:n] = tags
+        return padded
+    return tags if tags.is_contiguous() else tags.contiguous()
+
+
+def _match_words(x, B: int, device, what: str) -> torch.Tensor:
+    """match_mask / match_value of B queries on `device` as the tagged kernels read them (int32 [B], contiguous): an int32
+    [B] device tensor, or a Python int in [-2^31, 2^32) (its low 32 bits) for every query."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype not in _KEEP_DTYPES:
+            raise TypeError(f"{what} must be an int or an int32 / uint32 tensor, got {x.dtype}")
+        if x.device != device:
+            raise ValueError(f"{what} on {x.device} but the search runs on {device}")
+        if tuple(x.shape) != (B,):
+            raise ValueError(f"{what} must be one word per query, [B] = [{B}], got {tuple(x.shape)}")
+        x = x if x.dtype == torch.int32 else x.view(torch.int32)
+        return x if x.is_contiguous() else x.contiguous()
+    if isinstance(x, bool) or not isinstance(x, int):
+        raise TypeError(f"{what} must be an int or an int32 / uint32 tensor, got {type(x).__name__}")
+    if not -(1 << 31) <= x < (1 << 32):
+        raise ValueError(f"{what} = {x} is not a 32-bit word")
+    x &= 0xffffffff
+    return torch.full((B,), x - (1 << 32) if x >= (1 << 31) else x, dtype=torch.int32, device=device)
+
+
+TAGGED_KMAX = SMALL_KMAX  # tagged search keeps the k <= 64 lists only (tt_score_topk_tagged_*)
+
+
+def _tagged_into(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, mm: torch.Tensor, mv: torch.Tensor,
+                 keep: Optional[torch.Tensor], k: int, idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tt_score_topk_tagged_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, tags padded int32, mm / mv
+    int32 [B], keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
+    if not 1 <= k <= TAGGED_KMAX:
+        raise ValueError(f"tagged search answers 1 <= k <= {TAGGED_KMAX}, got k = {k}")
+    B, d = q.shape
+    N = docs.shape[0]
+    bf16 = docs.dtype == torch.bfloat16
+    vals, idx = _out_pair(B, k, q.device, out)
+    if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+        return (vals, idx) if out is None else out
+    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
+        L = _lib.lib()
+        ws = torch.empty(max(L.tt_score_topk_tagged_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
+        fn = L.tt_score_topk_tagged_bf16 if bf16 else L.tt_score_topk_tagged_f32
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, tags.data_ptr(), mm.data_ptr(), mv.data_ptr(),
+                      None if keep is None else keep.data_ptr(), k, idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                      ws.numel(), _stream(q)))
+    return (vals, idx) if out is None else out
+
+
+def score_topk_tagged(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, match_mask, match_value, k: int,
+                      idx_offset: int = 0, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """score_topk with a filter per query, in one pass over docs: query b sees document n iff
+    (tags[n] & match_mask[b]) == match_value[b] (and its bit in `keep`, a pack_keep_mask bitmask, when given).  tags: int32
+    [N] or [32*ceil(N/32)] on the documents' device, one word per document, read as unsigned (a [N] tensor is padded here).
+    match_mask / match_value: int32 [B] device tensors, or Python ints for every query.  Mask 0xffffffff is equality on the
+    whole tag, mask 0 with value 0 no filter, a value with a bit outside the mask matches nothing.  Returns the exact top-k
+    of each query's eligible documents, (score desc, index asc), tail (-inf, -1) -- what score_topk(q[b], docs, k, keep=
+    that eligibility) returns, bit for bit (tt_score_topk_tagged_f32 / _bf16; k <= 64).  An ineligible document is still read
+    and scored: the batch pays one full scan, whatever its filters."""
+    if q.dim() == 1:
+        return _squeezed(score_topk_tagged, q, docs, tags, match_mask, match_value, k, idx_offset, keep)
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), _docs_c(docs)
+    B, d = q.shape
+    N = docs.shape[0]
+    if docs.dim() != 2 or docs.shape[1] != d:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    tags = _check_tags(tags, N, docs.device)
+    mm = _match_words(match_mask, B, docs.device, "match_mask")
+    mv = _match_words(match_value, B, docs.device, "match_value")
+    if keep is not None:
+        keep = _check_keep(keep, N, docs.device)
+    return _tagged_into(q, docs, tags, mm, mv, keep, k, int(idx_offset))
 
 
 def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -598,6 +693,7 @@ class BruteForceIndex:
         self.keep_stats = False   # True: the most recent screened search's workspace is kept for search_stats()
         self._last_ws = None
         self._keep: Optional[torch.Tensor] = None  # the persistent keep-bitmask (remove_ids), None until the first removal
+        self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, padded to whole tiles (set_tags), for tagged_search
 
     @classmethod
     def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int,
@@ -688,6 +784,42 @@ class BruteForceIndex:
             out[1].copy_(i)
             return out
         return v, i
+
+    @property
+    def tags(self) -> Optional[torch.Tensor]:
+        """The rows' tags as the tagged kernels read them (int32 [32*ceil(N/32)], zero padding beyond N), or None: not set."""
+        return self._tags
+
+    def set_tags(self, tags: torch.Tensor) -> None:
+        """One 32-bit tag per row (int32 [N], or already padded to [32*ceil(N/32)]; the bits are read as unsigned), on the
+        index's device: a tenant / language / collection id, or several packed bit-fields.  Kept padded (4 bytes per row)."""
+        self._tags = _check_tags(tags, self.docs.shape[0], self.docs.device)
+
+    def tagged_search(self, q: torch.Tensor, k: int = 10, match_mask=0xffffffff, match_value=0,
+                      keep: Optional[torch.Tensor] = None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() with a filter per query, in ONE pass over the rows: query b sees row n iff
+        (tags[n] & match_mask[b]) == match_value[b] (score_topk_tagged; match_mask / match_value: int32 [B] device tensors or
+        Python ints for every query; q [B,d] or a single [d]).  keep= and remove_ids compose: the row's bit in the ANDed mask
+        must be set as well.  Always the exact kernel in its tagged mode (k <= 64), also on a screen=True index, whose
+        fallback_flags then read all ones as after search(keep=).  exclude= and candidates= are not taken.
+        ValueError: no tags (set_tags), or k > 64."""
+        if self._tags is None:
+            raise ValueError("tagged_search: this index has no tags (set_tags)")
+        if q.dim() == 1:
+            return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
+        _need_cuda(q)
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        if q.shape[-1] != self.docs.shape[1]:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        B = q.shape[0]
+        mm = _match_words(match_mask, B, self.docs.device, "match_mask")
+        mv = _match_words(match_value, B, self.docs.device, "match_value")
+        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        res = _tagged_into(_f32c(q), self.docs, self._tags, mm, mv, keep, k, self.idx_offset, out)
+        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
+            self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+        return res
 
     def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], want_idx: bool, what: str = "ids"):
         """tt_score_ids_* of q [B,d] over this index's rows under the ANDed mask `keep` (checked) or None: (scores f32 [B,C],
@@ -1226,6 +1358,38 @@ class ShardedIndex:
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
 
+    @property
+    def tags(self) -> Optional[torch.Tensor]:
+        """This rank's tags over its own rows (set_tags), or None."""
+        return self._index.tags
+
+    def set_tags(self, local_tags: torch.Tensor) -> None:
+        """One 32-bit tag per row of THIS RANK'S shard (BruteForceIndex.set_tags / StreamedIndex.set_tags).  Called on every
+        rank, like every call on this class: tagged search is a property of the job."""
+        self._index.set_tags(local_tags)
+
+    def tagged_search(self, q: torch.Tensor, k: int = 10, match_mask=0xffffffff, match_value=0,
+                      keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() with a filter per query (BruteForceIndex.tagged_search): q, match_mask and match_value are the same on
+        every rank, the tags are each rank's own.  The local tagged search runs for max(k, shard_k) (<= 64: ValueError above),
+        then the usual all-gather and merge on the caller's stream; no seed exchange is involved, so every rank enters the
+        same collectives whatever its tags hold.  A COLLECTIVE like every search of this class.  keep: as in search()."""
+        if self._index.tags is None:
+            raise ValueError("tagged_search: this index has no tags (set_tags)")
+        if q.dim() == 1:
+            return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
+        kp = max(k, self.shard_k)
+        if not 1 <= k or kp > TAGGED_KMAX:
+            raise ValueError(f"tagged search answers 1 <= max(k, shard_k) <= {TAGGED_KMAX}, got k = {k}, shard_k = {self.shard_k}")
+        sl = self._slot(q.shape[0], kp, k, 2)
+        cur = torch.cuda.current_stream(sl.send.device)
+        cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
+        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
+        self._index.tagged_search(q, kp, match_mask, match_value, keep=keep, out=(sl.send_v, sl.send_i))
+        self._exchange_merge(sl, q.shape[0], kp, k)
+        sl.merged.record(cur)
+        return sl.out_v.clone(), sl.out_i.clone()
+
     def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """float32 [B,C] ([C] for a single query), identical on every rank: the exact dense score of every id of ids int64
         [B,C] (GLOBAL ids, the same on every rank like q), -inf where the id is negative, beyond the corpus, removed or not
@@ -1342,6 +1506,7 @@ class StreamedIndex:
             self._d16 = [None, None]
         self._keep: Optional[torch.Tensor] = None  # persistent keep-bitmask (remove_ids): N/8 bytes, on the device
         self._gather = None  # two pinned [block,d] host buffers of the candidate gather (_score_ids), allocated on first use
+        self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, resident on the device (set_tags): 4 bytes per row
 
     def _walk(self, visit, stats=None):
         L = _lib.lib()
@@ -1502,6 +1667,61 @@ class StreamedIndex:
         self._walk(visit)
         if not run:
             run = _out_pair(q.shape[0], k, q.device)  # an empty corpus: padding only
+            run[0].fill_(float("-inf"))
+            run[1].fill_(-1)
+        if out is not None:
+            out[0].copy_(run[0])
+            out[1].copy_(run[1])
+            return out
+        return run[0], run[1]
+
+    @property
+    def tags(self) -> Optional[torch.Tensor]:
+        """The tags of the whole corpus, on the device (int32 [32*ceil(N/32)], zero padding beyond N), or None: not set."""
+        return self._tags
+
+    def set_tags(self, tags: torch.Tensor) -> None:
+        """One 32-bit tag per row of the whole corpus (int32 [N] or padded to [32*ceil(N/32)]), on the index's DEVICE: the rows
+        stream from the host, the tags stay resident at 4 bytes per row (N/8 bytes for a keep-bitmask, next to 2 N d of rows
+        that do not fit)."""
+        self._tags = _check_tags(tags, self.N, self.device)
+
+    def tagged_search(self, q: torch.Tensor, k: int = 10, match_mask=0xffffffff, match_value=0,
+                      keep: Optional[torch.Tensor] = None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() with a filter per query (BruteForceIndex.tagged_search; k <= 64): every streamed block runs the tagged
+        exact kernel under its slice of the tags (and of the ANDed keep-bitmask, if any), and the blocks' lists are merged as
+        in search().  A tile of 32 tags belongs to one block, so the blocks must start on multiples of 32 rows:
+        block_docs % 32 != 0 (with more than one block) raises ValueError."""
+        if self._tags is None:
+            raise ValueError("tagged_search: this index has no tags (set_tags)")
+        if q.dim() == 1:
+            return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
+        _need_cuda(q)
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        if not 1 <= k <= TAGGED_KMAX:
+            raise ValueError(f"tagged search answers 1 <= k <= {TAGGED_KMAX}, got k = {k}")
+        q = _f32c(q)
+        B = q.shape[0]
+        mm = _match_words(match_mask, B, self.device, "match_mask")
+        mv = _match_words(match_value, B, self.device, "match_value")
+        keep = _and_keep(self._keep, keep, self.N, self.device)
+        if self.block % 32 and self.N > self.block:
+            raise ValueError(f"a tagged StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
+        run = []  # the running top-k: (values, indices)
+
+        def visit(s, lo, n):
+            if lo % 32:
+                raise ValueError(f"block at row {lo}: the tags of a 32-document tile belong to one block")
+            v, i = _tagged_into(q, self._d32[s][:n], self._tags[lo:lo + _tag_words(n)], mm, mv,
+                                None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k, self.idx_offset + lo)
+            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+
+        self._walk(visit)
+        if not run:
+            run = _out_pair(B, k, q.device)  # an empty corpus: padding only
             run[0].fill_(float("-inf"))
             run[1].fill_(-1)
         if out is not None:
