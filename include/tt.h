@@ -768,6 +768,24 @@ int tt_contrastive_loss_f32(const float *q /*[B,H]*/, int B, const float *docs /
                             void *workspace, size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The same loss with GROUPED NEGATIVES: labels that take false negatives out of the softmax (a batch that holds a query several
+ * times, each with another of its positives; across ranks, a gathered pool).  q_groups [B], doc_groups [M] int64, device.
+ * The pair (i, j) is IGNORED iff  j != pos_offset + i  and  q_groups[i] >= 0  and  doc_groups[j] == q_groups[i];
+ * a negative label means "no group" and never matches, a query's own positive is always kept:
+ *   loss = mean_{i<B} (logsumexp_{j kept for i} s_ij - s_{i, pos_offset+i})
+ * An ignored pair contributes nothing to dq_i or ddocs_j (a document ignored by some queries still receives the others'
+ * gradient).  A query whose every other row is ignored has row loss exactly 0.0f and an all-zero dq row.
+ * With q_groups all negative, or with no match off the positives, loss, dq and ddocs are the bits of tt_contrastive_loss_f32.
+ * Shapes, workspace (tt_contrastive_loss_workspace_bytes(B, M, H)), refusals and guarantees as tt_contrastive_loss_f32
+ * (deterministic, whatever the workspace held; asynchronous; capture-clean; no atomics); a null q_groups or doc_groups is
+ * TT_ERR_BAD_SHAPE.
+ */
+int tt_contrastive_loss_grouped_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H, int pos_offset,
+                                    const int64_t *q_groups /*[B]*/, const int64_t *doc_groups /*[M]*/, float temperature,
+                                    float *loss /*[1]*/, float *dq /*[B,H]*/, float *ddocs /*[M,H]*/, void *workspace,
+                                    size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

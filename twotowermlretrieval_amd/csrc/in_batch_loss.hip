@@ -6,6 +6,15 @@
 // Two entries on the same kernels: tt_contrastive_loss_f32 (one contiguous pool `docs` [M,H]: the passages gathered from all
 // ranks, or several negatives per query) and tt_in_batch_loss_f32 (D = [p; n] as two pointers: M = 2B, pos_offset = 0).
 //
+// Grouped negatives (tt_contrastive_loss_grouped_f32, the GROUPED instantiations): int64 labels qg [B], dg [M]; the pair (i, j)
+// is IGNORED iff j != pos_offset + i, qg[i] >= 0 and dg[j] == qg[i] -- another positive of the same query is no negative.  An
+// ignored pair is left out of the maximum and of the sum of exponentials exactly as a document past M is, and its G entry is 0
+// on both gradient sides.  The positive is always kept, so lse_i is finite; but a tile, a lane's share of a slice or a whole
+// slice may hold no kept document for a query: such a partial is (max, sum) = (-inf, 0), every combine skips a zero sum before it
+// forms exp(max - total max), and no exp(-inf - -inf) is ever evaluated.  A query whose every other row is ignored has
+// lse_i = s_{i,pos} + log(1): row loss 0.0f and G row exp(0) - 1 = 0.  The ungrouped instantiations read no label and keep their
+// arithmetic and order.
+//
 // Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
 //   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
 //   2 ib_stats_kernel    a workgroup per (32 queries, slice of the documents): S^T tiles on v_mfma_f32_32x32x2_f32, online
@@ -131,6 +140,8 @@ __global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ 
 // four MFMA steps (the k order inside a group of 8 is permuted identically for both operands).  Two accumulators (even and odd
 // groups of 8) are added at the end.  One wave per SIMD has nobody to hide a load behind, so the loop is software-pipelined:
 // the 32 columns of the next step are in flight while the 16 MFMAs (1024 cycles) of this one issue.
+// after_first(): further loads of the caller's (the grouped kernels' labels), issued BEHIND the first step's operands, so that
+// the wait in front of the first MFMA does not cover them (loads retire in order) and they land behind the products.
 struct IBFrag {
     f32x4 a[4], b[4];
 };
@@ -144,13 +155,15 @@ __device__ __forceinline__ IBFrag ib_frag(const float *__restrict__ ap, const fl
     }
     return f;
 }
+template <class AfterFirst>
 __device__ __forceinline__ f32x16 ib_scores(const float *__restrict__ A, int a0, const float *__restrict__ Bm, int b0,
-                                            int Hp, int lane)
+                                            int Hp, int lane, AfterFirst after_first)
 {
     const float *ap = A + (size_t)(a0 + (lane & 31)) * Hp + 4 * (lane >> 5);
     const float *bp = Bm + (size_t)(b0 + (lane & 31)) * Hp + 4 * (lane >> 5);
     f32x16 acc0 = {}, acc1 = {};
     IBFrag cur = ib_frag(ap, bp, 0);
+    after_first();
     for (int k = 0; k < Hp; k += 32) {  // Hp % 32 == 0
         IBFrag nxt = cur;
         if (k + 32 < Hp)
@@ -169,12 +182,28 @@ __device__ __forceinline__ f32x16 ib_scores(const float *__restrict__ A, int a0,
 
 __device__ __forceinline__ int ib_rho(int reg) { return (reg & 3) + 8 * (reg >> 2); }
 
+// The labels of the 16 rows y0 + rho(r) + 4 * half a lane meets in an S^T tile.  Rows past n read row n - 1 (n >= 1): every load
+// is in bounds and unconditional (no branch around a load), and what such a row holds is never used -- the pair is out of range.
+__device__ __forceinline__ void ib_labels(const int64_t *__restrict__ g, int y0, int half, int n, int64_t (&out)[16])
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int y = y0 + ib_rho(r) + 4 * half;
+        out[r] = g[y < n ? y : n - 1];
+    }
+}
+
 // ------------------------------------------------------------------ 2: row statistics
 // Workgroup = 32 queries (on the lanes) x slice blockIdx.y of the documents; wave w takes the 32-document tiles w, w + 4, ... of
 // the slice.  Each lane keeps a running maximum and a sum of exponentials over the documents it sees; the 8 partials of a
-// query (4 waves x 2 lane halves) are combined in a fixed order into the slice's pair.  (A slice holds a valid document
-// for every query: slices are whole chunks, none empty.)
-__global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh, int B, int M,
+// query (4 waves x 2 lane halves) are combined in a fixed order into the slice's pair.  Ungrouped, a slice holds a valid
+// document for every query (slices are whole chunks, none empty).  GROUPED, every document of a slice may be ignored for a
+// query: its partials are (-inf, 0), the combine below skips them (part_l > 0) and the slice's pair is (-inf, 0).
+// GROUPED: the lane loads its query's label once and, per tile, the labels of its 16 documents behind the first operands of the
+// products (ib_scores: after_first), so that they arrive behind the MFMAs.
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                       const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B, int M,
                                                        int pos_offset, int Hp, int Bq, int tiles_per_slice, float temperature,
                                                        float *__restrict__ pm, float *__restrict__ pl,
                                                        float *__restrict__ pos)
@@ -186,25 +215,36 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     const int t_begin = blockIdx.y * tiles_per_slice;
     const int t_all = (ND + IB_TILE - 1) / IB_TILE, n_tiles = t_begin + tiles_per_slice < t_all ? t_begin + tiles_per_slice : t_all;
     float m = -INFINITY, l = 0.0f;
+    int64_t own_g = -1, oth_g[16];
+    if (GROUPED)
+        own_g = qg[i < B ? i : B - 1];  // (a lane past B: any label, its statistics are not written)
+    const bool grouped_q = own_g >= 0;
     for (int t = t_begin + wave; t < n_tiles; t += 4) {
         const int j0 = t * IB_TILE;
-        const f32x16 acc = ib_scores(dh, j0, qh, i0, Hp, lane);
+        const f32x16 acc = ib_scores(dh, j0, qh, i0, Hp, lane, [&] {
+            if (GROUPED)
+                ib_labels(dg, j0, half, ND, oth_g);
+        });
         float x[16], tm = -INFINITY;
+        bool keep[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int j = j0 + ib_rho(r) + 4 * half;
             x[r] = acc[r] / temperature;
-            if (j < ND)
+            keep[r] = j < ND;
+            if (GROUPED)  // (bitwise: one mask per pair, no branch per document)
+                keep[r] = keep[r] & !(grouped_q & (oth_g[r] == own_g) & (j != i + pos_offset));
+            if (keep[r])
                 tm = fmaxf(tm, x[r]);
             if (j == i + pos_offset && i < B)
                 pos[i] = x[r];  // (one lane of one wave of one slice, once)
         }
-        if (tm > -INFINITY) {  // (some document of the tile is valid for this lane half)
+        if (tm > -INFINITY) {  // (some document of the tile is valid, and kept, for this lane)
             const float mn = fmaxf(m, tm);
             float s = 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (j0 + ib_rho(r) + 4 * half < ND)
+                if (keep[r])
                     s += expf(x[r] - mn);
             l = l * expf(m - mn) + s;  // (m = -inf: l = 0 and exp(-inf) = 0)
             m = mn;
@@ -227,7 +267,9 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     }
 }
 
-// The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.
+// The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.  The slice of the
+// positive has a finite maximum, so M is finite; a slice that is empty for the query (grouped labels) comes as (-inf, 0) and
+// adds 0 * exp(-inf - M) = 0 * 0.
 __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ pm, const float *__restrict__ pl,
                                                      const float *__restrict__ pos, int B, int Bq, int n_slices,
                                                      float *__restrict__ lse, float *__restrict__ row_loss)
@@ -262,9 +304,12 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
 // of the owner rows' gradient, dXh^T [h 32][owner 32] += Other^T [h][128] G [128][owner] (A operand straight from the image,
 // coalesced; B operand from LDS).  A chunk's product starts from zero and is added to the running total (blocked summation).
 // The epilogue turns the [h][owner] accumulators into rows through LDS and stores the slice's partial [32][Hp] coalesced.
-template <bool QOWN>
+// GROUPED: G = 0 for an ignored pair, on either side; the owner row's label is loaded once, the walked rows' labels per tile
+// behind the lse loads and the first operands of the products (ib_scores: after_first).
+template <bool QOWN, bool GROUPED>
 __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restrict__ qh, const float *__restrict__ dh,
-                                             const float *__restrict__ lse, int B, int M, int pos_offset, int Hp,
+                                             const float *__restrict__ lse, const int64_t *__restrict__ qg,
+                                             const int64_t *__restrict__ dg, int B, int M, int pos_offset, int Hp,
                                              float temperature, int tile, int chunk_begin, int chunk_end,
                                              float *__restrict__ part)
 {
@@ -276,6 +321,10 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
     const int NT = Hp / 32;
     const float scale = 1.0f / ((float)B * temperature);
     const float lse_own = (QOWN && o < B) ? lse[o] : 0.0f;
+    const int n_own = QOWN ? B : M;
+    int64_t own_g = -1, oth_g[16];
+    if (GROUPED)
+        own_g = (QOWN ? qg : dg)[o < n_own ? o : n_own - 1];  // (an owner row past the end: any label, its pairs are out of range)
     f32x16 tot[4] = {};
     for (int ch = chunk_begin; ch < chunk_end; ++ch) {
         const int c0 = ch * IB_CHUNK, y0 = c0 + IB_TILE * wave;
@@ -287,7 +336,10 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ls_y[r] = QOWN ? lse_own : lse[y0 + ib_rho(r) + 4 * half];
-            const f32x16 acc = ib_scores(oth, y0, own, own0, Hp, lane);
+            const f32x16 acc = ib_scores(oth, y0, own, own0, Hp, lane, [&] {
+                if (GROUPED)
+                    ib_labels(QOWN ? dg : qg, y0, half, n_oth, oth_g);
+            });
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int y = y0 + ib_rho(r) + 4 * half;
@@ -296,6 +348,10 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
                 if (iq < B && jd < M) {
                     const float ls = ls_y[r];
                     v = (expf(acc[r] / temperature - ls) - (jd == iq + pos_offset ? 1.0f : 0.0f)) * scale;
+                    if (GROUPED) {
+                        const int64_t gq = QOWN ? own_g : oth_g[r], gd = QOWN ? oth_g[r] : own_g;
+                        v = ((gq >= 0) & (gd == gq) & (jd != iq + pos_offset)) ? 0.0f : v;  // (bitwise: a select, no branch)
+                    }
                 }
                 g[r] = v;
             }
@@ -360,8 +416,10 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
 }
 
 // Blocks [0, tiles_q * slices_q): query tiles (block = slice * tiles_q + tile); the rest: document tiles, the same way.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
-                                                      const float *__restrict__ lse, int B, int M, int pos_offset, int Hp,
+                                                      const float *__restrict__ lse, const int64_t *__restrict__ qg,
+                                                      const int64_t *__restrict__ dg, int B, int M, int pos_offset, int Hp,
                                                       int Bq, int Dp, float temperature, int tiles_q, int slices_q, int per_q, int tiles_d,
                                                       int per_d, float *__restrict__ part_q, float *__restrict__ part_d)
 {
@@ -370,14 +428,14 @@ __global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ 
     if (b < tiles_q * slices_q) {
         const int slice = b / tiles_q, chunks = (M + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
-        ib_grad_body<true>(ib_lds, qh, dh, lse, B, M, pos_offset, Hp, temperature, b % tiles_q, slice * per_q, end,
-                           part_q + (size_t)slice * Bq * Hp);
+        ib_grad_body<true, GROUPED>(ib_lds, qh, dh, lse, qg, dg, B, M, pos_offset, Hp, temperature, b % tiles_q, slice * per_q,
+                                    end, part_q + (size_t)slice * Bq * Hp);
     } else {
         b -= tiles_q * slices_q;
         const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
-        ib_grad_body<false>(ib_lds, qh, dh, lse, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d, end,
-                            part_d + (size_t)slice * Dp * Hp);
+        ib_grad_body<false, GROUPED>(ib_lds, qh, dh, lse, qg, dg, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d,
+                                     end, part_d + (size_t)slice * Dp * Hp);
     }
 }
 
@@ -453,9 +511,10 @@ __global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ 
     }
 }
 
-// The launches of one call; both entries have refused what they refuse.  dd.lo == nullptr: the loss only.
-void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, int pos_offset, float temperature, float *loss,
-               float *dq, IBDocGrads dd, void *workspace, hipStream_t st)
+// The launches of one call; the entries have refused what they refuse.  dd.lo == nullptr: the loss only.  qg == nullptr: no
+// labels (the ungrouped instantiations); else qg [B], dg [M].
+void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, int pos_offset, const int64_t *qg,
+               const int64_t *dg, float temperature, float *loss, float *dq, IBDocGrads dd, void *workspace, hipStream_t st)
 {
     char *ws = (char *)workspace;
     float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
@@ -465,17 +524,18 @@ void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H
     float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
     float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
     const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
-    hipLaunchKernelGGL(ib_stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, B, M,
-                       pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
+    const auto stats_kernel = qg ? ib_stats_kernel<true> : ib_stats_kernel<false>;
+    const auto grad_kernel = qg ? ib_grad_kernel<true> : ib_grad_kernel<false>;
+    hipLaunchKernelGGL(stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
+                       P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
     hipLaunchKernelGGL(ib_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
                        (const float *)pos, B, P.Bq, P.sq.n, lse, rows);
     hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
     if (dq) {
         const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
         const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
-        hipLaunchKernelGGL(ib_grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh,
-                           (const float *)dh, (const float *)lse, B, M, pos_offset, P.Hp, P.Bq, P.Dp, temperature, tiles_q,
-                           P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d);
+        hipLaunchKernelGGL(grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, qg, dg, B, M, pos_offset,
+                           P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d);
         hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
                            (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
                            (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dd);
@@ -513,10 +573,42 @@ TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *
     if (workspace_bytes < P.total)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
     // D = [p; n]: the pool of M = 2B documents in two pieces, the positive of query i in row i
-    ib_launch(P, q, IBDocs{p, n, B}, B, 2 * B, H, 0, temperature, loss, dq, IBDocGrads{dp, dn, B}, workspace, (hipStream_t)stream);
+    ib_launch(P, q, IBDocs{p, n, B}, B, 2 * B, H, 0, nullptr, nullptr, temperature, loss, dq, IBDocGrads{dp, dn, B}, workspace,
+              (hipStream_t)stream);
     TT_LAUNCH_CHECK();
     return TT_OK;
 }
+
+namespace {
+
+// The pool entries behind their names: `who` opens every message; grouped: the call brings labels (both non-null).
+int ib_pool_call(const char *who, bool grouped, const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                 const int64_t *q_groups, const int64_t *doc_groups, float temperature, float *loss, float *dq, float *ddocs,
+                 void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    if (!ib_shape_ok(B, M, H))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", who, B, M, H, IB_MAX_B,
+                       IB_MAX_M, IB_MAX_H);
+    if (pos_offset < 0 || pos_offset > M - B)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: pos_offset=%d outside [0, M - B = %d]", who, pos_offset, M - B);
+    if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: temperature=%g must be finite and > 0", who, (double)temperature);
+    if (!q || !docs || !loss || !workspace || (grouped && (!q_groups || !doc_groups)))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    if (!dq != !ddocs)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: dq, ddocs must be both null or both non-null", who);
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: the workspace must be 16-byte aligned", who);
+    const IBPlan P = ib_plan(B, M, H);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
+    ib_launch(P, q, IBDocs{docs, nullptr, M}, B, M, H, pos_offset, grouped ? q_groups : nullptr, grouped ? doc_groups : nullptr,
+              temperature, loss, dq, IBDocGrads{ddocs, nullptr, M}, workspace, (hipStream_t)stream);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+} // namespace
 
 TT_EXPORT size_t tt_contrastive_loss_workspace_bytes(int B, int M, int H)
 {
@@ -527,24 +619,14 @@ TT_EXPORT int tt_contrastive_loss_f32(const float *q, int B, const float *docs, 
                                       float *loss, float *dq, float *ddocs, void *workspace, size_t workspace_bytes,
                                       tt_stream_t stream)
 {
-    if (!ib_shape_ok(B, M, H))
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", B, M,
-                       H, IB_MAX_B, IB_MAX_M, IB_MAX_H);
-    if (pos_offset < 0 || pos_offset > M - B)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: pos_offset=%d outside [0, M - B = %d]", pos_offset, M - B);
-    if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: temperature=%g must be finite and > 0", (double)temperature);
-    if (!q || !docs || !loss || !workspace)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: null pointer");
-    if (!dq != !ddocs)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: dq, ddocs must be both null or both non-null");
-    if ((uintptr_t)workspace & 15)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: the workspace must be 16-byte aligned");
-    const IBPlan P = ib_plan(B, M, H);
-    if (workspace_bytes < P.total)
-        return tt_fail(TT_ERR_BAD_SHAPE, "tt_contrastive_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
-    ib_launch(P, q, IBDocs{docs, nullptr, M}, B, M, H, pos_offset, temperature, loss, dq, IBDocGrads{ddocs, nullptr, M}, workspace,
-              (hipStream_t)stream);
-    TT_LAUNCH_CHECK();
-    return TT_OK;
+    return ib_pool_call("tt_contrastive_loss_f32", false, q, B, docs, M, H, pos_offset, nullptr, nullptr, temperature, loss, dq,
+                        ddocs, workspace, workspace_bytes, stream);
+}
+
+TT_EXPORT int tt_contrastive_loss_grouped_f32(const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                                              const int64_t *q_groups, const int64_t *doc_groups, float temperature, float *loss,
+                                              float *dq, float *ddocs, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return ib_pool_call("tt_contrastive_loss_grouped_f32", true, q, B, docs, M, H, pos_offset, q_groups, doc_groups, temperature,
+                        loss, dq, ddocs, workspace, workspace_bytes, stream);
 }

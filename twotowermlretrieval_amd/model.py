@@ -7,6 +7,8 @@
     triplet_loss_cosine((q, p, n), margin=0.2) -> 0-d tensor                             model.py:109-114
     in_batch_softmax_loss((q, p, n), temperature=0.05) -> 0-d tensor                     (not in the reference: in-batch negatives)
     contrastive_softmax_loss(q, docs, pos_offset=0, temperature=0.05) -> 0-d tensor      (the same over any pool of documents)
+    ... both with group labels (groups=, neg_groups= / q_groups=, doc_groups=): a passage that carries a query's label, other
+    than its own positive, is no negative of it
 
 Same constructor arguments, attribute names (`query_encoder.embedding.embedding_dim` is read by
 backend/main.py:104) and state_dict keys ({query,doc}_encoder.{embedding.weight,
@@ -557,20 +559,35 @@ class _InBatchFn(torch.autograd.Function):
         return g * dq, g * dp, g * dn, None
 
 
-def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], temperature: float = 0.05) -> torch.Tensor:
+def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], temperature: float = 0.05,
+                          groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
     """In-batch negatives: mean_i(logsumexp_j s_ij - s_ii), s_ij = cos(q_i, D_j) / temperature over D = [p; n] -- every query
     is scored against all 2B passages of the batch (its own positive, the other queries' positives, all explicit negatives)
     instead of one hinge against one negative.  Cosine with eps 1e-8 per norm, as triplet_loss_cosine.  Differentiable (fused
     forward + gradient kernels on the f32 matrix pipe, deterministic).
     The pool is the triplet's own 2B passages; contrastive_softmax_loss takes any pool (the trainers gather the passages of all
-    ranks into one with gather_negatives=True)."""
+    ranks into one with gather_negatives=True).
+    groups [B] (int64 on the device): grouped negatives -- query i and its positive carry groups[i], the negatives carry
+    neg_groups [B] (None: -1, no group); a passage with query i's label >= 0, other than its own positive, is left out of its
+    softmax (contrastive_softmax_loss).  Rows of one query that the batch holds several times share a label."""
     query, pos_doc, neg_doc = triplet
+    if groups is None and neg_groups is not None:
+        raise ValueError("in_batch_softmax_loss: neg_groups needs groups")
     for t in (query, pos_doc, neg_doc):
         if not t.is_cuda:
             raise RuntimeError("in_batch_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
             raise ValueError("in_batch_softmax_loss wants three float32 [B,H] tensors of one shape")
-    return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)
+    if groups is None:
+        return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)
+    B = query.shape[0]
+    groups = _group_labels("in_batch_softmax_loss", "groups", groups, B, query.device)
+    if neg_groups is None:
+        neg_groups = torch.full_like(groups, -1)
+    else:
+        neg_groups = _group_labels("in_batch_softmax_loss", "neg_groups", neg_groups, B, query.device)
+    # (the pool entry on [p; n]: the in-batch entry's bits)
+    return contrastive_softmax_loss(query, torch.cat((pos_doc, neg_doc)), 0, temperature, groups, torch.cat((groups, neg_groups)))
 
 
 def contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
@@ -583,7 +600,7 @@ def contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
 
 class _ContrastiveFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, docs, pos_offset: int, temperature: float):
+    def forward(ctx, q, docs, pos_offset: int, temperature: float, q_groups=None, doc_groups=None):
         L = _lib.lib()
         q, docs = q.contiguous(), docs.contiguous()
         (B, H), M = q.shape, docs.shape[0]
@@ -591,24 +608,46 @@ class _ContrastiveFn(torch.autograd.Function):
         dq, ddocs = torch.empty_like(q), torch.empty_like(docs)
         ws = contrastive_workspace(B, M, H, q.device)
         with torch.cuda.device(q.device):
-            _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), float(temperature),
-                                                 loss.data_ptr(), dq.data_ptr(), ddocs.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 _stream(q.device)))
+            if q_groups is None:
+                _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), float(temperature),
+                                                     loss.data_ptr(), dq.data_ptr(), ddocs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _stream(q.device)))
+            else:
+                q_groups, doc_groups = q_groups.contiguous(), doc_groups.contiguous()
+                _lib.check(L.tt_contrastive_loss_grouped_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset),
+                                                             q_groups.data_ptr(), doc_groups.data_ptr(), float(temperature),
+                                                             loss.data_ptr(), dq.data_ptr(), ddocs.data_ptr(), ws.data_ptr(),
+                                                             ws.numel(), _stream(q.device)))
         ctx.save_for_backward(dq, ddocs)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         dq, ddocs = ctx.saved_tensors
-        return g * dq, g * ddocs, None, None
+        return g * dq, g * ddocs, None, None, None, None
 
 
-def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05) -> torch.Tensor:
+def _group_labels(who: str, name: str, t, rows: int, device) -> torch.Tensor:
+    """`t` as the labels of `rows` rows, or the ValueError that names the argument."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (rows,) or t.device != device:
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name} must be an int64 tensor [{rows}] on {device}, got {got}")
+    return t
+
+
+def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05,
+                             q_groups: Optional[torch.Tensor] = None, doc_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The softmax contrastive loss of B queries over a pool of M >= B documents:
     mean_i(logsumexp_j s_ij - s_{i, pos_offset+i}), s_ij = cos(q_i, docs_j) / temperature -- the positive of query i is row
     pos_offset + i of `docs`, every other row is a negative (the passages gathered from all ranks; or several explicit negatives
     per query).  in_batch_softmax_loss((q, p, n)) is contrastive_softmax_loss(q, cat(p, n)), bit for bit.  Cosine with eps 1e-8
-    per norm.  Differentiable in q and docs (fused forward + gradient kernels on the f32 matrix pipe, deterministic)."""
+    per norm.  Differentiable in q and docs (fused forward + gradient kernels on the f32 matrix pipe, deterministic).
+    q_groups [B], doc_groups [M] (int64 on the device, both or neither): grouped negatives.  Row j is left out of query i's
+    softmax -- logsumexp and both gradients -- when j != pos_offset + i, q_groups[i] >= 0 and doc_groups[j] == q_groups[i]:
+    the other positives of a query that the batch holds several times are no negatives of it.  A negative label is "no group".
+    With no match off the positives the result is the ungrouped call's, bit for bit."""
+    if (q_groups is None) != (doc_groups is None):
+        raise ValueError("contrastive_softmax_loss: q_groups and doc_groups must be both given or both None")
     for t in (q, docs):
         if not t.is_cuda:
             raise RuntimeError("contrastive_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
@@ -623,4 +662,8 @@ def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: in
         raise ValueError(f"contrastive_softmax_loss: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
     if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
         raise ValueError(f"contrastive_softmax_loss: temperature={temperature!r} must be finite and > 0")
-    return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature))
+    if q_groups is None:
+        return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature))
+    q_groups = _group_labels("contrastive_softmax_loss", "q_groups", q_groups, B, q.device)
+    doc_groups = _group_labels("contrastive_softmax_loss", "doc_groups", doc_groups, M, q.device)
+    return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature), q_groups, doc_groups)

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .collective import Collective
-from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _raise_status, contrastive_softmax_loss,
+from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, contrastive_softmax_loss,
                     contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
@@ -326,6 +326,26 @@ class _StepSpec(NamedTuple):
         return self
 
 
+def _batch_labels(who: str, spec: _StepSpec, batch, groups, neg_groups) -> Optional[torch.Tensor]:
+    """The batch's group labels as one int64 tensor [2B] = [groups; neg_groups], the labels of the 2B passages [p; n] (its first
+    B entries are the queries' too), or None without labels.  They are data of the batch and travel beside it, not in the spec.
+    neg_groups None: the negatives carry -1 (no group).  Raises the ValueError of labels no step can use before anything is
+    launched: they are for negatives="in_batch" alone."""
+    if groups is None and neg_groups is None:
+        return None
+    if spec.negatives != "in_batch":
+        raise ValueError(f'{who}: groups / neg_groups need negatives="in_batch", got negatives={spec.negatives!r}')
+    if groups is None:
+        raise ValueError(f"{who}: neg_groups needs groups")
+    queries, pos_docs, neg_docs = batch
+    B = queries.shape[0]
+    if not pos_docs.shape[0] == neg_docs.shape[0] == B:
+        raise ValueError(f"{who}: groups need as many negatives as positives as queries")
+    groups = _group_labels(who, "groups", groups, B, queries.device)
+    neg_groups = torch.full_like(groups, -1) if neg_groups is None else _group_labels(who, "neg_groups", neg_groups, B, queries.device)
+    return torch.cat((groups, neg_groups))
+
+
 _TOWER_STREAMS = {}
 
 
@@ -543,8 +563,9 @@ class _TowerForward(NamedTuple):
 class _DirectStep:
     """One direct step in flight: what its stages -- forward towers, loss, backward towers, apply or fold -- hand to each other."""
 
-    def __init__(self, model, optimizer, spec, capture):
+    def __init__(self, model, optimizer, spec, capture, labels=None):
         self.model, self.optimizer, self.spec, self.capture = model, optimizer, spec, capture
+        self.labels = labels     # the batch's group labels [2B] (_batch_labels), None: none
         self.encs = (model.doc_encoder, model.query_encoder)
         self.ordered = False     # the forward recurrences are ordered by events (syncs: what a call of each kind carries)
         self.into = self.ids_of = self.streams = self.cur = self.s_main = self.syncs = None
@@ -628,36 +649,57 @@ def _forward_towers(st: _DirectStep, batch) -> None:
                 st.fw[tower] = _TowerForward(*res, p_drop, seed, enc._opts_bwd())
 
 
-def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main):
+def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None):
     """The fused loss + gradient launch of the step's kind on s_main (the current stream): (loss, dq, dpn) for the towers' outputs
     q [B,H] and pn [2B,H] (positives, then negatives).  The kinds share the buffers; "in_batch" swaps the one launch, nothing else.
     gather_negatives: the loss runs over the passages of ALL ranks: all-gather of pn into the pool G [world * 2B, H] (rank order),
     tt_contrastive_loss_f32(q, G, pos_offset = rank * 2B) -> loss, dq, dG, summing all-reduce of dG, dpn = this rank's 2B rows of
     it.  Both collectives go out whatever the towers' status words say, in front of the query tower's reduce_prefix: every rank
-    issues gather, reduce, (prefix,) bucket in that order."""
+    issues gather, reduce, (prefix,) bucket in that order.
+    labels (the batch's group labels [2B], "in_batch" only): the grouped pool entry on pn as it lies (the in-batch entry's bits
+    where no label matches); gathered, the ranks' labels travel like the passages, by an all-gather right behind theirs --
+    gather, label gather, reduce on every rank."""
     (B, H), dev = q.shape, q.device
     loss = torch.empty((), dtype=torch.float32, device=dev)
     dq = torch.empty_like(q)
+    pool_labels = labels
     if spec.gather_negatives:
         coll = optimizer._coll
         pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
         d_pool = torch.empty_like(pool)
         dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
         rows = contrastive_workspace(B, pool.shape[0], H, dev)
+        if labels is not None:
+            pool_labels = torch.empty(coll.world * 2 * B, dtype=torch.int64, device=dev)
     else:
         dpn = torch.empty_like(pn)
-        rows = in_batch_workspace(B, H, dev) if spec.negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
-    for t in (q, pn, loss, dq, dpn, rows):
+        if labels is not None:
+            rows = contrastive_workspace(B, 2 * B, H, dev)
+        else:
+            rows = in_batch_workspace(B, H, dev) if spec.negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
+    for t in (q, pn, loss, dq, dpn, rows) + (() if labels is None else (labels, pool_labels)):
         t.record_stream(s_main)
     L, p, n = _lib.lib(), pn[:B], pn[B:]
     with torch.cuda.device(dev):
         if spec.gather_negatives:
             coll.all_gather_blocks(pn, pool)
-            _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
-                                                 float(spec.temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
-                                                 rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+            if labels is None:
+                _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
+                                                     float(spec.temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
+                                                     rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+            else:
+                coll.all_gather_blocks(labels, pool_labels)
+                _lib.check(L.tt_contrastive_loss_grouped_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
+                                                             labels.data_ptr(), pool_labels.data_ptr(), float(spec.temperature),
+                                                             loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(), rows.data_ptr(),
+                                                             rows.numel(), s_main.cuda_stream))
             # (no scale: a summed row is sum_r d loss_r / d D_j, and the optimizer's 1 / world makes it the mean's)
             coll.all_reduce_sum(d_pool.view(-1))
+        elif labels is not None:
+            # (the queries' labels are the first B of the passages': the positives')
+            _lib.check(L.tt_contrastive_loss_grouped_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, 0, labels.data_ptr(),
+                                                         labels.data_ptr(), float(spec.temperature), loss.data_ptr(), dq.data_ptr(),
+                                                         dpn.data_ptr(), rows.data_ptr(), rows.numel(), s_main.cuda_stream))
         elif spec.negatives == "in_batch":
             _lib.check(L.tt_in_batch_loss_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, H, float(spec.temperature),
                                               loss.data_ptr(), dq.data_ptr(), dpn[:B].data_ptr(), dpn[B:].data_ptr(),
@@ -675,7 +717,7 @@ def _loss_and_embedding_grads(st: _DirectStep) -> None:
     each way on that path: event wait + launch); the query tower's stream joins for the loss and again before the optimizer."""
     st.join()
     with torch.cuda.stream(st.s_main):
-        st.loss, dq, dpn = _direct_loss(st.spec, st.optimizer, st.fw[_QRY].out, st.fw[_DOC].out, st.s_main)
+        st.loss, dq, dpn = _direct_loss(st.spec, st.optimizer, st.fw[_QRY].out, st.fw[_DOC].out, st.s_main, st.labels)
     st.d_out = (dpn, dq)
 
 
@@ -729,7 +771,7 @@ def _apply_or_fold(st: _DirectStep) -> None:
 
 
 def _train_step_direct(model: TwoTowerModel, optimizer, batch, spec: _StepSpec, plan: Optional[_towers_in_flight],
-                       capture: Optional[_Capture]):
+                       capture: Optional[_Capture], labels: Optional[torch.Tensor] = None):
     """The same step without the autograd engine: tower forwards (train mode), the fused loss + gradient kernel, tower backwards
     written STRAIGHT into the optimizer's flat gradient buffer, optimizer step.  Every parameter receives its gradient exactly
     once (query tower once; positives and negatives as one 2B-row document-tower call), so nothing has to be zeroed or
@@ -737,8 +779,9 @@ def _train_step_direct(model: TwoTowerModel, optimizer, batch, spec: _StepSpec, 
     tower, the 3.4 MB zero fill -- is ~0.1 ms of small launches on the document tower's critical path.  Returns None when the
     shortcut does not apply (_direct_grad_views): the caller then takes the autograd path.
     batch: (queries, pos_docs, neg_docs); plan: the step's _towers_in_flight -- when the two towers' split recurrences do not fit
-    the device together their forward recurrence launches are ordered with events; capture: None for the eager step."""
-    st = _DirectStep(model, optimizer, spec, capture)
+    the device together their forward recurrence launches are ordered with events; capture: None for the eager step; labels: the
+    batch's group labels (_batch_labels), None: none."""
+    st = _DirectStep(model, optimizer, spec, capture, labels)
     st.into = _direct_grad_views(model, optimizer, batch, spec, capture)
     if st.into is None:
         return None
@@ -796,24 +839,33 @@ class _GatherPoolFn(torch.autograd.Function):
         return d_pool[ctx.coll.rank * ctx.rows:(ctx.coll.rank + 1) * ctx.rows], None
 
 
-def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn):
+def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None):
     """The loss of the step's kind as an autograd graph over the towers' outputs (q, p, n); pn: the 2B passages as one tensor
-    when the document tower ran once (None: it did not).  Gathered: the loss of this rank's queries over the passages of all ranks."""
+    when the document tower ran once (None: it did not).  Gathered: the loss of this rank's queries over the passages of all ranks.
+    labels: the batch's group labels [2B] (_batch_labels); gathered, the ranks' labels are gathered right behind the passages."""
     if spec.gather_negatives:
         coll = getattr(optimizer, "_coll", None)
         if coll is None:
             raise ValueError("gather_negatives=True needs a FusedClipAdam (the passages travel through its Collective)")
         if pn is None:
             pn = torch.cat(embeddings[1:])
-        return contrastive_softmax_loss(embeddings[0], _GatherPoolFn.apply(pn, coll), pos_offset=coll.rank * pn.shape[0],
-                                        temperature=spec.temperature)
+        pool = _GatherPoolFn.apply(pn, coll)
+        if labels is None:
+            return contrastive_softmax_loss(embeddings[0], pool, pos_offset=coll.rank * pn.shape[0], temperature=spec.temperature)
+        pool_labels = torch.empty(coll.world * labels.shape[0], dtype=torch.int64, device=labels.device)
+        coll.all_gather_blocks(labels, pool_labels)
+        return contrastive_softmax_loss(embeddings[0], pool, pos_offset=coll.rank * pn.shape[0], temperature=spec.temperature,
+                                        q_groups=labels[:embeddings[0].shape[0]], doc_groups=pool_labels)
     if spec.negatives == "in_batch":
+        if labels is not None:
+            B = embeddings[0].shape[0]
+            return in_batch_softmax_loss(embeddings, temperature=spec.temperature, groups=labels[:B], neg_groups=labels[B:])
         return in_batch_softmax_loss(embeddings, temperature=spec.temperature)
     return triplet_loss_cosine(embeddings, margin=spec.margin)
 
 
-def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_flight):
-    loss = _train_step_direct(model, optimizer, batch, spec, plan, None)
+def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_flight, labels=None):
+    loss = _train_step_direct(model, optimizer, batch, spec, plan, None, labels)
     if loss is not None:
         return loss
     plan.use_one_workgroup()   # (autograd calls cannot carry the ordering events)
@@ -858,15 +910,15 @@ def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_
         q = model.encode_query(queries)
         p = model.encode_document(pos_docs)
         n = model.encode_document(neg_docs)
-    loss = _autograd_loss(spec, optimizer, (q, p, n), pn)
+    loss = _autograd_loss(spec, optimizer, (q, p, n), pn, labels)
     loss.backward()
     optimizer.step()
     return loss.detach()
 
 
-def _eager_step(model, optimizer, batch, spec: _StepSpec):
+def _eager_step(model, optimizer, batch, spec: _StepSpec, labels=None):
     """One step with the read of the gate wherever optimizer.check puts it; a time-out of a column-split recurrence redoes the
-    step on the one-workgroup kernels (ordinary relaunch, same bits as the split forward)."""
+    step on the one-workgroup kernels (ordinary relaunch, same bits as the split forward), with the same labels."""
     queries, pos_docs, neg_docs = batch
     encs = (model.query_encoder, model.doc_encoder)
     n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (spec.concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
@@ -875,35 +927,36 @@ def _eager_step(model, optimizer, batch, spec: _StepSpec):
     rng = torch.get_rng_state() if any(e.dropout > 0.0 and e.training for e in encs) else None
     try:
         with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
-            return _train_step_once(model, optimizer, batch, spec, plan)
+            return _train_step_once(model, optimizer, batch, spec, plan, labels)
     except SplitRecurrenceTimeout:
         if rng is not None:
             torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
         with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
-            return _train_step_once(model, optimizer, batch, spec, plan)
+            return _train_step_once(model, optimizer, batch, spec, plan, labels)
 
 
-def _step(model, optimizer, batch, spec: _StepSpec, defer_check: bool):
-    """train_step behind its argument list (DataParallelTrainer.step enters here with its own record)."""
+def _step(model, optimizer, batch, spec: _StepSpec, defer_check: bool, labels=None):
+    """train_step behind its argument list (DataParallelTrainer.step enters here with its own record).  labels: _batch_labels."""
     queries, pos_docs, neg_docs = batch
     if spec.gather_negatives and not queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]:
         raise ValueError("gather_negatives=True needs as many negatives as positives as queries")
     if not (defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda):
-        return _eager_step(model, optimizer, batch, spec)
+        return _eager_step(model, optimizer, batch, spec, labels)
     keep, optimizer.check = optimizer.check, False
     try:
-        loss = _eager_step(model, optimizer, batch, spec)
+        loss = _eager_step(model, optimizer, batch, spec, labels)
     finally:
         optimizer.check = keep
     if keep:
-        optimizer.snapshot_gate(redo=lambda: _eager_step(model, optimizer, batch, spec))
+        optimizer.snapshot_gate(redo=lambda: _eager_step(model, optimizer, batch, spec, labels))
     return loss
 
 
 def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Tensor, pos_docs: torch.Tensor,
                neg_docs: torch.Tensor, margin: float = 0.2, concurrent_towers: bool = True, direct: bool = True,
                defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05,
-               gather_negatives: bool = False) -> torch.Tensor:
+               gather_negatives: bool = False, groups: Optional[torch.Tensor] = None,
+               neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One step of backend/main.py:244-259 on this rank's (equal-sized) share of the global batch.
     Returns the local loss as a 0-d device tensor (no .item(): the reference's per-step sync is dropped).
 
@@ -934,9 +987,19 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     optimizer's 1/world the update is the gradient of the mean of the ranks' losses, which is the loss of the global batch.
     Every rank must bring the same B.  Returns the rank's own loss: the mean over its B queries against the global pool.
     Both collectives are issued whatever the batch holds, so failure stays collective (above); a redo after a recurrence
-    time-out repeats them on all ranks.  One process without a group: the same bits as without the flag."""
+    time-out repeats them on all ranks.  One process without a group: the same bits as without the flag.
+
+    groups / neg_groups (negatives="in_batch" only; int64 [B] on the batch's device): grouped negatives.  Row i's query and
+    positive carry groups[i], its negative neg_groups[i] (None: -1, no group).  A passage that carries a query's label >= 0, other
+    than the query's own positive, is left out of that query's softmax (model.contrastive_softmax_loss): a batch that holds one
+    query several times, each with another of its positives, gives the copies one label, and they stop pushing each other's
+    positives away.  Derive the label from the loader's query index.  With gather_negatives=True the ranks'
+    labels are all-gathered right behind the passages (one more collective, in front of the summing all-reduce), so labels must
+    be global (the same query has the same label on every rank) and EVERY rank must pass labels, or none -- like "every rank
+    must bring the same B".  The direct and the autograd path give the same bits; a redo keeps the labels."""
     spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct).checked(graphs=False)
-    return _step(model, optimizer, (queries, pos_docs, neg_docs), spec, defer_check)
+    batch = (queries, pos_docs, neg_docs)
+    return _step(model, optimizer, batch, spec, defer_check, _batch_labels("train_step", spec, batch, groups, neg_groups))
 
 
 class DataParallelTrainer:
@@ -974,19 +1037,21 @@ class DataParallelTrainer:
             dist.broadcast(self.optimizer.flat_params, src=src, group=self.optimizer.group)
         self.optimizer.mark_params_changed()  # (the broadcast wrote the flat buffer, not the parameter tensors)
 
-    def _graph_for(self, batch, spec: _StepSpec) -> Optional["GraphedTrainStep"]:
+    def _graph_for(self, batch, spec: _StepSpec, grouped: bool = False) -> Optional["GraphedTrainStep"]:
         queries, pos_docs, neg_docs = batch
         if not (_standard_batch(batch) and queries.dtype == torch.int64 and _frozen_tables(self.model)
                 and self.model.query_encoder.check_inputs and self.model.doc_encoder.check_inputs):
             return None
         up = lambda x: max(self.width_step, -(-int(x) // self.width_step) * self.width_step)  # noqa: E731
         key = (queries.shape[0], up(queries.shape[1]), up(max(pos_docs.shape[1], neg_docs.shape[1])))
+        if grouped:
+            key += ("grouped",)   # (a step with labels is another graph: its loss node is the grouped entry's; others keep their key)
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
                 self._graphs.pop(next(iter(self._graphs)))
             g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], spec.margin, defer_check=self.defer_check,
-                                 negatives=spec.negatives, temperature=spec.temperature)
+                                 negatives=spec.negatives, temperature=spec.temperature, grouped=bool(grouped))
         self._graphs[key] = g                                      # (re-inserted: most recently used last)
         return g
 
@@ -994,14 +1059,17 @@ class DataParallelTrainer:
         """defer_check: settle the last step's pending check."""
         return self.optimizer.settle()
 
-    def step(self, queries, pos_docs, neg_docs) -> torch.Tensor:
+    def step(self, queries, pos_docs, neg_docs, groups=None, neg_groups=None) -> torch.Tensor:
+        """groups / neg_groups: grouped negatives, see train_step (negatives="in_batch" only; with gather_negatives=True every
+        rank passes labels or none)."""
         self.model.train()
         batch, spec = (queries, pos_docs, neg_docs), self._spec()
+        labels = _batch_labels("DataParallelTrainer.step", spec, batch, groups, neg_groups)
         if self.graphs:
-            g = self._graph_for(batch, spec)
+            g = self._graph_for(batch, spec, labels is not None)
             if g is not None:
-                return g(queries, pos_docs, neg_docs)
-        return _step(self.model, self.optimizer, batch, spec, self.defer_check)
+                return g(queries, pos_docs, neg_docs, groups, neg_groups)
+        return _step(self.model, self.optimizer, batch, spec, self.defer_check, labels)
 
 
 class _SeedRing:
@@ -1051,12 +1119,17 @@ class GraphedTrainStep:
     optimizer's own parameters on a GPU, GloVe-frozen tables, input checking on (default).  Inter-layer dropout (the reference's
     default model has it) is captured with its seeds as device words (TT_ENC_SEED_ON_DEVICE, include/tt.h): every call draws them
     from torch's CPU generator in the eager step's order and copies them in front of the replay, so a replay computes what the
-    eager step would have computed with the generator in the same state."""
+    eager step would have computed with the generator in the same state.
+    grouped=True (negatives="in_batch" only): the captured loss is the grouped entry's; the batch's group labels (train_step:
+    groups, neg_groups) are a static int64 input [2B] like the ids, copied in front of the replay.  A call without labels fills
+    -1 (no group: the bits of the ungrouped step); neg_groups=None fills -1 for the negatives."""
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
-                 defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05):
+                 defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05, grouped: bool = False):
         # (margin, negatives and temperature are arguments of the captured loss launches)
         self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True).checked(graphs=True)
+        if grouped and negatives != "in_batch":
+            raise ValueError(f'GraphedTrainStep: grouped=True needs negatives="in_batch", got negatives={negatives!r}')
         encs = (model.query_encoder, model.doc_encoder)
         if not isinstance(optimizer, _FlatClipAdam) or optimizer._gated_step_fn is None:
             raise TypeError("GraphedTrainStep needs a FusedClipAdam")
@@ -1069,6 +1142,8 @@ class GraphedTrainStep:
         dev = optimizer.flat_params.device
         self.q = torch.zeros((self.B, self.q_width), dtype=torch.int64, device=dev)
         self.both = torch.zeros((2 * self.B, self.doc_width), dtype=torch.int64, device=dev)
+        self.grouped = bool(grouped)
+        self.labels = torch.full((2 * self.B,), -1, dtype=torch.int64, device=dev) if self.grouped else None
         # inter-layer dropout: the seeds are device words the captured kernels read when they run (TT_ENC_SEED_ON_DEVICE); every
         # call draws them from torch's CPU generator exactly as the eager step does and copies them there in front of the replay
         self._seeds = _SeedRing(dev) if any(e.dropout > 0.0 for e in encs) else None
@@ -1104,14 +1179,17 @@ class GraphedTrainStep:
     def _run(self):
         rows = {self.model.query_encoder: self.B, self.model.doc_encoder: 2 * self.B}
         with _towers_in_flight(self.model, self.optimizer, rows) as plan:
-            return _train_step_direct(self.model, self.optimizer, (self.q, None, None), self._spec, plan, self._capture)
+            return _train_step_direct(self.model, self.optimizer, (self.q, None, None), self._spec, plan, self._capture, self.labels)
 
     def flush(self):
         """defer_check: settle the optimizer's pending check (raises that step's exception, if any)."""
         return self.optimizer.settle()
 
-    def __call__(self, queries: torch.Tensor, pos_docs: torch.Tensor, neg_docs: torch.Tensor) -> torch.Tensor:
+    def __call__(self, queries: torch.Tensor, pos_docs: torch.Tensor, neg_docs: torch.Tensor,
+                 groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns the step's loss (a static 0-d device tensor, valid until the next call)."""
+        if (groups is not None or neg_groups is not None) and not self.grouped:
+            raise ValueError("GraphedTrainStep was captured without labels (grouped=False), got groups / neg_groups")
         for src, width, what in ((queries, self.q_width, "queries"), (pos_docs, self.doc_width, "pos_docs"), (neg_docs, self.doc_width, "neg_docs")):
             if src.dim() != 2 or src.shape[0] != self.B or src.shape[1] > width or src.dtype != torch.int64:
                 raise ValueError(f"GraphedTrainStep was captured for int64 {what} [{self.B}, <= {width}], got {src.dtype} {tuple(src.shape)}")
@@ -1121,6 +1199,15 @@ class GraphedTrainStep:
                              "arguments of the captured launches); build a new GraphedTrainStep")
         _stage_ids(self.q, queries, None)
         _stage_ids(self.both, pos_docs, neg_docs)
+        if self.grouped:
+            # (checked like train_step's: the eager redo takes the same labels)
+            labels = _batch_labels("GraphedTrainStep", self._spec, (queries, pos_docs, neg_docs), groups, neg_groups)
+            if labels is None:
+                self.labels.fill_(-1)
+            else:
+                self.labels.copy_(labels)
+        else:
+            labels = None
         if self._seeds is not None:
             drawn = _draw_dropout_seeds(self.model)
             self._seeds.put(drawn[id(self.model.query_encoder)], drawn[id(self.model.doc_encoder)])
@@ -1131,7 +1218,7 @@ class GraphedTrainStep:
         if not opt.check:
             return self.loss
         # (the eager redo takes the one-workgroup retry itself if it must)
-        opt.snapshot_gate(redo=lambda: _eager_step(self.model, opt, (queries, pos_docs, neg_docs), self._spec))
+        opt.snapshot_gate(redo=lambda: _eager_step(self.model, opt, (queries, pos_docs, neg_docs), self._spec, labels))
         if not self.defer_check:
             redone = opt.settle()            # the step's one host synchronisation
             if redone is not None:
