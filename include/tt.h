@@ -206,6 +206,39 @@ int tt_score_topk_tagged_bf16(const float *Q, int B, int d, const void *D_bf16, 
                               tt_stream_t stream);
 
 /*
+ * Biased search: the masked exact search with a per-document term added to every score, in one pass over the corpus -- a
+ * popularity or recency prior, a log-probability correction, a curated boost or demotion; with bias[n] = -|d_n|^2 / 2 the
+ * ranking is that of the Euclidean distance.  Replaces
+ *     scores = torch.matmul(q, D.t()) + bias[None, :]; torch.topk(scores, k)
+ * (backend/evaluators.py:185-186 with a prior), which materialises [B, N] floats.
+ * bias: device memory, one float per document, 32 * ceil(N/32) floats (padded to whole 32-document tiles; the words at or
+ * beyond N are read and ignored whatever they hold, NaN and infinities included), 16-byte aligned (a misaligned pointer:
+ * TT_ERR_BAD_SHAPE).  Document n's score for query b is
+ *     fl32( s[b, n] + bias[n] )
+ * where s is the score of tt_score_topk_f32 / _bf16 (the fp32 fmaf chain over the feature index ascending from 0): ONE fp32
+ * add, round to nearest even, after the chain has finished -- not an initial accumulator and not an fma.  The result is the
+ * exact top-k of that biased score over the kept documents (keep: tt_score_topk_masked_f32's bitmask, or NULL: all),
+ * (score desc, index asc), tail (-inf, -1); the values returned are the biased scores.  Every bias[n], n < N, must be finite and
+ * s + bias must not overflow: anything else is outside the contract (nothing here checks it).
+ * bias == NULL: the call then IS the masked call: same launches, same bits.  A bias of all +0.0 returns the masked call's
+ * indices and equal values.
+ * 1 <= k <= 64 (above: TT_ERR_UNSUPPORTED, and the size query returns 0, as it does for B = 0); d and dtype support, N's bound,
+ * the alignment of Q / D / keep / workspace and the status codes are the masked call's.  N = 0 writes the tail.  Asynchronous,
+ * capturable, no host synchronisation, no allocation, no global state: the kernels read bias, so a captured call follows the
+ * values the buffer holds at replay.  The result does not depend on what the workspace (tt_score_topk_biased_workspace_bytes:
+ * the masked call's) and the outputs held.
+ * The bias acts where the keep-bitmask does: in the sample maxima that seed the thresholds, in the append pass and in the
+ * give-up redo.
+ */
+size_t tt_score_topk_biased_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_biased_f32(const float *Q, int B, int d, const float *D, int64_t N, const float *bias, const uint32_t *keep,
+                             int k, int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                             size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_biased_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const float *bias,
+                              const uint32_t *keep, int k, int64_t idx_offset, float *out_val, int64_t *out_idx, void *workspace,
+                              size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
  * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
  * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it

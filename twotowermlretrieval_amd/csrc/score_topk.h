@@ -63,6 +63,8 @@ struct ExactCall {
     const unsigned *tags = nullptr;
     const unsigned *match_mask = nullptr;
     const unsigned *match_value = nullptr;
+    // biased search (tt_score_topk_biased_f32 / _bf16): one float per document, padded to whole 32-document tiles, or nullptr
+    const float *bias = nullptr;
 };
 
 // What varies between the main passes of one call.  (The sample pass always seeds for the call's k.)

@@ -31,6 +31,7 @@
 #include "score_topk.h"
 #include "keep_word.h"
 #include "tag_words.h"
+#include "bias_words.h"
 
 #include <limits.h>
 #include <math.h>
@@ -101,6 +102,9 @@ struct ScoreParams {
     const unsigned *tags = nullptr;
     const unsigned *match_mask = nullptr;
     const unsigned *match_value = nullptr;
+    // BIASED instantiations (biased search): bias [32 * n_tiles] one float per document -- the score of document n is
+    // fl32(q.d + bias[n]); nullptr in every other launch
+    const float *bias = nullptr;
 };
 
 // The keep word of one tile (MASKED): keep_word_issue / keep_word_wait (keep_word.h, shared with screen.hip).  Here the load is
@@ -207,14 +211,20 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // keep word does under MASKED, so the sample maxima, the append pass and the give-up redo see the same predicate.  The tile skip
 // moves in front of the ballot: a tile may be dead for one query of the wave and live for another.  TAGGED = false is the kernel
 // as it was.
+// BIASED (with MASKED, never with TAGGED or COUNT; tt_score_topk_biased_f32 / _bf16, DESIGN.md "Biased search"): every score
+// becomes fl32(score + p.bias[document]).  The tile's 32 biases take the tags' route into the epilogue (bias_words.h) and are
+// added to the accumulators before anything else reads them, so the sample maxima, the tile maximum, the threshold test and
+// the append store all see the biased score.  p.keep may be nullptr (tested wave-uniformly, as under TAGGED: one instantiation
+// serves both).  BIASED = false is the kernel as it was.
 template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false, bool COUNT = false,
-          bool TAGGED = false>
+          bool TAGGED = false, bool BIASED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!BF || NS % 2 == 0, "bf16 rows: d a multiple of 64");
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
+    static_assert(!BIASED || (MASKED && !COUNT && !TAGGED), "biased search: a mode of the masked lists and maxima");
     constexpr int NST = NT ? NSTAGE_NT : NSTAGE;
     constexpr int WAVE_LDS = NST * SLAB_BYTES;
     constexpr int NSD = BF ? NS / 2 : NS; // 128-B slabs per document row
@@ -376,6 +386,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             unsigned kw = 0xffffffffu; // the tile's keep word (MASKED)
             TagWords tg;               // the tile's tags (TAGGED)
+            BiasWords bw;              // the tile's biases (BIASED)
 #pragma unroll
             for (int s = 0; s < NSD; ++s) {
                 // slab (tile,s) has landed once at most (NST-2) younger slabs are pending
@@ -396,8 +407,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 //  replaced by all ones behind the wait -- so that the tile loop has no branch on p.keep)
                 if (TAGGED && s == NSD - 1)
                     tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, frag[0]);
+                // (BIASED: the same route and the same stand-in, the tile's first bias)
+                if (BIASED && s == NSD - 1)
+                    bias_words_issue(p.bias + (size_t)tile * TILE_DOCS, bw, frag[0]);
                 if (MASKED && s == NSD - 1)
-                    keep_word_issue((!TAGGED || p.keep) ? p.keep + tile : p.tags + (size_t)tile * TILE_DOCS, kw, frag[0]);
+                    keep_word_issue((!(TAGGED || BIASED) || p.keep) ? p.keep + tile
+                                    : TAGGED                        ? p.tags + (size_t)tile * TILE_DOCS
+                                                                    : (const unsigned *)p.bias + (size_t)tile * TILE_DOCS,
+                                    kw, frag[0]);
                 dma_issue((stage + NST - 1) % NST);
                 if (BF) {
                     // chunk c holds features 8c..8c+7 of the slab; word w = features (8c+2w, 8c+2w+1) in its (low, high)
@@ -436,6 +453,23 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 tag_words_wait(tg, kw, acc);
                 kwq = tag_match_word(tg, mm, mv) & (p.keep ? kw : 0xffffffffu);
                 kwh = kwq >> (4 * h);
+            } else if (BIASED) {
+                // acc[r] += bias of tile row (r & 3) + 8 (r >> 2) + 4 h, in front of every reader of acc.  (Words at or
+                // beyond N are read, NaN and inf patterns included: the doc < p.N tests below keep such an element out of the
+                // sample maxima and the append pass, and in the tile maximum m a NaN loses every fmaxf against a number -- m
+                // is then the maximum over the lane's real documents -- while an inf only costs the append pass a look.)
+                bias_words_wait(bw, kw, acc);
+                if (!p.keep)
+                    kw = 0xffffffffu;
+                kwh = kw >> (4 * h);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float bq[4];
+                    bias_pick_half(bw, 8 * g, bq);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        acc[4 * g + i] = bias_add(acc[4 * g + i], bq[i]);
+                }
             } else if (MASKED) {
                 keep_word_wait(kw, acc);
                 kwh = kw >> (4 * h);
@@ -601,12 +635,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 // (tools/experiments/mfma16_order.hip), so the oracle parity carries over.  Ring, DMA, thresholds, candidate
 // buffers, compaction, partial lists and merge are K4's; the launch is bound by HBM streaming (d * 4 bytes per doc).
 // ---------------------------------------------------------------------------
-template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false, bool TAGGED = false>
+template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false, bool TAGGED = false,
+          bool BIASED = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
+    static_assert(!BIASED || (MASKED && !COUNT && !TAGGED), "biased search: a mode of the masked lists and maxima");
     constexpr int WAVE_LDS = NSTAGE * SLAB_BYTES;
     constexpr int ROW_BYTES = NS * 128;
     const int lane = threadIdx.x & 63;
@@ -711,6 +747,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
             f32x4 acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
             unsigned kw = 0xffffffffu; // the tile's keep word (MASKED: see score_topk_kernel)
             TagWords tg;               // the tile's tags (TAGGED)
+            BiasWords bw;              // the tile's biases (BIASED)
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_SLAB * (NSTAGE - 2)) : "memory");
@@ -725,7 +762,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
                     float a00[2] = {a[0][0], a[1][0]}; // (both chains' first operands)
                     if (TAGGED)
                         tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, a00);
-                    keep_word_issue((!TAGGED || p.keep) ? p.keep + tile : p.tags + (size_t)tile * TILE_DOCS, kw, a00);
+                    if (BIASED)
+                        bias_words_issue(p.bias + (size_t)tile * TILE_DOCS, bw, a00);
+                    keep_word_issue((!(TAGGED || BIASED) || p.keep) ? p.keep + tile
+                                    : TAGGED                        ? p.tags + (size_t)tile * TILE_DOCS
+                                                                    : (const unsigned *)p.bias + (size_t)tile * TILE_DOCS,
+                                    kw, a00);
                     a[0][0] = a00[0];
                     a[1][0] = a00[1];
                 }
@@ -744,6 +786,19 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
             if (TAGGED) { // the lane's own word: (eligibility word of query n) & (keep word, if any)
                 tag_words_wait(tg, kw, acc[1]);
                 kwh = (tag_match_word(tg, mm, mv) & (p.keep ? kw : 0xffffffffu)) >> (4 * kq);
+            } else if (BIASED) { // acc[u][r] += bias of tile row 16 u + 4 kq + r (see score_topk_kernel)
+                bias_words_wait(bw, kw, acc[1]);
+                if (!p.keep)
+                    kw = 0xffffffffu;
+                kwh = kw >> (4 * kq);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    float bq[4];
+                    bias_pick_quarter(bw, 16 * u, bq);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        acc[u][r] = bias_add(acc[u][r], bq[r]);
+                }
             } else if (MASKED) {
                 keep_word_wait(kw, acc[1]);
                 kwh = kw >> (4 * kq);
@@ -1327,33 +1382,33 @@ constexpr bool score_dim_ok(int d, bool bf16)
 enum PassKind { PASS_LISTS, PASS_MAXONLY, PASS_COUNT };
 
 struct Score32 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT, TAGGED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT, TAGGED, BIASED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
 };
 struct Score32Bf16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT, TAGGED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT, TAGGED, BIASED>; }
     static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false>
-    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT, TAGGED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT, TAGGED, BIASED>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
 };
 
 // (TAGGED: the tagged search's instantiations -- lists and maxima only, there is no tagged count -- one per shape, with or
-//  without a keep-bitmask, which the kernel tests itself)
-template <class K, int NS, bool MASKED, bool TAGGED = false>
+//  without a keep-bitmask, which the kernel tests itself; BIASED: the biased search's, the same set)
+template <class K, int NS, bool MASKED, bool TAGGED = false, bool BIASED = false>
 int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
     const void *fn;
     size_t smem = pl.smem;
     if (kind == PASS_MAXONLY) {
-        fn = K::template fn<NS, 64, true, false, MASKED, false, TAGGED>();
+        fn = K::template fn<NS, 64, true, false, MASKED, false, TAGGED, BIASED>();
     } else if (kind == PASS_COUNT) { // (the nt form under the main pass's own rule: one query tile at d = 256)
-        if constexpr (TAGGED) {
-            return tt_fail(TT_ERR_UNSUPPORTED, "the counting pass takes no tags");
+        if constexpr (TAGGED || BIASED) {
+            return tt_fail(TT_ERR_UNSUPPORTED, "the counting pass takes no tags and no bias");
         } else if (NS == 8 && sp.n_qtiles == 1) {
             fn = K::template fn<8, 64, false, true, MASKED, true>();
             smem = K::smem_nt;
@@ -1361,12 +1416,12 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind 
             fn = K::template fn<NS, 64, false, false, MASKED, true>();
         }
     } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
-        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED, false, TAGGED>()
-                          : K::template fn<8, 128, false, true, MASKED, false, TAGGED>();
+        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED, false, TAGGED, BIASED>()
+                          : K::template fn<8, 128, false, true, MASKED, false, TAGGED, BIASED>();
         smem = K::smem_nt;
     } else {
-        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED, false, TAGGED>()
-                          : K::template fn<NS, 128, false, false, MASKED, false, TAGGED>();
+        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED, false, TAGGED, BIASED>()
+                          : K::template fn<NS, 128, false, false, MASKED, false, TAGGED, BIASED>();
     }
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     ScoreParams args = sp;
@@ -1375,10 +1430,13 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind 
     return TT_OK;
 }
 
-// sp.keep set: the MASKED instantiation of the same kernel; sp.tags set: the TAGGED one, with or without sp.keep
+// sp.keep set: the MASKED instantiation of the same kernel; sp.tags set: the TAGGED one, with or without sp.keep; sp.bias
+// set (never with sp.tags: the biased entries carry none): the BIASED one, with or without sp.keep
 template <class K, int NS>
 int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
+    if (sp.bias)
+        return launch_ns_m<K, NS, true, false, true>(sp, pl, st, kind);
     if (sp.tags)
         return launch_ns_m<K, NS, true, true>(sp, pl, st, kind);
     return sp.keep ? launch_ns_m<K, NS, true>(sp, pl, st, kind) : launch_ns_m<K, NS, false>(sp, pl, st, kind);
@@ -1454,6 +1512,7 @@ ScoreParams pass_params(const Pass &ps, const ExactCall &c, int list_k, int64_t 
     sp.tags = c.tags;
     sp.match_mask = c.match_mask;
     sp.match_value = c.match_value;
+    sp.bias = c.bias;
     return sp;
 }
 

@@ -754,6 +754,42 @@ TT_EXPORT int tt_score_topk_tagged_bf16(const float *Q, int B, int d, const void
                                        (hipStream_t)stream, "tt_score_topk_tagged_bf16", false, tags, match_mask, match_value});
 }
 
+// ---- Biased search (DESIGN.md "Biased search") -------------------------------------------------------------------------------
+// The masked call for k <= 64 with a per-document score bias: the same plan, workspace and launches, on the BIASED
+// instantiations of the main and sample passes (score_topk.hip).  bias == NULL is the masked call itself.
+namespace {
+int score_topk_biased(ExactCall c)
+{
+    if (c.k > MERGE_KMAX)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d (biased search keeps the k <= 64 lists only)", c.who, c.k, MERGE_KMAX);
+    // (a tile's 128 bytes are read as two 16-word scalar loads)
+    if ((uintptr_t)c.bias & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: bias must be 16-byte aligned", c.who);
+    return score_topk_large(c);
+}
+} // namespace
+
+TT_EXPORT size_t tt_score_topk_biased_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return k > MERGE_KMAX ? 0 : tt_score_topk_large_workspace_bytes(B, N, d, k, bf16);
+}
+
+TT_EXPORT int tt_score_topk_biased_f32(const float *Q, int B, int d, const float *D, int64_t N, const float *bias,
+                                       const uint32_t *keep, int k, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                       void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_biased(ExactCall{Q, B, d, D, false, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                       (hipStream_t)stream, "tt_score_topk_biased_f32", false, nullptr, nullptr, nullptr, bias});
+}
+
+TT_EXPORT int tt_score_topk_biased_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const float *bias,
+                                        const uint32_t *keep, int k, int64_t idx_offset, float *out_val, int64_t *out_idx,
+                                        void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_biased(ExactCall{Q, B, d, D_bf16, true, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                       (hipStream_t)stream, "tt_score_topk_biased_bf16", false, nullptr, nullptr, nullptr, bias});
+}
+
 namespace {
 // keep word w = the ballots of keep_bool[32 w .. 32 w + 31] != 0 (a wave packs two words); bits at or beyond N are zero
 __global__ __launch_bounds__(256) void keep_pack_kernel(const uint8_t *__restrict__ keep_bool, int64_t N, unsigned *__restrict__ keep)

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 
 __all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
-           "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged"]
+           "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances"]
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -292,6 +292,98 @@ def score_topk_tagged(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, m
     if keep is not None:
         keep = _check_keep(keep, N, docs.device)
     return _tagged_into(q, docs, tags, mm, mv, keep, k, int(idx_offset))
+
+
+def _check_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
+    """The biases of n documents on `device` as tt_score_topk_biased_* reads them: float32 [32*ceil(n/32)], contiguous.  A
+    [n] tensor is padded with zeros (the kernels ignore the words beyond n whatever they hold)."""
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+        raise TypeError(f"bias must be a float32 tensor, one value per document, got {getattr(bias, 'dtype', type(bias))}")
+    if bias.device != device:
+        raise ValueError(f"bias on {bias.device} but the documents live on {device}")
+    if bias.dim() != 1 or bias.numel() not in (n, _tag_words(n)):
+        raise ValueError(f"bias must hold N = {n} values (or N padded to whole tiles, {_tag_words(n)}), got {tuple(bias.shape)}")
+    if bias.numel() != _tag_words(n):
+        padded = torch.zeros(_tag_words(n), dtype=torch.float32, device=device)
+        padded[:n] = bias
+        return padded
+    return bias if bias.is_contiguous() else bias.contiguous()
+
+
+def _finite_bias(bias: torch.Tensor, n: int) -> None:
+    """set_bias of the indexes: the one finiteness check of the first n values (a host synchronisation on a device tensor)."""
+    if not bool(torch.isfinite(bias[:n]).all()):
+        raise ValueError("set_bias: every bias must be finite (NaN or +-inf found)")
+
+
+BIASED_KMAX = SMALL_KMAX  # biased search keeps the k <= 64 lists only (tt_score_topk_biased_*)
+
+
+def _biased_into(q: torch.Tensor, docs: torch.Tensor, bias: torch.Tensor, keep: Optional[torch.Tensor], k: int,
+                 idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tt_score_topk_biased_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, bias padded f32 whose
+    storage is 16-byte aligned, keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
+    if not 1 <= k <= BIASED_KMAX:
+        raise ValueError(f"biased search answers 1 <= k <= {BIASED_KMAX}, got k = {k}")
+    B, d = q.shape
+    N = docs.shape[0]
+    bf16 = docs.dtype == torch.bfloat16
+    vals, idx = _out_pair(B, k, q.device, out)
+    if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+        return (vals, idx) if out is None else out
+    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
+        L = _lib.lib()
+        ws = torch.empty(max(L.tt_score_topk_biased_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
+        fn = L.tt_score_topk_biased_bf16 if bf16 else L.tt_score_topk_biased_f32
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, bias.data_ptr(), None if keep is None else keep.data_ptr(), k,
+                      idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
+    return (vals, idx) if out is None else out
+
+
+def score_topk_biased(q: torch.Tensor, docs: torch.Tensor, bias: torch.Tensor, k: int, idx_offset: int = 0,
+                      keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """topk(q @ docs.T + bias[None, :], k) fused, in one pass over docs and without the [B,N] matrix: document n scores
+    fl32(s + bias[n]), s being score_topk's score -- one fp32 add behind the finished multiply chain.  bias: float32 [N] or
+    [32*ceil(N/32)] on the documents' device (a [N] tensor is padded here): a popularity or recency prior, a boost or a
+    demotion; l2_bias(docs) makes the ranking that of the Euclidean distance.  keep: a pack_keep_mask bitmask, as in
+    score_topk.  Returns the exact top-k of the biased score over the kept documents, (score desc, index asc), tail
+    (-inf, -1); the values are the biased scores (tt_score_topk_biased_f32 / _bf16; k <= 64).  The biases must be finite: this
+    function does NOT check it, a check would need a host synchronisation (the indexes' set_bias checks once)."""
+    if q.dim() == 1:
+        return _squeezed(score_topk_biased, q, docs, bias, k, idx_offset, keep)
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), _docs_c(docs)
+    B, d = q.shape
+    N = docs.shape[0]
+    if docs.dim() != 2 or docs.shape[1] != d:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    bias = _check_bias(bias, N, docs.device)
+    if keep is not None:
+        keep = _check_keep(keep, N, docs.device)
+    return _biased_into(q, docs, bias, keep, k, int(idx_offset))
+
+
+def l2_bias(docs: torch.Tensor) -> torch.Tensor:
+    """float32 [N]: -|d_n|^2 / 2 of every row of docs [N,d] (float32 or bfloat16, any device), each row's sum of squares taken
+    in float64 (bf16 rows: over their widened values) and rounded once.  With this bias a biased search ranks by
+    q.d - |d|^2/2 = (|q|^2 - |q - d|^2) / 2, the order of the Euclidean distance; l2_distances maps the values back."""
+    if docs.dim() != 2:
+        raise ValueError(f"l2_bias wants docs [N,d], got {tuple(docs.shape)}")
+    out = torch.empty(docs.shape[0], dtype=torch.float32, device=docs.device)
+    step = 1 << 16  # (rows per chunk: the float64 copy stays small next to the corpus)
+    for lo in range(0, docs.shape[0], step):
+        rows = docs[lo:lo + step].to(torch.float64)
+        out[lo:lo + step] = (rows * rows).sum(dim=1).mul_(-0.5).to(torch.float32)
+    return out
+
+
+def l2_distances(q: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
+    """Squared Euclidean distances of a biased search under l2_bias: q [B,d] (or [d]) and the values [B,k] (or [k]) it
+    returned -> |q|^2 - 2 vals, clamped at 0, with the (-inf) tail mapped to +inf.  float32, ascending along k."""
+    qn = (q.to(torch.float32) ** 2).sum(dim=-1, keepdim=True)
+    return (qn - 2.0 * vals).clamp_(min=0.0)
 
 
 def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -694,6 +786,7 @@ class BruteForceIndex:
         self._last_ws = None
         self._keep: Optional[torch.Tensor] = None  # the persistent keep-bitmask (remove_ids), None until the first removal
         self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, padded to whole tiles (set_tags), for tagged_search
+        self._bias: Optional[torch.Tensor] = None  # one float per row, padded to whole tiles (set_bias), for biased_search
 
     @classmethod
     def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int,
@@ -817,6 +910,55 @@ class BruteForceIndex:
         mv = _match_words(match_value, B, self.docs.device, "match_value")
         keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
         res = _tagged_into(_f32c(q), self.docs, self._tags, mm, mv, keep, k, self.idx_offset, out)
+        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
+            self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+        return res
+
+    @property
+    def bias(self) -> Optional[torch.Tensor]:
+        """The rows' biases as the biased kernels read them (float32 [32*ceil(N/32)], zero padding beyond N), or None: not set."""
+        return self._bias
+
+    def set_bias(self, bias: Optional[torch.Tensor]) -> None:
+        """One float32 bias per row (float32 [N], or already padded to [32*ceil(N/32)]), on the index's device: a prior, a boost
+        or a demotion added to every score by biased_search; l2_bias(docs) for Euclidean neighbours.  Kept padded (4 bytes per
+        row).  Checked once here: a NaN or an infinity among the N values raises ValueError (a host synchronisation).
+        None clears it."""
+        if bias is None:
+            self._bias = None
+            return
+        bias = _check_bias(bias, self.docs.shape[0], self.docs.device)
+        _finite_bias(bias, self.docs.shape[0])
+        self._bias = bias
+
+    def biased_search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
+                      exclude: Optional[torch.Tensor] = None, out=None, candidates=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() ranked by q.d + bias[n] (score_topk_biased; q [B,d] or a single [d]); the values returned are the biased
+        scores.  keep= and remove_ids compose as in tagged_search.  exclude= (int64 [B,E]; [E] with a 1-D q) takes search()'s
+        route: a biased search for k + E, then the filter (tt_topk_exclude_ids); the bound here is k + E <= 64.  Always the
+        exact kernel in its biased mode, also on a screen=True index, whose fallback_flags then read all ones as after
+        search(keep=).  Not taken: tags (tagged_search ignores the bias, this search the tags), a count / range_search, k > 64.
+        ValueError: no bias (set_bias), k (+ E) > 64, or candidates= (named only to be refused: tt_score_ids_* adds no bias)."""
+        if self._bias is None:
+            raise ValueError("biased_search: this index has no bias (set_bias)")
+        if candidates is not None:
+            raise ValueError("biased_search takes no candidates=: the candidate scores (score_ids) carry no bias")
+        if q.dim() == 1:
+            return _squeezed(self.biased_search, q, k, keep, _exclude_row(exclude))
+        _need_cuda(q)
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        if q.shape[-1] != self.docs.shape[1]:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        B = q.shape[0]
+        if exclude is not None:
+            exclude, kk = _check_exclude(exclude, B, k, self.docs.device)
+            if kk > BIASED_KMAX:
+                raise ValueError(f"a biased search with an exclusion list runs for k + E = {kk} > {BIASED_KMAX}")
+            v, i = self.biased_search(q, kk, keep)
+            return topk_exclude(v, i, exclude, k, out)
+        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        res = _biased_into(_f32c(q), self.docs, self._bias, keep, k, self.idx_offset, out)
         if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
             self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
         return res
@@ -1290,7 +1432,8 @@ class ShardedIndex:
 
     def _slot(self, B: int, kp: int, k: int, which: int) -> _Slot:
         """which: 0 / 1 = the two slots submit() alternates between, 2 = search()'s own (a search() between a submit() and
-        its .result() must not overwrite that PendingSearch's outputs).  Slot sets are kept per (B, kp, k) shape; when
+        its .result() must not overwrite that PendingSearch's outputs), 3 = biased_search()'s own, made on first use (its values
+        are biased scores: they share no buffer with a search's).  Slot sets are kept per (B, kp, k) shape; when
         more than _MAX_SLOT_SHAPES shapes have been seen the oldest set is retired, after its queued exchanges have
         completed (its buffers are used on the exchange stream, which the caching allocator does not know about)."""
         key = (B, kp, k, self._coll.world)
@@ -1300,6 +1443,8 @@ class ShardedIndex:
                 for sl in old:
                     sl.merged.synchronize()
             self._slots[key] = [_Slot(B, kp, k, self._coll.world, self._dev) for _ in range(3)]
+        while len(self._slots[key]) <= which:
+            self._slots[key].append(_Slot(B, kp, k, self._coll.world, self._dev))
         return self._slots[key][which]
 
     def _flush(self, only: Optional[_Slot] = None) -> None:
@@ -1386,6 +1531,37 @@ class ShardedIndex:
         cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
         self._index.tagged_search(q, kp, match_mask, match_value, keep=keep, out=(sl.send_v, sl.send_i))
+        self._exchange_merge(sl, q.shape[0], kp, k)
+        sl.merged.record(cur)
+        return sl.out_v.clone(), sl.out_i.clone()
+
+    @property
+    def bias(self) -> Optional[torch.Tensor]:
+        """This rank's biases over its own rows (set_bias), or None."""
+        return self._index.bias
+
+    def set_bias(self, local_bias: Optional[torch.Tensor]) -> None:
+        """One float32 bias per row of THIS RANK'S shard (BruteForceIndex.set_bias / StreamedIndex.set_bias; None clears it).
+        Called on every rank, like every call on this class: biased search is a property of the job."""
+        self._index.set_bias(local_bias)
+
+    def biased_search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() ranked by q.d + bias[n] (BruteForceIndex.biased_search): q is the same on every rank, the biases are each
+        rank's own.  The local biased search runs for max(k, shard_k) (<= 64: ValueError above), then the usual all-gather and
+        merge on the caller's stream -- the merges see values that are already biased; no seed exchange is involved.  A
+        COLLECTIVE like every search of this class.  keep: as in search()."""
+        if self._index.bias is None:
+            raise ValueError("biased_search: this index has no bias (set_bias)")
+        if q.dim() == 1:
+            return _squeezed(self.biased_search, q, k, keep)
+        kp = max(k, self.shard_k)
+        if not 1 <= k or kp > BIASED_KMAX:
+            raise ValueError(f"biased search answers 1 <= max(k, shard_k) <= {BIASED_KMAX}, got k = {k}, shard_k = {self.shard_k}")
+        sl = self._slot(q.shape[0], kp, k, 3)
+        cur = torch.cuda.current_stream(sl.send.device)
+        cur.wait_event(sl.merged)  # (a biased_search() on another stream may still own the slot)
+        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
+        self._index.biased_search(q, kp, keep=keep, out=(sl.send_v, sl.send_i))
         self._exchange_merge(sl, q.shape[0], kp, k)
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
@@ -1507,6 +1683,7 @@ class StreamedIndex:
         self._keep: Optional[torch.Tensor] = None  # persistent keep-bitmask (remove_ids): N/8 bytes, on the device
         self._gather = None  # two pinned [block,d] host buffers of the candidate gather (_score_ids), allocated on first use
         self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, resident on the device (set_tags): 4 bytes per row
+        self._bias: Optional[torch.Tensor] = None  # one float per row, resident on the device (set_bias): 4 bytes per row
 
     def _walk(self, visit, stats=None):
         L = _lib.lib()
@@ -1717,6 +1894,68 @@ class StreamedIndex:
                 raise ValueError(f"block at row {lo}: the tags of a 32-document tile belong to one block")
             v, i = _tagged_into(q, self._d32[s][:n], self._tags[lo:lo + _tag_words(n)], mm, mv,
                                 None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k, self.idx_offset + lo)
+            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+
+        self._walk(visit)
+        if not run:
+            run = _out_pair(B, k, q.device)  # an empty corpus: padding only
+            run[0].fill_(float("-inf"))
+            run[1].fill_(-1)
+        if out is not None:
+            out[0].copy_(run[0])
+            out[1].copy_(run[1])
+            return out
+        return run[0], run[1]
+
+    @property
+    def bias(self) -> Optional[torch.Tensor]:
+        """The biases of the whole corpus, on the device (float32 [32*ceil(N/32)], zero padding beyond N), or None: not set."""
+        return self._bias
+
+    def set_bias(self, bias: Optional[torch.Tensor]) -> None:
+        """One float32 bias per row of the whole corpus (float32 [N] or padded to [32*ceil(N/32)]), on the index's DEVICE: the
+        rows stream from the host, the biases stay resident at 4 bytes per row.  Checked for NaN and infinities once, here
+        (ValueError; a host synchronisation).  None clears it."""
+        if bias is None:
+            self._bias = None
+            return
+        bias = _check_bias(bias, self.N, self.device)
+        _finite_bias(bias, self.N)
+        self._bias = bias
+
+    def biased_search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
+                      out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search() ranked by q.d + bias[n] (BruteForceIndex.biased_search; k <= 64): every streamed block runs the biased exact
+        kernel under its slice of the biases (and of the ANDed keep-bitmask, if any), and the blocks' lists -- biased values --
+        are merged as in search().  A block that starts on a multiple of 32 rows reads its slice in place; with a block_docs
+        that is no multiple of 32 every block takes a padded copy of its slice (4 bytes per row of the block).  A keep-bitmask
+        still needs whole words per block: keep with block_docs % 32 != 0 (and more than one block) raises ValueError."""
+        if self._bias is None:
+            raise ValueError("biased_search: this index has no bias (set_bias)")
+        if q.dim() == 1:
+            return _squeezed(self.biased_search, q, k, keep)
+        _need_cuda(q)
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        if not 1 <= k <= BIASED_KMAX:
+            raise ValueError(f"biased search answers 1 <= k <= {BIASED_KMAX}, got k = {k}")
+        q = _f32c(q)
+        B = q.shape[0]
+        keep = _and_keep(self._keep, keep, self.N, self.device)
+        if keep is not None and self.block % 32 and self.N > self.block:
+            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
+        run = []  # the running top-k: (values, indices)
+
+        def visit(s, lo, n):
+            if lo % 32 == 0:  # whole tiles from a 128-byte aligned start: read in place
+                b = self._bias[lo:lo + _tag_words(n)]
+            else:
+                b = torch.zeros(_tag_words(n), dtype=torch.float32, device=self.device)
+                b[:n] = self._bias[lo:lo + n]
+            v, i = _biased_into(q, self._d32[s][:n], b, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k,
+                                self.idx_offset + lo)
             run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
 
         self._walk(visit)
