@@ -525,6 +525,47 @@ int tt_score_ids_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t 
                       int64_t *out_idx /*[B][C], nullable*/, tt_stream_t stream);
 
 /*
+ * Diversified selection (maximal marginal relevance): k picks out of a per-query candidate list, each pick trading the
+ * candidate's relevance against its similarity to what is already picked.  Replaces, in one launch and bit-defined,
+ *   G = bmm(D[ids], D[ids].T); k greedy steps of max / argmax over G      (LangChain's max_marginal_relevance_search)
+ * Inputs per query b: in_val[b][c] (relevance, whatever the caller searched with: the kernel never recomputes q.d) and
+ * in_idx[b][c] (GLOBAL id) for c in [0, C), in the order a search writes them ((score desc, index asc), padding (-inf, -1));
+ * lambda in [0, 1]; mu = 1.0f - lambda, formed once in fp32; k.
+ * Validity: candidate c is valid iff in_val is finite, in_idx >= 0 and n = in_idx - idx_offset (formed as tt_score_ids_f32
+ * forms it) lies in [0, N).  Invalid candidates are never selected and their rows are never read.  Row values are
+ * assumed finite.
+ * Similarity: G[i][j] = the project's score of two documents: the fp32 fmaf chain over the feature index ascending, acc0 = 0,
+ * of x_i[f] * x_j[f] (bf16 rows widened exactly, bits << 16).  Each product commutes exactly, so G is bitwise symmetric.
+ * Greedy steps t = 0 .. k-1 over the valid, not yet selected candidates:
+ *   a_c = fl32(lambda * rel_c)
+ *   t = 0:  m_c = a_c
+ *   t >= 1: pen_c = max over the selected s of G[c][s]  (may be negative; includes a duplicate's twin)
+ *           m_c = fl32(a_c - fl32(mu * pen_c))          two rounded products and one rounded subtraction, no fma
+ *   pick the largest m_c; ties go to the lower position c.  A repeated id gets no special treatment: its twin's similarity
+ *   is |x|^2, which demotes it by itself.
+ * Outputs in selection order: out_val[b][t] = in_val of the pick (the relevance, not m), out_idx[b][t] its id, and, unless
+ * NULL, out_pos[b][t] its position c (to carry other per-candidate data along).  When the valid candidates run out the
+ * tail is (-inf, -1, -1).  Every output element is written on every call.
+ * Limits: 0 <= C <= 128; 1 <= k <= 128 (k may exceed C: padded tail); d a multiple of 4 (f32) / 8 (bf16), at most 512
+ * (TT_ERR_UNSUPPORTED, the message names the value); any B >= 0 (B = 0 does nothing), N >= 0; lambda outside [0, 1] or NaN
+ * is TT_ERR_BAD_SHAPE.  Also TT_ERR_BAD_SHAPE: negative sizes, a NULL in_val / in_idx (with C > 0) / out_val / out_idx / D
+ * (with N > 0 and C > 0) / rows, D or rows not 16-byte aligned, indices not 8-byte, values and positions not 4-byte aligned.
+ * Every check runs before any HIP call.  Row addresses are size_t.  One launch (one workgroup per query), no workspace, no
+ * atomics, no host synchronisation: capturable, and the result depends only on the inputs.
+ * _rows_f32: the candidate rows already gathered, rows[b][c][:] belongs to entry c; validity is in_idx >= 0 and a finite
+ * in_val.  For callers whose rows do not sit in one device array (sharded, streamed).
+ */
+int tt_mmr_select_f32(const float *in_val /*[B][C]*/, const int64_t *in_idx /*[B][C]*/, int B, int C, const float *D, int64_t N,
+                      int d, int64_t idx_offset, float lambda, int k, float *out_val /*[B][k]*/, int64_t *out_idx /*[B][k]*/,
+                      int32_t *out_pos /*[B][k], nullable*/, tt_stream_t stream);
+int tt_mmr_select_bf16(const float *in_val /*[B][C]*/, const int64_t *in_idx /*[B][C]*/, int B, int C, const void *D_bf16,
+                       int64_t N, int d, int64_t idx_offset, float lambda, int k, float *out_val /*[B][k]*/,
+                       int64_t *out_idx /*[B][k]*/, int32_t *out_pos /*[B][k], nullable*/, tt_stream_t stream);
+int tt_mmr_select_rows_f32(const float *in_val /*[B][C]*/, const int64_t *in_idx /*[B][C]*/, int B, int C,
+                           const float *rows /*[B][C][d]*/, int d, float lambda, int k, float *out_val /*[B][k]*/,
+                           int64_t *out_idx /*[B][k]*/, int32_t *out_pos /*[B][k], nullable*/, tt_stream_t stream);
+
+/*
  * Lexical search: sparse TF-IDF rows times a sparse query, exact top-k, no [B,N] matrix -- the lexical half of the hybrid
  * search on the device.  Replaces the whole-corpus TF-IDF cosine and the sort of every document behind it:
  *   cosine_similarity(query_tfidf, doc_tfidf_matrix) ; argsort ; score > 1e-5        frontend/main.py:119-147

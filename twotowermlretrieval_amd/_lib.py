@@ -94,6 +94,9 @@ SIGNATURES = {
     "tt_score_all_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp]),
     "tt_score_ids_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "tt_score_ids_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "tt_mmr_select_f32": (_i, [_vp, _vp, _i, _i, _vp, _i64, _i, _i64, _f, _i, _vp, _vp, _vp, _vp]),
+    "tt_mmr_select_bf16": (_i, [_vp, _vp, _i, _i, _vp, _i64, _i, _i64, _f, _i, _vp, _vp, _vp, _vp]),
+    "tt_mmr_select_rows_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "tt_lexical_chunk_docs": (_i, []),
     "tt_lexical_workspace_bytes": (_sz, [_i, _i64, _i]),
     "tt_lexical_score_topk_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _f, _f, _i, _i64,

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
+__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "mmr_select", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
            "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances"]
 
 
@@ -655,6 +655,102 @@ def _merge_candidates(vals: torch.Tensor, idx: torch.Tensor, k: int, out=None) -
     return ov, oi
 
 
+MMR_CMAX = 128  # tt_mmr_select_*: candidates per query
+MMR_KMAX = 128  # ... and picks
+
+
+def _check_lambda(lambda_) -> float:
+    """lambda of the diversified selection: a number in [0, 1] (1 = relevance only, 0 = diversity only); NaN is refused."""
+    lam = float(lambda_)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_ must lie in [0, 1], got {lambda_}")
+    return lam
+
+
+def _mmr_fetch_k(k: int, fetch_k: Optional[int]) -> int:
+    """How many candidates a diverse_search for k fetches: fetch_k, by default min(128, 4 k); k <= fetch_k <= 128."""
+    k = int(k)
+    if not 1 <= k <= MMR_KMAX:
+        raise ValueError(f"diverse_search answers 1 <= k <= {MMR_KMAX}, got k = {k}")
+    fk = min(MMR_CMAX, 4 * k) if fetch_k is None else int(fetch_k)
+    if fk > MMR_CMAX:
+        raise ValueError(f"diverse_search selects out of at most {MMR_CMAX} candidates, got fetch_k = {fk}")
+    if fk < k:
+        raise ValueError(f"diverse_search needs fetch_k >= k, got fetch_k = {fk} < k = {k}")
+    return fk
+
+
+def mmr_select(vals: torch.Tensor, idx: torch.Tensor, docs: Optional[torch.Tensor], k: int, lambda_: float = 0.5,
+               idx_offset: int = 0, rows: Optional[torch.Tensor] = None, return_pos: bool = False):
+    """Maximal-marginal-relevance selection out of per-query candidate lists (tt_mmr_select_f32 / _bf16 / _rows_f32: one
+    launch, the rule of include/tt.h, bit-defined): (values f32 [B,k], ids int64 [B,k]) in selection order, and with
+    return_pos the picks' positions int32 [B,k] in the list.  vals f32 [B,C] and idx int64 [B,C] are a search's output
+    (relevance and GLOBAL id, padding (-inf, -1)); C <= 128, 1 <= k <= 128 (k > C: tail (-inf, -1, -1)).  Step t picks the
+    largest lambda_ * rel_c - (1 - lambda_) * max over the picked s of <x_c, x_s>, ties to the lower position; the values
+    returned are the relevances.  docs [N,d] float32 or bfloat16 are the rows the ids name (idx - idx_offset); or rows=
+    float32 [B,C,d] gives the candidates' rows themselves and docs may be None.  1-D vals / idx ([C], rows [C,d]) are one
+    query's.  It composes with the output of any search of this package (tagged, biased, hybrid lists included)."""
+    if isinstance(vals, torch.Tensor) and vals.dim() == 1:
+        if rows is not None and rows.dim() != 2:
+            raise ValueError(f"a single query takes rows [C,d], got {tuple(rows.shape)}")
+        out = mmr_select(vals.unsqueeze(0), _ids_row(idx, "idx"), docs, k, lambda_, idx_offset,
+                         None if rows is None else rows.unsqueeze(0), return_pos)
+        return tuple(t[0] for t in out)
+    lam = _check_lambda(lambda_)
+    if rows is None and docs is None:
+        raise ValueError("mmr_select needs docs or rows=")
+    _need_cuda(vals, rows if rows is not None else docs)
+    vals = _f32c(vals)
+    if vals.dim() != 2:
+        raise ValueError(f"vals must be [B,C] ([C] for a single query), got {tuple(vals.shape)}")
+    B, C = vals.shape
+    idx = _check_ids(idx, B, vals.device, "idx")
+    if idx.shape[1] != C:
+        raise ValueError(f"vals {tuple(vals.shape)} and idx {tuple(idx.shape)} must be one list per query")
+    k = int(k)
+    if C > MMR_CMAX or not 1 <= k <= MMR_KMAX:
+        raise ValueError(f"mmr_select takes C <= {MMR_CMAX} candidates and 1 <= k <= {MMR_KMAX}, got C = {C}, k = {k}")
+    out_v, out_i = _out_pair(B, k, vals.device)
+    out_p = torch.empty((B, k), dtype=torch.int32, device=vals.device) if return_pos else None
+    pos_ptr = None if out_p is None else out_p.data_ptr()
+    L = _lib.lib()
+    if rows is not None:
+        rows = _f32c(rows)
+        if rows.dim() != 3 or tuple(rows.shape[:2]) != (B, C) or rows.device != vals.device:
+            raise ValueError(f"rows must be float32 [B,C,d] = [{B},{C},d] on {vals.device}, got {tuple(rows.shape)} on {rows.device}")
+        with torch.cuda.device(vals.device):
+            _lib.check(L.tt_mmr_select_rows_f32(vals.data_ptr(), idx.data_ptr(), B, C, rows.data_ptr(), rows.shape[2], lam, k,
+                                                out_v.data_ptr(), out_i.data_ptr(), pos_ptr, _stream(vals)))
+    else:
+        docs = _docs_c(docs)
+        if docs.dim() != 2 or docs.device != vals.device:
+            raise ValueError(f"docs must be [N,d] on {vals.device}, got {tuple(docs.shape)} on {docs.device}")
+        fn = L.tt_mmr_select_bf16 if docs.dtype == torch.bfloat16 else L.tt_mmr_select_f32
+        with torch.cuda.device(vals.device):
+            _lib.check(fn(vals.data_ptr(), idx.data_ptr(), B, C, docs.data_ptr() if docs.shape[0] else None, docs.shape[0],
+                          docs.shape[1], int(idx_offset), lam, k, out_v.data_ptr(), out_i.data_ptr(), pos_ptr, _stream(vals)))
+    return (out_v, out_i, out_p) if return_pos else (out_v, out_i)
+
+
+def _owned_rows(docs: torch.Tensor, ids: torch.Tensor, idx_offset: int) -> torch.Tensor:
+    """float32 [B,C,d]: row ids[b][c] - idx_offset of docs [N,d] (bf16 widened exactly) where that lies in [0, N), zeros
+    elsewhere -- one rank's share of the candidate rows of a sharded diverse_search."""
+    N, d = docs.shape
+    n = ids - idx_offset
+    own = (ids >= 0) & (n >= 0) & (n < N)
+    if N == 0:
+        return torch.zeros(tuple(ids.shape) + (d,), dtype=torch.float32, device=ids.device)
+    rows = docs[torch.where(own, n, torch.zeros_like(n))].to(torch.float32)
+    return rows.masked_fill_(~own.unsqueeze(-1), 0.0)
+
+
+_DIVERSE_DOC = """(values f32 [B,k], ids int64 [B,k]) in SELECTION order: relevant, but not k times the same thing.  It is
+        search(q, fetch_k, keep=, exclude=) followed by one launch of the diversified selection (mmr_select: maximal marginal
+        relevance over the fetched candidates, lambda_ in [0, 1]: 1 = the plain search's first k, lower = more diverse).
+        fetch_k defaults to min(128, 4 k); k <= fetch_k <= 128.  The values are the search's scores of the picks; the tail is
+        (-inf, -1) when fewer than k candidates exist."""
+
+
 SCREEN_MIN_BATCH = 1     # the screened path wins at every batch size once the corpus is large enough to sample:
                          # B <= 64 streaming form (half the bytes of the fp32 kernel), above it the shared-tile form
 SCREEN_PADDED_MIN_BATCH = 33  # d < 256 (zero-padded screen copy): only where the exact kernel is MFMA-bound
@@ -985,6 +1081,22 @@ class BruteForceIndex:
         if q.shape[-1] != self.docs.shape[1]:
             raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
         return self._score_ids(q, ids, _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device), False)[0]
+
+    def diverse_search(self, q: torch.Tensor, k: int = 10, lambda_: float = 0.5, fetch_k: Optional[int] = None,
+                       keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if q.dim() == 1:
+            return _squeezed(self.diverse_search, q, k, lambda_, fetch_k, keep, _exclude_row(exclude))
+        fk, lam = _mmr_fetch_k(k, fetch_k), _check_lambda(lambda_)
+        v, i = self.search(q, fk, keep=keep, exclude=exclude)
+        return mmr_select(v, i, self.docs, k, lam, self.idx_offset)
+
+    def _candidate_rows(self, ids: torch.Tensor) -> torch.Tensor:
+        """float32 [B,C,d]: the rows of the global ids this index owns, zeros elsewhere (ShardedIndex.diverse_search)."""
+        return _owned_rows(self.docs, ids, self.idx_offset)
+
+    diverse_search.__doc__ = _DIVERSE_DOC + """
+        The candidates' rows are gathered from this index's own rows (fp32, or bf16 widened exactly) by the kernel, whichever
+        layout searched: the screened and the exact route return the same list, so the result does not depend on it."""
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 [B] (0-d for a single query): how many documents of this index -- not removed (remove_ids), and kept by
@@ -1584,6 +1696,30 @@ class ShardedIndex:
                 scores = recv.amax(0)
         return scores
 
+    def diverse_search(self, q: torch.Tensor, k: int = 10, lambda_: float = 0.5, fetch_k: Optional[int] = None,
+                       keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if q.dim() == 1:
+            return _squeezed(self.diverse_search, q, k, lambda_, fetch_k, keep, _exclude_row(exclude))
+        fk, lam = _mmr_fetch_k(k, fetch_k), _check_lambda(lambda_)
+        v, i = self.search(q, fk, keep=keep, exclude=exclude)
+        rows = self._index._candidate_rows(i)
+        if self._coll.world > 1:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=self.group)
+            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' blocks and add)
+                recv = torch.empty((self._coll.world,) + tuple(rows.shape), dtype=torch.float32, device=rows.device)
+                self._coll.all_gather_blocks(rows.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
+                rows = recv.sum(0)
+        return mmr_select(v, i, None, k, lam, rows=rows)
+
+    diverse_search.__doc__ = _DIVERSE_DOC + """
+        Sharded, a COLLECTIVE like every search of this class: the sharded search for fetch_k, identical on every rank; then
+        each rank fills a float32 [B,fetch_k,d] block with the rows of the candidates it owns (zeros elsewhere) and the
+        blocks are summed over the ranks -- one all_reduce(SUM) of B * fetch_k * d * 4 bytes on the index's group (13 MB at
+        B = 100, fetch_k = 128, d = 256).  Exactly one rank contributes each row and x + 0 is exact, so every rank holds the
+        candidates' rows and runs the selection on them (tt_mmr_select_rows_f32): the single-GPU result on every rank."""
+
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The count of the whole corpus, identical on every rank: this rank's count over its shard under its mask (keep: over
         THIS RANK'S rows, on all ranks or on none, as in search()), then one all_reduce(SUM) of the int64 [B] on the index's
@@ -1968,6 +2104,33 @@ class StreamedIndex:
             out[1].copy_(run[1])
             return out
         return run[0], run[1]
+
+    def _candidate_rows(self, ids: torch.Tensor) -> torch.Tensor:
+        """float32 [B,C,d]: the rows of the global ids this index owns (bf16 widened exactly), zeros elsewhere.  The rows are
+        in host memory: one synchronising copy of the ids to the host, index_select there into pinned staging, one copy back."""
+        n = ids - self.idx_offset
+        own = (ids >= 0) & (n >= 0) & (n < self.N)
+        if self.N == 0 or ids.numel() == 0:
+            return torch.zeros(tuple(ids.shape) + (self.d,), dtype=torch.float32, device=self.device)
+        at = torch.where(own, n, torch.zeros_like(n)).reshape(-1).cpu()  # (the one synchronisation: which rows to fetch)
+        staged = torch.empty((at.numel(), self.d), dtype=torch.bfloat16).pin_memory()
+        torch.index_select(self.host, 0, at, out=staged)
+        rows = staged.to(self.device, non_blocking=True).to(torch.float32).view(tuple(ids.shape) + (self.d,))
+        return rows.masked_fill_(~own.unsqueeze(-1), 0.0)
+
+    def diverse_search(self, q: torch.Tensor, k: int = 10, lambda_: float = 0.5, fetch_k: Optional[int] = None,
+                       keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if q.dim() == 1:
+            return _squeezed(self.diverse_search, q, k, lambda_, fetch_k, keep, _exclude_row(exclude))
+        fk, lam = _mmr_fetch_k(k, fetch_k), _check_lambda(lambda_)
+        v, i = self.search(q, fk, keep=keep, exclude=exclude)
+        return mmr_select(v, i, None, k, lam, rows=self._candidate_rows(i))
+
+    diverse_search.__doc__ = _DIVERSE_DOC + """
+        Streamed: the walk for fetch_k, then -- SYNCHRONISING with the host once, like score_ids -- the candidates' ids are
+        copied to the host, their rows gathered there (index_select from the pinned corpus into pinned staging), sent to the
+        device (B * fetch_k * d * 2 bytes), widened exactly and selected from (tt_mmr_select_rows_f32): the resident bf16
+        index's result."""
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 [B] (0-d for a single query): the documents of the whole corpus (not removed, kept by `keep`: a mask over the
