@@ -446,6 +446,37 @@ int tt_topk_exclude_ids(const float *in_val, const int64_t *in_idx, int B, int M
                         int k, float *out_val, int64_t *out_idx, tt_stream_t stream);
 
 /*
+ * Collapsed search (field collapsing, "at most n per document"): the best k entries of a sorted row with at most
+ * max_per_group entries per document group.  Replaces the over-fetch, the copy to the host and the Python dict over
+ *   torch.topk(torch.matmul(q, D.t()), k)                     backend/evaluators.py:185-186
+ * that a passage index needs when its rows are pieces of pages.  Every row of an index may carry a group id (int64; negative =
+ * ungrouped, never collapsed).  The rule, per row b of in_val / in_idx [B,M] (as the searches and merges write them: (score
+ * desc, index asc), padding (-inf, idx < 0) at the tail): walk the row; an entry is KEPT if its group id is negative or fewer
+ * than max_per_group entries of its group were kept before it -- equivalently, if fewer than max_per_group EARLIER ENTRIES OF
+ * THE ROW carry its group id, which every entry can decide on its own.  out_val / out_idx / out_gid [B,k] = the first k kept
+ * entries in input order (values and indices copied, no arithmetic; out_gid = the entry's group id as it was read), then
+ * (-inf, -1, -1).  Entries with idx < 0 are dropped and count against no group.  out_info int32 [B,2] = (kept, complete): kept =
+ * min(k, kept entries of the row); complete = 1 when kept == k or the input row ends in padding (in_idx[M-1] < 0: the row holds
+ * every eligible document, so nothing can follow), else 0 -- the result is then the exact PREFIX of the answer, which a
+ * longer row completes (whether an entry is kept depends on the entries before it only).
+ * _table: the group of an entry is groups[in_idx - idx_offset] (groups int64 [N], device, 8-byte aligned; the difference is
+ * formed in 64 bits), and an index outside [idx_offset, idx_offset + N) is ungrouped -- the lookup is bounds-checked, ids of
+ * other shards may arrive; N = 0 (groups may be NULL) makes every entry ungrouped.
+ * _gids: in_gid int64 [B,M] gives every entry's group id.
+ * 1 <= k <= M, max_per_group >= 1, N >= 0 (else TT_ERR_BAD_SHAPE, like null or misaligned pointers and an output that overlaps
+ * an input), M <= TT_TOPK_LARGE_KMAX (above: TT_ERR_UNSUPPORTED); B = 0 does nothing.  One launch, one workgroup per row: the
+ * row's group ids sit in LDS (8 KB at most), every entry counts the earlier ones with its id (broadcast reads, 128 bits each),
+ * then the order-preserving compaction of tt_topk_exclude_ids in chunks of 256 entries, up to the chunk of the k-th kept one.
+ * Asynchronous, capturable: no workspace, no host synchronisation, no atomics; the result depends only on the inputs.
+ */
+int tt_topk_collapse_table(const float *in_val, const int64_t *in_idx, int B, int M, const int64_t *groups /*[N]*/, int64_t N,
+                           int64_t idx_offset, int max_per_group, int k, float *out_val, int64_t *out_idx, int64_t *out_gid,
+                           int32_t *out_info /*[B][2]*/, tt_stream_t stream);
+int tt_topk_collapse_gids(const float *in_val, const int64_t *in_idx, const int64_t *in_gid /*[B][M]*/, int B, int M,
+                          int max_per_group, int k, float *out_val, int64_t *out_idx, int64_t *out_gid,
+                          int32_t *out_info /*[B][2]*/, tt_stream_t stream);
+
+/*
  * Threshold search (FAISS users: range_search): how many documents score at least min_score[b] for query b, and the best k
  * of them.  Replaces
  *   s = torch.matmul(q, D.t()) ; (s >= t).sum(1) ; torch.topk(s, k) with the entries below t masked

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "mmr_select", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
+__all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "mmr_select", "topk_collapse", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
            "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances"]
 
 
@@ -751,6 +751,214 @@ _DIVERSE_DOC = """(values f32 [B,k], ids int64 [B,k]) in SELECTION order: releva
         (-inf, -1) when fewer than k candidates exist."""
 
 
+COLLAPSE_MMAX = 1024       # entries of a row the collapse filter reads: TT_TOPK_LARGE_KMAX, what every search answers exactly
+COLLAPSE_EXACT_KMAX = 512  # k + E of an exact collapsed search: every continuation round then fetches at least 512 new rows
+
+
+def _check_groups(groups: torch.Tensor, n: int, device) -> torch.Tensor:
+    """One group id per row of n documents on `device`, as tt_topk_collapse_table reads it (int64 [n], contiguous)."""
+    if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int64:
+        raise TypeError(f"groups must be an int64 tensor, got {getattr(groups, 'dtype', type(groups))}")
+    if groups.device != device:
+        raise ValueError(f"groups on {groups.device} but the documents live on {device}")
+    if groups.dim() != 1 or groups.numel() != n:
+        raise ValueError(f"groups must hold one id per row, [{n}], got {tuple(groups.shape)}")
+    return groups if groups.is_contiguous() else groups.contiguous()
+
+
+def topk_collapse(vals: torch.Tensor, idx: torch.Tensor, k: int, groups: Optional[torch.Tensor] = None,
+                  gids: Optional[torch.Tensor] = None, max_per_group: int = 1, idx_offset: int = 0, out=None):
+    """At most max_per_group entries per document group out of sorted lists the caller holds (tt_topk_collapse_table /
+    _gids, one launch): vals f32 / idx int64 [B,M] as the searches and merges return them ((score desc, index asc), padding
+    at the tail), M <= 1024, 1 <= k <= M -> (vals f32 [B,k], idx int64 [B,k], gids int64 [B,k], info int32 [B,2]).  Walking a
+    row, an entry is kept if its group id is negative (ungrouped) or fewer than max_per_group earlier entries of the row
+    carry its id; the result is the first k kept entries in input order -- values and indices copied, no arithmetic -- then
+    (-inf, -1, -1).  info[b] = (kept, complete): complete = 1 when k entries were kept or the row ends in padding, else the
+    result is the exact prefix of the answer and a longer row completes it.  Pass exactly one of groups= (int64 [N]: the
+    group of entry idx is groups[idx - idx_offset], ungrouped outside the table) and gids= (int64 [B,M], one id per entry).
+    1-D vals / idx ([M], gids [M]) are one query's.  out: optional (vals, idx, gids, info) to write into."""
+    if (groups is None) == (gids is None):
+        raise ValueError("topk_collapse takes exactly one of groups= (a table over the rows) and gids= (one id per entry)")
+    if isinstance(vals, torch.Tensor) and vals.dim() == 1:
+        res = topk_collapse(vals.unsqueeze(0), _ids_row(idx, "idx"), k, groups, _ids_row(gids, "gids"), max_per_group, idx_offset)
+        return tuple(t[0] for t in res)
+    src = groups if gids is None else gids
+    _need_cuda(vals, idx, src)
+    vals = _f32c(vals)
+    if idx.dtype != torch.int64 or vals.shape != idx.shape or vals.dim() != 2 or idx.device != vals.device:
+        raise ValueError("topk_collapse wants vals f32 [B,M] and idx int64 [B,M] on one device")
+    idx = idx.contiguous()
+    B, M = vals.shape
+    k, m = int(k), int(max_per_group)
+    if src.dtype != torch.int64 or src.device != vals.device:
+        raise ValueError(f"topk_collapse wants int64 group ids on {vals.device}, got {src.dtype} on {src.device}")
+    if gids is not None and tuple(gids.shape) != (B, M):
+        raise ValueError(f"gids must be [B,M] = [{B},{M}] (one id per entry), got {tuple(gids.shape)}")
+    if groups is not None and groups.dim() != 1:
+        raise ValueError(f"groups must be [N] (one id per row of the index), got {tuple(groups.shape)}")
+    src = src.contiguous()
+    dev = vals.device
+    if out is None:
+        out = (*_out_pair(B, k, dev), torch.empty((B, k), dtype=torch.int64, device=dev),
+               torch.empty((B, 2), dtype=torch.int32, device=dev))
+    ov, oi, og, info = out
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        if gids is None:
+            _lib.check(L.tt_topk_collapse_table(vals.data_ptr(), idx.data_ptr(), B, M, src.data_ptr() if src.numel() else None,
+                                                src.numel(), int(idx_offset), m, k, ov.data_ptr(), oi.data_ptr(), og.data_ptr(),
+                                                info.data_ptr(), _stream(vals)))
+        else:
+            _lib.check(L.tt_topk_collapse_gids(vals.data_ptr(), idx.data_ptr(), src.data_ptr(), B, M, m, k, ov.data_ptr(),
+                                               oi.data_ptr(), og.data_ptr(), info.data_ptr(), _stream(vals)))
+    return ov, oi, og, info
+
+
+def _collapse_fetch_k(k: int, ntotal: Optional[int] = None, fetch_k: Optional[int] = None, E: int = 0) -> int:
+    """How many rows round 0 of a collapsed search for k fetches: fetch_k, by default min(ntotal, max(k, min(64, 4 k))) up to
+    k = 64 -- the inner search stays at or below the k = 64 routing cliff -- and min(ntotal, 1024, 2 k) above (the default
+    also gives way to an exclusion list: at most 1024 - E).  ValueError: k < 1, fetch_k < k, fetch_k + E > 1024."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"collapsed_search: k = {k} < 1")
+    if fetch_k is None:
+        fk = max(k, min(SMALL_KMAX, 4 * k)) if k <= SMALL_KMAX else min(COLLAPSE_MMAX, 2 * k)
+        fk = max(k, min(fk, COLLAPSE_MMAX - E))
+        if ntotal is not None:
+            fk = min(fk, max(int(ntotal), 1))
+    else:
+        fk = int(fetch_k)
+        if fk < k:
+            raise ValueError(f"collapsed_search needs fetch_k >= k, got fetch_k = {fk} < k = {k}")
+    if fk + E > COLLAPSE_MMAX:
+        raise ValueError(f"collapsed_search: fetch_k + E = {fk} + {E} = {fk + E} > {COLLAPSE_MMAX}")
+    return fk
+
+
+def _collapse_rounds(search_fn: Callable, collapse_fn: Callable, mask_fn: Callable, max_per_group: int, fetch_k: int, E: int,
+                     ntotal: Optional[int], exact: bool, stats: Optional[dict] = None):
+    """The rounds of a collapsed search, over callables, on whatever device their tensors live (the tests run it on the host):
+      search_fn(rows, kk, keep) -> (vals [R,kk], idx [R,kk]): the exact top-kk of the eligible documents for the queries
+        `rows` (an int64 tensor of query numbers; None = all of them) under the per-call mask `keep` (None = the caller's own);
+      collapse_fn(vals, idx) -> (vals [R,k], idx [R,k], gids [R,k], info [R,2]): the filter (topk_collapse) for the final k;
+      mask_fn(saturated, selected) -> keep: the caller's mask without the rows of the group ids `saturated` and the ids `selected`.
+    Round 0 searches every query for fetch_k; exact=False returns it.  Round 1 searches the incomplete queries, as one batch,
+    for 1024 - E.  After that every still incomplete query runs alone: with j entries selected, it searches for 1024 - E - j rows
+    under a mask without its saturated groups (max_per_group entries selected) and its selected rows, and filters [selected ;
+    new rows] -- a sorted row, every new row follows the old list -- until the filter reports complete.  A round that does not
+    finish dropped a row, whose group is then saturated: the saturated groups grow every round, so the loop ends.  Reading
+    `complete` SYNCHRONISES with the host once per round.  ntotal: the number of rows when the caller knows it (a search for all
+    of them is complete whatever its tail).  stats: optional dict, receives batched_rounds / masked_rounds.
+    Returns (vals [B,k], idx [B,k], gids [B,k], complete int32 [B])."""
+    width = COLLAPSE_MMAX - E
+    whole = (lambda kk: ntotal is not None and kk >= ntotal)
+    counts = {"batched_rounds": 1, "masked_rounds": 0}
+    ov, oi, og, info = collapse_fn(*search_fn(None, fetch_k, None))
+    complete = info[:, 1].clone()
+    if whole(fetch_k):
+        complete.fill_(1)
+    if exact:
+        todo = torch.nonzero(complete == 0).flatten()  # (the host reads it: one synchronisation per round)
+        if todo.numel() and width > fetch_k:
+            counts["batched_rounds"] += 1
+            rv, ri, rg, rinfo = collapse_fn(*search_fn(todo, width, None))
+            ov[todo], oi[todo], og[todo], info[todo] = rv, ri, rg, rinfo
+            done = rinfo[:, 1] != 0 if not whole(width) else torch.ones_like(rinfo[:, 1], dtype=torch.bool)
+            complete[todo] = done.to(complete.dtype)
+            todo = todo[~done]
+        for b in todo.tolist():
+            while True:
+                j = int(info[b, 0])
+                g = og[b, :j]
+                uniq, cnt = torch.unique(g[g >= 0], return_counts=True)
+                kk = width - j
+                nv, ni = search_fn(todo.new_tensor([b]), kk, mask_fn(uniq[cnt >= max_per_group], oi[b, :j]))
+                counts["masked_rounds"] += 1
+                rv, ri, rg, rinfo = collapse_fn(torch.cat([ov[b:b + 1, :j], nv], 1), torch.cat([oi[b:b + 1, :j], ni], 1))
+                ov[b], oi[b], og[b], info[b] = rv[0], ri[0], rg[0], rinfo[0]
+                if whole(kk) or int(rinfo[0, 1]):
+                    complete[b] = 1
+                    break
+    if stats is not None:
+        stats.update(counts)
+    return ov, oi, og, complete
+
+
+def _owned_gids(groups: torch.Tensor, ids: torch.Tensor, idx_offset: int) -> torch.Tensor:
+    """int64 like ids: groups[ids - idx_offset] where that lies in the table, zeros elsewhere -- one rank's share of the group
+    ids of a sharded collapsed search (the shares add up to the ids: exactly one rank owns a row)."""
+    N = groups.numel()
+    n = ids - idx_offset
+    own = (ids >= 0) & (n >= 0) & (n < N)
+    if N == 0:
+        return torch.zeros_like(ids)
+    return groups[torch.where(own, n, torch.zeros_like(n))].masked_fill_(~own, 0)
+
+
+def _collapsed_search(index, q: torch.Tensor, k: int, max_per_group: int, fetch_k: Optional[int], keep, exclude, exact: bool,
+                      groups: Optional[torch.Tensor], n_rows: int, idx_offset: int, device, ntotal: Optional[int], gid_fn=None):
+    """collapsed_search of the three indexes: index.search is the inner search, groups the group table over the n_rows rows
+    this index (this rank) holds, numbered from idx_offset.  gid_fn(idx) -> the entries' group ids where the table does not
+    cover the result (ShardedIndex); None = look them up in the table."""
+    if groups is None:
+        raise ValueError("collapsed_search: this index has no groups (set_groups)")
+    if q.dim() == 1:
+        res = _collapsed_search(index, q.unsqueeze(0), k, max_per_group, fetch_k, keep, _exclude_row(exclude), exact, groups, n_rows,
+                                idx_offset, device, ntotal, gid_fn)
+        return tuple(t[0] for t in res)
+    _need_cuda(q)
+    k, m = int(k), int(max_per_group)
+    if m < 1:
+        raise ValueError(f"collapsed_search: max_per_group = {m} < 1")
+    E = 0
+    if exclude is not None:
+        exclude, _ = _check_exclude(exclude, q.shape[0], 1, device)
+        E = exclude.shape[1]
+    fk = _collapse_fetch_k(k, ntotal, fetch_k, E)
+    if exact and k + E > COLLAPSE_EXACT_KMAX:
+        raise ValueError(f"an exact collapsed search answers k + E <= {COLLAPSE_EXACT_KMAX}, got {k} + {E} (exact=False has no such bound)")
+
+    def search_fn(rows, kk, keep_r):
+        return index.search(q if rows is None else q[rows], kk, keep=keep if keep_r is None else keep_r,
+                            exclude=exclude if exclude is None or rows is None else exclude[rows])
+
+    def collapse_fn(v, i):
+        if v.shape[1] < k:  # (fewer rows than k were asked for: a corpus smaller than k)
+            pad = k - v.shape[1]
+            v = torch.cat([v, v.new_full((v.shape[0], pad), float("-inf"))], 1)
+            i = torch.cat([i, i.new_full((i.shape[0], pad), -1)], 1)
+        if gid_fn is not None:
+            return topk_collapse(v, i, k, gids=gid_fn(i), max_per_group=m)
+        return topk_collapse(v, i, k, groups=groups, max_per_group=m, idx_offset=idx_offset)
+
+    def mask_fn(saturated, selected):
+        keep_r = pack_keep_mask(~torch.isin(groups, saturated))
+        if keep is not None:
+            keep_r &= _check_keep(keep, n_rows, device)
+        return _clear_ids(keep_r, n_rows, device, selected, idx_offset)
+
+    stats = {}
+    res = _collapse_rounds(search_fn, collapse_fn, mask_fn, m, fk, E, ntotal, exact, stats)
+    index.collapse_rounds = (stats["batched_rounds"], stats["masked_rounds"])
+    return res
+
+
+_COLLAPSED_DOC = """(values f32 [B,k], ids int64 [B,k], group ids int64 [B,k], complete int32 [B]): the best k rows with at most
+        max_per_group rows per document group (set_groups; a negative group id = ungrouped, never collapsed) -- field collapsing.
+        The eligible rows (not removed, kept by keep=, not in exclude=) in (score desc, index asc) order are walked, a row is
+        kept if it is ungrouped or fewer than max_per_group rows of its group were kept before it, and the result is the
+        first k kept rows, tail (-inf, -1, -1).  Values and ids are the search's own, copied.  It is search(q, fetch_k, keep=,
+        exclude=) followed by one filter launch (topk_collapse).  fetch_k defaults to min(ntotal, max(k, min(64, 4 k))) up to
+        k = 64 and to min(ntotal, 1024, 2 k) above; fetch_k + E <= 1024.
+        exact=False returns that one round and does NOT synchronise with the host: complete[b] = 1 says the row is the answer
+        (k rows kept, or the fetch saw every eligible row), 0 that it is an exact PREFIX of it (a group owned the head of the
+        list; values beyond `kept` are the tail).  exact=True (the default) goes on by rounds until every query is complete,
+        and SYNCHRONISES with the host once per round: the incomplete queries once more as a batch for 1024 - E rows, then
+        each still incomplete query alone under a keep-bitmask without its saturated groups and selected rows (torch.isin
+        over the group table: a pass over N ids per round).  It needs k + E <= 512.  collapse_rounds afterwards holds
+        (batched rounds, masked rounds) of the most recent call."""
+
+
 SCREEN_MIN_BATCH = 1     # the screened path wins at every batch size once the corpus is large enough to sample:
                          # B <= 64 streaming form (half the bytes of the fp32 kernel), above it the shared-tile form
 SCREEN_PADDED_MIN_BATCH = 33  # d < 256 (zero-padded screen copy): only where the exact kernel is MFMA-bound
@@ -883,6 +1091,8 @@ class BruteForceIndex:
         self._keep: Optional[torch.Tensor] = None  # the persistent keep-bitmask (remove_ids), None until the first removal
         self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, padded to whole tiles (set_tags), for tagged_search
         self._bias: Optional[torch.Tensor] = None  # one float per row, padded to whole tiles (set_bias), for biased_search
+        self._groups: Optional[torch.Tensor] = None  # one int64 group id per row (set_groups), for collapsed_search
+        self.collapse_rounds = (0, 0)  # (batched, masked) rounds of the most recent collapsed_search
 
     @classmethod
     def _from_buffers(cls, docs32: torch.Tensor, docs16: Optional[torch.Tensor], dmax_norm: float, idx_offset: int,
@@ -1097,6 +1307,23 @@ class BruteForceIndex:
     diverse_search.__doc__ = _DIVERSE_DOC + """
         The candidates' rows are gathered from this index's own rows (fp32, or bf16 widened exactly) by the kernel, whichever
         layout searched: the screened and the exact route return the same list, so the result does not depend on it."""
+
+    @property
+    def groups(self) -> Optional[torch.Tensor]:
+        """The rows' document-group ids (int64 [N]; negative = ungrouped), or None: not set."""
+        return self._groups
+
+    def set_groups(self, groups: Optional[torch.Tensor]) -> None:
+        """One int64 group id per row (int64 [N] on the index's device): the page a passage came from, the thread of a message.
+        A negative id means ungrouped: such a row is never collapsed.  Kept as given (8 bytes per row).  None clears it."""
+        self._groups = None if groups is None else _check_groups(groups, self.docs.shape[0], self.docs.device)
+
+    def collapsed_search(self, q: torch.Tensor, k: int = 10, max_per_group: int = 1, fetch_k: Optional[int] = None,
+                         keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, exact: bool = True):
+        return _collapsed_search(self, q, k, max_per_group, fetch_k, keep, exclude, exact, self._groups, self.docs.shape[0],
+                                 self.idx_offset, self.docs.device, self.docs.shape[0])
+
+    collapsed_search.__doc__ = _COLLAPSED_DOC
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 [B] (0-d for a single query): how many documents of this index -- not removed (remove_ids), and kept by
@@ -1430,6 +1657,7 @@ class ShardedIndex:
             self._coll.all_gather_blocks(send.view(torch.uint8), recv.view(torch.uint8))
             mine = int(recv.min().item())
         self._seed_exchange = bool(mine)  # the same on every rank
+        self.collapse_rounds = (0, 0)  # (batched, masked) rounds of the most recent collapsed_search
 
     def _seed_plan(self, k: int):
         return seed_plan(self._coll.world, k, self._seed_exchange)
@@ -1720,6 +1948,43 @@ class ShardedIndex:
         B = 100, fetch_k = 128, d = 256).  Exactly one rank contributes each row and x + 0 is exact, so every rank holds the
         candidates' rows and runs the selection on them (tt_mmr_select_rows_f32): the single-GPU result on every rank."""
 
+    @property
+    def groups(self) -> Optional[torch.Tensor]:
+        """This rank's group ids over its own rows (set_groups), or None."""
+        return self._index.groups
+
+    def set_groups(self, local_groups: Optional[torch.Tensor]) -> None:
+        """One int64 group id per row of THIS RANK'S shard (BruteForceIndex.set_groups / StreamedIndex.set_groups; None clears
+        it); the ids are global names, a group may span shards.  Called on every rank, like every call on this class."""
+        self._index.set_groups(local_groups)
+
+    def _gather_gids(self, ids: torch.Tensor) -> torch.Tensor:
+        """The group ids of merged result ids on every rank: each rank fills in the ids it owns (zeros elsewhere), one
+        all_reduce(SUM) of the int64 block on the index's group."""
+        g = _owned_gids(self._index.groups, ids, self.row_offset)
+        if self._coll.world > 1:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group)
+            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' blocks and add)
+                recv = torch.empty((self._coll.world,) + tuple(g.shape), dtype=torch.int64, device=g.device)
+                self._coll.all_gather_blocks(g.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
+                g = recv.sum(0)
+        return g
+
+    def collapsed_search(self, q: torch.Tensor, k: int = 10, max_per_group: int = 1, fetch_k: Optional[int] = None,
+                         keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, exact: bool = True):
+        return _collapsed_search(self, q, k, max_per_group, fetch_k, keep, exclude, exact, self._index.groups, self._index.ntotal,
+                                 self.row_offset, self._dev, None, self._gather_gids)
+
+    collapsed_search.__doc__ = _COLLAPSED_DOC + """
+        Sharded, a COLLECTIVE like every search of this class (q, exclude and the arguments the same on every rank; keep over
+        THIS RANK'S rows, on all ranks or on none): the sharded search for fetch_k, identical on every rank; each rank fills
+        the group ids of the result ids it owns and zeros elsewhere, one all_reduce(SUM) of the int64 [B,fetch_k] block
+        completes them, and every rank runs the filter on the ids (tt_topk_collapse_gids): the single-index result on every
+        rank.  In a masked round every rank clears its own rows of the saturated groups -- every rank derives the same set
+        from the identical merged result.  The corpus size is not known to a rank, so the default fetch_k is not cut to it."""
+
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The count of the whole corpus, identical on every rank: this rank's count over its shard under its mask (keep: over
         THIS RANK'S rows, on all ranks or on none, as in search()), then one all_reduce(SUM) of the int64 [B] on the index's
@@ -1820,6 +2085,8 @@ class StreamedIndex:
         self._gather = None  # two pinned [block,d] host buffers of the candidate gather (_score_ids), allocated on first use
         self._tags: Optional[torch.Tensor] = None  # one 32-bit tag per row, resident on the device (set_tags): 4 bytes per row
         self._bias: Optional[torch.Tensor] = None  # one float per row, resident on the device (set_bias): 4 bytes per row
+        self._groups: Optional[torch.Tensor] = None  # one int64 group id per row, resident on the device (set_groups)
+        self.collapse_rounds = (0, 0)  # (batched, masked) rounds of the most recent collapsed_search
 
     def _walk(self, visit, stats=None):
         L = _lib.lib()
@@ -2131,6 +2398,25 @@ class StreamedIndex:
         copied to the host, their rows gathered there (index_select from the pinned corpus into pinned staging), sent to the
         device (B * fetch_k * d * 2 bytes), widened exactly and selected from (tt_mmr_select_rows_f32): the resident bf16
         index's result."""
+
+    @property
+    def groups(self) -> Optional[torch.Tensor]:
+        """The group ids of the whole corpus, on the device (int64 [N]; negative = ungrouped), or None: not set."""
+        return self._groups
+
+    def set_groups(self, groups: Optional[torch.Tensor]) -> None:
+        """One int64 group id per row of the whole corpus (int64 [N]), on the index's DEVICE: the rows stream from the host, the
+        group table stays resident at 8 bytes per row.  None clears it."""
+        self._groups = None if groups is None else _check_groups(groups, self.N, self.device)
+
+    def collapsed_search(self, q: torch.Tensor, k: int = 10, max_per_group: int = 1, fetch_k: Optional[int] = None,
+                         keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, exact: bool = True):
+        return _collapsed_search(self, q, k, max_per_group, fetch_k, keep, exclude, exact, self._groups, self.N, self.idx_offset,
+                                 self.device, self.N)
+
+    collapsed_search.__doc__ = _COLLAPSED_DOC + """
+        Streamed: every round is one walk over the host rows; a masked round needs block_docs to be a multiple of 32 like
+        every masked search of this class."""
 
     def count(self, q: torch.Tensor, min_score, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 [B] (0-d for a single query): the documents of the whole corpus (not removed, kept by `keep`: a mask over the
