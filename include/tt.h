@@ -239,6 +239,47 @@ int tt_score_topk_biased_bf16(const float *Q, int B, int d, const void *D_bf16, 
                               size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * Cursor search ("search_after", "scroll"): the masked exact search restricted, per query, to the documents that lie strictly
+ * AFTER a cursor in the library's total order (score desc, index asc), in one pass over the corpus.  With the cursor at the last
+ * (score, id) of a page it returns the next page -- at any depth, for the price of a first page -- and with the cursor at
+ * (ceiling, -1) the k best documents that score at most `ceiling` (hard negatives below a positive's score).  Replaces
+ *     torch.topk(torch.matmul(q, D.t()), k_deep) and a cut (backend/evaluators.py:185-186 asked for a deep page),
+ * which cannot reach past k = TT_TOPK_LARGE_KMAX at all.
+ * after_val [B] floats, after_idx [B] int64: device memory, one cursor (a_b, i_b) per query, i_b a GLOBAL id (the ids this call
+ * returns: position in D + idx_offset).  Document n (global id g = n + idx_offset) with score s -- the score of
+ * tt_score_topk_f32 / _bf16, the same bits -- is eligible for query b iff
+ *     s < a_b  ||  (s == a_b  &&  g > i_b)
+ * in IEEE comparisons: a NaN a_b makes nothing eligible, -0.0 == +0.0, and a NaN score is never eligible.  Any int64 is a legal
+ * i_b: ids of other shards, ids below idx_offset (every tie at a_b is then eligible) and at or beyond idx_offset + N (no tie is)
+ * are ordinary; g > i_b is decided as if in exact integers (the kernels compare the position n against
+ * clamp(i_b - idx_offset, -1, N), saturated, never wrapped: tt_after_local_bound gives that value).
+ * The result for query b is the exact top-k of its eligible kept documents (keep: tt_score_topk_masked_f32's bitmask, or NULL:
+ * all), (score desc, index asc), tail (-inf, -1): bit for bit what tt_score_topk_masked_f32 / _bf16 returns for query b alone
+ * under a keep-bitmask of that eligibility.
+ * after_val == after_idx == NULL: the call then IS the masked call: same launches, same bits.  One of the two NULL, after_val
+ * not 4-byte or after_idx not 8-byte aligned: TT_ERR_BAD_SHAPE.  The cursor (+inf, -1) returns the masked call's bits; the
+ * cursor (-inf, anything) returns the tail when every score is finite, so the last entry of an exhausted page, (-inf, -1), is a
+ * valid cursor that returns nothing.
+ * 1 <= k <= 64 (above: TT_ERR_UNSUPPORTED, and the size query returns 0, as it does for B = 0): a larger page is two consecutive
+ * calls, the second with the first's last column as its cursor.  d and dtype support, N's bound, the alignment of Q / D / keep /
+ * workspace and the status codes are the masked call's.  N = 0 writes the tail.  Asynchronous, capturable, no host
+ * synchronisation, no allocation, no global state: the kernels read the cursor buffers, so a captured call follows the values
+ * they hold at replay (copy a page's last column into them on the device and replay: the next page).  The result does not depend
+ * on what the workspace (tt_score_topk_after_workspace_bytes: the masked call's) and the outputs held.
+ * The cursor acts where the keep-bitmask does: in the sample maxima that seed the thresholds (a maximum taken from a document
+ * already returned is no lower bound of the k-th eligible score), in the append pass and in the give-up redo.
+ */
+size_t tt_score_topk_after_workspace_bytes(int B, int64_t N, int d, int k, int bf16);
+int tt_score_topk_after_f32(const float *Q, int B, int d, const float *D, int64_t N, const float *after_val,
+                            const int64_t *after_idx, const uint32_t *keep, int k, int64_t idx_offset, float *out_val,
+                            int64_t *out_idx, void *workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_score_topk_after_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const float *after_val,
+                             const int64_t *after_idx, const uint32_t *keep, int k, int64_t idx_offset, float *out_val,
+                             int64_t *out_idx, void *workspace, size_t workspace_bytes, tt_stream_t stream);
+/* clamp(after_idx - idx_offset, -1, N) in exact integers, as the cursor kernels form it (N < 0 counts as 0).  Host code, no GPU. */
+int tt_after_local_bound(int64_t after_idx, int64_t idx_offset, int N);
+
+/*
  * The screened search over a bf16 corpus kept as bf16 (BASELINE configs[4]'s layout; replaces
  * backend/evaluators.py:185-186 like tt_score_topk_screened_f32): the f32 contracts below with D32 + D16 replaced by the
  * one D_bf16 [N,256] (16-byte aligned).  The screen kernels DMA the bf16 rows and each wave converts, in LDS, the pieces it

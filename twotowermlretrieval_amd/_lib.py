@@ -56,6 +56,10 @@ SIGNATURES = {
     "tt_score_topk_biased_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
     "tt_score_topk_biased_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "tt_score_topk_biased_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_after_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "tt_score_topk_after_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_score_topk_after_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "tt_after_local_bound": (_i, [_i64, _i64, _i]),
     "tt_score_topk_screened_bf16_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
     "tt_index_stats_bf16": (_i, [_vp, _i64, _i, _vp, _i, _vp]),
     "tt_score_topk_screened_bf16": (_i, [_vp, _i, _i, _vp, _i64, _i, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),

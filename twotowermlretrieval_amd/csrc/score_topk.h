@@ -65,6 +65,9 @@ struct ExactCall {
     const unsigned *match_value = nullptr;
     // biased search (tt_score_topk_biased_f32 / _bf16): one float per document, padded to whole 32-document tiles, or nullptr
     const float *bias = nullptr;
+    // cursor search (tt_score_topk_after_f32 / _bf16): one (score, GLOBAL id) cursor per query; both set, or both nullptr
+    const float *after_val = nullptr;
+    const int64_t *after_idx = nullptr;
 };
 
 // What varies between the main passes of one call.  (The sample pass always seeds for the call's k.)

@@ -32,6 +32,7 @@
 #include "keep_word.h"
 #include "tag_words.h"
 #include "bias_words.h"
+#include "after_words.h"
 
 #include <limits.h>
 #include <math.h>
@@ -105,6 +106,12 @@ struct ScoreParams {
     // BIASED instantiations (biased search): bias [32 * n_tiles] one float per document -- the score of document n is
     // fl32(q.d + bias[n]); nullptr in every other launch
     const float *bias = nullptr;
+    // AFTER instantiations (cursor search): after_val / after_idx [B] one (score, GLOBAL id) cursor per query -- document n is
+    // eligible for query b iff it lies strictly after the cursor in (score desc, index asc); after_off: the call's idx_offset
+    // (the sample pass runs with idx_offset = 0, its cursor must not); both nullptr in every other launch
+    const float *after_val = nullptr;
+    const int64_t *after_idx = nullptr;
+    int64_t after_off = 0;
 };
 
 // The keep word of one tile (MASKED): keep_word_issue / keep_word_wait (keep_word.h, shared with screen.hip).  Here the load is
@@ -216,8 +223,15 @@ __device__ __forceinline__ void compact_query(Cand *base, int n, int k, int lane
 // added to the accumulators before anything else reads them, so the sample maxima, the tile maximum, the threshold test and
 // the append store all see the biased score.  p.keep may be nullptr (tested wave-uniformly, as under TAGGED: one instantiation
 // serves both).  BIASED = false is the kernel as it was.
+// AFTER (with MASKED, never with TAGGED, BIASED or COUNT; tt_score_topk_after_f32 / _bf16, DESIGN.md "Cursor search"): document
+// doc with score s is eligible for the lane's query iff s < a || (s == a && doc > cl), (a, cl) the query's cursor (after_words.h),
+// read once per lane.  The predicate reads the accumulator, so it is formed in the epilogue: the lane's eligibility bits are ANDed
+// into kwh, which feeds kept(r) as the keep word does -- sample maxima, append pass and give-up redo see one predicate -- and an
+// ineligible accumulator becomes -inf in front of the tile maximum, so that a tile whose only scores above the threshold were
+// returned by earlier pages does not enter the append pass.  p.keep may be nullptr (tested wave-uniformly).  AFTER = false is
+// the kernel as it was.
 template <int NS, int CAP, bool MAXONLY, bool NT = false, bool BF = false, bool MASKED = false, bool COUNT = false,
-          bool TAGGED = false, bool BIASED = false>
+          bool TAGGED = false, bool BIASED = false, bool AFTER = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -225,6 +239,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
     static_assert(!BIASED || (MASKED && !COUNT && !TAGGED), "biased search: a mode of the masked lists and maxima");
+    static_assert(!AFTER || (MASKED && !COUNT && !TAGGED && !BIASED), "cursor search: a mode of the masked lists and maxima");
     constexpr int NST = NT ? NSTAGE_NT : NSTAGE;
     constexpr int WAVE_LDS = NST * SLAB_BYTES;
     constexpr int NSD = BF ? NS / 2 : NS; // 128-B slabs per document row
@@ -290,6 +305,13 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
     if (TAGGED && qrow < p.B) {
         mm = p.match_mask[qrow];
         mv = p.match_value[qrow];
+    }
+    // AFTER: the query's cursor, read once; a padded query reads nothing and matches nothing (a NaN cursor score)
+    float ca = __builtin_nanf("");
+    int cl = 0;
+    if (AFTER && qrow < p.B) {
+        ca = p.after_val[qrow];
+        cl = after_local_bound(p.after_idx[qrow], p.after_off, p.N);
     }
     int nmatch = 0; // COUNT: this lane's documents with score >= thr (16 of a tile's 32 per lane half)
     float runmax = -INFINITY;
@@ -408,12 +430,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                 if (TAGGED && s == NSD - 1)
                     tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, frag[0]);
                 // (BIASED: the same route and the same stand-in, the tile's first bias)
+                // (AFTER: the stand-in is the first cursor score)
                 if (BIASED && s == NSD - 1)
                     bias_words_issue(p.bias + (size_t)tile * TILE_DOCS, bw, frag[0]);
                 if (MASKED && s == NSD - 1)
-                    keep_word_issue((!(TAGGED || BIASED) || p.keep) ? p.keep + tile
-                                    : TAGGED                        ? p.tags + (size_t)tile * TILE_DOCS
-                                                                    : (const unsigned *)p.bias + (size_t)tile * TILE_DOCS,
+                    keep_word_issue((!(TAGGED || BIASED || AFTER) || p.keep) ? p.keep + tile
+                                    : TAGGED                                 ? p.tags + (size_t)tile * TILE_DOCS
+                                    : BIASED ? (const unsigned *)p.bias + (size_t)tile * TILE_DOCS
+                                             : (const unsigned *)p.after_val,
                                     kw, frag[0]);
                 dma_issue((stage + NST - 1) % NST);
                 if (BF) {
@@ -470,6 +494,32 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
                     for (int i = 0; i < 4; ++i)
                         acc[4 * g + i] = bias_add(acc[4 * g + i], bq[i]);
                 }
+            } else if (AFTER) {
+                // the lane's eligibility bits join the keep bits, and an ineligible accumulator leaves the tile maximum.  (A
+                // row at or beyond N repeats row N - 1's score under a larger doc: the doc < p.N tests below keep it out.)
+                // Only a score at or above the cursor's can be ineligible, so a tile whose maxima all lie below their query's
+                // cursor score -- every tile under the open cursor, nearly every tile under a deep one -- skips the 16 tests
+                // (wave-uniform; !(m0 < ca) sends a NaN on either side to the tests, a padded query's NaN cursor excepted: it
+                // never appends and its maxima are not written).
+                keep_word_wait(kw, acc);
+                if (!p.keep)
+                    kw = 0xffffffffu;
+                kwh = kw >> (4 * h);
+                float m0 = acc[0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r)
+                    m0 = fmaxf(m0, acc[r]);
+                if (__ballot(qrow < p.B && !(m0 < ca)) != 0ull) {
+                    unsigned em = 0u;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = (r & 3) + 8 * (r >> 2);
+                        const bool e = after_eligible(acc[r], tile * TILE_DOCS + row + 4 * h, ca, cl);
+                        em |= e ? 1u << row : 0u;
+                        acc[r] = e ? acc[r] : -INFINITY;
+                    }
+                    kwh &= em;
+                }
             } else if (MASKED) {
                 keep_word_wait(kw, acc);
                 kwh = kw >> (4 * h);
@@ -499,7 +549,9 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
             // (MASKED: m may come from a masked document -- that only costs the slow path a look; a tile with nothing kept
             //  skips it)
             // (TAGGED: "nothing kept" is per lane -- a tile may be dead for one query of the wave and live for another)
-            if (!COUNT && (!MASKED || TAGGED || kw != 0u) && __ballot((!TAGGED || kwq != 0u) && m >= thr) != 0ull) {
+            // (AFTER: as under TAGGED, "nothing eligible" is per lane)
+            if (!COUNT && (!MASKED || TAGGED || kw != 0u) &&
+                __ballot((!TAGGED || kwq != 0u) && (!AFTER || kwh != 0u) && m >= thr) != 0ull) {
                 // Append pass.  The store is inline asm on purpose: a compiler-visible global store
                 // (or the compaction's loads) inside this loop makes hipcc emit s_waitcnt vmcnt(0) at
                 // every join, which drains the LDS-DMA ring on each tile that has a candidate.
@@ -636,13 +688,14 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk_kernel(ScoreParams p)
 // buffers, compaction, partial lists and merge are K4's; the launch is bound by HBM streaming (d * 4 bytes per doc).
 // ---------------------------------------------------------------------------
 template <int NS, int CAP, bool MAXONLY, bool NT = false, bool MASKED = false, bool COUNT = false, bool TAGGED = false,
-          bool BIASED = false>
+          bool BIASED = false, bool AFTER = false>
 __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!COUNT || !MAXONLY, "the counting pass is a mode of the main pass");
     static_assert(!TAGGED || (MASKED && !COUNT), "tagged search: a mode of the masked lists and maxima");
     static_assert(!BIASED || (MASKED && !COUNT && !TAGGED), "biased search: a mode of the masked lists and maxima");
+    static_assert(!AFTER || (MASKED && !COUNT && !TAGGED && !BIASED), "cursor search: a mode of the masked lists and maxima");
     constexpr int WAVE_LDS = NSTAGE * SLAB_BYTES;
     constexpr int ROW_BYTES = NS * 128;
     const int lane = threadIdx.x & 63;
@@ -677,6 +730,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
     if (TAGGED && qrow < p.B) {
         mm = p.match_mask[qrow];
         mv = p.match_value[qrow];
+    }
+    float ca = __builtin_nanf(""); // AFTER: the query's cursor (see score_topk_kernel)
+    int cl = 0;
+    if (AFTER && qrow < p.B) {
+        ca = p.after_val[qrow];
+        cl = after_local_bound(p.after_idx[qrow], p.after_off, p.N);
     }
     int nmatch = 0; // COUNT: this lane's documents with score >= thr (8 of a tile's 32 per lane quarter)
     float runmax = -INFINITY;
@@ -764,9 +823,10 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
                         tag_words_issue(p.tags + (size_t)tile * TILE_DOCS, tg, a00);
                     if (BIASED)
                         bias_words_issue(p.bias + (size_t)tile * TILE_DOCS, bw, a00);
-                    keep_word_issue((!(TAGGED || BIASED) || p.keep) ? p.keep + tile
-                                    : TAGGED                        ? p.tags + (size_t)tile * TILE_DOCS
-                                                                    : (const unsigned *)p.bias + (size_t)tile * TILE_DOCS,
+                    keep_word_issue((!(TAGGED || BIASED || AFTER) || p.keep) ? p.keep + tile
+                                    : TAGGED                                 ? p.tags + (size_t)tile * TILE_DOCS
+                                    : BIASED ? (const unsigned *)p.bias + (size_t)tile * TILE_DOCS
+                                             : (const unsigned *)p.after_val,
                                     kw, a00);
                     a[0][0] = a00[0];
                     a[1][0] = a00[1];
@@ -798,6 +858,22 @@ __global__ __launch_bounds__(WPB * 64, 2) void score_topk16_kernel(ScoreParams p
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         acc[u][r] = bias_add(acc[u][r], bq[r]);
+                }
+            } else if (AFTER) { // the lane's eligibility bits join the keep bits (see score_topk_kernel; m below is over kept())
+                keep_word_wait(kw, acc[1]);
+                if (!p.keep)
+                    kw = 0xffffffffu;
+                kwh = kw >> (4 * kq);
+                float m0 = fmaxf(fmaxf(fmaxf(acc[0][0], acc[0][1]), fmaxf(acc[0][2], acc[0][3])),
+                                 fmaxf(fmaxf(acc[1][0], acc[1][1]), fmaxf(acc[1][2], acc[1][3])));
+                if (__ballot(qrow < p.B && !(m0 < ca)) != 0ull) { // (the tests only where a score reaches a cursor's)
+                    unsigned em = 0u;
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            em |= after_eligible(acc[u][r], tile * TILE_DOCS + 16 * u + 4 * kq + r, ca, cl) ? 1u << (16 * u + r) : 0u;
+                    kwh &= em;
                 }
             } else if (MASKED) {
                 keep_word_wait(kw, acc[1]);
@@ -1382,33 +1458,37 @@ constexpr bool score_dim_ok(int d, bool bf16)
 enum PassKind { PASS_LISTS, PASS_MAXONLY, PASS_COUNT };
 
 struct Score32 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT, TAGGED, BIASED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false,
+              bool AFTER = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, false, MASKED, COUNT, TAGGED, BIASED, AFTER>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE_NT * SLAB_BYTES; // the NT form's own ring depth
 };
 struct Score32Bf16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
-    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT, TAGGED, BIASED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false,
+              bool AFTER = false>
+    static const void *fn() { return (const void *)score_topk_kernel<NS, CAP, MAXONLY, NT, true, MASKED, COUNT, TAGGED, BIASED, AFTER>; }
     static constexpr size_t smem_nt = Score32::smem_nt;
 };
 struct Score16 {
-    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false>
-    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT, TAGGED, BIASED>; }
+    template <int NS, int CAP, bool MAXONLY, bool NT, bool MASKED, bool COUNT = false, bool TAGGED = false, bool BIASED = false,
+              bool AFTER = false>
+    static const void *fn() { return (const void *)score_topk16_kernel<NS, CAP, MAXONLY, NT, MASKED, COUNT, TAGGED, BIASED, AFTER>; }
     static constexpr size_t smem_nt = (size_t)WPB * NSTAGE * SLAB_BYTES;
 };
 
 // (TAGGED: the tagged search's instantiations -- lists and maxima only, there is no tagged count -- one per shape, with or
-//  without a keep-bitmask, which the kernel tests itself; BIASED: the biased search's, the same set)
-template <class K, int NS, bool MASKED, bool TAGGED = false, bool BIASED = false>
+//  without a keep-bitmask, which the kernel tests itself; BIASED: the biased search's, the same set; AFTER: the cursor
+//  search's, the same set)
+template <class K, int NS, bool MASKED, bool TAGGED = false, bool BIASED = false, bool AFTER = false>
 int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
     const void *fn;
     size_t smem = pl.smem;
     if (kind == PASS_MAXONLY) {
-        fn = K::template fn<NS, 64, true, false, MASKED, false, TAGGED, BIASED>();
+        fn = K::template fn<NS, 64, true, false, MASKED, false, TAGGED, BIASED, AFTER>();
     } else if (kind == PASS_COUNT) { // (the nt form under the main pass's own rule: one query tile at d = 256)
-        if constexpr (TAGGED || BIASED) {
-            return tt_fail(TT_ERR_UNSUPPORTED, "the counting pass takes no tags and no bias");
+        if constexpr (TAGGED || BIASED || AFTER) {
+            return tt_fail(TT_ERR_UNSUPPORTED, "the counting pass takes no tags, no bias and no cursor");
         } else if (NS == 8 && sp.n_qtiles == 1) {
             fn = K::template fn<8, 64, false, true, MASKED, true>();
             smem = K::smem_nt;
@@ -1416,12 +1496,12 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind 
             fn = K::template fn<NS, 64, false, false, MASKED, true>();
         }
     } else if (NS == 8 && sp.n_qtiles == 1) { // (d = 256 only: the instantiations are not free)
-        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED, false, TAGGED, BIASED>()
-                          : K::template fn<8, 128, false, true, MASKED, false, TAGGED, BIASED>();
+        fn = pl.cap == 64 ? K::template fn<8, 64, false, true, MASKED, false, TAGGED, BIASED, AFTER>()
+                          : K::template fn<8, 128, false, true, MASKED, false, TAGGED, BIASED, AFTER>();
         smem = K::smem_nt;
     } else {
-        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED, false, TAGGED, BIASED>()
-                          : K::template fn<NS, 128, false, false, MASKED, false, TAGGED, BIASED>();
+        fn = pl.cap == 64 ? K::template fn<NS, 64, false, false, MASKED, false, TAGGED, BIASED, AFTER>()
+                          : K::template fn<NS, 128, false, false, MASKED, false, TAGGED, BIASED, AFTER>();
     }
     TT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     ScoreParams args = sp;
@@ -1431,10 +1511,13 @@ int launch_ns_m(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind 
 }
 
 // sp.keep set: the MASKED instantiation of the same kernel; sp.tags set: the TAGGED one, with or without sp.keep; sp.bias
-// set (never with sp.tags: the biased entries carry none): the BIASED one, with or without sp.keep
+// set (never with sp.tags: the biased entries carry none): the BIASED one, with or without sp.keep; sp.after_val set (the
+// cursor entries carry neither tags nor bias): the AFTER one, with or without sp.keep
 template <class K, int NS>
 int launch_ns(const ScoreParams &sp, const Plan &pl, hipStream_t st, PassKind kind)
 {
+    if (sp.after_val)
+        return launch_ns_m<K, NS, true, false, false, true>(sp, pl, st, kind);
     if (sp.bias)
         return launch_ns_m<K, NS, true, false, true>(sp, pl, st, kind);
     if (sp.tags)
@@ -1513,6 +1596,9 @@ ScoreParams pass_params(const Pass &ps, const ExactCall &c, int list_k, int64_t 
     sp.match_mask = c.match_mask;
     sp.match_value = c.match_value;
     sp.bias = c.bias;
+    sp.after_val = c.after_val;
+    sp.after_idx = c.after_idx;
+    sp.after_off = c.idx_offset; // (not the pass's own idx_offset: the sample pass numbers its lists from 0)
     return sp;
 }
 

@@ -1,5 +1,6 @@
 // K4L / K4m: exact top-k for 64 < k <= TT_TOPK_LARGE_KMAX, and under a keep-bitmask, on the main pass of score_topk.hip.
 #include "score_topk.h"
+#include "after_words.h"
 
 #include <limits.h>
 #include <math.h>
@@ -788,6 +789,52 @@ TT_EXPORT int tt_score_topk_biased_bf16(const float *Q, int B, int d, const void
 {
     return score_topk_biased(ExactCall{Q, B, d, D_bf16, true, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
                                        (hipStream_t)stream, "tt_score_topk_biased_bf16", false, nullptr, nullptr, nullptr, bias});
+}
+
+// ---- Cursor search (DESIGN.md "Cursor search") -------------------------------------------------------------------------------
+// The masked call for k <= 64 restricted, per query, to the documents strictly after a (score, id) cursor in the order (score
+// desc, index asc): the same plan, workspace and launches, on the AFTER instantiations of the main and sample passes
+// (score_topk.hip).  after_val == after_idx == NULL is the masked call itself.
+namespace {
+int score_topk_after(ExactCall c)
+{
+    if (c.k > MERGE_KMAX)
+        return tt_fail(TT_ERR_UNSUPPORTED, "%s: k=%d > %d (a larger page is two consecutive calls)", c.who, c.k, MERGE_KMAX);
+    if ((c.after_val != nullptr) != (c.after_idx != nullptr))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: after_val and after_idx must be both NULL or both non-NULL", c.who);
+    if (((uintptr_t)c.after_val & 3) || ((uintptr_t)c.after_idx & 7))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: after_val must be 4-byte and after_idx 8-byte aligned", c.who);
+    return score_topk_large(c);
+}
+} // namespace
+
+TT_EXPORT size_t tt_score_topk_after_workspace_bytes(int B, int64_t N, int d, int k, int bf16)
+{
+    return k > MERGE_KMAX ? 0 : tt_score_topk_large_workspace_bytes(B, N, d, k, bf16);
+}
+
+TT_EXPORT int tt_score_topk_after_f32(const float *Q, int B, int d, const float *D, int64_t N, const float *after_val,
+                                      const int64_t *after_idx, const uint32_t *keep, int k, int64_t idx_offset, float *out_val,
+                                      int64_t *out_idx, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_after(ExactCall{Q, B, d, D, false, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                      (hipStream_t)stream, "tt_score_topk_after_f32", false, nullptr, nullptr, nullptr, nullptr,
+                                      after_val, after_idx});
+}
+
+TT_EXPORT int tt_score_topk_after_bf16(const float *Q, int B, int d, const void *D_bf16, int64_t N, const float *after_val,
+                                       const int64_t *after_idx, const uint32_t *keep, int k, int64_t idx_offset, float *out_val,
+                                       int64_t *out_idx, void *workspace, size_t workspace_bytes, tt_stream_t stream)
+{
+    return score_topk_after(ExactCall{Q, B, d, D_bf16, true, N, k, idx_offset, keep, out_val, out_idx, workspace, workspace_bytes,
+                                      (hipStream_t)stream, "tt_score_topk_after_bf16", false, nullptr, nullptr, nullptr, nullptr,
+                                      after_val, after_idx});
+}
+
+// The kernels' local id bound of a cursor (after_words.h), for a caller that wants to see it: host code only.
+TT_EXPORT int tt_after_local_bound(int64_t after_idx, int64_t idx_offset, int N)
+{
+    return after_local_bound(after_idx, idx_offset, N < 0 ? 0 : N);
 }
 
 namespace {

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 
 __all__ = ["GraphedSearch", "score_topk", "pack_keep_mask", "topk_merge", "topk_exclude", "score_rank", "score_all", "score_ids", "mmr_select", "topk_collapse", "BruteForceIndex", "ShardedIndex", "PendingSearch", "StreamedIndex",
-           "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances"]
+           "shard_bounds", "seed_union", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances", "score_topk_after"]
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -384,6 +384,132 @@ def l2_distances(q: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
     returned -> |q|^2 - 2 vals, clamped at 0, with the (-inf) tail mapped to +inf.  float32, ascending along k."""
     qn = (q.to(torch.float32) ** 2).sum(dim=-1, keepdim=True)
     return (qn - 2.0 * vals).clamp_(min=0.0)
+
+
+AFTER_KMAX = SMALL_KMAX  # one cursor call answers k <= 64 (tt_score_topk_after_*): a larger page is two consecutive calls
+
+
+def _cursor(after, B: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The cursors of B queries on `device` as tt_score_topk_after_* reads them: (float32 [B], int64 [B]), contiguous.
+    after = (vals, ids): each a tensor of B elements on the device (a 0-d tensor or [1] for a single query) or a Python
+    number for every query; None = the open cursor (+inf, -1), in front of every document."""
+    av, ai = (float("inf"), -1) if after is None else after
+    parts = []
+    for x, dtype, what in ((av, torch.float32, "score"), (ai, torch.int64, "id")):
+        if isinstance(x, torch.Tensor):
+            if x.dtype != dtype:
+                raise TypeError(f"the cursor's {what}s must be {dtype}, got {x.dtype}")
+            if x.device != device:
+                raise ValueError(f"the cursor's {what}s on {x.device} but the search runs on {device}")
+            if x.numel() != B or x.dim() > 1:
+                raise ValueError(f"the cursor holds one {what} per query ([{B}]), got {tuple(x.shape)}")
+            parts.append(x.reshape(B).contiguous())
+        elif isinstance(x, bool) or not isinstance(x, (int, float)) or (dtype == torch.int64 and not isinstance(x, int)):
+            raise TypeError(f"the cursor's {what} must be a {dtype} tensor or a Python {'int' if dtype == torch.int64 else 'float'}, got {type(x)}")
+        else:
+            if dtype == torch.int64 and not -(1 << 63) <= x < (1 << 63):
+                raise ValueError(f"the cursor's id {x} is no int64")
+            parts.append(torch.full((B,), x, dtype=dtype, device=device))
+    return parts[0], parts[1]
+
+
+def _after_into(q: torch.Tensor, docs: torch.Tensor, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], k: int,
+                idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """tt_score_topk_after_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, (av, ai) a checked cursor
+    (_cursor), keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
+    if not 1 <= k <= AFTER_KMAX:
+        raise ValueError(f"a cursor search answers 1 <= k <= {AFTER_KMAX} per call, got k = {k} (pages() / deep_search() go deeper)")
+    B, d = q.shape
+    N = docs.shape[0]
+    bf16 = docs.dtype == torch.bfloat16
+    vals, idx = _out_pair(B, k, q.device, out)
+    if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+        return (vals, idx) if out is None else out
+    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
+        L = _lib.lib()
+        ws = torch.empty(max(L.tt_score_topk_after_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
+        fn = L.tt_score_topk_after_bf16 if bf16 else L.tt_score_topk_after_f32
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, av.data_ptr(), ai.data_ptr(), None if keep is None else keep.data_ptr(),
+                      k, idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
+    return (vals, idx) if out is None else out
+
+
+def score_topk_after(q: torch.Tensor, docs: torch.Tensor, after_val, after_idx, k: int, idx_offset: int = 0,
+                     keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The next k results after a cursor, in one pass over docs: document n (global id g = n + idx_offset) with score s --
+    score_topk's score, the same bits -- is eligible for query b iff it lies strictly after (after_val[b], after_idx[b]) in the
+    order (score desc, index asc): s < a or (s == a and g > i).  after_val: float32 [B] on the device or a Python float,
+    after_idx: int64 [B] GLOBAL ids or a Python int (any int64: ids of other shards are ordinary).  (+inf, -1) is the open
+    cursor (score_topk's result), (ceiling, -1) asks for the k best documents that score at most `ceiling`, the last column of
+    a page asks for the next page, and (-inf, -1) -- the tail of an exhausted page -- returns nothing.  keep: a pack_keep_mask
+    bitmask, as in score_topk.  Returns the exact top-k of the eligible kept documents, tail (-inf, -1)
+    (tt_score_topk_after_f32 / _bf16; k <= 64 per call)."""
+    if q.dim() == 1:
+        return _squeezed(score_topk_after, q, docs, after_val, after_idx, k, idx_offset, keep)
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), _docs_c(docs)
+    B, d = q.shape
+    N = docs.shape[0]
+    if docs.dim() != 2 or docs.shape[1] != d:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    av, ai = _cursor((after_val, after_idx), B, docs.device)
+    if keep is not None:
+        keep = _check_keep(keep, N, docs.device)
+    return _after_into(q, docs, av, ai, keep, k, int(idx_offset))
+
+
+class _CursorSearch:
+    """What the three indexes share of the cursor search: search_after's front (a single query, exclude=), pages() and
+    deep_search().  An index supplies _search_after(q [B,d], k, av, ai, keep, out) and _cursor_device()."""
+
+    def search_after(self, q: torch.Tensor, k: int, after=None, keep: Optional[torch.Tensor] = None,
+                     exclude: Optional[torch.Tensor] = None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The next k results after a cursor (score_topk_after): after = (vals [B], ids [B]) with GLOBAL ids -- tensors on
+        the index's device or Python numbers -- or None, the open cursor; q [B,d] or a single [d].  The last column of a page
+        is the cursor of the next one; (ceiling, -1) asks for the k best rows that score at most `ceiling`.  Exact at any
+        depth, one pass over the rows per call.  keep= and remove_ids compose as in tagged_search.  exclude= (int64 [B,E];
+        [E] with a 1-D q) takes biased_search's route: a cursor search for k + E, then the filter (tt_topk_exclude_ids); the
+        bound is k + E <= 64.  Always the exact kernel in its cursor mode, also on a screen=True index, whose fallback_flags
+        then read all ones as after tagged_search.  ValueError: k (+ E) > 64 -- pages() and deep_search() go deeper."""
+        if q.dim() == 1:
+            return _squeezed(self.search_after, q, k, after, keep, _exclude_row(exclude))
+        _need_cuda(q)
+        dev = self._cursor_device()
+        B = q.shape[0]
+        if exclude is not None:
+            exclude, kk = _check_exclude(exclude, B, k, dev)
+            if kk > AFTER_KMAX:
+                raise ValueError(f"a cursor search with an exclusion list runs for k + E = {kk} > {AFTER_KMAX}")
+            v, i = self.search_after(q, kk, after, keep)
+            return topk_exclude(v, i, exclude, k, out)
+        av, ai = _cursor(after, B, dev)
+        return self._search_after(q, k, av, ai, keep, out)
+
+    def pages(self, q: torch.Tensor, k: int, n_pages: Optional[int] = None, keep: Optional[torch.Tensor] = None):
+        """A generator of consecutive result pages (vals [B,k], idx [B,k]) of q, k <= 64 per page: the first is search_after's
+        under the open cursor, and each further page's cursor is the previous page's last column, taken on the device with
+        no host synchronisation.  One pass over the rows per page, however deep.  It stops after n_pages; with n_pages=None it
+        never stops by itself -- a query whose rows are used up yields (-inf, -1) tails from then on (the tail is a valid
+        cursor that returns nothing), and telling that takes a look at the values, which is the caller's to spend."""
+        after = None
+        n = 0
+        while n_pages is None or n < n_pages:
+            v, i = self.search_after(q, k, after, keep=keep)
+            yield v, i
+            after = (v[..., -1].clone(), i[..., -1].clone())
+            n += 1
+
+    def deep_search(self, q: torch.Tensor, k_total: int, keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The exact top-k_total at ANY depth (search() stops at k = 1024): ceil(k_total / 64) pages of 64 concatenated and cut
+        to k_total.  The cost is one pass over the rows per 64 results -- 16 passes where search(k = 1024) takes one to three,
+        so below 1024 search() is the call to make."""
+        if k_total < 1:
+            raise ValueError(f"k_total = {k_total} < 1")
+        got = list(self.pages(q, AFTER_KMAX, n_pages=(k_total + AFTER_KMAX - 1) // AFTER_KMAX, keep=keep))
+        return (torch.cat([v for v, _ in got], dim=-1)[..., :k_total].contiguous(),
+                torch.cat([i for _, i in got], dim=-1)[..., :k_total].contiguous())
 
 
 def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1047,7 +1173,7 @@ class _Screen:
                       idx.data_ptr(), flags.data_ptr(), *thr, ws.data_ptr(), ws.numel(), prof_events, _stream(q)))
 
 
-class BruteForceIndex:
+class BruteForceIndex(_CursorSearch):
     """A [N,d] fp32 document matrix resident in HBM (document_embeddings.npy layout, backend/main.py:125-138: row i <->
     documents[i]) with exact top-k search.
 
@@ -1267,6 +1393,21 @@ class BruteForceIndex:
         res = _biased_into(_f32c(q), self.docs, self._bias, keep, k, self.idx_offset, out)
         if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
             self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+        return res
+
+    def _cursor_device(self) -> torch.device:
+        return self.docs.device
+
+    def _search_after(self, q: torch.Tensor, k: int, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], out=None):
+        """search_after (_CursorSearch) of q [B,d] under a checked cursor: the exact kernel in its cursor mode over the rows."""
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        if q.shape[-1] != self.docs.shape[1]:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        res = _after_into(_f32c(q), self.docs, av, ai, keep, k, self.idx_offset, out)
+        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
+            self.fallback_flags = torch.ones((q.shape[0] + 31) // 32, dtype=torch.int32, device=self.docs.device)
         return res
 
     def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], want_idx: bool, what: str = "ids"):
@@ -1584,7 +1725,7 @@ class PendingSearch:
         return self._slot.out_v, self._slot.out_i
 
 
-class ShardedIndex:
+class ShardedIndex(_CursorSearch):
     """Row-sharded corpus: every rank holds rows [lo,hi) and the SAME queries; search =
     local top-k' (global indices) -> one all-gather (RCCL over xGMI) -> merge on every rank.  Result is identical on
     all ranks and identical to the single-GPU search for any world size (the global top-k is a subset of the union of
@@ -1906,6 +2047,31 @@ class ShardedIndex:
         sl.merged.record(cur)
         return sl.out_v.clone(), sl.out_i.clone()
 
+    def _cursor_device(self) -> torch.device:
+        return self._dev
+
+    def _search_after(self, q: torch.Tensor, k: int, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], out=None):
+        """search_after (_CursorSearch) over the job: q and the cursor are the same on every rank -- a global (score, id) cursor
+        means the same on every shard, whichever shard its document lives on.  The local cursor search runs for
+        max(k, shard_k) (<= 64: ValueError above), then the usual all-gather and merge on the caller's stream; no seed exchange
+        is involved.  A COLLECTIVE like every search of this class, and so are pages(), deep_search() and
+        mine_hard_negatives over it.  keep: as in search()."""
+        kp = max(k, self.shard_k)
+        if not 1 <= k or kp > AFTER_KMAX:
+            raise ValueError(f"a cursor search answers 1 <= max(k, shard_k) <= {AFTER_KMAX}, got k = {k}, shard_k = {self.shard_k}")
+        sl = self._slot(q.shape[0], kp, k, 2)
+        cur = torch.cuda.current_stream(sl.send.device)
+        cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
+        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
+        self._index._search_after(q, kp, av, ai, keep, (sl.send_v, sl.send_i))
+        self._exchange_merge(sl, q.shape[0], kp, k)
+        sl.merged.record(cur)
+        if out is not None:
+            out[0].copy_(sl.out_v)
+            out[1].copy_(sl.out_i)
+            return out
+        return sl.out_v.clone(), sl.out_i.clone()
+
     def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """float32 [B,C] ([C] for a single query), identical on every rank: the exact dense score of every id of ids int64
         [B,C] (GLOBAL ids, the same on every rank like q), -inf where the id is negative, beyond the corpus, removed or not
@@ -2045,7 +2211,7 @@ class ShardedIndex:
         return PendingSearch(sl, self, exclude, k_out, shape, generation)
 
 
-class StreamedIndex:
+class StreamedIndex(_CursorSearch):
     """BASELINE configs[4]: a corpus kept as bf16 rows in (pinned) host DRAM and streamed through the GPU.
 
     search() walks the corpus in blocks: a copy stream moves block i+1 host -> device (hipMemcpyAsync from
@@ -2364,6 +2530,41 @@ class StreamedIndex:
         self._walk(visit)
         if not run:
             run = _out_pair(B, k, q.device)  # an empty corpus: padding only
+            run[0].fill_(float("-inf"))
+            run[1].fill_(-1)
+        if out is not None:
+            out[0].copy_(run[0])
+            out[1].copy_(run[1])
+            return out
+        return run[0], run[1]
+
+    def _cursor_device(self) -> torch.device:
+        return self.device
+
+    def _search_after(self, q: torch.Tensor, k: int, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], out=None):
+        """search_after (_CursorSearch) over the streamed rows: every block runs the exact kernel in its cursor mode under
+        the same global cursor (and its slice of the ANDed keep-bitmask, if any), and the blocks' lists are merged as in
+        search().  A keep-bitmask needs whole words per block, as in search()."""
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        if not 1 <= k <= AFTER_KMAX:
+            raise ValueError(f"a cursor search answers 1 <= k <= {AFTER_KMAX} per call, got k = {k}")
+        q = _f32c(q)
+        keep = _and_keep(self._keep, keep, self.N, self.device)
+        if keep is not None and self.block % 32 and self.N > self.block:
+            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
+        run = []  # the running top-k: (values, indices)
+
+        def visit(s, lo, n):
+            v, i = _after_into(q, self._d32[s][:n], av, ai, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k,
+                               self.idx_offset + lo)
+            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+
+        self._walk(visit)
+        if not run:
+            run = _out_pair(q.shape[0], k, q.device)  # an empty corpus: padding only
             run[0].fill_(float("-inf"))
             run[1].fill_(-1)
         if out is not None:
