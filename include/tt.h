@@ -932,6 +932,33 @@ int tt_contrastive_loss_grouped_f32(const float *q /*[B,H]*/, int B, const float
                                     size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The same softmax against SOFT TARGETS: a weight t_ij per (query, document) pair in place of the one positive per query
+ * (distillation from a teacher's distribution over the pool; several positives of a query at 1/|P_i| each).  targets [B,M] f32,
+ * row-major, contiguous, device; qh, Dh, s_ij and eps as tt_contrastive_loss_f32; there is no pos_offset:
+ *   w_i  = sum_{j<M} t_ij                 lse_i = logsumexp_{j<M} s_ij
+ *   loss = mean_{i<B} (w_i lse_i - sum_j t_ij s_ij)          (= mean_i sum_j t_ij (lse_i - s_ij): the cross-entropy of row i's
+ *                                                             softmax p_i against t_i)
+ *   d loss / d s_ij = (w_i exp(s_ij - lse_i) - t_ij) / B
+ * loss [1]; dq [B,H], ddocs [M,H] through the norms (both or none, nullable; without them only the loss is written, the same
+ * bits as with them).  Targets are any finite f32: rows need not sum to 1, a negative weight is a linear term; non-finite
+ * targets give unspecified values, never an access out of bounds.  For a probability row the row loss is KL(t_i || p_i) + H(t_i);
+ * the entropy has no gradient and is the caller's to subtract where KL is reported.
+ * Exact: (1) with t_ij = 1 at j = pos_offset + i and +0.0f elsewhere, loss, dq and ddocs are the bits of
+ * tt_contrastive_loss_f32(..., pos_offset, ...), with and without gradients; (2) a query whose target row is all zeros has row
+ * loss exactly 0, an all-zero dq row, and adds nothing to any ddocs row.
+ * 1 <= B <= 2^24, B <= M <= 2^25, 1 <= H <= 512; temperature finite and > 0; element i M + j is addressed in 64 bits (B M may
+ * pass 2^32).  Deterministic: no atomics, every sum in one fixed order that depends on (B, M, H) alone, whatever the workspace
+ * and the outputs held on entry.  Writes nothing but loss, dq, ddocs and the workspace.
+ * workspace: tt_contrastive_loss_soft_workspace_bytes(B, M, H) bytes (0 for a shape the call refuses; no GPU needed): the plan
+ * of tt_contrastive_loss_workspace_bytes plus the per-slice sums of t and t s and w [B]; 16-byte aligned, caller-owned.
+ * Asynchronous on `stream`; capture-clean.  Refusals are TT_ERR_BAD_SHAPE, a null `targets` among them.
+ */
+size_t tt_contrastive_loss_soft_workspace_bytes(int B, int M, int H);
+int tt_contrastive_loss_soft_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H,
+                                 const float *targets /*[B,M]*/, float temperature, float *loss /*[1]*/, float *dq /*[B,H]*/,
+                                 float *ddocs /*[M,H]*/, void *workspace, size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

@@ -138,7 +138,9 @@ SIGNATURES = {
     "tt_contrastive_loss_workspace_bytes": (_sz, [_i, _i, _i]),
     "tt_contrastive_loss_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tt_contrastive_loss_grouped_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "tt_allgather_topk": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tt_contrastive_loss_soft_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tt_contrastive_loss_soft_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tt_allgather_topk":(_i, [_vp, _vp, _vp, _sz, _vp]),
     "tt_allreduce_grads": (_i, [_vp, _vp, _i64, _vp]),
     "tt_comm_library": (C.c_char_p, []),
     "tt_comm_unique_id": (_i, [_vp]),

@@ -15,6 +15,17 @@
 // lse_i = s_{i,pos} + log(1): row loss 0.0f and G row exp(0) - 1 = 0.  The ungrouped instantiations read no label and keep their
 // arithmetic and order.
 //
+// Soft targets (tt_contrastive_loss_soft_f32, the SOFT instantiations; never together with GROUPED): f32 weights t [B][M] in
+// place of the one positive per query,
+//   w_i = sum_j t_ij     loss = mean_i (w_i lse_i - sum_j t_ij s_ij)     d loss / d s_ij = (w_i exp(s_ij - lse_i) - t_ij) / B
+// the cross-entropy of the row softmax against t_i.  The softmax statistics are the plain instantiation's, statement for
+// statement; beside them a lane sums tw += t and ts = fmaf(t, s, ts) over its documents in the same order (16 per tile in
+// register order, tiles ascending, the 8 partials of a query in wave * 2 + half order, slices ascending).  A one-hot row gives
+// w = 1.0f and ts = s_pos exactly (zeros leave an fmaf chain where it is), so w lse - ts and w e - t are the pooled entry's
+// lse - s_pos and e - onehot bit for bit; an all-zero row gives 0 lse - 0 and (0 e - 0) scale: nothing.  Targets are loaded
+// like the labels -- unconditionally, at indices clamped into [0, B) x [0, M), element i M + j addressed in 64 bits -- and a pair
+// past the end selects 0.
+//
 // Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
 //   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
 //   2 ib_stats_kernel    a workgroup per (32 queries, slice of the documents): S^T tiles on v_mfma_f32_32x32x2_f32, online
@@ -61,9 +72,10 @@ struct IBPlan {
     int Hp, Bq, Dp;   // image width (H up to a multiple of 32), image heights (B, M up to multiples of IB_CHUNK)
     IBSlices sq, sd;  // slices of the documents a query tile walks / of the queries a document tile walks
     size_t qh, dh, den, flag, lse, rows, pm, pl, pos, part_q, part_d, total;
+    size_t pw, pt, w;  // soft targets only, behind everything else
 };
 
-IBPlan ib_plan(int B, int M, int H)
+IBPlan ib_plan(int B, int M, int H, bool soft = false)
 {
     IBPlan P;
     P.Hp = (H + 31) / 32 * 32;
@@ -83,6 +95,12 @@ IBPlan ib_plan(int B, int M, int H)
     P.pos = w.take(sizeof(float) * (size_t)P.Bq);          // s_{i, pos_offset + i}
     P.part_q = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq * P.Hp);  // per slice: partial dqh [Bq][Hp], dDh [Dp][Hp]
     P.part_d = w.take(sizeof(float) * (size_t)P.sd.n * P.Dp * P.Hp);
+    P.pw = P.pt = P.w = 0;
+    if (soft) {  // (appended: the offsets above are the plain plan's)
+        P.pw = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);  // per (slice, query): sum of the targets, sum of target * score
+        P.pt = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);
+        P.w = w.take(sizeof(float) * (size_t)P.Bq);            // w_i, padded like lse
+    }
     P.total = w.off;
     return P;
 }
@@ -193,6 +211,23 @@ __device__ __forceinline__ void ib_labels(const int64_t *__restrict__ g, int y0,
     }
 }
 
+// The targets t[i][y0 + rho(r) + 4 * half] (ALONG: the lane's own query i, 16 documents: row stride M between lanes) or
+// t[y0 + rho(r) + 4 * half][j] (!ALONG: 16 queries, the lane's own document j: consecutive lanes, consecutive addresses).  Like
+// ib_labels: both indices clamped into the array, every load in bounds and unconditional; what a pair past the end loads is
+// replaced by 0 where it is used.  The element index is formed in 64 bits (B * M passes 2^32).
+template <bool ALONG>
+__device__ __forceinline__ void ib_targets(const float *__restrict__ t, int own, int n_own, int y0, int half, int n_oth, int M,
+                                           float (&out)[16])
+{
+    const size_t fixed = (size_t)(own < n_own ? own : n_own - 1);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int y = y0 + ib_rho(r) + 4 * half;
+        const size_t yc = (size_t)(y < n_oth ? y : n_oth - 1);
+        out[r] = ALONG ? t[fixed * (size_t)M + yc] : t[yc * (size_t)M + fixed];
+    }
+}
+
 // ------------------------------------------------------------------ 2: row statistics
 // Workgroup = 32 queries (on the lanes) x slice blockIdx.y of the documents; wave w takes the 32-document tiles w, w + 4, ... of
 // the slice.  Each lane keeps a running maximum and a sum of exponentials over the documents it sees; the 8 partials of a
@@ -201,14 +236,18 @@ __device__ __forceinline__ void ib_labels(const int64_t *__restrict__ g, int y0,
 // query: its partials are (-inf, 0), the combine below skips them (part_l > 0) and the slice's pair is (-inf, 0).
 // GROUPED: the lane loads its query's label once and, per tile, the labels of its 16 documents behind the first operands of the
 // products (ib_scores: after_first), so that they arrive behind the MFMAs.
-template <bool GROUPED>
+// SOFT: the lane loads the 16 targets of its query's row in the same place and sums (t, t * s) beside (max, sum exp): per lane
+// in register order, tiles ascending; the 8 partials of a query in the order of the combine below; pos[] is not written.
+template <bool GROUPED, bool SOFT>
 __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
                                                        const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B, int M,
                                                        int pos_offset, int Hp, int Bq, int tiles_per_slice, float temperature,
                                                        float *__restrict__ pm, float *__restrict__ pl,
-                                                       float *__restrict__ pos)
+                                                       float *__restrict__ pos, const float *__restrict__ tg,
+                                                       float *__restrict__ pw, float *__restrict__ pt)
 {
     __shared__ float part_m[8][IB_TILE], part_l[8][IB_TILE];
+    __shared__ float part_w[SOFT ? 8 : 1][IB_TILE], part_t[SOFT ? 8 : 1][IB_TILE];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5;
     const int i0 = blockIdx.x * IB_TILE, i = i0 + (lane & 31);
     const int ND = M;
@@ -219,11 +258,14 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     if (GROUPED)
         own_g = qg[i < B ? i : B - 1];  // (a lane past B: any label, its statistics are not written)
     const bool grouped_q = own_g >= 0;
+    float tw = 0.0f, ts = 0.0f, tv[16];
     for (int t = t_begin + wave; t < n_tiles; t += 4) {
         const int j0 = t * IB_TILE;
         const f32x16 acc = ib_scores(dh, j0, qh, i0, Hp, lane, [&] {
             if (GROUPED)
                 ib_labels(dg, j0, half, ND, oth_g);
+            if (SOFT)
+                ib_targets<true>(tg, i, B, j0, half, ND, M, tv);
         });
         float x[16], tm = -INFINITY;
         bool keep[16];
@@ -236,8 +278,13 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
                 keep[r] = keep[r] & !(grouped_q & (oth_g[r] == own_g) & (j != i + pos_offset));
             if (keep[r])
                 tm = fmaxf(tm, x[r]);
-            if (j == i + pos_offset && i < B)
+            if (!SOFT && j == i + pos_offset && i < B)
                 pos[i] = x[r];  // (one lane of one wave of one slice, once)
+            if (SOFT) {  // (a document past M: weight 0, and its score is that of a zero row: finite)
+                const float tr = j < ND ? tv[r] : 0.0f;
+                tw += tr;
+                ts = fmaf(tr, x[r], ts);
+            }
         }
         if (tm > -INFINITY) {  // (some document of the tile is valid, and kept, for this lane)
             const float mn = fmaxf(m, tm);
@@ -252,6 +299,10 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     }
     part_m[wave * 2 + half][lane & 31] = m;
     part_l[wave * 2 + half][lane & 31] = l;
+    if (SOFT) {
+        part_w[wave * 2 + half][lane & 31] = tw;
+        part_t[wave * 2 + half][lane & 31] = ts;
+    }
     __syncthreads();
     if (threadIdx.x < IB_TILE && i0 + (int)threadIdx.x < B) {
         const int c = threadIdx.x;
@@ -264,15 +315,30 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
                 L += part_l[k][c] * expf(part_m[k][c] - M);
         pm[(size_t)blockIdx.y * Bq + i0 + c] = M;
         pl[(size_t)blockIdx.y * Bq + i0 + c] = L;
+        if (SOFT) {
+            float W = 0.0f, T = 0.0f;
+            for (int k = 0; k < 8; ++k) {
+                W += part_w[k][c];
+                T += part_t[k][c];
+            }
+            pw[(size_t)blockIdx.y * Bq + i0 + c] = W;
+            pt[(size_t)blockIdx.y * Bq + i0 + c] = T;
+        }
     }
 }
 
 // The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.  The slice of the
 // positive has a finite maximum, so M is finite; a slice that is empty for the query (grouped labels) comes as (-inf, 0) and
 // adds 0 * exp(-inf - M) = 0 * 0.
+// SOFT: the slices' (sum t, sum t s) in the same ascending order -> w_i and the row's loss
+// w_i lse_i - sum_j t_ij s_ij; pos is not read.  (One-hot targets: w = 1.0f and the sum is s_pos, so this is lse - s_pos whether
+// or not the product is fused into the subtraction.)
+template <bool SOFT>
 __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ pm, const float *__restrict__ pl,
                                                      const float *__restrict__ pos, int B, int Bq, int n_slices,
-                                                     float *__restrict__ lse, float *__restrict__ row_loss)
+                                                     float *__restrict__ lse, float *__restrict__ row_loss,
+                                                     const float *__restrict__ pw, const float *__restrict__ pt,
+                                                     float *__restrict__ w)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B)
@@ -294,6 +360,16 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
             L += l[s] * expf(m[s] - M);
     const float v = M + logf(L);
     lse[i] = v;
+    if (SOFT) {
+        float W = 0.0f, T = 0.0f;
+        for (int s = 0; s < n_slices; ++s) {
+            W += pw[(size_t)s * Bq + i];
+            T += pt[(size_t)s * Bq + i];
+        }
+        w[i] = W;
+        row_loss[i] = W * v - T;
+        return;
+    }
     row_loss[i] = v - pos[i];
 }
 
@@ -306,10 +382,14 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
 // The epilogue turns the [h][owner] accumulators into rows through LDS and stores the slice's partial [32][Hp] coalesced.
 // GROUPED: G = 0 for an ignored pair, on either side; the owner row's label is loaded once, the walked rows' labels per tile
 // behind the lse loads and the first operands of the products (ib_scores: after_first).
-template <bool QOWN, bool GROUPED>
+// SOFT: G = (w_i exp(s - lse_i) - t_ij) scale.  w is fetched with lse (the owner's once, the walked queries' per tile; w[] is
+// padded like lse[]); the 16 targets of a tile are loaded where the labels are: along the own query's row on the query-owned
+// side, down the own document's column (coalesced over the lanes) on the document-owned side.
+template <bool QOWN, bool GROUPED, bool SOFT>
 __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restrict__ qh, const float *__restrict__ dh,
                                              const float *__restrict__ lse, const int64_t *__restrict__ qg,
-                                             const int64_t *__restrict__ dg, int B, int M, int pos_offset, int Hp,
+                                             const int64_t *__restrict__ dg, const float *__restrict__ tg,
+                                             const float *__restrict__ wq, int B, int M, int pos_offset, int Hp,
                                              float temperature, int tile, int chunk_begin, int chunk_end,
                                              float *__restrict__ part)
 {
@@ -321,6 +401,7 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
     const int NT = Hp / 32;
     const float scale = 1.0f / ((float)B * temperature);
     const float lse_own = (QOWN && o < B) ? lse[o] : 0.0f;
+    const float w_own = (SOFT && QOWN && o < B) ? wq[o] : 0.0f;
     const int n_own = QOWN ? B : M;
     int64_t own_g = -1, oth_g[16];
     if (GROUPED)
@@ -332,13 +413,19 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
         if (y0 < n_oth) {  // (wave-uniform; a tile wholly past the end stores zeros)
             // the walked queries' lse, asked for before the products so that they arrive behind them (entries past B hold
             // anything and are not used; the array is padded like the images)
-            float ls_y[16];
+            float ls_y[16], w_y[16], tv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ls_y[r] = QOWN ? lse_own : lse[y0 + ib_rho(r) + 4 * half];
+            if (SOFT)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    w_y[r] = QOWN ? w_own : wq[y0 + ib_rho(r) + 4 * half];
             const f32x16 acc = ib_scores(oth, y0, own, own0, Hp, lane, [&] {
                 if (GROUPED)
                     ib_labels(QOWN ? dg : qg, y0, half, n_oth, oth_g);
+                if (SOFT)
+                    ib_targets<QOWN>(tg, o, n_own, y0, half, n_oth, M, tv);
             });
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -347,7 +434,10 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
                 float v = 0.0f;
                 if (iq < B && jd < M) {
                     const float ls = ls_y[r];
-                    v = (expf(acc[r] / temperature - ls) - (jd == iq + pos_offset ? 1.0f : 0.0f)) * scale;
+                    if (SOFT)
+                        v = (w_y[r] * expf(acc[r] / temperature - ls) - tv[r]) * scale;
+                    else
+                        v = (expf(acc[r] / temperature - ls) - (jd == iq + pos_offset ? 1.0f : 0.0f)) * scale;
                     if (GROUPED) {
                         const int64_t gq = QOWN ? own_g : oth_g[r], gd = QOWN ? oth_g[r] : own_g;
                         v = ((gq >= 0) & (gd == gq) & (jd != iq + pos_offset)) ? 0.0f : v;  // (bitwise: a select, no branch)
@@ -416,25 +506,26 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
 }
 
 // Blocks [0, tiles_q * slices_q): query tiles (block = slice * tiles_q + tile); the rest: document tiles, the same way.
-template <bool GROUPED>
+template <bool GROUPED, bool SOFT>
 __global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
                                                       const float *__restrict__ lse, const int64_t *__restrict__ qg,
                                                       const int64_t *__restrict__ dg, int B, int M, int pos_offset, int Hp,
                                                       int Bq, int Dp, float temperature, int tiles_q, int slices_q, int per_q, int tiles_d,
-                                                      int per_d, float *__restrict__ part_q, float *__restrict__ part_d)
+                                                      int per_d, float *__restrict__ part_q, float *__restrict__ part_d,
+                                                      const float *__restrict__ tg, const float *__restrict__ wq)
 {
     extern __shared__ __attribute__((aligned(16))) float ib_lds[];  // G [128][32], later the gradient tile [32][Hp]
     int b = blockIdx.x;
     if (b < tiles_q * slices_q) {
         const int slice = b / tiles_q, chunks = (M + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
-        ib_grad_body<true, GROUPED>(ib_lds, qh, dh, lse, qg, dg, B, M, pos_offset, Hp, temperature, b % tiles_q, slice * per_q,
+        ib_grad_body<true, GROUPED, SOFT>(ib_lds, qh, dh, lse, qg, dg, tg, wq, B, M, pos_offset, Hp, temperature, b % tiles_q, slice * per_q,
                                     end, part_q + (size_t)slice * Bq * Hp);
     } else {
         b -= tiles_q * slices_q;
         const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
         const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
-        ib_grad_body<false, GROUPED>(ib_lds, qh, dh, lse, qg, dg, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d,
+        ib_grad_body<false, GROUPED, SOFT>(ib_lds, qh, dh, lse, qg, dg, tg, wq, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d,
                                      end, part_d + (size_t)slice * Dp * Hp);
     }
 }
@@ -512,9 +603,11 @@ __global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ 
 }
 
 // The launches of one call; the entries have refused what they refuse.  dd.lo == nullptr: the loss only.  qg == nullptr: no
-// labels (the ungrouped instantiations); else qg [B], dg [M].
+// labels (the ungrouped instantiations); else qg [B], dg [M].  tg != nullptr: soft targets [B][M] (P is the soft plan, no labels,
+// pos_offset unused).
 void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, int pos_offset, const int64_t *qg,
-               const int64_t *dg, float temperature, float *loss, float *dq, IBDocGrads dd, void *workspace, hipStream_t st)
+               const int64_t *dg, const float *tg, float temperature, float *loss, float *dq, IBDocGrads dd, void *workspace,
+               hipStream_t st)
 {
     char *ws = (char *)workspace;
     float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
@@ -524,18 +617,20 @@ void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H
     float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
     float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
     const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
-    const auto stats_kernel = qg ? ib_stats_kernel<true> : ib_stats_kernel<false>;
-    const auto grad_kernel = qg ? ib_grad_kernel<true> : ib_grad_kernel<false>;
-    hipLaunchKernelGGL(stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
-                       P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos);
-    hipLaunchKernelGGL(ib_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
-                       (const float *)pos, B, P.Bq, P.sq.n, lse, rows);
+    float *pw = tg ? (float *)(ws + P.pw) : nullptr, *pt = tg ? (float *)(ws + P.pt) : nullptr;
+    float *wq = tg ? (float *)(ws + P.w) : nullptr;
+    const auto stats_kernel = tg ? ib_stats_kernel<false, true> : qg ? ib_stats_kernel<true, false> : ib_stats_kernel<false, false>;
+    const auto grad_kernel = tg ? ib_grad_kernel<false, true> : qg ? ib_grad_kernel<true, false> : ib_grad_kernel<false, false>;
+    hipLaunchKernelGGL(stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M,
+                       pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos, tg, pw, pt);
+    hipLaunchKernelGGL(tg ? ib_lse_kernel<true> : ib_lse_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
+                       (const float *)pos, B, P.Bq, P.sq.n, lse, rows, (const float *)pw, (const float *)pt, wq);
     hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
     if (dq) {
         const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
         const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
         hipLaunchKernelGGL(grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, qg, dg, B, M, pos_offset,
-                           P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d);
+                           P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d, tg, (const float *)wq);
         hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
                            (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
                            (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dd);
@@ -573,7 +668,7 @@ TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *
     if (workspace_bytes < P.total)
         return tt_fail(TT_ERR_BAD_SHAPE, "tt_in_batch_loss_f32: workspace %zu < %zu bytes", workspace_bytes, P.total);
     // D = [p; n]: the pool of M = 2B documents in two pieces, the positive of query i in row i
-    ib_launch(P, q, IBDocs{p, n, B}, B, 2 * B, H, 0, nullptr, nullptr, temperature, loss, dq, IBDocGrads{dp, dn, B}, workspace,
+    ib_launch(P, q, IBDocs{p, n, B}, B, 2 * B, H, 0, nullptr, nullptr, nullptr, temperature, loss, dq, IBDocGrads{dp, dn, B}, workspace,
               (hipStream_t)stream);
     TT_LAUNCH_CHECK();
     return TT_OK;
@@ -581,9 +676,10 @@ TT_EXPORT int tt_in_batch_loss_f32(const float *q, const float *p, const float *
 
 namespace {
 
-// The pool entries behind their names: `who` opens every message; grouped: the call brings labels (both non-null).
-int ib_pool_call(const char *who, bool grouped, const float *q, int B, const float *docs, int M, int H, int pos_offset,
-                 const int64_t *q_groups, const int64_t *doc_groups, float temperature, float *loss, float *dq, float *ddocs,
+// The pool entries behind their names: `who` opens every message; grouped: the call brings labels (both non-null); soft: it
+// brings targets [B][M] (non-null), no labels, and pos_offset 0.
+int ib_pool_call(const char *who, bool grouped, bool soft, const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                 const int64_t *q_groups, const int64_t *doc_groups, const float *targets, float temperature, float *loss, float *dq, float *ddocs,
                  void *workspace, size_t workspace_bytes, tt_stream_t stream)
 {
     if (!ib_shape_ok(B, M, H))
@@ -593,17 +689,17 @@ int ib_pool_call(const char *who, bool grouped, const float *q, int B, const flo
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: pos_offset=%d outside [0, M - B = %d]", who, pos_offset, M - B);
     if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: temperature=%g must be finite and > 0", who, (double)temperature);
-    if (!q || !docs || !loss || !workspace || (grouped && (!q_groups || !doc_groups)))
+    if (!q || !docs || !loss || !workspace || (grouped && (!q_groups || !doc_groups)) || (soft && !targets))
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
     if (!dq != !ddocs)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: dq, ddocs must be both null or both non-null", who);
     if ((uintptr_t)workspace & 15)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: the workspace must be 16-byte aligned", who);
-    const IBPlan P = ib_plan(B, M, H);
+    const IBPlan P = ib_plan(B, M, H, soft);
     if (workspace_bytes < P.total)
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
     ib_launch(P, q, IBDocs{docs, nullptr, M}, B, M, H, pos_offset, grouped ? q_groups : nullptr, grouped ? doc_groups : nullptr,
-              temperature, loss, dq, IBDocGrads{ddocs, nullptr, M}, workspace, (hipStream_t)stream);
+              soft ? targets : nullptr, temperature, loss, dq, IBDocGrads{ddocs, nullptr, M}, workspace, (hipStream_t)stream);
     TT_LAUNCH_CHECK();
     return TT_OK;
 }
@@ -619,7 +715,7 @@ TT_EXPORT int tt_contrastive_loss_f32(const float *q, int B, const float *docs, 
                                       float *loss, float *dq, float *ddocs, void *workspace, size_t workspace_bytes,
                                       tt_stream_t stream)
 {
-    return ib_pool_call("tt_contrastive_loss_f32", false, q, B, docs, M, H, pos_offset, nullptr, nullptr, temperature, loss, dq,
+    return ib_pool_call("tt_contrastive_loss_f32", false, false, q, B, docs, M, H, pos_offset, nullptr, nullptr, nullptr, temperature, loss, dq,
                         ddocs, workspace, workspace_bytes, stream);
 }
 
@@ -627,6 +723,19 @@ TT_EXPORT int tt_contrastive_loss_grouped_f32(const float *q, int B, const float
                                               const int64_t *q_groups, const int64_t *doc_groups, float temperature, float *loss,
                                               float *dq, float *ddocs, void *workspace, size_t workspace_bytes, tt_stream_t stream)
 {
-    return ib_pool_call("tt_contrastive_loss_grouped_f32", true, q, B, docs, M, H, pos_offset, q_groups, doc_groups, temperature,
+    return ib_pool_call("tt_contrastive_loss_grouped_f32", true, false, q, B, docs, M, H, pos_offset, q_groups, doc_groups, nullptr, temperature,
+                        loss, dq, ddocs, workspace, workspace_bytes, stream);
+}
+
+TT_EXPORT size_t tt_contrastive_loss_soft_workspace_bytes(int B, int M, int H)
+{
+    return ib_shape_ok(B, M, H) ? ib_plan(B, M, H, true).total : 0;
+}
+
+TT_EXPORT int tt_contrastive_loss_soft_f32(const float *q, int B, const float *docs, int M, int H, const float *targets,
+                                           float temperature, float *loss, float *dq, float *ddocs, void *workspace,
+                                           size_t workspace_bytes, tt_stream_t stream)
+{
+    return ib_pool_call("tt_contrastive_loss_soft_f32", false, true, q, B, docs, M, H, 0, nullptr, nullptr, targets, temperature,
                         loss, dq, ddocs, workspace, workspace_bytes, stream);
 }

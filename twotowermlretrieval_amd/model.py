@@ -9,6 +9,8 @@
     contrastive_softmax_loss(q, docs, pos_offset=0, temperature=0.05) -> 0-d tensor      (the same over any pool of documents)
     ... both with group labels (groups=, neg_groups= / q_groups=, doc_groups=): a passage that carries a query's label, other
     than its own positive, is no negative of it
+    soft_contrastive_loss(q, docs, targets, temperature=0.05) -> 0-d tensor              (the same softmax against a weight per pair:
+    distillation_targets(teacher_scores, ...), multi_positive_targets(q_groups, doc_groups, pos_offset) make the weights)
 
 Same constructor arguments, attribute names (`query_encoder.embedding.embedding_dim` is read by
 backend/main.py:104) and state_dict keys ({query,doc}_encoder.{embedding.weight,
@@ -30,7 +32,8 @@ import torch.nn as nn
 
 from . import _lib
 
-__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "SplitRecurrenceTimeout"]
+__all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "soft_contrastive_loss",
+           "distillation_targets", "multi_positive_targets", "SplitRecurrenceTimeout"]
 
 
 class SplitRecurrenceTimeout(RuntimeError):
@@ -667,3 +670,113 @@ def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: in
     q_groups = _group_labels("contrastive_softmax_loss", "q_groups", q_groups, B, q.device)
     doc_groups = _group_labels("contrastive_softmax_loss", "doc_groups", doc_groups, M, q.device)
     return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature), q_groups, doc_groups)
+
+
+def soft_contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
+    """An uninitialised workspace for tt_contrastive_loss_soft_f32 at q [B,H], docs [M,H] (the call rewrites all of it that it reads)."""
+    need = _lib.lib().tt_contrastive_loss_soft_workspace_bytes(B, M, H)
+    if need == 0:
+        raise ValueError(f"soft_contrastive_loss: B={B} M={M} H={H} (1 <= B <= M <= 2^25, B <= 2^24, 1 <= H <= 512)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+class _SoftContrastiveFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, docs, targets, temperature: float):
+        L = _lib.lib()
+        q, docs, targets = q.contiguous(), docs.contiguous(), targets.contiguous()
+        (B, H), M = q.shape, docs.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        dq, ddocs = torch.empty_like(q), torch.empty_like(docs)
+        ws = soft_contrastive_workspace(B, M, H, q.device)
+        with torch.cuda.device(q.device):
+            _lib.check(L.tt_contrastive_loss_soft_f32(q.data_ptr(), B, docs.data_ptr(), M, H, targets.data_ptr(), float(temperature),
+                                                      loss.data_ptr(), dq.data_ptr(), ddocs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _stream(q.device)))
+        ctx.save_for_backward(dq, ddocs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, ddocs = ctx.saved_tensors
+        return g * dq, g * ddocs, None, None
+
+
+def _soft_targets(who: str, t, B: int, M: int, device) -> torch.Tensor:
+    """`t` as the targets of B queries over M documents, or the ValueError that names the argument."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, M) or t.device != device:
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: targets must be a float32 tensor [{B}, {M}] on {device}, got {got}")
+    return t
+
+
+def soft_contrastive_loss(q: torch.Tensor, docs: torch.Tensor, targets: torch.Tensor, temperature: float = 0.05) -> torch.Tensor:
+    """The softmax loss of B queries over a pool of M >= B documents against SOFT TARGETS t [B,M] (float32 on q's device):
+    mean_i(w_i logsumexp_j s_ij - sum_j t_ij s_ij), w_i = sum_j t_ij, s_ij = cos(q_i, docs_j) / temperature -- the cross-entropy
+    of each query's softmax over the pool against its target row.  distillation_targets makes the rows from a teacher's scores,
+    multi_positive_targets from group labels.  Rows need not sum to 1 and weights may be negative (any finite float32).
+    For a probability row t_i the row loss is KL(t_i || p_i) + H(t_i): the entropy H(t_i) has no gradient and is not subtracted
+    here; subtract it where KL itself is reported.
+    One-hot targets (1 at pos_offset + i) give contrastive_softmax_loss(q, docs, pos_offset), bit for bit; an all-zero row
+    gives that query no loss and no gradient.  Differentiable in q and docs, not in targets (fused forward + gradient kernels
+    on the f32 matrix pipe, deterministic; [B,M] logits never reach memory)."""
+    for t in (q, docs):
+        if not t.is_cuda:
+            raise RuntimeError("soft_contrastive_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError("soft_contrastive_loss wants float32 q [B,H] and docs [M,H]")
+    (B, H), M = q.shape, docs.shape[0]
+    if docs.shape[1] != H:
+        raise ValueError(f"soft_contrastive_loss: q has H={H}, docs has H={docs.shape[1]}")
+    if M < B:
+        raise ValueError(f"soft_contrastive_loss: M={M} documents for B={B} queries (the pool entries want M >= B)")
+    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
+        raise ValueError(f"soft_contrastive_loss: temperature={temperature!r} must be finite and > 0")
+    targets = _soft_targets("soft_contrastive_loss", targets, B, M, q.device)
+    return _SoftContrastiveFn.apply(q, docs, targets.detach(), float(temperature))
+
+
+def distillation_targets(teacher_scores: torch.Tensor, teacher_temperature: float = 1.0,
+                         valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Targets for soft_contrastive_loss from a teacher's scores [B,M] (cross-encoder, BM25 / TF-IDF, an earlier checkpoint):
+    softmax(teacher_scores / teacher_temperature) over the pairs where `valid` (bool [B,M], default all) holds, 0 elsewhere; a
+    row with no valid pair is all zeros (that query then has no loss and no gradient).  float32 [B,M] on the scores' device;
+    stock torch ops, any device."""
+    if not isinstance(teacher_scores, torch.Tensor) or teacher_scores.dim() != 2 or not teacher_scores.is_floating_point():
+        got = f"{teacher_scores.dtype} {tuple(teacher_scores.shape)}" if isinstance(teacher_scores, torch.Tensor) else type(teacher_scores).__name__
+        raise ValueError(f"distillation_targets: teacher_scores must be a floating-point tensor [B,M], got {got}")
+    if not 0.0 < float(teacher_temperature) < float("inf"):
+        raise ValueError(f"distillation_targets: teacher_temperature={teacher_temperature!r} must be finite and > 0")
+    z = teacher_scores.detach().to(torch.float32) / float(teacher_temperature)
+    if valid is None:
+        return torch.softmax(z, dim=1)
+    if (not isinstance(valid, torch.Tensor) or valid.dtype != torch.bool or valid.shape != teacher_scores.shape
+            or valid.device != teacher_scores.device):
+        got = f"{valid.dtype} {tuple(valid.shape)} on {valid.device}" if isinstance(valid, torch.Tensor) else type(valid).__name__
+        raise ValueError(f"distillation_targets: valid must be a bool tensor {tuple(teacher_scores.shape)} on "
+                         f"{teacher_scores.device}, got {got}")
+    some = valid.any(dim=1, keepdim=True)
+    # (a row without a valid pair: softmax of all -inf would be NaN; it is scored as it lies and zeroed)
+    t = torch.softmax(z.masked_fill(~valid & some, float("-inf")), dim=1)
+    return torch.where(valid, t, torch.zeros_like(t))
+
+
+def multi_positive_targets(q_groups: torch.Tensor, doc_groups: torch.Tensor, pos_offset: int = 0) -> torch.Tensor:
+    """Targets for soft_contrastive_loss that pull a query towards ALL its positives in the pool (the SupCon / multi-label form):
+    1/|P_i| on each j in P_i = {j : q_groups[i] >= 0 and doc_groups[j] == q_groups[i]} + {pos_offset + i}, 0 elsewhere.  Labels
+    as contrastive_softmax_loss takes them: int64 q_groups [B], doc_groups [M] on one device, a negative label is "no group".
+    P_i is the own positive plus exactly the rows that grouped negatives would leave out.  float32 [B,M]; stock torch ops."""
+    if not isinstance(q_groups, torch.Tensor) or q_groups.dim() != 1:
+        raise ValueError(f"multi_positive_targets: q_groups must be an int64 tensor [B], got {type(q_groups).__name__}")
+    B = q_groups.shape[0]
+    q_groups = _group_labels("multi_positive_targets", "q_groups", q_groups, B, q_groups.device)
+    if not isinstance(doc_groups, torch.Tensor) or doc_groups.dim() != 1:
+        raise ValueError(f"multi_positive_targets: doc_groups must be an int64 tensor [M], got {type(doc_groups).__name__}")
+    M = doc_groups.shape[0]
+    doc_groups = _group_labels("multi_positive_targets", "doc_groups", doc_groups, M, q_groups.device)
+    if M < B or not 0 <= pos_offset <= M - B:
+        raise ValueError(f"multi_positive_targets: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
+    member = (q_groups[:, None] >= 0) & (doc_groups[None, :] == q_groups[:, None])
+    i = torch.arange(B, device=q_groups.device)
+    member[i, pos_offset + i] = True
+    return member.to(torch.float32) / member.sum(dim=1, keepdim=True).to(torch.float32)

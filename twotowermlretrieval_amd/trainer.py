@@ -25,8 +25,9 @@ import torch
 
 from . import _lib
 from .collective import Collective
-from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, contrastive_softmax_loss,
-                    contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, triplet_loss_cosine)
+from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, _soft_targets, contrastive_softmax_loss,
+                    contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, soft_contrastive_loss,
+                    soft_contrastive_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -346,6 +347,25 @@ def _batch_labels(who: str, spec: _StepSpec, batch, groups, neg_groups) -> Optio
     return torch.cat((groups, neg_groups))
 
 
+def _batch_targets(who: str, spec: _StepSpec, optimizer, batch, targets, groups=None, neg_groups=None) -> Optional[torch.Tensor]:
+    """The batch's soft targets: float32 [B, 2B] over the passages [p; n] -- gathered, [B, world * 2B] over the pool of all ranks,
+    rank r's [p_r; n_r] at column r * 2B -- or None without targets.  Data of the batch like the labels: they travel beside it.
+    Raises the ValueError of targets no step can use before anything is launched: they are for negatives="in_batch" alone and
+    never come together with group labels."""
+    if targets is None:
+        return None
+    if groups is not None or neg_groups is not None:
+        raise ValueError(f"{who}: targets and groups / neg_groups exclude each other (soft targets say what every pair weighs)")
+    if spec.negatives != "in_batch":
+        raise ValueError(f'{who}: targets need negatives="in_batch", got negatives={spec.negatives!r}')
+    queries, pos_docs, neg_docs = batch
+    B = queries.shape[0]
+    if not pos_docs.shape[0] == neg_docs.shape[0] == B:
+        raise ValueError(f"{who}: targets need as many negatives as positives as queries")
+    world = getattr(getattr(optimizer, "_coll", None), "world", 1) if spec.gather_negatives else 1
+    return _soft_targets(who, targets, B, world * 2 * B, queries.device)
+
+
 _TOWER_STREAMS = {}
 
 
@@ -563,9 +583,10 @@ class _TowerForward(NamedTuple):
 class _DirectStep:
     """One direct step in flight: what its stages -- forward towers, loss, backward towers, apply or fold -- hand to each other."""
 
-    def __init__(self, model, optimizer, spec, capture, labels=None):
+    def __init__(self, model, optimizer, spec, capture, labels=None, targets=None):
         self.model, self.optimizer, self.spec, self.capture = model, optimizer, spec, capture
         self.labels = labels     # the batch's group labels [2B] (_batch_labels), None: none
+        self.targets = targets   # the batch's soft targets [B, 2B] or [B, world * 2B] (_batch_targets), None: none
         self.encs = (model.doc_encoder, model.query_encoder)
         self.ordered = False     # the forward recurrences are ordered by events (syncs: what a call of each kind carries)
         self.into = self.ids_of = self.streams = self.cur = self.s_main = self.syncs = None
@@ -649,7 +670,7 @@ def _forward_towers(st: _DirectStep, batch) -> None:
                 st.fw[tower] = _TowerForward(*res, p_drop, seed, enc._opts_bwd())
 
 
-def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None):
+def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets=None):
     """The fused loss + gradient launch of the step's kind on s_main (the current stream): (loss, dq, dpn) for the towers' outputs
     q [B,H] and pn [2B,H] (positives, then negatives).  The kinds share the buffers; "in_batch" swaps the one launch, nothing else.
     gather_negatives: the loss runs over the passages of ALL ranks: all-gather of pn into the pool G [world * 2B, H] (rank order),
@@ -658,7 +679,10 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None):
     issues gather, reduce, (prefix,) bucket in that order.
     labels (the batch's group labels [2B], "in_batch" only): the grouped pool entry on pn as it lies (the in-batch entry's bits
     where no label matches); gathered, the ranks' labels travel like the passages, by an all-gather right behind theirs --
-    gather, label gather, reduce on every rank."""
+    gather, label gather, reduce on every rank.
+    targets (the batch's soft targets, "in_batch" only, never with labels): the soft entry on pn as it lies (M = 2B; the in-batch
+    entry's bits for one-hot targets); gathered, on the pool with this rank's rows [B, world * 2B] -- the targets are rank-local,
+    so no collective is added and their order stays gather, reduce."""
     (B, H), dev = q.shape, q.device
     loss = torch.empty((), dtype=torch.float32, device=dev)
     dq = torch.empty_like(q)
@@ -668,22 +692,28 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None):
         pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
         d_pool = torch.empty_like(pool)
         dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
-        rows = contrastive_workspace(B, pool.shape[0], H, dev)
+        rows = (soft_contrastive_workspace if targets is not None else contrastive_workspace)(B, pool.shape[0], H, dev)
         if labels is not None:
             pool_labels = torch.empty(coll.world * 2 * B, dtype=torch.int64, device=dev)
     else:
         dpn = torch.empty_like(pn)
-        if labels is not None:
+        if targets is not None:
+            rows = soft_contrastive_workspace(B, 2 * B, H, dev)
+        elif labels is not None:
             rows = contrastive_workspace(B, 2 * B, H, dev)
         else:
             rows = in_batch_workspace(B, H, dev) if spec.negatives == "in_batch" else torch.empty(B, dtype=torch.float32, device=dev)
-    for t in (q, pn, loss, dq, dpn, rows) + (() if labels is None else (labels, pool_labels)):
+    for t in (q, pn, loss, dq, dpn, rows) + (() if labels is None else (labels, pool_labels)) + (() if targets is None else (targets,)):
         t.record_stream(s_main)
     L, p, n = _lib.lib(), pn[:B], pn[B:]
     with torch.cuda.device(dev):
         if spec.gather_negatives:
             coll.all_gather_blocks(pn, pool)
-            if labels is None:
+            if targets is not None:
+                _lib.check(L.tt_contrastive_loss_soft_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, targets.data_ptr(),
+                                                          float(spec.temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
+                                                          rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+            elif labels is None:
                 _lib.check(L.tt_contrastive_loss_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, coll.rank * 2 * B,
                                                      float(spec.temperature), loss.data_ptr(), dq.data_ptr(), d_pool.data_ptr(),
                                                      rows.data_ptr(), rows.numel(), s_main.cuda_stream))
@@ -695,6 +725,10 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None):
                                                              rows.numel(), s_main.cuda_stream))
             # (no scale: a summed row is sum_r d loss_r / d D_j, and the optimizer's 1 / world makes it the mean's)
             coll.all_reduce_sum(d_pool.view(-1))
+        elif targets is not None:
+            _lib.check(L.tt_contrastive_loss_soft_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, targets.data_ptr(),
+                                                      float(spec.temperature), loss.data_ptr(), dq.data_ptr(), dpn.data_ptr(),
+                                                      rows.data_ptr(), rows.numel(), s_main.cuda_stream))
         elif labels is not None:
             # (the queries' labels are the first B of the passages': the positives')
             _lib.check(L.tt_contrastive_loss_grouped_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, 0, labels.data_ptr(),
@@ -717,7 +751,8 @@ def _loss_and_embedding_grads(st: _DirectStep) -> None:
     each way on that path: event wait + launch); the query tower's stream joins for the loss and again before the optimizer."""
     st.join()
     with torch.cuda.stream(st.s_main):
-        st.loss, dq, dpn = _direct_loss(st.spec, st.optimizer, st.fw[_QRY].out, st.fw[_DOC].out, st.s_main, st.labels)
+        st.loss, dq, dpn = _direct_loss(st.spec, st.optimizer, st.fw[_QRY].out, st.fw[_DOC].out, st.s_main, st.labels,
+                                            st.targets)
     st.d_out = (dpn, dq)
 
 
@@ -771,7 +806,8 @@ def _apply_or_fold(st: _DirectStep) -> None:
 
 
 def _train_step_direct(model: TwoTowerModel, optimizer, batch, spec: _StepSpec, plan: Optional[_towers_in_flight],
-                       capture: Optional[_Capture], labels: Optional[torch.Tensor] = None):
+                       capture: Optional[_Capture], labels: Optional[torch.Tensor] = None,
+                       targets: Optional[torch.Tensor] = None):
     """The same step without the autograd engine: tower forwards (train mode), the fused loss + gradient kernel, tower backwards
     written STRAIGHT into the optimizer's flat gradient buffer, optimizer step.  Every parameter receives its gradient exactly
     once (query tower once; positives and negatives as one 2B-row document-tower call), so nothing has to be zeroed or
@@ -780,8 +816,8 @@ def _train_step_direct(model: TwoTowerModel, optimizer, batch, spec: _StepSpec, 
     shortcut does not apply (_direct_grad_views): the caller then takes the autograd path.
     batch: (queries, pos_docs, neg_docs); plan: the step's _towers_in_flight -- when the two towers' split recurrences do not fit
     the device together their forward recurrence launches are ordered with events; capture: None for the eager step; labels: the
-    batch's group labels (_batch_labels), None: none."""
-    st = _DirectStep(model, optimizer, spec, capture, labels)
+    batch's group labels (_batch_labels), None: none; targets: its soft targets (_batch_targets), None: none."""
+    st = _DirectStep(model, optimizer, spec, capture, labels, targets)
     st.into = _direct_grad_views(model, optimizer, batch, spec, capture)
     if st.into is None:
         return None
@@ -839,10 +875,11 @@ class _GatherPoolFn(torch.autograd.Function):
         return d_pool[ctx.coll.rank * ctx.rows:(ctx.coll.rank + 1) * ctx.rows], None
 
 
-def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None):
+def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None, targets=None):
     """The loss of the step's kind as an autograd graph over the towers' outputs (q, p, n); pn: the 2B passages as one tensor
     when the document tower ran once (None: it did not).  Gathered: the loss of this rank's queries over the passages of all ranks.
-    labels: the batch's group labels [2B] (_batch_labels); gathered, the ranks' labels are gathered right behind the passages."""
+    labels: the batch's group labels [2B] (_batch_labels); gathered, the ranks' labels are gathered right behind the passages.
+    targets: the batch's soft targets (_batch_targets), over [p; n] or, gathered, over the pool: soft_contrastive_loss."""
     if spec.gather_negatives:
         coll = getattr(optimizer, "_coll", None)
         if coll is None:
@@ -850,6 +887,8 @@ def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None):
         if pn is None:
             pn = torch.cat(embeddings[1:])
         pool = _GatherPoolFn.apply(pn, coll)
+        if targets is not None:
+            return soft_contrastive_loss(embeddings[0], pool, targets, temperature=spec.temperature)
         if labels is None:
             return contrastive_softmax_loss(embeddings[0], pool, pos_offset=coll.rank * pn.shape[0], temperature=spec.temperature)
         pool_labels = torch.empty(coll.world * labels.shape[0], dtype=torch.int64, device=labels.device)
@@ -857,6 +896,9 @@ def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None):
         return contrastive_softmax_loss(embeddings[0], pool, pos_offset=coll.rank * pn.shape[0], temperature=spec.temperature,
                                         q_groups=labels[:embeddings[0].shape[0]], doc_groups=pool_labels)
     if spec.negatives == "in_batch":
+        if targets is not None:
+            return soft_contrastive_loss(embeddings[0], pn if pn is not None else torch.cat(embeddings[1:]), targets,
+                                         temperature=spec.temperature)
         if labels is not None:
             B = embeddings[0].shape[0]
             return in_batch_softmax_loss(embeddings, temperature=spec.temperature, groups=labels[:B], neg_groups=labels[B:])
@@ -864,8 +906,8 @@ def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None):
     return triplet_loss_cosine(embeddings, margin=spec.margin)
 
 
-def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_flight, labels=None):
-    loss = _train_step_direct(model, optimizer, batch, spec, plan, None, labels)
+def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_flight, labels=None, targets=None):
+    loss = _train_step_direct(model, optimizer, batch, spec, plan, None, labels, targets)
     if loss is not None:
         return loss
     plan.use_one_workgroup()   # (autograd calls cannot carry the ordering events)
@@ -910,15 +952,15 @@ def _train_step_once(model, optimizer, batch, spec: _StepSpec, plan: _towers_in_
         q = model.encode_query(queries)
         p = model.encode_document(pos_docs)
         n = model.encode_document(neg_docs)
-    loss = _autograd_loss(spec, optimizer, (q, p, n), pn, labels)
+    loss = _autograd_loss(spec, optimizer, (q, p, n), pn, labels, targets)
     loss.backward()
     optimizer.step()
     return loss.detach()
 
 
-def _eager_step(model, optimizer, batch, spec: _StepSpec, labels=None):
+def _eager_step(model, optimizer, batch, spec: _StepSpec, labels=None, targets=None):
     """One step with the read of the gate wherever optimizer.check puts it; a time-out of a column-split recurrence redoes the
-    step on the one-workgroup kernels (ordinary relaunch, same bits as the split forward), with the same labels."""
+    step on the one-workgroup kernels (ordinary relaunch, same bits as the split forward), with the same labels and targets."""
     queries, pos_docs, neg_docs = batch
     encs = (model.query_encoder, model.doc_encoder)
     n_doc = pos_docs.shape[0] + neg_docs.shape[0] if (spec.concurrent_towers and neg_docs.shape[0] == pos_docs.shape[0]) else max(
@@ -927,28 +969,29 @@ def _eager_step(model, optimizer, batch, spec: _StepSpec, labels=None):
     rng = torch.get_rng_state() if any(e.dropout > 0.0 and e.training for e in encs) else None
     try:
         with _towers_in_flight(model, optimizer, rows if queries.is_cuda else {}) as plan:
-            return _train_step_once(model, optimizer, batch, spec, plan, labels)
+            return _train_step_once(model, optimizer, batch, spec, plan, labels, targets)
     except SplitRecurrenceTimeout:
         if rng is not None:
             torch.set_rng_state(rng)  # (the redone step draws the dropout seeds the failed attempt drew)
         with _towers_in_flight(model, optimizer, {}, force_one_workgroup=True) as plan:
-            return _train_step_once(model, optimizer, batch, spec, plan, labels)
+            return _train_step_once(model, optimizer, batch, spec, plan, labels, targets)
 
 
-def _step(model, optimizer, batch, spec: _StepSpec, defer_check: bool, labels=None):
-    """train_step behind its argument list (DataParallelTrainer.step enters here with its own record).  labels: _batch_labels."""
+def _step(model, optimizer, batch, spec: _StepSpec, defer_check: bool, labels=None, targets=None):
+    """train_step behind its argument list (DataParallelTrainer.step enters here with its own record).  labels: _batch_labels;
+    targets: _batch_targets."""
     queries, pos_docs, neg_docs = batch
     if spec.gather_negatives and not queries.shape[0] == pos_docs.shape[0] == neg_docs.shape[0]:
         raise ValueError("gather_negatives=True needs as many negatives as positives as queries")
     if not (defer_check and isinstance(optimizer, _FlatClipAdam) and queries.is_cuda):
-        return _eager_step(model, optimizer, batch, spec, labels)
+        return _eager_step(model, optimizer, batch, spec, labels, targets)
     keep, optimizer.check = optimizer.check, False
     try:
-        loss = _eager_step(model, optimizer, batch, spec, labels)
+        loss = _eager_step(model, optimizer, batch, spec, labels, targets)
     finally:
         optimizer.check = keep
     if keep:
-        optimizer.snapshot_gate(redo=lambda: _eager_step(model, optimizer, batch, spec, labels))
+        optimizer.snapshot_gate(redo=lambda: _eager_step(model, optimizer, batch, spec, labels, targets))
     return loss
 
 
@@ -956,7 +999,7 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
                neg_docs: torch.Tensor, margin: float = 0.2, concurrent_towers: bool = True, direct: bool = True,
                defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05,
                gather_negatives: bool = False, groups: Optional[torch.Tensor] = None,
-               neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
+               neg_groups: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One step of backend/main.py:244-259 on this rank's (equal-sized) share of the global batch.
     Returns the local loss as a 0-d device tensor (no .item(): the reference's per-step sync is dropped).
 
@@ -996,10 +1039,18 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     positives away.  Derive the label from the loader's query index.  With gather_negatives=True the ranks'
     labels are all-gathered right behind the passages (one more collective, in front of the summing all-reduce), so labels must
     be global (the same query has the same label on every rank) and EVERY rank must pass labels, or none -- like "every rank
-    must bring the same B".  The direct and the autograd path give the same bits; a redo keeps the labels."""
+    must bring the same B".  The direct and the autograd path give the same bits; a redo keeps the labels.
+
+    targets (negatives="in_batch" only, never with groups / neg_groups; float32 [B, 2B] on the batch's device): soft targets, a
+    weight per (query, passage of [p; n]) in place of the one positive per query -- model.soft_contrastive_loss: distillation
+    from a teacher (model.distillation_targets) or several positives per query, each pulled (model.multi_positive_targets).
+    One-hot targets (1 at column i) give the bits of the plain "in_batch" step.  With gather_negatives=True the targets are
+    [B, world * 2B] with the columns in pool order (rank r's [p_r; n_r] at column r * 2B); they are this rank's own rows, so no
+    collective is added.  Not differentiated.  The direct and the autograd path give the same bits; a redo keeps the targets."""
     spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct).checked(graphs=False)
     batch = (queries, pos_docs, neg_docs)
-    return _step(model, optimizer, batch, spec, defer_check, _batch_labels("train_step", spec, batch, groups, neg_groups))
+    targets = _batch_targets("train_step", spec, optimizer, batch, targets, groups, neg_groups)
+    return _step(model, optimizer, batch, spec, defer_check, _batch_labels("train_step", spec, batch, groups, neg_groups), targets)
 
 
 class DataParallelTrainer:
@@ -1037,7 +1088,7 @@ class DataParallelTrainer:
             dist.broadcast(self.optimizer.flat_params, src=src, group=self.optimizer.group)
         self.optimizer.mark_params_changed()  # (the broadcast wrote the flat buffer, not the parameter tensors)
 
-    def _graph_for(self, batch, spec: _StepSpec, grouped: bool = False) -> Optional["GraphedTrainStep"]:
+    def _graph_for(self, batch, spec: _StepSpec, grouped: bool = False, soft: bool = False) -> Optional["GraphedTrainStep"]:
         queries, pos_docs, neg_docs = batch
         if not (_standard_batch(batch) and queries.dtype == torch.int64 and _frozen_tables(self.model)
                 and self.model.query_encoder.check_inputs and self.model.doc_encoder.check_inputs):
@@ -1046,12 +1097,14 @@ class DataParallelTrainer:
         key = (queries.shape[0], up(queries.shape[1]), up(max(pos_docs.shape[1], neg_docs.shape[1])))
         if grouped:
             key += ("grouped",)   # (a step with labels is another graph: its loss node is the grouped entry's; others keep their key)
+        if soft:
+            key += ("soft",)      # (and so is a step with soft targets: the soft entry's)
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
                 self._graphs.pop(next(iter(self._graphs)))
             g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], spec.margin, defer_check=self.defer_check,
-                                 negatives=spec.negatives, temperature=spec.temperature, grouped=bool(grouped))
+                                 negatives=spec.negatives, temperature=spec.temperature, grouped=bool(grouped), soft=bool(soft))
         self._graphs[key] = g                                      # (re-inserted: most recently used last)
         return g
 
@@ -1059,17 +1112,19 @@ class DataParallelTrainer:
         """defer_check: settle the last step's pending check."""
         return self.optimizer.settle()
 
-    def step(self, queries, pos_docs, neg_docs, groups=None, neg_groups=None) -> torch.Tensor:
+    def step(self, queries, pos_docs, neg_docs, groups=None, neg_groups=None, targets=None) -> torch.Tensor:
         """groups / neg_groups: grouped negatives, see train_step (negatives="in_batch" only; with gather_negatives=True every
-        rank passes labels or none)."""
+        rank passes labels or none).  targets: soft targets, see train_step (negatives="in_batch" only, never with labels;
+        float32 [B, 2B], with gather_negatives=True [B, world * 2B] in pool order)."""
         self.model.train()
         batch, spec = (queries, pos_docs, neg_docs), self._spec()
+        targets = _batch_targets("DataParallelTrainer.step", spec, self.optimizer, batch, targets, groups, neg_groups)
         labels = _batch_labels("DataParallelTrainer.step", spec, batch, groups, neg_groups)
         if self.graphs:
-            g = self._graph_for(batch, spec, labels is not None)
+            g = self._graph_for(batch, spec, labels is not None, targets is not None)
             if g is not None:
-                return g(queries, pos_docs, neg_docs, groups, neg_groups)
-        return _step(self.model, self.optimizer, batch, spec, self.defer_check, labels)
+                return g(queries, pos_docs, neg_docs, groups, neg_groups, targets)
+        return _step(self.model, self.optimizer, batch, spec, self.defer_check, labels, targets)
 
 
 class _SeedRing:
@@ -1122,14 +1177,22 @@ class GraphedTrainStep:
     eager step would have computed with the generator in the same state.
     grouped=True (negatives="in_batch" only): the captured loss is the grouped entry's; the batch's group labels (train_step:
     groups, neg_groups) are a static int64 input [2B] like the ids, copied in front of the replay.  A call without labels fills
-    -1 (no group: the bits of the ungrouped step); neg_groups=None fills -1 for the negatives."""
+    -1 (no group: the bits of the ungrouped step); neg_groups=None fills -1 for the negatives.
+    soft=True (negatives="in_batch" only, not with grouped): the captured loss is the soft entry's; the batch's soft targets
+    (train_step: targets) are a static float32 input [B, 2B], refilled in front of every replay.  A call without targets fills
+    the one-hot (1 at column i: the bits of the plain "in_batch" step)."""
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
-                 defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05, grouped: bool = False):
+                 defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05, grouped: bool = False,
+                 soft: bool = False):
         # (margin, negatives and temperature are arguments of the captured loss launches)
         self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True).checked(graphs=True)
         if grouped and negatives != "in_batch":
             raise ValueError(f'GraphedTrainStep: grouped=True needs negatives="in_batch", got negatives={negatives!r}')
+        if soft and negatives != "in_batch":
+            raise ValueError(f'GraphedTrainStep: soft=True needs negatives="in_batch", got negatives={negatives!r}')
+        if soft and grouped:
+            raise ValueError("GraphedTrainStep: soft=True and grouped=True exclude each other")
         encs = (model.query_encoder, model.doc_encoder)
         if not isinstance(optimizer, _FlatClipAdam) or optimizer._gated_step_fn is None:
             raise TypeError("GraphedTrainStep needs a FusedClipAdam")
@@ -1144,6 +1207,10 @@ class GraphedTrainStep:
         self.both = torch.zeros((2 * self.B, self.doc_width), dtype=torch.int64, device=dev)
         self.grouped = bool(grouped)
         self.labels = torch.full((2 * self.B,), -1, dtype=torch.int64, device=dev) if self.grouped else None
+        self.soft = bool(soft)
+        # (the static targets start as the one-hot that a call without targets refills them with)
+        self._one_hot = torch.eye(self.B, 2 * self.B, dtype=torch.float32, device=dev) if self.soft else None
+        self.targets = self._one_hot.clone() if self.soft else None
         # inter-layer dropout: the seeds are device words the captured kernels read when they run (TT_ENC_SEED_ON_DEVICE); every
         # call draws them from torch's CPU generator exactly as the eager step does and copies them there in front of the replay
         self._seeds = _SeedRing(dev) if any(e.dropout > 0.0 for e in encs) else None
@@ -1179,20 +1246,26 @@ class GraphedTrainStep:
     def _run(self):
         rows = {self.model.query_encoder: self.B, self.model.doc_encoder: 2 * self.B}
         with _towers_in_flight(self.model, self.optimizer, rows) as plan:
-            return _train_step_direct(self.model, self.optimizer, (self.q, None, None), self._spec, plan, self._capture, self.labels)
+            return _train_step_direct(self.model, self.optimizer, (self.q, None, None), self._spec, plan, self._capture, self.labels,
+                                      self.targets)
 
     def flush(self):
         """defer_check: settle the optimizer's pending check (raises that step's exception, if any)."""
         return self.optimizer.settle()
 
     def __call__(self, queries: torch.Tensor, pos_docs: torch.Tensor, neg_docs: torch.Tensor,
-                 groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None,
+                 targets: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns the step's loss (a static 0-d device tensor, valid until the next call)."""
+        if targets is not None and not self.soft:
+            raise ValueError("GraphedTrainStep was captured without soft targets (soft=False), got targets")
         if (groups is not None or neg_groups is not None) and not self.grouped:
             raise ValueError("GraphedTrainStep was captured without labels (grouped=False), got groups / neg_groups")
         for src, width, what in ((queries, self.q_width, "queries"), (pos_docs, self.doc_width, "pos_docs"), (neg_docs, self.doc_width, "neg_docs")):
             if src.dim() != 2 or src.shape[0] != self.B or src.shape[1] > width or src.dtype != torch.int64:
                 raise ValueError(f"GraphedTrainStep was captured for int64 {what} [{self.B}, <= {width}], got {src.dtype} {tuple(src.shape)}")
+        if self.soft:   # (checked like train_step's, before anything is staged)
+            targets = _batch_targets("GraphedTrainStep", self._spec, None, (queries, pos_docs, neg_docs), targets, groups, neg_groups)
         opt = self.optimizer
         if self._phase == "all" and (opt.lr, opt.betas, opt.eps, opt.max_norm) != self._hyper:
             raise ValueError("GraphedTrainStep: the optimizer's lr / betas / eps / max_norm changed since the capture (they are "
@@ -1208,6 +1281,10 @@ class GraphedTrainStep:
                 self.labels.copy_(labels)
         else:
             labels = None
+        if self.soft:
+            # (none: the one-hot, the plain step's bits; the eager redo takes the same targets)
+            targets = self._one_hot if targets is None else targets
+            self.targets.copy_(targets)
         if self._seeds is not None:
             drawn = _draw_dropout_seeds(self.model)
             self._seeds.put(drawn[id(self.model.query_encoder)], drawn[id(self.model.doc_encoder)])
@@ -1218,7 +1295,7 @@ class GraphedTrainStep:
         if not opt.check:
             return self.loss
         # (the eager redo takes the one-workgroup retry itself if it must)
-        opt.snapshot_gate(redo=lambda: _eager_step(self.model, opt, (queries, pos_docs, neg_docs), self._spec, labels))
+        opt.snapshot_gate(redo=lambda: _eager_step(self.model, opt, (queries, pos_docs, neg_docs), self._spec, labels, targets))
         if not self.defer_check:
             redone = opt.settle()            # the step's one host synchronisation
             if redone is not None:
