@@ -959,6 +959,40 @@ int tt_contrastive_loss_soft_f32(const float *q /*[B,H]*/, int B, const float *d
                                  float *ddocs /*[M,H]*/, void *workspace, size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The SYMMETRIC loss (the bidirectional InfoNCE of CLIP): the positive document P_i = pos_offset + i of query i is also
+ * classified among the B queries, down column P_i of the score matrix, and the two cross-entropies are mixed.  q, docs, qh,
+ * Dh, s_ij and eps as tt_contrastive_loss_f32:
+ *   L_qd = mean_{i<B} (logsumexp_{j<M}  s_ij       - s_{i,P_i})          (what tt_contrastive_loss_f32 computes)
+ *   L_dq = mean_{i<B} (logsumexp_{i'<B} s_{i',P_i} - s_{i,P_i})          (column P_i, over the B queries)
+ *   loss = (1 - alpha) L_qd + alpha L_dq         0 <= alpha <= 1; alpha = 0.5 is the CLIP loss
+ *   B T d loss / d s_ij = (1 - alpha) (exp(s_ij - lse_i) - [j == P_i]) + alpha [0 <= c < B] (exp(s_ij - clse_c) - [j == P_i]),
+ *                         c = j - pos_offset
+ * Only the B positive columns [pos_offset, pos_offset + B) have a column softmax: explicit negatives and the rest of a pool
+ * have no query of their own and stay negatives of the row direction alone.
+ * q_groups [B], doc_groups [M] int64, device: both or neither.  With labels the ignore predicate of
+ * tt_contrastive_loss_grouped_f32 applies to both softmaxes: an ignored pair (i', j) leaves row i''s sum, column j's sum and
+ * both gradients.  A column whose every other query is ignored has column loss exactly 0.0f.
+ * loss [1]; loss_dirs [2] nullable: L_qd, L_dq, both always computed, whatever alpha is; dq [B,H], ddocs [M,H] through the
+ * norms (both or none, nullable; without them loss and loss_dirs are the same bits as with them).
+ * Exact: (1) with alpha = 0, loss, dq and ddocs are the bits of tt_contrastive_loss_f32, or of
+ * tt_contrastive_loss_grouped_f32 with labels; (2) with alpha = 1, every ddocs row outside [pos_offset, pos_offset + B) is
+ * exactly zero.
+ * Shapes, refusals and guarantees as tt_contrastive_loss_f32 (neither [B,M] nor [B,B] is ever stored; deterministic: no
+ * atomics, every sum in one fixed order that depends on (B, M, H) alone, whatever the workspace and the outputs held on entry;
+ * asynchronous on `stream`; capture-clean); also TT_ERR_BAD_SHAPE: alpha outside [0, 1] (NaN included), one of q_groups,
+ * doc_groups null and the other not.
+ * workspace: tt_contrastive_loss_sym_workspace_bytes(B, M, H) bytes (0 for a shape the call refuses; no GPU needed): the plan
+ * of tt_contrastive_loss_workspace_bytes plus the per-slice column statistics, clse [B] and the two directions' row losses;
+ * 16-byte aligned, caller-owned.
+ */
+size_t tt_contrastive_loss_sym_workspace_bytes(int B, int M, int H);
+int tt_contrastive_loss_sym_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H, int pos_offset,
+                                const int64_t *q_groups /*[B] nullable*/, const int64_t *doc_groups /*[M] nullable*/,
+                                float temperature, float alpha, float *loss /*[1]*/,
+                                float *loss_dirs /*[2] nullable: L_qd, L_dq*/, float *dq /*[B,H]*/, float *ddocs /*[M,H]*/,
+                                void *workspace, size_t workspace_bytes, tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

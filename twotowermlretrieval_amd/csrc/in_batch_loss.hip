@@ -26,6 +26,25 @@
 // like the labels -- unconditionally, at indices clamped into [0, B) x [0, M), element i M + j addressed in 64 bits -- and a pair
 // past the end selects 0.
 //
+// Symmetric loss (tt_contrastive_loss_sym_f32, the ib_sym_* kernels; with or without labels, never SOFT): the positive document
+// P_i = pos_offset + i is also classified among the B queries, down column P_i of the score matrix,
+//   L_qd = mean_i (lse_i - s_{i,P_i})     L_dq = mean_i (clse_i - s_{i,P_i})     clse_c = logsumexp_{i'<B} s_{i',pos_offset+c}
+//   loss = (1 - alpha) L_qd + alpha L_dq      B T dL/ds_ij = (1 - alpha) (e^{s_ij - lse_i} - [j == P_i])
+//                                                            + alpha [0 <= c < B] (e^{s_ij - clse_c} - [j == P_i]),  c = j - pos_offset
+// Only the B positive columns have a softmax of their own; every other document is a negative of the row direction alone.
+// The column statistics are the row statistics with the roles swapped (ib_stats_body<.., COLS>): a workgroup owns the 32
+// documents of an ALIGNED tile of the image that meets [pos_offset, pos_offset + B) (pos_offset need not be a multiple of 32:
+// a lane whose document is no positive column computes and writes nothing; every tile lies inside the padded image) and walks
+// a slice of the queries, ib_slices(B, B).  A query past B is a zero image row that scores a finite 0: it is masked out of
+// the column sums exactly as a document past M is masked out of the rows.  With labels the one ignore predicate takes the
+// pair out of row i's sum, of column j's sum and of G; column c always keeps (c, P_c), so clse_c is finite, and a column
+// whose every other query is ignored has clse_c = s_{c,P_c} + log(1): column loss 0.0f.  The row statistics, lse_i and the
+// sum of the mixed row losses are the plain kernels' statements; the row loss is (1 - alpha) a + alpha b and G likewise, so
+// alpha = 0 gives the plain (grouped) entry's bits (1 a + 0 b = a for finite b), and alpha = 1 gives an exact zero in every
+// G entry outside the positive columns.  Launches: 1, ib_sym_stats_kernel (2 with the column tiles behind the row tiles in one
+// grid), ib_sym_lse_kernel (3, also clse and the two directions' row losses), 4 three times (loss, L_qd, L_dq),
+// ib_sym_grad_kernel (5), 6.
+//
 // Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
 //   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
 //   2 ib_stats_kernel    a workgroup per (32 queries, slice of the documents): S^T tiles on v_mfma_f32_32x32x2_f32, online
@@ -73,9 +92,11 @@ struct IBPlan {
     IBSlices sq, sd;  // slices of the documents a query tile walks / of the queries a document tile walks
     size_t qh, dh, den, flag, lse, rows, pm, pl, pos, part_q, part_d, total;
     size_t pw, pt, w;  // soft targets only, behind everything else
+    IBSlices sc;       // symmetric only: slices of the queries a tile of positive columns walks (statistics)
+    size_t cpm, cpl, clse, rows_qd, rows_dq;  // symmetric only, behind everything else
 };
 
-IBPlan ib_plan(int B, int M, int H, bool soft = false)
+IBPlan ib_plan(int B, int M, int H, bool soft = false, bool sym = false)
 {
     IBPlan P;
     P.Hp = (H + 31) / 32 * 32;
@@ -100,6 +121,15 @@ IBPlan ib_plan(int B, int M, int H, bool soft = false)
         P.pw = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);  // per (slice, query): sum of the targets, sum of target * score
         P.pt = w.take(sizeof(float) * (size_t)P.sq.n * P.Bq);
         P.w = w.take(sizeof(float) * (size_t)P.Bq);            // w_i, padded like lse
+    }
+    P.sc = ib_slices(B, B);
+    P.cpm = P.cpl = P.clse = P.rows_qd = P.rows_dq = 0;
+    if (sym) {  // (appended likewise)
+        P.cpm = w.take(sizeof(float) * (size_t)P.sc.n * P.Bq);  // per (slice, positive column): maximum, sum of exponentials
+        P.cpl = w.take(sizeof(float) * (size_t)P.sc.n * P.Bq);
+        P.clse = w.take(sizeof(float) * (size_t)P.Bq);          // clse_c, padded like lse
+        P.rows_qd = w.take(sizeof(float) * (size_t)P.Bq);       // lse_i - s_pos, clse_i - s_pos
+        P.rows_dq = w.take(sizeof(float) * (size_t)P.Bq);
     }
     P.total = w.off;
     return P;
@@ -327,6 +357,133 @@ __global__ __launch_bounds__(256) void ib_stats_kernel(const float *__restrict__
     }
 }
 
+// ib_stats_kernel's body as a function of (tile, slice), for the symmetric loss's statistics launch.  !COLS: the statements of
+// the kernel above, one for one (the kernel itself keeps its text: moving it behind a call changes what the compiler knows
+// about its pointers, and with that its registers).
+// COLS (the symmetric loss's column statistics; never SOFT): the roles swapped.  The workgroup owns the 32 DOCUMENTS of image
+// tile `tile` (on the lanes) and walks slice `slice` of the QUERIES; the lane's column is c = document - pos_offset, and
+// pm/pl are the column partials [slice][Bq] indexed by c, written for 0 <= c < B alone (a document tile is aligned to the
+// image, not to pos_offset: the lanes in front of the first and behind the last positive column compute and write nothing
+// that is kept).  A query past B is masked as a document past M is above; the pair (i', j) is ignored by the same predicate,
+// read from the other side: the walked query's label is non-negative and equals the own document's, and i' != c.  pos[] is
+// the row pass's to write.
+template <bool GROUPED, bool SOFT, bool COLS>
+__device__ __forceinline__ void ib_stats_body(const float *__restrict__ qh, const float *__restrict__ dh, const int64_t *__restrict__ qg,
+                                              const int64_t *__restrict__ dg, int B, int M, int pos_offset, int Hp, int Bq,
+                                              int tiles_per_slice, float temperature, float *__restrict__ pm,
+                                              float *__restrict__ pl, float *__restrict__ pos, const float *__restrict__ tg,
+                                              float *__restrict__ pw, float *__restrict__ pt, unsigned tile, unsigned slice)
+{
+    __shared__ float part_m[8][IB_TILE], part_l[8][IB_TILE];
+    __shared__ float part_w[SOFT ? 8 : 1][IB_TILE], part_t[SOFT ? 8 : 1][IB_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5;
+    const int i0 = tile * IB_TILE, i = i0 + (lane & 31);
+    const int ND = COLS ? B : M;
+    const int t_begin = slice * tiles_per_slice;
+    const int t_all = (ND + IB_TILE - 1) / IB_TILE, n_tiles = t_begin + tiles_per_slice < t_all ? t_begin + tiles_per_slice : t_all;
+    float m = -INFINITY, l = 0.0f;
+    int64_t own_g = -1, oth_g[16];
+    if (GROUPED)
+        own_g = COLS ? dg[i < M ? i : M - 1] : qg[i < B ? i : B - 1];  // (a lane past the end: any label, its statistics are not written)
+    const bool grouped_q = own_g >= 0;
+    float tw = 0.0f, ts = 0.0f, tv[16];
+    for (int t = t_begin + wave; t < n_tiles; t += 4) {
+        const int j0 = t * IB_TILE;
+        const f32x16 acc = ib_scores(COLS ? qh : dh, j0, COLS ? dh : qh, i0, Hp, lane, [&] {
+            if (GROUPED)
+                ib_labels(COLS ? qg : dg, j0, half, ND, oth_g);
+            if (SOFT)
+                ib_targets<true>(tg, i, B, j0, half, ND, M, tv);
+        });
+        float x[16], tm = -INFINITY;
+        bool keep[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = j0 + ib_rho(r) + 4 * half;
+            x[r] = acc[r] / temperature;
+            keep[r] = j < ND;
+            if (GROUPED && !COLS)  // (bitwise: one mask per pair, no branch per document)
+                keep[r] = keep[r] & !(grouped_q & (oth_g[r] == own_g) & (j != i + pos_offset));
+            if (GROUPED && COLS)   // (j is the walked query, i the own document)
+                keep[r] = keep[r] & !((oth_g[r] >= 0) & (oth_g[r] == own_g) & (i != j + pos_offset));
+            if (keep[r])
+                tm = fmaxf(tm, x[r]);
+            if (!SOFT && !COLS && j == i + pos_offset && i < B)
+                pos[i] = x[r];  // (one lane of one wave of one slice, once)
+            if (SOFT) {  // (a document past M: weight 0, and its score is that of a zero row: finite)
+                const float tr = j < ND ? tv[r] : 0.0f;
+                tw += tr;
+                ts = fmaf(tr, x[r], ts);
+            }
+        }
+        if (tm > -INFINITY) {  // (some document of the tile is valid, and kept, for this lane)
+            const float mn = fmaxf(m, tm);
+            float s = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (keep[r])
+                    s += expf(x[r] - mn);
+            l = l * expf(m - mn) + s;  // (m = -inf: l = 0 and exp(-inf) = 0)
+            m = mn;
+        }
+    }
+    part_m[wave * 2 + half][lane & 31] = m;
+    part_l[wave * 2 + half][lane & 31] = l;
+    if (SOFT) {
+        part_w[wave * 2 + half][lane & 31] = tw;
+        part_t[wave * 2 + half][lane & 31] = ts;
+    }
+    __syncthreads();
+    // (the row this thread writes: the query i0 + c, or the positive column of document i0 + c)
+    const int out0 = COLS ? i0 - pos_offset : i0;
+    if (threadIdx.x < IB_TILE && out0 + (int)threadIdx.x < B && (!COLS || out0 + (int)threadIdx.x >= 0)) {
+        const int c = threadIdx.x;
+        float M = -INFINITY;
+        for (int k = 0; k < 8; ++k)
+            M = fmaxf(M, part_m[k][c]);
+        float L = 0.0f;
+        for (int k = 0; k < 8; ++k)
+            if (part_l[k][c] > 0.0f)
+                L += part_l[k][c] * expf(part_m[k][c] - M);
+        pm[(size_t)slice * Bq + out0 + c] = M;
+        pl[(size_t)slice * Bq + out0 + c] = L;
+        if (SOFT) {
+            float W = 0.0f, T = 0.0f;
+            for (int k = 0; k < 8; ++k) {
+                W += part_w[k][c];
+                T += part_t[k][c];
+            }
+            pw[(size_t)slice * Bq + out0 + c] = W;
+            pt[(size_t)slice * Bq + out0 + c] = T;
+        }
+    }
+}
+
+// The symmetric loss's statistics in one grid: blocks [0, tiles_q * slices_q) are the row statistics (block = slice * tiles_q
+// + tile), statement for statement ib_stats_kernel<GROUPED, false>; the rest are the column statistics of the document tiles
+// tile_c0 .. tile_c0 + tiles_c - 1 (the aligned tiles that meet the positive columns), the same way.
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void ib_sym_stats_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                           const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B,
+                                                           int M, int pos_offset, int Hp, int Bq, int tiles_per_slice,
+                                                           int tiles_per_slice_c, float temperature, int tiles_q, int slices_q,
+                                                           int tile_c0, int tiles_c, float *__restrict__ pm,
+                                                           float *__restrict__ pl, float *__restrict__ pos,
+                                                           float *__restrict__ cpm, float *__restrict__ cpl)
+{
+    int b = blockIdx.x;
+    if (b < tiles_q * slices_q) {
+        ib_stats_body<GROUPED, false, false>(qh, dh, qg, dg, B, M, pos_offset, Hp, Bq,
+                                             tiles_per_slice, temperature, pm, pl, pos, nullptr, nullptr, nullptr, b % tiles_q,
+                                             b / tiles_q);
+    } else {
+        b -= tiles_q * slices_q;
+        ib_stats_body<GROUPED, false, true>(qh, dh, qg, dg, B, M, pos_offset, Hp, Bq,
+                                            tiles_per_slice_c, temperature, cpm, cpl, nullptr, nullptr, nullptr, nullptr,
+                                            tile_c0 + b % tiles_c, b / tiles_c);
+    }
+}
+
 // The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.  The slice of the
 // positive has a finite maximum, so M is finite; a slice that is empty for the query (grouped labels) comes as (-inf, 0) and
 // adds 0 * exp(-inf - M) = 0 * 0.
@@ -373,6 +530,49 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
     row_loss[i] = v - pos[i];
 }
 
+// The fold of ib_lse_kernel<false>, statement for statement: the n_slices pairs of entry i in ascending order -> M + log L.
+__device__ __forceinline__ float ib_fold(const float *__restrict__ pm, const float *__restrict__ pl, int i, int Bq, int n_slices)
+{
+    float m[IB_MAX_SLICES], l[IB_MAX_SLICES];
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s) {
+        m[s] = s < n_slices ? pm[(size_t)s * Bq + i] : -INFINITY;
+        l[s] = s < n_slices ? pl[(size_t)s * Bq + i] : 0.0f;
+    }
+    float M = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s)
+        M = fmaxf(M, m[s]);
+    float L = 0.0f;
+#pragma unroll
+    for (int s = 0; s < IB_MAX_SLICES; ++s)
+        if (s < n_slices)
+            L += l[s] * expf(m[s] - M);
+    return M + logf(L);
+}
+
+// Symmetric: a thread per query i, which is also positive column i.  lse_i as above; clse_i from the column partials the same
+// way (column i keeps the pair (i, P_i), so its maximum is finite too).  a = lse_i - s_pos and b = clse_i - s_pos are the two
+// directions' row losses; the mixed one is (1 - alpha) a + alpha b: a itself at alpha = 0 (b is finite), b at alpha = 1.
+__global__ __launch_bounds__(256) void ib_sym_lse_kernel(const float *__restrict__ pm, const float *__restrict__ pl,
+                                                         const float *__restrict__ cpm, const float *__restrict__ cpl,
+                                                         const float *__restrict__ pos, int B, int Bq, int n_slices,
+                                                         int n_slices_c, float alpha, float *__restrict__ lse,
+                                                         float *__restrict__ clse, float *__restrict__ row_loss,
+                                                         float *__restrict__ row_qd, float *__restrict__ row_dq)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B)
+        return;
+    const float v = ib_fold(pm, pl, i, Bq, n_slices), cv = ib_fold(cpm, cpl, i, Bq, n_slices_c);
+    lse[i] = v;
+    clse[i] = cv;
+    const float a = v - pos[i], b = cv - pos[i];
+    row_qd[i] = a;
+    row_dq[i] = b;
+    row_loss[i] = (1.0f - alpha) * a + alpha * b;
+}
+
 // ------------------------------------------------------------------ 5: gradients of the images
 // QOWN: the workgroup owns 32 queries and walks a slice of the documents (dqh = G Dh); else it owns 32 documents and walks a
 // slice of the queries (dDh = G^T qh).  Per chunk of 128 rows of the other side: each wave recomputes one S^T tile
@@ -385,13 +585,19 @@ __global__ __launch_bounds__(256) void ib_lse_kernel(const float *__restrict__ p
 // SOFT: G = (w_i exp(s - lse_i) - t_ij) scale.  w is fetched with lse (the owner's once, the walked queries' per tile; w[] is
 // padded like lse[]); the 16 targets of a tile are loaded where the labels are: along the own query's row on the query-owned
 // side, down the own document's column (coalesced over the lanes) on the document-owned side.
-template <bool QOWN, bool GROUPED, bool SOFT>
+// SYM (never SOFT): G = ((1 - alpha) (exp(s - lse_i) - onehot) + alpha [0 <= c < B] (exp(s - clse_c) - onehot)) scale with
+// c = j - pos_offset.  clse[] is padded like lse[]; it is loaded at c clamped into [0, B) -- in bounds, unconditional, and
+// what a document off the positive columns loads is replaced by 0 where it is used: the walked documents' 16 per tile on the
+// query-owned side, behind the first operands of the products where the labels go; the own document's once on the other.
+// The second exponential is evaluated for pairs in positive columns alone.
+template <bool QOWN, bool GROUPED, bool SOFT, bool SYM = false>
 __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restrict__ qh, const float *__restrict__ dh,
                                              const float *__restrict__ lse, const int64_t *__restrict__ qg,
                                              const int64_t *__restrict__ dg, const float *__restrict__ tg,
                                              const float *__restrict__ wq, int B, int M, int pos_offset, int Hp,
                                              float temperature, int tile, int chunk_begin, int chunk_end,
-                                             float *__restrict__ part)
+                                             float *__restrict__ part, const float *__restrict__ clse = nullptr,
+                                             float alpha = 0.0f)
 {
     // (the wave index as a scalar: the compiler then branches on it instead of masking lanes)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), half = lane >> 5, col = lane & 31;
@@ -406,6 +612,12 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
     int64_t own_g = -1, oth_g[16];
     if (GROUPED)
         own_g = (QOWN ? qg : dg)[o < n_own ? o : n_own - 1];  // (an owner row past the end: any label, its pairs are out of range)
+    float cl_own = 0.0f;
+    if (SYM && !QOWN) {
+        const int c = o - pos_offset;
+        cl_own = clse[c < 0 ? 0 : (c < B ? c : B - 1)];
+    }
+    const float beta = 1.0f - alpha;
     f32x16 tot[4] = {};
     for (int ch = chunk_begin; ch < chunk_end; ++ch) {
         const int c0 = ch * IB_CHUNK, y0 = c0 + IB_TILE * wave;
@@ -413,7 +625,7 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
         if (y0 < n_oth) {  // (wave-uniform; a tile wholly past the end stores zeros)
             // the walked queries' lse, asked for before the products so that they arrive behind them (entries past B hold
             // anything and are not used; the array is padded like the images)
-            float ls_y[16], w_y[16], tv[16];
+            float ls_y[16], w_y[16], tv[16], cl_y[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ls_y[r] = QOWN ? lse_own : lse[y0 + ib_rho(r) + 4 * half];
@@ -426,6 +638,12 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
                     ib_labels(QOWN ? dg : qg, y0, half, n_oth, oth_g);
                 if (SOFT)
                     ib_targets<QOWN>(tg, o, n_own, y0, half, n_oth, M, tv);
+                if (SYM)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int c = y0 + ib_rho(r) + 4 * half - pos_offset;
+                        cl_y[r] = QOWN ? clse[c < 0 ? 0 : (c < B ? c : B - 1)] : cl_own;
+                    }
             });
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -436,7 +654,14 @@ __device__ __forceinline__ void ib_grad_body(float *ib_lds, const float *__restr
                     const float ls = ls_y[r];
                     if (SOFT)
                         v = (w_y[r] * expf(acc[r] / temperature - ls) - tv[r]) * scale;
-                    else
+                    else if (SYM) {
+                        const float x = acc[r] / temperature, hot = jd == iq + pos_offset ? 1.0f : 0.0f;
+                        const float u = expf(x - ls) - hot;
+                        float uc = 0.0f;
+                        if (jd >= pos_offset && jd - pos_offset < B)
+                            uc = expf(x - cl_y[r]) - hot;
+                        v = (beta * u + alpha * uc) * scale;
+                    } else
                         v = (expf(acc[r] / temperature - ls) - (jd == iq + pos_offset ? 1.0f : 0.0f)) * scale;
                     if (GROUPED) {
                         const int64_t gq = QOWN ? own_g : oth_g[r], gd = QOWN ? oth_g[r] : own_g;
@@ -527,6 +752,31 @@ __global__ __launch_bounds__(256) void ib_grad_kernel(const float *__restrict__ 
         const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
         ib_grad_body<false, GROUPED, SOFT>(ib_lds, qh, dh, lse, qg, dg, tg, wq, B, M, pos_offset, Hp, temperature, b % tiles_d, slice * per_d,
                                      end, part_d + (size_t)slice * Dp * Hp);
+    }
+}
+
+// The symmetric loss's gradient launch: ib_grad_kernel's grid and slicing, the SYM bodies.
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void ib_sym_grad_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                          const float *__restrict__ lse, const float *__restrict__ clse,
+                                                          const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B,
+                                                          int M, int pos_offset, int Hp, int Bq, int Dp, float temperature,
+                                                          float alpha, int tiles_q, int slices_q, int per_q, int tiles_d, int per_d,
+                                                          float *__restrict__ part_q, float *__restrict__ part_d)
+{
+    extern __shared__ __attribute__((aligned(16))) float ib_lds[];  // G [128][32], later the gradient tile [32][Hp]
+    int b = blockIdx.x;
+    if (b < tiles_q * slices_q) {
+        const int slice = b / tiles_q, chunks = (M + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
+        ib_grad_body<true, GROUPED, false, true>(ib_lds, qh, dh, lse, qg, dg, nullptr, nullptr, B, M, pos_offset, Hp, temperature,
+                                                 b % tiles_q, slice * per_q, end, part_q + (size_t)slice * Bq * Hp, clse, alpha);
+    } else {
+        b -= tiles_q * slices_q;
+        const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
+        ib_grad_body<false, GROUPED, false, true>(ib_lds, qh, dh, lse, qg, dg, nullptr, nullptr, B, M, pos_offset, Hp, temperature,
+                                                  b % tiles_d, slice * per_d, end, part_d + (size_t)slice * Dp * Hp, clse, alpha);
     }
 }
 
@@ -637,6 +887,49 @@ void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H
     }
 }
 
+// The launches of one symmetric call (P is the sym plan; the entry has refused what it refuses).  qg == nullptr: no labels.
+// loss_dirs == nullptr: the two directions' means are not written (their row losses are).
+void ib_sym_launch(const IBPlan &P, const float *q, const float *docs, int B, int M, int H, int pos_offset, const int64_t *qg,
+                   const int64_t *dg, float temperature, float alpha, float *loss, float *loss_dirs, float *dq, float *ddocs,
+                   void *workspace, hipStream_t st)
+{
+    char *ws = (char *)workspace;
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
+    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
+    float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
+    float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
+    float *cpm = (float *)(ws + P.cpm), *cpl = (float *)(ws + P.cpl), *clse = (float *)(ws + P.clse);
+    float *rows_qd = (float *)(ws + P.rows_qd), *rows_dq = (float *)(ws + P.rows_dq);
+    const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
+    // the aligned document tiles that meet the positive columns [pos_offset, pos_offset + B)
+    const int tile_c0 = pos_offset / IB_TILE, tiles_c = (pos_offset + B - 1) / IB_TILE - tile_c0 + 1;
+    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, IBDocs{docs, nullptr, M}, B, M, H, P.Hp,
+                       P.Bq, P.Dp, qh, dh, den, flag);
+    hipLaunchKernelGGL(qg ? ib_sym_stats_kernel<true> : ib_sym_stats_kernel<false>, dim3(tiles_q * P.sq.n + tiles_c * P.sc.n),
+                       dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
+                       P.sq.per * (IB_CHUNK / IB_TILE), P.sc.per * (IB_CHUNK / IB_TILE), temperature, tiles_q, P.sq.n, tile_c0,
+                       tiles_c, pm, pl, pos, cpm, cpl);
+    hipLaunchKernelGGL(ib_sym_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
+                       (const float *)cpm, (const float *)cpl, (const float *)pos, B, P.Bq, P.sq.n, P.sc.n, alpha, lse, clse, rows,
+                       rows_qd, rows_dq);
+    hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
+    if (loss_dirs) {
+        hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows_qd, B, 1.0f / (float)B, loss_dirs);
+        hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows_dq, B, 1.0f / (float)B, loss_dirs + 1);
+    }
+    if (dq) {
+        const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
+        const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
+        hipLaunchKernelGGL(qg ? ib_sym_grad_kernel<true> : ib_sym_grad_kernel<false>, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n),
+                           dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, (const float *)clse, qg,
+                           dg, B, M, pos_offset, P.Hp, P.Bq, P.Dp, temperature, alpha, tiles_q, P.sq.n, P.sq.per, tiles_d,
+                           P.sd.per, part_q, part_d);
+        hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
+                           (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
+                           (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, IBDocGrads{ddocs, nullptr, M});
+    }
+}
+
 constexpr int IB_MAX_B = 1 << 24, IB_MAX_M = 1 << 25;
 
 bool ib_shape_ok(int B, int M, int H) { return B >= 1 && B <= IB_MAX_B && M >= B && M <= IB_MAX_M && H >= 1 && H <= IB_MAX_H; }
@@ -738,4 +1031,41 @@ TT_EXPORT int tt_contrastive_loss_soft_f32(const float *q, int B, const float *d
 {
     return ib_pool_call("tt_contrastive_loss_soft_f32", false, true, q, B, docs, M, H, 0, nullptr, nullptr, targets, temperature,
                         loss, dq, ddocs, workspace, workspace_bytes, stream);
+}
+
+TT_EXPORT size_t tt_contrastive_loss_sym_workspace_bytes(int B, int M, int H)
+{
+    return ib_shape_ok(B, M, H) ? ib_plan(B, M, H, false, true).total : 0;
+}
+
+TT_EXPORT int tt_contrastive_loss_sym_f32(const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                                          const int64_t *q_groups, const int64_t *doc_groups, float temperature, float alpha,
+                                          float *loss, float *loss_dirs, float *dq, float *ddocs, void *workspace,
+                                          size_t workspace_bytes, tt_stream_t stream)
+{
+    const char *who = "tt_contrastive_loss_sym_f32";
+    if (!ib_shape_ok(B, M, H))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", who, B, M, H, IB_MAX_B,
+                       IB_MAX_M, IB_MAX_H);
+    if (pos_offset < 0 || pos_offset > M - B)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: pos_offset=%d outside [0, M - B = %d]", who, pos_offset, M - B);
+    if (!(temperature > 0.0f && temperature <= FLT_MAX))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: temperature=%g must be finite and > 0", who, (double)temperature);
+    if (!(alpha >= 0.0f && alpha <= 1.0f))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: alpha=%g outside [0, 1]", who, (double)alpha);
+    if (!q_groups != !doc_groups)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: q_groups, doc_groups must be both null or both non-null", who);
+    if (!q || !docs || !loss || !workspace)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    if (!dq != !ddocs)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: dq, ddocs must be both null or both non-null", who);
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: the workspace must be 16-byte aligned", who);
+    const IBPlan P = ib_plan(B, M, H, false, true);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
+    ib_sym_launch(P, q, docs, B, M, H, pos_offset, q_groups, doc_groups, temperature, alpha, loss, loss_dirs, dq, ddocs, workspace,
+                  (hipStream_t)stream);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
 }

@@ -9,6 +9,8 @@
     contrastive_softmax_loss(q, docs, pos_offset=0, temperature=0.05) -> 0-d tensor      (the same over any pool of documents)
     ... both with group labels (groups=, neg_groups= / q_groups=, doc_groups=): a passage that carries a query's label, other
     than its own positive, is no negative of it
+    ... and with symmetric=alpha in (0, 1]: the bidirectional (CLIP-style) loss, each positive also classified among the queries;
+    symmetric_contrastive_losses(q, docs, ...) -> (L_qd, L_dq) reports the two directions
     soft_contrastive_loss(q, docs, targets, temperature=0.05) -> 0-d tensor              (the same softmax against a weight per pair:
     distillation_targets(teacher_scores, ...), multi_positive_targets(q_groups, doc_groups, pos_offset) make the weights)
 
@@ -33,6 +35,7 @@ import torch.nn as nn
 from . import _lib
 
 __all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "soft_contrastive_loss",
+           "symmetric_contrastive_losses",
            "distillation_targets", "multi_positive_targets", "SplitRecurrenceTimeout"]
 
 
@@ -563,7 +566,8 @@ class _InBatchFn(torch.autograd.Function):
 
 
 def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], temperature: float = 0.05,
-                          groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          groups: Optional[torch.Tensor] = None, neg_groups: Optional[torch.Tensor] = None,
+                          symmetric: float = 0.0) -> torch.Tensor:
     """In-batch negatives: mean_i(logsumexp_j s_ij - s_ii), s_ij = cos(q_i, D_j) / temperature over D = [p; n] -- every query
     is scored against all 2B passages of the batch (its own positive, the other queries' positives, all explicit negatives)
     instead of one hinge against one negative.  Cosine with eps 1e-8 per norm, as triplet_loss_cosine.  Differentiable (fused
@@ -572,8 +576,11 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
     ranks into one with gather_negatives=True).
     groups [B] (int64 on the device): grouped negatives -- query i and its positive carry groups[i], the negatives carry
     neg_groups [B] (None: -1, no group); a passage with query i's label >= 0, other than its own positive, is left out of its
-    softmax (contrastive_softmax_loss).  Rows of one query that the batch holds several times share a label."""
+    softmax (contrastive_softmax_loss).  Rows of one query that the batch holds several times share a label.
+    symmetric in (0, 1]: the weight of the document-to-query direction (contrastive_softmax_loss, on the pool [p; n]: each
+    positive is classified among the B queries; the explicit negatives have no query of their own)."""
     query, pos_doc, neg_doc = triplet
+    symmetric = _symmetric_weight("in_batch_softmax_loss", symmetric)
     if groups is None and neg_groups is not None:
         raise ValueError("in_batch_softmax_loss: neg_groups needs groups")
     for t in (query, pos_doc, neg_doc):
@@ -581,6 +588,8 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
             raise RuntimeError("in_batch_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
             raise ValueError("in_batch_softmax_loss wants three float32 [B,H] tensors of one shape")
+    if groups is None and symmetric > 0.0:
+        return contrastive_softmax_loss(query, torch.cat((pos_doc, neg_doc)), 0, temperature, symmetric=symmetric)
     if groups is None:
         return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)
     B = query.shape[0]
@@ -590,7 +599,8 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
     else:
         neg_groups = _group_labels("in_batch_softmax_loss", "neg_groups", neg_groups, B, query.device)
     # (the pool entry on [p; n]: the in-batch entry's bits)
-    return contrastive_softmax_loss(query, torch.cat((pos_doc, neg_doc)), 0, temperature, groups, torch.cat((groups, neg_groups)))
+    return contrastive_softmax_loss(query, torch.cat((pos_doc, neg_doc)), 0, temperature, groups, torch.cat((groups, neg_groups)),
+                                    symmetric=symmetric)
 
 
 def contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
@@ -630,6 +640,51 @@ class _ContrastiveFn(torch.autograd.Function):
         return g * dq, g * ddocs, None, None, None, None
 
 
+def symmetric_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
+    """An uninitialised workspace for tt_contrastive_loss_sym_f32 at q [B,H], docs [M,H] (the call rewrites all of it that it reads)."""
+    need = _lib.lib().tt_contrastive_loss_sym_workspace_bytes(B, M, H)
+    if need == 0:
+        raise ValueError(f"contrastive_softmax_loss: B={B} M={M} H={H} (1 <= B <= M <= 2^25, B <= 2^24, 1 <= H <= 512)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _symmetric_call(q, docs, pos_offset, temperature, alpha, q_groups, doc_groups, loss, dirs, dq, ddocs):
+    """tt_contrastive_loss_sym_f32 on contiguous tensors; dirs [2] and the gradients may be None."""
+    L = _lib.lib()
+    (B, H), M = q.shape, docs.shape[0]
+    ws = symmetric_workspace(B, M, H, q.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(q.device):
+        _lib.check(L.tt_contrastive_loss_sym_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), ptr(q_groups),
+                                                 ptr(doc_groups), float(temperature), float(alpha), loss.data_ptr(), ptr(dirs),
+                                                 ptr(dq), ptr(ddocs), ws.data_ptr(), ws.numel(), _stream(q.device)))
+
+
+class _SymmetricFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, docs, pos_offset: int, temperature: float, alpha: float, q_groups=None, doc_groups=None):
+        q, docs = q.contiguous(), docs.contiguous()
+        if q_groups is not None:
+            q_groups, doc_groups = q_groups.contiguous(), doc_groups.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        dq, ddocs = torch.empty_like(q), torch.empty_like(docs)
+        _symmetric_call(q, docs, pos_offset, temperature, alpha, q_groups, doc_groups, loss, None, dq, ddocs)
+        ctx.save_for_backward(dq, ddocs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, ddocs = ctx.saved_tensors
+        return g * dq, g * ddocs, None, None, None, None, None
+
+
+def _symmetric_weight(who: str, symmetric) -> float:
+    """`symmetric` as a float in [0, 1], or the ValueError (before any launch)."""
+    if isinstance(symmetric, bool) or not isinstance(symmetric, (int, float)) or not 0.0 <= float(symmetric) <= 1.0:  # (NaN fails)
+        raise ValueError(f"{who}: symmetric={symmetric!r} must be a number in [0, 1]")
+    return float(symmetric)
+
+
 def _group_labels(who: str, name: str, t, rows: int, device) -> torch.Tensor:
     """`t` as the labels of `rows` rows, or the ValueError that names the argument."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (rows,) or t.device != device:
@@ -638,8 +693,33 @@ def _group_labels(who: str, name: str, t, rows: int, device) -> torch.Tensor:
     return t
 
 
+def _contrastive_args(who: str, q, docs, pos_offset, temperature, q_groups, doc_groups):
+    """The checks of the pool losses, before any launch -> (B, M, q_groups, doc_groups)."""
+    if (q_groups is None) != (doc_groups is None):
+        raise ValueError(f"{who}: q_groups and doc_groups must be both given or both None")
+    for t in (q, docs):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who} runs only on an AMD GPU via libtt.so (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"{who} wants float32 q [B,H] and docs [M,H]")
+    (B, H), M = q.shape, docs.shape[0]
+    if docs.shape[1] != H:
+        raise ValueError(f"{who}: q has H={H}, docs has H={docs.shape[1]}")
+    if M < B:
+        raise ValueError(f"{who}: M={M} documents for B={B} queries (every query needs its positive: M >= B)")
+    if not 0 <= pos_offset <= M - B:
+        raise ValueError(f"{who}: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
+    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
+        raise ValueError(f"{who}: temperature={temperature!r} must be finite and > 0")
+    if q_groups is not None:
+        q_groups = _group_labels(who, "q_groups", q_groups, B, q.device)
+        doc_groups = _group_labels(who, "doc_groups", doc_groups, M, q.device)
+    return B, M, q_groups, doc_groups
+
+
 def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05,
-                             q_groups: Optional[torch.Tensor] = None, doc_groups: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             q_groups: Optional[torch.Tensor] = None, doc_groups: Optional[torch.Tensor] = None,
+                             symmetric: float = 0.0) -> torch.Tensor:
     """The softmax contrastive loss of B queries over a pool of M >= B documents:
     mean_i(logsumexp_j s_ij - s_{i, pos_offset+i}), s_ij = cos(q_i, docs_j) / temperature -- the positive of query i is row
     pos_offset + i of `docs`, every other row is a negative (the passages gathered from all ranks; or several explicit negatives
@@ -648,28 +728,36 @@ def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: in
     q_groups [B], doc_groups [M] (int64 on the device, both or neither): grouped negatives.  Row j is left out of query i's
     softmax -- logsumexp and both gradients -- when j != pos_offset + i, q_groups[i] >= 0 and doc_groups[j] == q_groups[i]:
     the other positives of a query that the batch holds several times are no negatives of it.  A negative label is "no group".
-    With no match off the positives the result is the ungrouped call's, bit for bit."""
-    if (q_groups is None) != (doc_groups is None):
-        raise ValueError("contrastive_softmax_loss: q_groups and doc_groups must be both given or both None")
-    for t in (q, docs):
-        if not t.is_cuda:
-            raise RuntimeError("contrastive_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
-        if t.dtype != torch.float32 or t.dim() != 2:
-            raise ValueError("contrastive_softmax_loss wants float32 q [B,H] and docs [M,H]")
-    (B, H), M = q.shape, docs.shape[0]
-    if docs.shape[1] != H:
-        raise ValueError(f"contrastive_softmax_loss: q has H={H}, docs has H={docs.shape[1]}")
-    if M < B:
-        raise ValueError(f"contrastive_softmax_loss: M={M} documents for B={B} queries (every query needs its positive: M >= B)")
-    if not 0 <= pos_offset <= M - B:
-        raise ValueError(f"contrastive_softmax_loss: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
-    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
-        raise ValueError(f"contrastive_softmax_loss: temperature={temperature!r} must be finite and > 0")
+    With no match off the positives the result is the ungrouped call's, bit for bit.
+    symmetric = alpha in (0, 1]: the SYMMETRIC loss (1 - alpha) L_qd + alpha L_dq -- L_qd the loss above, L_dq =
+    mean_i(logsumexp_{i'<B} s_{i', pos_offset+i} - s_{i, pos_offset+i}) classifies each positive document among the B queries
+    (the bidirectional InfoNCE; 0.5 is the CLIP loss).  Only the B positive rows of `docs` have a softmax of their own; every
+    other row stays a negative of the query-to-document direction alone.  With labels an ignored pair leaves both softmaxes.
+    0.0 is the one-directional loss above, on its own kernels; symmetric_contrastive_losses reports the two directions.
+    Soft targets (soft_contrastive_loss) do not combine with it."""
+    symmetric = _symmetric_weight("contrastive_softmax_loss", symmetric)
+    B, M, q_groups, doc_groups = _contrastive_args("contrastive_softmax_loss", q, docs, pos_offset, temperature, q_groups, doc_groups)
+    if symmetric > 0.0:
+        return _SymmetricFn.apply(q, docs, int(pos_offset), float(temperature), symmetric, q_groups, doc_groups)
     if q_groups is None:
         return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature))
-    q_groups = _group_labels("contrastive_softmax_loss", "q_groups", q_groups, B, q.device)
-    doc_groups = _group_labels("contrastive_softmax_loss", "doc_groups", doc_groups, M, q.device)
     return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature), q_groups, doc_groups)
+
+
+def symmetric_contrastive_losses(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05,
+                                 q_groups: Optional[torch.Tensor] = None,
+                                 doc_groups: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(L_qd, L_dq): the two directions of the symmetric contrastive_softmax_loss as 0-d tensors, for logging (one loss-only
+    call; not differentiable).  Whatever weight a step trains with, its loss is (1 - symmetric) L_qd + symmetric L_dq."""
+    _, _, q_groups, doc_groups = _contrastive_args("symmetric_contrastive_losses", q, docs, pos_offset, temperature, q_groups,
+                                                   doc_groups)
+    q, docs = q.detach().contiguous(), docs.detach().contiguous()
+    if q_groups is not None:
+        q_groups, doc_groups = q_groups.contiguous(), doc_groups.contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=q.device)
+    dirs = torch.empty(2, dtype=torch.float32, device=q.device)
+    _symmetric_call(q, docs, pos_offset, temperature, 0.0, q_groups, doc_groups, loss, dirs, None, None)
+    return dirs[0], dirs[1]
 
 
 def soft_contrastive_workspace(B: int, M: int, H: int, device) -> torch.Tensor:
@@ -719,7 +807,9 @@ def soft_contrastive_loss(q: torch.Tensor, docs: torch.Tensor, targets: torch.Te
     here; subtract it where KL itself is reported.
     One-hot targets (1 at pos_offset + i) give contrastive_softmax_loss(q, docs, pos_offset), bit for bit; an all-zero row
     gives that query no loss and no gradient.  Differentiable in q and docs, not in targets (fused forward + gradient kernels
-    on the f32 matrix pipe, deterministic; [B,M] logits never reach memory)."""
+    on the f32 matrix pipe, deterministic; [B,M] logits never reach memory).
+    The symmetric loss (contrastive_softmax_loss(symmetric=)) does not combine with soft targets: they define their own rows
+    and there are no column targets."""
     for t in (q, docs):
         if not t.is_cuda:
             raise RuntimeError("soft_contrastive_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")

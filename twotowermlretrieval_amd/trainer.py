@@ -27,7 +27,7 @@ from . import _lib
 from .collective import Collective
 from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, _soft_targets, contrastive_softmax_loss,
                     contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, soft_contrastive_loss,
-                    soft_contrastive_workspace, triplet_loss_cosine)
+                    soft_contrastive_workspace, symmetric_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -305,15 +305,45 @@ class FusedClipAdam(_FlatClipAdam):
                          _lib.lib().tt_clip_adam_scratch_bytes(), gate_fn=_hip_step_gate, gated_step_fn=_hip_clip_adam_gated)
 
 
-class _StepSpec(NamedTuple):
-    """What one train step is asked to do, apart from its batch (the arguments are train_step's: see there).  Built and checked
-    once at the public entries -- train_step, DataParallelTrainer, GraphedTrainStep --; everything below them takes the record."""
+class _StepSpecFields(NamedTuple):
     margin: float
     negatives: str
     temperature: float
     gather_negatives: bool
     concurrent_towers: bool
     direct: bool
+
+
+class _StepSpec(_StepSpecFields):
+    """What one train step is asked to do, apart from its batch (the arguments are train_step's: see there).  Built and checked
+    once at the public entries -- train_step, DataParallelTrainer, GraphedTrainStep --; everything below them takes the record.
+    The six tuple fields are what the record has always been (callers and tests compare and unpack it as that 6-tuple);
+    `symmetric`, the weight of the document-to-query direction of the "in_batch" loss (0.0: the one-directional loss), is the
+    seventh constructor argument and a read-only attribute beside them.  Two records are equal when fields and weight are."""
+
+    def __new__(cls, margin, negatives, temperature, gather_negatives, concurrent_towers, direct, symmetric=0.0):
+        self = super().__new__(cls, margin, negatives, temperature, gather_negatives, concurrent_towers, direct)
+        object.__setattr__(self, "symmetric", symmetric)
+        return self
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"can't set attribute {name!r}: a step specification is frozen")
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) and (not isinstance(other, _StepSpec) or self.symmetric == other.symmetric)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.symmetric))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", symmetric={self.symmetric!r})"
+
+    def _replace(self, **kw):
+        symmetric = kw.pop("symmetric", self.symmetric)
+        return type(self)(*_StepSpecFields._replace(self, **kw), symmetric)
 
     def checked(self, graphs: bool) -> "_StepSpec":
         """This record, or the ValueError of a combination no step can run: raised before anything is launched."""
@@ -324,6 +354,15 @@ class _StepSpec(NamedTuple):
         if self.gather_negatives and graphs:
             raise ValueError("gather_negatives=True is not available with graphs=True (the exchange of the passages sits between "
                              "the captured forward and backward)")
+        sym = self.symmetric
+        if isinstance(sym, bool) or not isinstance(sym, (int, float)) or not 0.0 <= float(sym) <= 1.0:  # (NaN fails)
+            raise ValueError(f"symmetric={sym!r} must be a number in [0, 1]")
+        if sym > 0 and self.negatives != "in_batch":
+            raise ValueError(f'symmetric={sym!r} needs negatives="in_batch", got negatives={self.negatives!r}')
+        if sym > 0 and self.gather_negatives:
+            raise ValueError("symmetric > 0 is not available with gather_negatives=True: over a gathered pool the softmax of a "
+                             "positive's column runs over the queries of ALL ranks, which needs a gather of the queries and a "
+                             "reduction of their gradients (a second exchange in the step's collective order)")
         return self
 
 
@@ -354,6 +393,9 @@ def _batch_targets(who: str, spec: _StepSpec, optimizer, batch, targets, groups=
     never come together with group labels."""
     if targets is None:
         return None
+    if spec.symmetric > 0:
+        raise ValueError(f"{who}: targets and symmetric > 0 exclude each other (soft targets define their own rows and there are "
+                         "no column targets)")
     if groups is not None or neg_groups is not None:
         raise ValueError(f"{who}: targets and groups / neg_groups exclude each other (soft targets say what every pair weighs)")
     if spec.negatives != "in_batch":
@@ -682,7 +724,9 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
     gather, label gather, reduce on every rank.
     targets (the batch's soft targets, "in_batch" only, never with labels): the soft entry on pn as it lies (M = 2B; the in-batch
     entry's bits for one-hot targets); gathered, on the pool with this rank's rows [B, world * 2B] -- the targets are rank-local,
-    so no collective is added and their order stays gather, reduce."""
+    so no collective is added and their order stays gather, reduce.
+    spec.symmetric > 0 ("in_batch" only, never gathered, never with targets): the symmetric entry on pn as it lies (M = 2B,
+    pos_offset = 0), with the labels when there are any."""
     (B, H), dev = q.shape, q.device
     loss = torch.empty((), dtype=torch.float32, device=dev)
     dq = torch.empty_like(q)
@@ -699,6 +743,8 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
         dpn = torch.empty_like(pn)
         if targets is not None:
             rows = soft_contrastive_workspace(B, 2 * B, H, dev)
+        elif spec.symmetric > 0:
+            rows = symmetric_workspace(B, 2 * B, H, dev)
         elif labels is not None:
             rows = contrastive_workspace(B, 2 * B, H, dev)
         else:
@@ -729,6 +775,11 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
             _lib.check(L.tt_contrastive_loss_soft_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, targets.data_ptr(),
                                                       float(spec.temperature), loss.data_ptr(), dq.data_ptr(), dpn.data_ptr(),
                                                       rows.data_ptr(), rows.numel(), s_main.cuda_stream))
+        elif spec.symmetric > 0:
+            lp = None if labels is None else labels.data_ptr()
+            _lib.check(L.tt_contrastive_loss_sym_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, 0, lp, lp, float(spec.temperature),
+                                                     float(spec.symmetric), loss.data_ptr(), None, dq.data_ptr(), dpn.data_ptr(),
+                                                     rows.data_ptr(), rows.numel(), s_main.cuda_stream))
         elif labels is not None:
             # (the queries' labels are the first B of the passages': the positives')
             _lib.check(L.tt_contrastive_loss_grouped_f32(q.data_ptr(), B, pn.data_ptr(), 2 * B, H, 0, labels.data_ptr(),
@@ -901,8 +952,9 @@ def _autograd_loss(spec: _StepSpec, optimizer, embeddings, pn, labels=None, targ
                                          temperature=spec.temperature)
         if labels is not None:
             B = embeddings[0].shape[0]
-            return in_batch_softmax_loss(embeddings, temperature=spec.temperature, groups=labels[:B], neg_groups=labels[B:])
-        return in_batch_softmax_loss(embeddings, temperature=spec.temperature)
+            return in_batch_softmax_loss(embeddings, temperature=spec.temperature, groups=labels[:B], neg_groups=labels[B:],
+                                         symmetric=spec.symmetric)
+        return in_batch_softmax_loss(embeddings, temperature=spec.temperature, symmetric=spec.symmetric)
     return triplet_loss_cosine(embeddings, margin=spec.margin)
 
 
@@ -999,7 +1051,8 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
                neg_docs: torch.Tensor, margin: float = 0.2, concurrent_towers: bool = True, direct: bool = True,
                defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05,
                gather_negatives: bool = False, groups: Optional[torch.Tensor] = None,
-               neg_groups: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None) -> torch.Tensor:
+               neg_groups: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
+               symmetric: float = 0.0) -> torch.Tensor:
     """One step of backend/main.py:244-259 on this rank's (equal-sized) share of the global batch.
     Returns the local loss as a 0-d device tensor (no .item(): the reference's per-step sync is dropped).
 
@@ -1046,8 +1099,16 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     from a teacher (model.distillation_targets) or several positives per query, each pulled (model.multi_positive_targets).
     One-hot targets (1 at column i) give the bits of the plain "in_batch" step.  With gather_negatives=True the targets are
     [B, world * 2B] with the columns in pool order (rank r's [p_r; n_r] at column r * 2B); they are this rank's own rows, so no
-    collective is added.  Not differentiated.  The direct and the autograd path give the same bits; a redo keeps the targets."""
-    spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct).checked(graphs=False)
+    collective is added.  Not differentiated.  The direct and the autograd path give the same bits; a redo keeps the targets.
+
+    symmetric (negatives="in_batch" only; a number in [0, 1]): the weight alpha of the document-to-query direction.  The loss
+    becomes (1 - alpha) L_qd + alpha L_dq (model.contrastive_softmax_loss): each positive passage is also classified among the
+    batch's B queries; the explicit negatives have no query of their own and stay negatives of the queries alone.  0.5 is the
+    CLIP loss; 0.0 (default) is the one-directional step, launch for launch.  Combines with groups / neg_groups (an ignored
+    pair leaves both softmaxes), not with targets (soft targets define their own rows; there are no column targets) and not
+    with gather_negatives=True (the column softmax would run over the queries of all ranks: a gather of the queries and a
+    reduction of their gradients, a second exchange in the step's collective order).  The negatives are rank-local."""
+    spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct, symmetric).checked(graphs=False)
     batch = (queries, pos_docs, neg_docs)
     targets = _batch_targets("train_step", spec, optimizer, batch, targets, groups, neg_groups)
     return _step(model, optimizer, batch, spec, defer_check, _batch_labels("train_step", spec, batch, groups, neg_groups), targets)
@@ -1064,14 +1125,17 @@ class DataParallelTrainer:
     negatives / temperature / gather_negatives: see train_step.  "in_batch" negatives are rank-local (each rank's softmax over
     its own 2B passages, gradients averaged over the ranks as for the triplet loss) unless gather_negatives=True: then the
     passages of all ranks are gathered and every query sees world * 2B - 1 negatives (every rank must bring the same B; two
-    more collectives per step, same order on every rank).  Not with graphs=True."""
+    more collectives per step, same order on every rank).  Not with graphs=True.
+    symmetric: see train_step (the symmetric "in_batch" loss on each rank's own batch: rank-local negatives, the gradients
+    averaged over the ranks as always; not with gather_negatives=True, not with targets)."""
 
     def __init__(self, model: TwoTowerModel, lr: float = 1e-4, margin: float = 0.2, max_norm: float = 1.0, group=None,
                  graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False,
-                 negatives: str = "paired", temperature: float = 0.05, gather_negatives: bool = False):
+                 negatives: str = "paired", temperature: float = 0.05, gather_negatives: bool = False, symmetric: float = 0.0):
         self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
         self.margin = margin
         self.negatives, self.temperature, self.gather_negatives = negatives, float(temperature), bool(gather_negatives)
+        self.symmetric = symmetric
         self._spec()
         self.model = model
         self.optimizer = FusedClipAdam(model.parameters(), lr=lr, max_norm=max_norm, group=group)
@@ -1080,7 +1144,8 @@ class DataParallelTrainer:
 
     def _spec(self) -> _StepSpec:
         """What a step does now (the attributes may be changed between steps)."""
-        return _StepSpec(self.margin, self.negatives, self.temperature, self.gather_negatives, True, True).checked(self.graphs)
+        return _StepSpec(self.margin, self.negatives, self.temperature, self.gather_negatives, True, True,
+                         self.symmetric).checked(self.graphs)
 
     def broadcast_parameters(self, src: int = 0) -> None:
         import torch.distributed as dist
@@ -1099,12 +1164,15 @@ class DataParallelTrainer:
             key += ("grouped",)   # (a step with labels is another graph: its loss node is the grouped entry's; others keep their key)
         if soft:
             key += ("soft",)      # (and so is a step with soft targets: the soft entry's)
+        if spec.symmetric > 0:
+            key += (("symmetric", float(spec.symmetric)),)   # (the weight is an argument of the captured symmetric entry)
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
                 self._graphs.pop(next(iter(self._graphs)))
             g = GraphedTrainStep(self.model, self.optimizer, key[0], key[1], key[2], spec.margin, defer_check=self.defer_check,
-                                 negatives=spec.negatives, temperature=spec.temperature, grouped=bool(grouped), soft=bool(soft))
+                                 negatives=spec.negatives, temperature=spec.temperature, grouped=bool(grouped), soft=bool(soft),
+                                 symmetric=spec.symmetric)
         self._graphs[key] = g                                      # (re-inserted: most recently used last)
         return g
 
@@ -1180,26 +1248,31 @@ class GraphedTrainStep:
     -1 (no group: the bits of the ungrouped step); neg_groups=None fills -1 for the negatives.
     soft=True (negatives="in_batch" only, not with grouped): the captured loss is the soft entry's; the batch's soft targets
     (train_step: targets) are a static float32 input [B, 2B], refilled in front of every replay.  A call without targets fills
-    the one-hot (1 at column i: the bits of the plain "in_batch" step)."""
+    the one-hot (1 at column i: the bits of the plain "in_batch" step).
+    symmetric (negatives="in_batch" only; train_step: symmetric): a captured argument like temperature; > 0 captures the
+    symmetric entry as the loss.  Combines with grouped=True; with soft=True it raises ValueError."""
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
                  defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05, grouped: bool = False,
-                 soft: bool = False):
-        # (margin, negatives and temperature are arguments of the captured loss launches)
-        self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True).checked(graphs=True)
+                 soft: bool = False, symmetric: float = 0.0):
+        # (margin, negatives, temperature and symmetric are arguments of the captured loss launches)
+        self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True, symmetric).checked(graphs=True)
         if grouped and negatives != "in_batch":
             raise ValueError(f'GraphedTrainStep: grouped=True needs negatives="in_batch", got negatives={negatives!r}')
         if soft and negatives != "in_batch":
             raise ValueError(f'GraphedTrainStep: soft=True needs negatives="in_batch", got negatives={negatives!r}')
         if soft and grouped:
             raise ValueError("GraphedTrainStep: soft=True and grouped=True exclude each other")
+        if soft and self._spec.symmetric > 0:
+            raise ValueError("GraphedTrainStep: soft=True and symmetric > 0 exclude each other (soft targets define their own rows "
+                             "and there are no column targets)")
         encs = (model.query_encoder, model.doc_encoder)
         if not isinstance(optimizer, _FlatClipAdam) or optimizer._gated_step_fn is None:
             raise TypeError("GraphedTrainStep needs a FusedClipAdam")
         if not all(e.check_inputs for e in encs):
             raise ValueError("GraphedTrainStep: input checking must be on (the gate is what keeps a bad batch from being applied)")
         self.model, self.optimizer, self.margin = model, optimizer, float(margin)
-        self.negatives, self.temperature = negatives, float(temperature)
+        self.negatives, self.temperature, self.symmetric = negatives, float(temperature), float(symmetric)
         self.B, self.q_width, self.doc_width = int(batch), int(q_width), int(doc_width)
         self.defer_check = bool(defer_check)
         dev = optimizer.flat_params.device
