@@ -993,6 +993,57 @@ int tt_contrastive_loss_sym_f32(const float *q /*[B,H]*/, int B, const float *do
                                 void *workspace, size_t workspace_bytes, tt_stream_t stream);
 
 /*
+ * The same losses with a DEVICE-RESIDENT, learnable logit scale (CLIP's logit_scale, clamped) in place of `float temperature`.
+ * log_scale [1] f32, device: the word l = log(1 / T).  The kernels read it WHEN THEY RUN -- never on the host, never at enqueue
+ * time -- so a captured graph that holds this call sees, at every replay, what the word holds then (an optimizer's update, a
+ * schedule's next value), with nothing staged.
+ *   lc = clamp(l, min_log_scale, max_log_scale)      T = expf(-lc)      s_ij = (qh_i . Dh_j) / T
+ * One thread of the first launch forms T and stores it in the workspace, and in temperature_out [1] (nullable, device); every
+ * later launch of the call reads that stored word.  Everything else is the float entries' arithmetic, statement for statement:
+ *
+ * tt_contrastive_loss_ls_f32: no labels, no targets = tt_contrastive_loss_f32; q_groups and doc_groups (both or neither) =
+ *   tt_contrastive_loss_grouped_f32; targets [B,M] (never with labels; pos_offset is then checked and not used) =
+ *   tt_contrastive_loss_soft_f32.  tt_contrastive_loss_sym_ls_f32 = tt_contrastive_loss_sym_f32.
+ * Exact: the matching float entry, called with temperature = the value read back from temperature_out, writes the same bytes
+ * to loss, loss_dirs, dq and ddocs.
+ *
+ * d_log_scale [1] (nullable, device) = d loss / d l.  With G = (d loss / d s) / T, the matrix the gradient pass forms, and
+ * c_ij = qh_i . Dh_j:
+ *   d loss / d log(1/T) = sum_ij (d loss / d s_ij) s_ij = sum_ij G_ij c_ij = sum_{i<B} qh_i . dqh_i,    dqh_i = sum_j G_ij Dh_j
+ * for every variant alike (dqh carries every term of G).  The last launch forms qh_i . dqh_i per query, from the sum of the
+ * slices' partials, in front of its back-projection (which is why dq cannot give it: q_i . dq_i = 0); one more one-block launch
+ * adds the B dots in one fixed order.  The clamp's derivative is torch.clamp's: the sum where min <= l <= max, and exactly +0.0f
+ * elsewhere -- a select, so that no NaN of a clamped call reaches it.
+ * dq, ddocs: both or none.  d_log_scale may be null on its own (a fixed temperature that lives on the device: dq and ddocs
+ * are the same bits with and without it) and must be null when dq is.  A loss-only call writes the same loss bits.
+ * A NaN in l is data and cannot be refused: it passes the clamp (comparisons, not fminf/fmaxf) and gives NaN in loss and
+ * d_log_scale; no address depends on T, so nothing faults.
+ * Refusals (TT_ERR_BAD_SHAPE): what the float entries refuse; labels together with targets; a null log_scale; bounds that are
+ * NaN, min > max, or outside [-80, 80] (expf stays finite and normal); d_log_scale without dq; a short workspace.
+ * Deterministic: no atomics, every sum in one fixed order that depends on (B, M, H) alone, whatever the workspace and the
+ * outputs held on entry.  Asynchronous on `stream`; capture-clean.  Launches: the float entry's, plus one with d_log_scale.
+ * workspace: tt_contrastive_loss_ls_workspace_bytes(B, M, H, soft) (soft != 0: for a call with targets) and
+ * tt_contrastive_loss_sym_ls_workspace_bytes(B, M, H) bytes (0 for a shape the call refuses; no GPU needed): the float entry's
+ * plan plus T, the clamp's gate and the B dots; 16-byte aligned, caller-owned.
+ */
+size_t tt_contrastive_loss_ls_workspace_bytes(int B, int M, int H, int soft);
+int tt_contrastive_loss_ls_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H, int pos_offset,
+                               const int64_t *q_groups /*[B] nullable*/, const int64_t *doc_groups /*[M] nullable*/,
+                               const float *targets /*[B,M] nullable*/, const float *log_scale /*[1] device*/,
+                               float min_log_scale, float max_log_scale, float *loss /*[1]*/,
+                               float *temperature_out /*[1] nullable*/, float *d_log_scale /*[1] nullable*/,
+                               float *dq /*[B,H]*/, float *ddocs /*[M,H]*/, void *workspace, size_t workspace_bytes,
+                               tt_stream_t stream);
+size_t tt_contrastive_loss_sym_ls_workspace_bytes(int B, int M, int H);
+int tt_contrastive_loss_sym_ls_f32(const float *q /*[B,H]*/, int B, const float *docs /*[M,H]*/, int M, int H, int pos_offset,
+                                   const int64_t *q_groups /*[B] nullable*/, const int64_t *doc_groups /*[M] nullable*/,
+                                   const float *log_scale /*[1] device*/, float min_log_scale, float max_log_scale,
+                                   float alpha, float *loss /*[1]*/, float *loss_dirs /*[2] nullable: L_qd, L_dq*/,
+                                   float *temperature_out /*[1] nullable*/, float *d_log_scale /*[1] nullable*/,
+                                   float *dq /*[B,H]*/, float *ddocs /*[M,H]*/, void *workspace, size_t workspace_bytes,
+                                   tt_stream_t stream);
+
+/*
  * Replaces torch.nn.utils.clip_grad_norm_(params, max_norm) ; torch.optim.Adam(...).step()
  *   backend/main.py:257,259 (optimizer built at :222; betas (0.9,0.999), eps 1e-8, no weight decay)
  * over ONE flat fp32 buffer of n elements (params, grads, exp_avg, exp_avg_sq).  grads are first

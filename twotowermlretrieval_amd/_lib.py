@@ -142,6 +142,12 @@ SIGNATURES = {
     "tt_contrastive_loss_soft_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tt_contrastive_loss_sym_workspace_bytes": (_sz, [_i, _i, _i]),
     "tt_contrastive_loss_sym_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tt_contrastive_loss_ls_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "tt_contrastive_loss_ls_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                        _vp]),
+    "tt_contrastive_loss_sym_ls_workspace_bytes": (_sz, [_i, _i, _i]),
+    "tt_contrastive_loss_sym_ls_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _sz, _vp]),
     "tt_allgather_topk":(_i, [_vp, _vp, _vp, _sz, _vp]),
     "tt_allreduce_grads": (_i, [_vp, _vp, _i64, _vp]),
     "tt_comm_library": (C.c_char_p, []),

@@ -45,6 +45,18 @@
 // grid), ib_sym_lse_kernel (3, also clse and the two directions' row losses), 4 three times (loss, L_qd, L_dq),
 // ib_sym_grad_kernel (5), 6.
 //
+// Device-resident logit scale (tt_contrastive_loss_ls_f32 = plain / grouped / soft, tt_contrastive_loss_sym_ls_f32; the *_ls
+// and *_dots kernels): the temperature is no argument but a word l = log(1 / T) in device memory that the kernels read WHEN THEY
+// RUN (a graph replay sees what the word holds then).  The first thread of launch 1 forms T = expf(-clamp(l, lo, hi)) once --
+// the clamp as comparisons, so a NaN stays a NaN -- and stores it in the workspace (and in temperature_out); launches 2 and 5 load
+// that word and are otherwise the float entries' bodies with `temperature` = it: scores acc / T, scale 1 / (B T), statement
+// for statement, so the float entry called at the T read back writes the same bytes.  The scale's gradient needs nothing new:
+// with G = (dL/ds) / T the matrix launch 5 forms and c_ij = qh_i . Dh_j,
+//   dL/dl = dL/d log(1/T) = sum_ij (dL/ds_ij) s_ij = sum_ij G_ij c_ij = sum_{i<B} qh_i . dqh_i        (dqh = G Dh)
+// for every variant (dqh carries every term of G), and qh_i . dqh_i is the dot launch 6 forms for its back-projection (which is
+// why dq cannot give it back: q_i . dq_i = 0).  ib_project_dots_kernel stores it per query -- +0.0f where the clamp holds
+// gradient back, by a select -- and one more ib_sum_kernel adds the B dots, scale 1, in its fixed order.  No address depends on T.
+//
 // Six launches on one stream (four without gradients), no cross-workgroup wait, no atomics:
 //   1 ib_prep_kernel     one wave per row: clamped norm, normalised zero-padded images qh [Bq][Hp], Dh [Dp][Hp]
 //   2 ib_stats_kernel    a workgroup per (32 queries, slice of the documents): S^T tiles on v_mfma_f32_32x32x2_f32, online
@@ -94,9 +106,10 @@ struct IBPlan {
     size_t pw, pt, w;  // soft targets only, behind everything else
     IBSlices sc;       // symmetric only: slices of the queries a tile of positive columns walks (statistics)
     size_t cpm, cpl, clse, rows_qd, rows_dq;  // symmetric only, behind everything else
+    size_t tword, dots;  // device-resident scale only, behind everything else
 };
 
-IBPlan ib_plan(int B, int M, int H, bool soft = false, bool sym = false)
+IBPlan ib_plan(int B, int M, int H, bool soft = false, bool sym = false, bool ls = false)
 {
     IBPlan P;
     P.Hp = (H + 31) / 32 * 32;
@@ -131,6 +144,11 @@ IBPlan ib_plan(int B, int M, int H, bool soft = false, bool sym = false)
         P.rows_qd = w.take(sizeof(float) * (size_t)P.Bq);       // lse_i - s_pos, clse_i - s_pos
         P.rows_dq = w.take(sizeof(float) * (size_t)P.Bq);
     }
+    P.tword = P.dots = 0;
+    if (ls) {  // (appended likewise)
+        P.tword = w.take(sizeof(float) * 4);               // T = exp(-clamp(l)); 1 where the clamp passes gradient, else 0
+        P.dots = w.take(sizeof(float) * (size_t)P.Bq);     // qh_i . dqh_i
+    }
     P.total = w.off;
     return P;
 }
@@ -147,10 +165,9 @@ struct IBDocGrads {
 };
 
 // Row r of [queries (Bq rows); documents (Dp rows)]; rows past B / M and columns past H are written as zeros.
-__global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ q, IBDocs docs, int B, int M, int H, int Hp,
-                                                      int Bq, int Dp,
-                                                      float *__restrict__ qh, float *__restrict__ dh,
-                                                      float *__restrict__ den, float *__restrict__ flag)
+__device__ __forceinline__ void ib_prep_body(const float *__restrict__ q, IBDocs docs, int B, int M, int H, int Hp, int Bq,
+                                             int Dp, float *__restrict__ qh, float *__restrict__ dh,
+                                             float *__restrict__ den, float *__restrict__ flag)
 {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -181,6 +198,37 @@ __global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ 
         den[r] = d;
         flag[r] = norm >= IB_EPS ? 1.0f : 0.0f;
     }
+}
+
+__global__ __launch_bounds__(256) void ib_prep_kernel(const float *__restrict__ q, IBDocs docs, int B, int M, int H, int Hp,
+                                                      int Bq, int Dp,
+                                                      float *__restrict__ qh, float *__restrict__ dh,
+                                                      float *__restrict__ den, float *__restrict__ flag)
+{
+    ib_prep_body(q, docs, B, M, H, Hp, Bq, Dp, qh, dh, den, flag);
+}
+
+// The device-resident scale (the *_ls entries): the same launch, and its first thread forms the temperature of the whole call
+// from the word l = *log_scale as it is NOW, when the kernel runs (a graph replay reads what the word holds at replay):
+//   T = expf(-clamp(l, lo, hi)) -> tw[0] (and t_out);  tw[1] = 1 where lo <= l <= hi (the clamp passes gradient), else 0.
+// The clamp is comparisons, not fminf/fmaxf: a NaN l fails both and stays a NaN (and its gate is 1: the NaN reaches every
+// output that depends on T).  Every later launch of the call reads tw[0]; no address depends on it.
+__global__ __launch_bounds__(256) void ib_prep_ls_kernel(const float *__restrict__ q, IBDocs docs, int B, int M, int H, int Hp,
+                                                         int Bq, int Dp, float *__restrict__ qh, float *__restrict__ dh,
+                                                         float *__restrict__ den, float *__restrict__ flag,
+                                                         const float *__restrict__ log_scale, float lo, float hi,
+                                                         float *__restrict__ tw, float *__restrict__ t_out)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const float l = log_scale[0];
+        const float lc = l < lo ? lo : (l > hi ? hi : l);
+        const float T = expf(-lc);
+        tw[0] = T;
+        tw[1] = (l < lo || l > hi) ? 0.0f : 1.0f;
+        if (t_out)
+            t_out[0] = T;
+    }
+    ib_prep_body(q, docs, B, M, H, Hp, Bq, Dp, qh, dh, den, flag);
 }
 
 // S^T tile on the matrix pipe: acc[reg] = A_row(a0 + rho(reg) + 4 * (lane >> 5)) . B_row(b0 + (lane & 31)), rho(reg) =
@@ -484,6 +532,31 @@ __global__ __launch_bounds__(256) void ib_sym_stats_kernel(const float *__restri
     }
 }
 
+// The statistics launch of the *_ls entries, every variant in one 1-D grid laid out like ib_sym_stats_kernel's (!SYM: no column
+// blocks): the temperature is the word the first launch stored, read here, and the bodies are the ones above.
+template <bool GROUPED, bool SOFT, bool SYM>
+__global__ __launch_bounds__(256) void ib_stats_ls_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                          const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B,
+                                                          int M, int pos_offset, int Hp, int Bq, int tiles_per_slice,
+                                                          int tiles_per_slice_c, const float *__restrict__ tw, int tiles_q,
+                                                          int slices_q, int tile_c0, int tiles_c, float *__restrict__ pm,
+                                                          float *__restrict__ pl, float *__restrict__ pos,
+                                                          float *__restrict__ cpm, float *__restrict__ cpl,
+                                                          const float *__restrict__ tg, float *__restrict__ pw,
+                                                          float *__restrict__ pt)
+{
+    const float temperature = tw[0];
+    int b = blockIdx.x;
+    if (!SYM || b < tiles_q * slices_q) {
+        ib_stats_body<GROUPED, SOFT, false>(qh, dh, qg, dg, B, M, pos_offset, Hp, Bq, tiles_per_slice, temperature, pm, pl, pos,
+                                            tg, pw, pt, b % tiles_q, b / tiles_q);
+    } else {
+        b -= tiles_q * slices_q;
+        ib_stats_body<GROUPED, false, true>(qh, dh, qg, dg, B, M, pos_offset, Hp, Bq, tiles_per_slice_c, temperature, cpm, cpl,
+                                            nullptr, nullptr, nullptr, nullptr, tile_c0 + b % tiles_c, b / tiles_c);
+    }
+}
+
 // The slices' pairs of a query in ascending order -> lse_i and the row's loss lse_i - s_{i, pos_offset + i}.  The slice of the
 // positive has a finite maximum, so M is finite; a slice that is empty for the query (grouped labels) comes as (-inf, 0) and
 // adds 0 * exp(-inf - M) = 0 * 0.
@@ -780,6 +853,35 @@ __global__ __launch_bounds__(256) void ib_sym_grad_kernel(const float *__restric
     }
 }
 
+// The gradient launch of the *_ls entries, every variant: ib_grad_kernel's grid and slicing, the temperature read from the word
+// the first launch stored.
+template <bool GROUPED, bool SOFT, bool SYM>
+__global__ __launch_bounds__(256) void ib_grad_ls_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                         const float *__restrict__ lse, const float *__restrict__ clse,
+                                                         const int64_t *__restrict__ qg, const int64_t *__restrict__ dg, int B,
+                                                         int M, int pos_offset, int Hp, int Bq, int Dp,
+                                                         const float *__restrict__ tw, float alpha, int tiles_q, int slices_q,
+                                                         int per_q, int tiles_d, int per_d, float *__restrict__ part_q,
+                                                         float *__restrict__ part_d, const float *__restrict__ tg,
+                                                         const float *__restrict__ wq)
+{
+    extern __shared__ __attribute__((aligned(16))) float ib_lds[];  // G [128][32], later the gradient tile [32][Hp]
+    const float temperature = tw[0];
+    int b = blockIdx.x;
+    if (b < tiles_q * slices_q) {
+        const int slice = b / tiles_q, chunks = (M + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_q < chunks ? (slice + 1) * per_q : chunks;
+        ib_grad_body<true, GROUPED, SOFT, SYM>(ib_lds, qh, dh, lse, qg, dg, tg, wq, B, M, pos_offset, Hp, temperature, b % tiles_q,
+                                               slice * per_q, end, part_q + (size_t)slice * Bq * Hp, clse, alpha);
+    } else {
+        b -= tiles_q * slices_q;
+        const int slice = b / tiles_d, chunks = (B + IB_CHUNK - 1) / IB_CHUNK;
+        const int end = (slice + 1) * per_d < chunks ? (slice + 1) * per_d : chunks;
+        ib_grad_body<false, GROUPED, SOFT, SYM>(ib_lds, qh, dh, lse, qg, dg, tg, wq, B, M, pos_offset, Hp, temperature, b % tiles_d,
+                                                slice * per_d, end, part_d + (size_t)slice * Dp * Hp, clse, alpha);
+    }
+}
+
 // ------------------------------------------------------------------ 6: through the norms
 // One wave per row of [q; documents]: the slices' partials in ascending order -> dxh, then
 // dx = (dxh - xh (xh . dxh)) / ||x||, or dxh / eps for a row shorter than eps: (dxh - flag xh (xh . dxh)) / max(||x||, eps).
@@ -831,6 +933,62 @@ __global__ __launch_bounds__(256) void ib_project_kernel(const float *__restrict
     }
 }
 
+// The *_ls entries with d_log_scale: ib_project_kernel's statements, one for one (the kernel above keeps its text, as
+// ib_stats_kernel does: behind a shared function its registers change), and a query's wave also stores its xh . dxh =
+// qh_i . dqh_i to dots[i] -- the row's share of dL/d(log 1/T) = sum_ij G_ij c_ij -- or, where the clamp of the scale holds
+// gradient back (tw[1] == 0), +0.0f: a select per row, so that no NaN of a clamped call reaches the sum.
+__global__ __launch_bounds__(256) void ib_project_dots_kernel(const float *__restrict__ qh, const float *__restrict__ dh,
+                                                              const float *__restrict__ den, const float *__restrict__ flag,
+                                                              const float *__restrict__ part_q,
+                                                              const float *__restrict__ part_d, int B, int M, int H, int Hp,
+                                                              int Bq, int Dp, int slices_q, int slices_d,
+                                                              float *__restrict__ dq, IBDocGrads dd,
+                                                              const float *__restrict__ tw, float *__restrict__ dots)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= B + M)
+        return;
+    const bool is_q = r < B;
+    const int row = is_q ? r : r - B;  // row of the image
+    const float *xh = (is_q ? qh : dh) + (size_t)row * Hp;
+    const float *part = (is_q ? part_q : part_d) + (size_t)row * Hp;
+    const size_t stride = (size_t)(is_q ? Bq : Dp) * Hp;
+    const int ns = is_q ? slices_q : slices_d, nr = is_q ? row : Bq + row;
+    float gv[IB_MAX_H / 64], dot = 0.0f;
+#pragma unroll
+    for (int e = 0; e < IB_MAX_H / 64; ++e) {
+        const int u = lane + 64 * e;
+        float g = 0.0f;
+        if (u < Hp) {
+            float v[IB_MAX_SLICES];  // (all slices asked for at once, added in ascending order)
+#pragma unroll
+            for (int s = 0; s < IB_MAX_SLICES; ++s)
+                v[s] = s < ns ? part[s * stride + u] : 0.0f;
+            g = v[0];
+#pragma unroll
+            for (int s = 1; s < IB_MAX_SLICES; ++s)
+                if (s < ns)
+                    g += v[s];
+            dot += xh[u] * g;
+        }
+        gv[e] = g;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        dot += __shfl_xor(dot, off);
+    if (is_q && lane == 0)
+        dots[row] = tw[1] != 0.0f ? dot : 0.0f;
+    const float d = den[nr], f = flag[nr] * dot;
+    float *out = is_q ? dq + (size_t)row * H : (row < dd.split ? dd.lo + (size_t)row * H : dd.hi + (size_t)(row - dd.split) * H);
+#pragma unroll
+    for (int e = 0; e < IB_MAX_H / 64; ++e) {
+        const int u = lane + 64 * e;
+        if (u < H)
+            out[u] = (gv[e] - f * xh[u]) / d;
+    }
+}
+
 // Fixed-order sum of x[0..n) by one block -> out[0] * scale.
 __global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ x, int n, float scale, float *__restrict__ out)
 {
@@ -852,50 +1010,102 @@ __global__ __launch_bounds__(1024) void ib_sum_kernel(const float *__restrict__ 
     }
 }
 
+// The device-resident scale of a *_ls call (null for the float entries): the word, its clamp, and where T and dL/dl go.
+struct IBScale {
+    const float *log_scale;
+    float lo, hi;
+    float *t_out, *d_out;  // nullable each
+};
+
+// Launches 1 and 6 of every entry.  ls: the first thread of launch 1 also forms T (P is then an ls plan); with ls->d_out,
+// launch 6 also stores the row dots and one more ib_sum_kernel adds them, scale 1, in its fixed order.
+void ib_launch_prep(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, const IBScale *ls, char *ws, hipStream_t st)
+{
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den), *flag = (float *)(ws + P.flag);
+    if (ls)
+        hipLaunchKernelGGL(ib_prep_ls_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, docs, B, M, H, P.Hp, P.Bq, P.Dp, qh,
+                           dh, den, flag, ls->log_scale, ls->lo, ls->hi, (float *)(ws + P.tword), ls->t_out);
+    else
+        hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, docs, B, M, H, P.Hp, P.Bq, P.Dp, qh, dh,
+                           den, flag);
+}
+void ib_launch_project(const IBPlan &P, int B, int M, int H, float *dq, IBDocGrads dd, const IBScale *ls, char *ws, hipStream_t st)
+{
+    const float *qh = (const float *)(ws + P.qh), *dh = (const float *)(ws + P.dh), *den = (const float *)(ws + P.den);
+    const float *flag = (const float *)(ws + P.flag), *part_q = (const float *)(ws + P.part_q);
+    const float *part_d = (const float *)(ws + P.part_d);
+    const dim3 grid((unsigned)(((size_t)B + M + 3) / 4));
+    if (ls && ls->d_out) {
+        float *dots = (float *)(ws + P.dots);
+        hipLaunchKernelGGL(ib_project_dots_kernel, grid, dim3(256), 0, st, qh, dh, den, flag, part_q, part_d, B, M, H, P.Hp, P.Bq,
+                           P.Dp, P.sq.n, P.sd.n, dq, dd, (const float *)(ws + P.tword), dots);
+        hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)dots, B, 1.0f, ls->d_out);
+    } else
+        hipLaunchKernelGGL(ib_project_kernel, grid, dim3(256), 0, st, qh, dh, den, flag, part_q, part_d, B, M, H, P.Hp, P.Bq, P.Dp,
+                           P.sq.n, P.sd.n, dq, dd);
+}
+
 // The launches of one call; the entries have refused what they refuse.  dd.lo == nullptr: the loss only.  qg == nullptr: no
 // labels (the ungrouped instantiations); else qg [B], dg [M].  tg != nullptr: soft targets [B][M] (P is the soft plan, no labels,
-// pos_offset unused).
+// pos_offset unused).  ls != nullptr: `temperature` is unused, launches 2 and 5 are the *_ls_kernel forms.
 void ib_launch(const IBPlan &P, const float *q, IBDocs docs, int B, int M, int H, int pos_offset, const int64_t *qg,
                const int64_t *dg, const float *tg, float temperature, float *loss, float *dq, IBDocGrads dd, void *workspace,
-               hipStream_t st)
+               hipStream_t st, const IBScale *ls = nullptr)
 {
     char *ws = (char *)workspace;
-    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
-    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
-    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, docs, B, M, H, P.Hp, P.Bq, P.Dp, qh, dh,
-                       den, flag);
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh);
+    float *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
+    ib_launch_prep(P, q, docs, B, M, H, ls, ws, st);
     float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
     float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
     const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
     float *pw = tg ? (float *)(ws + P.pw) : nullptr, *pt = tg ? (float *)(ws + P.pt) : nullptr;
     float *wq = tg ? (float *)(ws + P.w) : nullptr;
-    const auto stats_kernel = tg ? ib_stats_kernel<false, true> : qg ? ib_stats_kernel<true, false> : ib_stats_kernel<false, false>;
-    const auto grad_kernel = tg ? ib_grad_kernel<false, true> : qg ? ib_grad_kernel<true, false> : ib_grad_kernel<false, false>;
-    hipLaunchKernelGGL(stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M,
-                       pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos, tg, pw, pt);
+    const float *tw = (const float *)(ws + P.tword);
+    if (ls) {
+        const auto stats_kernel = tg   ? ib_stats_ls_kernel<false, true, false>
+                                  : qg ? ib_stats_ls_kernel<true, false, false>
+                                       : ib_stats_ls_kernel<false, false, false>;
+        hipLaunchKernelGGL(stats_kernel, dim3(tiles_q * P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B,
+                           M, pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), 0, tw, tiles_q, P.sq.n, 0, 0, pm, pl, pos,
+                           (float *)nullptr, (float *)nullptr, tg, pw, pt);
+    } else {
+        const auto stats_kernel = tg ? ib_stats_kernel<false, true> : qg ? ib_stats_kernel<true, false> : ib_stats_kernel<false, false>;
+        hipLaunchKernelGGL(stats_kernel, dim3(tiles_q, P.sq.n), dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M,
+                           pos_offset, P.Hp, P.Bq, P.sq.per * (IB_CHUNK / IB_TILE), temperature, pm, pl, pos, tg, pw, pt);
+    }
     hipLaunchKernelGGL(tg ? ib_lse_kernel<true> : ib_lse_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
                        (const float *)pos, B, P.Bq, P.sq.n, lse, rows, (const float *)pw, (const float *)pt, wq);
     hipLaunchKernelGGL(ib_sum_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, B, 1.0f / (float)B, loss);
     if (dq) {
         const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
         const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
-        hipLaunchKernelGGL(grad_kernel, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n), dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, qg, dg, B, M, pos_offset,
-                           P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d, tg, (const float *)wq);
-        hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
-                           (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
-                           (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, dd);
+        const dim3 grid(tiles_q * P.sq.n + tiles_d * P.sd.n);
+        if (ls) {
+            const auto grad_kernel = tg   ? ib_grad_ls_kernel<false, true, false>
+                                     : qg ? ib_grad_ls_kernel<true, false, false>
+                                          : ib_grad_ls_kernel<false, false, false>;
+            hipLaunchKernelGGL(grad_kernel, grid, dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse,
+                               (const float *)nullptr, qg, dg, B, M, pos_offset, P.Hp, P.Bq, P.Dp, tw, 0.0f, tiles_q, P.sq.n,
+                               P.sq.per, tiles_d, P.sd.per, part_q, part_d, tg, (const float *)wq);
+        } else {
+            const auto grad_kernel = tg ? ib_grad_kernel<false, true> : qg ? ib_grad_kernel<true, false> : ib_grad_kernel<false, false>;
+            hipLaunchKernelGGL(grad_kernel, grid, dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, qg, dg, B, M, pos_offset,
+                               P.Hp, P.Bq, P.Dp, temperature, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d, tg, (const float *)wq);
+        }
+        ib_launch_project(P, B, M, H, dq, dd, ls, ws, st);
     }
 }
 
 // The launches of one symmetric call (P is the sym plan; the entry has refused what it refuses).  qg == nullptr: no labels.
-// loss_dirs == nullptr: the two directions' means are not written (their row losses are).
+// loss_dirs == nullptr: the two directions' means are not written (their row losses are).  ls as in ib_launch.
 void ib_sym_launch(const IBPlan &P, const float *q, const float *docs, int B, int M, int H, int pos_offset, const int64_t *qg,
                    const int64_t *dg, float temperature, float alpha, float *loss, float *loss_dirs, float *dq, float *ddocs,
-                   void *workspace, hipStream_t st)
+                   void *workspace, hipStream_t st, const IBScale *ls = nullptr)
 {
     char *ws = (char *)workspace;
-    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh), *den = (float *)(ws + P.den);
-    float *flag = (float *)(ws + P.flag), *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
+    float *qh = (float *)(ws + P.qh), *dh = (float *)(ws + P.dh);
+    float *lse = (float *)(ws + P.lse), *rows = (float *)(ws + P.rows);
     float *pm = (float *)(ws + P.pm), *pl = (float *)(ws + P.pl), *pos = (float *)(ws + P.pos);
     float *part_q = (float *)(ws + P.part_q), *part_d = (float *)(ws + P.part_d);
     float *cpm = (float *)(ws + P.cpm), *cpl = (float *)(ws + P.cpl), *clse = (float *)(ws + P.clse);
@@ -903,12 +1113,20 @@ void ib_sym_launch(const IBPlan &P, const float *q, const float *docs, int B, in
     const int tiles_q = (B + IB_TILE - 1) / IB_TILE, tiles_d = (M + IB_TILE - 1) / IB_TILE;
     // the aligned document tiles that meet the positive columns [pos_offset, pos_offset + B)
     const int tile_c0 = pos_offset / IB_TILE, tiles_c = (pos_offset + B - 1) / IB_TILE - tile_c0 + 1;
-    hipLaunchKernelGGL(ib_prep_kernel, dim3((P.Bq + P.Dp + 3) / 4), dim3(256), 0, st, q, IBDocs{docs, nullptr, M}, B, M, H, P.Hp,
-                       P.Bq, P.Dp, qh, dh, den, flag);
-    hipLaunchKernelGGL(qg ? ib_sym_stats_kernel<true> : ib_sym_stats_kernel<false>, dim3(tiles_q * P.sq.n + tiles_c * P.sc.n),
-                       dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
-                       P.sq.per * (IB_CHUNK / IB_TILE), P.sc.per * (IB_CHUNK / IB_TILE), temperature, tiles_q, P.sq.n, tile_c0,
-                       tiles_c, pm, pl, pos, cpm, cpl);
+    const float *tw = (const float *)(ws + P.tword);
+    ib_launch_prep(P, q, IBDocs{docs, nullptr, M}, B, M, H, ls, ws, st);
+    const dim3 stats_grid(tiles_q * P.sq.n + tiles_c * P.sc.n);
+    if (ls) {
+        const auto stats_kernel = qg ? ib_stats_ls_kernel<true, false, true> : ib_stats_ls_kernel<false, false, true>;
+        hipLaunchKernelGGL(stats_kernel, stats_grid,
+                           dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
+                           P.sq.per * (IB_CHUNK / IB_TILE), P.sc.per * (IB_CHUNK / IB_TILE), tw, tiles_q, P.sq.n, tile_c0, tiles_c,
+                           pm, pl, pos, cpm, cpl, (const float *)nullptr, (float *)nullptr, (float *)nullptr);
+    } else
+        hipLaunchKernelGGL(qg ? ib_sym_stats_kernel<true> : ib_sym_stats_kernel<false>, stats_grid,
+                           dim3(256), 0, st, (const float *)qh, (const float *)dh, qg, dg, B, M, pos_offset, P.Hp, P.Bq,
+                           P.sq.per * (IB_CHUNK / IB_TILE), P.sc.per * (IB_CHUNK / IB_TILE), temperature, tiles_q, P.sq.n, tile_c0,
+                           tiles_c, pm, pl, pos, cpm, cpl);
     hipLaunchKernelGGL(ib_sym_lse_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const float *)pm, (const float *)pl,
                        (const float *)cpm, (const float *)cpl, (const float *)pos, B, P.Bq, P.sq.n, P.sc.n, alpha, lse, clse, rows,
                        rows_qd, rows_dq);
@@ -920,13 +1138,19 @@ void ib_sym_launch(const IBPlan &P, const float *q, const float *docs, int B, in
     if (dq) {
         const size_t g_bytes = sizeof(float) * IB_CHUNK * IB_TILE, t_bytes = sizeof(float) * IB_TILE * (size_t)P.Hp;
         const size_t lds = g_bytes > t_bytes ? g_bytes : t_bytes;  // <= 64 KiB at H = 512
-        hipLaunchKernelGGL(qg ? ib_sym_grad_kernel<true> : ib_sym_grad_kernel<false>, dim3(tiles_q * P.sq.n + tiles_d * P.sd.n),
-                           dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, (const float *)clse, qg,
-                           dg, B, M, pos_offset, P.Hp, P.Bq, P.Dp, temperature, alpha, tiles_q, P.sq.n, P.sq.per, tiles_d,
-                           P.sd.per, part_q, part_d);
-        hipLaunchKernelGGL(ib_project_kernel, dim3((unsigned)(((size_t)B + M + 3) / 4)), dim3(256), 0, st, (const float *)qh,
-                           (const float *)dh, (const float *)den, (const float *)flag, (const float *)part_q,
-                           (const float *)part_d, B, M, H, P.Hp, P.Bq, P.Dp, P.sq.n, P.sd.n, dq, IBDocGrads{ddocs, nullptr, M});
+        const dim3 grid(tiles_q * P.sq.n + tiles_d * P.sd.n);
+        if (ls) {
+            const auto grad_kernel = qg ? ib_grad_ls_kernel<true, false, true> : ib_grad_ls_kernel<false, false, true>;
+            hipLaunchKernelGGL(grad_kernel, grid, dim3(256),
+                               lds, st, (const float *)qh, (const float *)dh, (const float *)lse, (const float *)clse, qg, dg, B, M,
+                               pos_offset, P.Hp, P.Bq, P.Dp, tw, alpha, tiles_q, P.sq.n, P.sq.per, tiles_d, P.sd.per, part_q, part_d,
+                               (const float *)nullptr, (const float *)nullptr);
+        } else
+            hipLaunchKernelGGL(qg ? ib_sym_grad_kernel<true> : ib_sym_grad_kernel<false>, grid,
+                               dim3(256), lds, st, (const float *)qh, (const float *)dh, (const float *)lse, (const float *)clse, qg,
+                               dg, B, M, pos_offset, P.Hp, P.Bq, P.Dp, temperature, alpha, tiles_q, P.sq.n, P.sq.per, tiles_d,
+                               P.sd.per, part_q, part_d);
+        ib_launch_project(P, B, M, H, dq, IBDocGrads{ddocs, nullptr, M}, ls, ws, st);
     }
 }
 
@@ -1066,6 +1290,101 @@ TT_EXPORT int tt_contrastive_loss_sym_f32(const float *q, int B, const float *do
         return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
     ib_sym_launch(P, q, docs, B, M, H, pos_offset, q_groups, doc_groups, temperature, alpha, loss, loss_dirs, dq, ddocs, workspace,
                   (hipStream_t)stream);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+namespace {
+
+// What the two *_ls entries refuse beyond their float entries' refusals.
+int ib_scale_check(const char *who, const float *log_scale, float lo, float hi, const float *d_log_scale, const float *dq)
+{
+    if (!log_scale)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null log_scale", who);
+    if (!(lo >= -80.0f && hi <= 80.0f && lo <= hi))  // (NaN fails a comparison)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: log-scale bounds [%g, %g] must satisfy -80 <= min <= max <= 80", who, (double)lo,
+                       (double)hi);
+    if (d_log_scale && !dq)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: d_log_scale without dq", who);
+    return TT_OK;
+}
+
+} // namespace
+
+TT_EXPORT size_t tt_contrastive_loss_ls_workspace_bytes(int B, int M, int H, int soft)
+{
+    return ib_shape_ok(B, M, H) ? ib_plan(B, M, H, soft != 0, false, true).total : 0;
+}
+
+TT_EXPORT int tt_contrastive_loss_ls_f32(const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                                         const int64_t *q_groups, const int64_t *doc_groups, const float *targets,
+                                         const float *log_scale, float min_log_scale, float max_log_scale, float *loss,
+                                         float *temperature_out, float *d_log_scale, float *dq, float *ddocs, void *workspace,
+                                         size_t workspace_bytes, tt_stream_t stream)
+{
+    const char *who = "tt_contrastive_loss_ls_f32";
+    if (!ib_shape_ok(B, M, H))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", who, B, M, H, IB_MAX_B,
+                       IB_MAX_M, IB_MAX_H);
+    if (pos_offset < 0 || pos_offset > M - B)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: pos_offset=%d outside [0, M - B = %d]", who, pos_offset, M - B);
+    if (!q_groups != !doc_groups)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: q_groups, doc_groups must be both null or both non-null", who);
+    if (q_groups && targets)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: labels and targets exclude each other", who);
+    if (!q || !docs || !loss || !workspace)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    if (!dq != !ddocs)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: dq, ddocs must be both null or both non-null", who);
+    if (const int rc = ib_scale_check(who, log_scale, min_log_scale, max_log_scale, d_log_scale, dq))
+        return rc;
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: the workspace must be 16-byte aligned", who);
+    const IBPlan P = ib_plan(B, M, H, targets != nullptr, false, true);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
+    const IBScale ls{log_scale, min_log_scale, max_log_scale, temperature_out, d_log_scale};
+    ib_launch(P, q, IBDocs{docs, nullptr, M}, B, M, H, targets ? 0 : pos_offset, q_groups, doc_groups, targets, 0.0f, loss, dq,
+              IBDocGrads{ddocs, nullptr, M}, workspace, (hipStream_t)stream, &ls);
+    TT_LAUNCH_CHECK();
+    return TT_OK;
+}
+
+TT_EXPORT size_t tt_contrastive_loss_sym_ls_workspace_bytes(int B, int M, int H)
+{
+    return ib_shape_ok(B, M, H) ? ib_plan(B, M, H, false, true, true).total : 0;
+}
+
+TT_EXPORT int tt_contrastive_loss_sym_ls_f32(const float *q, int B, const float *docs, int M, int H, int pos_offset,
+                                             const int64_t *q_groups, const int64_t *doc_groups, const float *log_scale,
+                                             float min_log_scale, float max_log_scale, float alpha, float *loss, float *loss_dirs,
+                                             float *temperature_out, float *d_log_scale, float *dq, float *ddocs, void *workspace,
+                                             size_t workspace_bytes, tt_stream_t stream)
+{
+    const char *who = "tt_contrastive_loss_sym_ls_f32";
+    if (!ib_shape_ok(B, M, H))
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: B=%d M=%d H=%d (1 <= B <= %d, B <= M <= %d, 1 <= H <= %d)", who, B, M, H, IB_MAX_B,
+                       IB_MAX_M, IB_MAX_H);
+    if (pos_offset < 0 || pos_offset > M - B)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: pos_offset=%d outside [0, M - B = %d]", who, pos_offset, M - B);
+    if (!(alpha >= 0.0f && alpha <= 1.0f))  // (NaN fails both comparisons)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: alpha=%g outside [0, 1]", who, (double)alpha);
+    if (!q_groups != !doc_groups)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: q_groups, doc_groups must be both null or both non-null", who);
+    if (!q || !docs || !loss || !workspace)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: null pointer", who);
+    if (!dq != !ddocs)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: dq, ddocs must be both null or both non-null", who);
+    if (const int rc = ib_scale_check(who, log_scale, min_log_scale, max_log_scale, d_log_scale, dq))
+        return rc;
+    if ((uintptr_t)workspace & 15)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: the workspace must be 16-byte aligned", who);
+    const IBPlan P = ib_plan(B, M, H, false, true, true);
+    if (workspace_bytes < P.total)
+        return tt_fail(TT_ERR_BAD_SHAPE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, P.total);
+    const IBScale ls{log_scale, min_log_scale, max_log_scale, temperature_out, d_log_scale};
+    ib_sym_launch(P, q, docs, B, M, H, pos_offset, q_groups, doc_groups, 0.0f, alpha, loss, loss_dirs, dq, ddocs, workspace,
+                  (hipStream_t)stream, &ls);
     TT_LAUNCH_CHECK();
     return TT_OK;
 }

@@ -13,6 +13,8 @@
     symmetric_contrastive_losses(q, docs, ...) -> (L_qd, L_dq) reports the two directions
     soft_contrastive_loss(q, docs, targets, temperature=0.05) -> 0-d tensor              (the same softmax against a weight per pair:
     distillation_targets(teacher_scores, ...), multi_positive_targets(q_groups, doc_groups, pos_offset) make the weights)
+    LogitScale(temperature=0.05, min_temperature=0.01, max_temperature=1.0, learnable=True)  a temperature on the device, for
+    every `temperature=` above: learned (the kernels return its gradient) or a word a schedule rewrites
 
 Same constructor arguments, attribute names (`query_encoder.embedding.embedding_dim` is read by
 backend/main.py:104) and state_dict keys ({query,doc}_encoder.{embedding.weight,
@@ -35,7 +37,7 @@ import torch.nn as nn
 from . import _lib
 
 __all__ = ["RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "soft_contrastive_loss",
-           "symmetric_contrastive_losses",
+           "symmetric_contrastive_losses", "LogitScale",
            "distillation_targets", "multi_positive_targets", "SplitRecurrenceTimeout"]
 
 
@@ -578,7 +580,8 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
     neg_groups [B] (None: -1, no group); a passage with query i's label >= 0, other than its own positive, is left out of its
     softmax (contrastive_softmax_loss).  Rows of one query that the batch holds several times share a label.
     symmetric in (0, 1]: the weight of the document-to-query direction (contrastive_softmax_loss, on the pool [p; n]: each
-    positive is classified among the B queries; the explicit negatives have no query of their own)."""
+    positive is classified among the B queries; the explicit negatives have no query of their own).
+    temperature: a float, or a LogitScale (the pool form on [p; n] at the module's word: contrastive_softmax_loss)."""
     query, pos_doc, neg_doc = triplet
     symmetric = _symmetric_weight("in_batch_softmax_loss", symmetric)
     if groups is None and neg_groups is not None:
@@ -588,7 +591,7 @@ def in_batch_softmax_loss(triplet: Tuple[torch.Tensor, torch.Tensor, torch.Tenso
             raise RuntimeError("in_batch_softmax_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != query.shape:
             raise ValueError("in_batch_softmax_loss wants three float32 [B,H] tensors of one shape")
-    if groups is None and symmetric > 0.0:
+    if groups is None and (symmetric > 0.0 or isinstance(temperature, LogitScale)):
         return contrastive_softmax_loss(query, torch.cat((pos_doc, neg_doc)), 0, temperature, symmetric=symmetric)
     if groups is None:
         return _InBatchFn.apply(query, pos_doc, neg_doc, temperature)
@@ -678,6 +681,104 @@ class _SymmetricFn(torch.autograd.Function):
         return g * dq, g * ddocs, None, None, None, None, None
 
 
+class LogitScale(nn.Module):
+    """A temperature that lives on the device: log_scale [1] f32 = log(1 / temperature) (CLIP's logit_scale), clamped into
+    [log(1 / max_temperature), log(1 / min_temperature)] inside the loss kernels.  Pass it as `temperature=` to
+    in_batch_softmax_loss, contrastive_softmax_loss, soft_contrastive_loss, symmetric_contrastive_losses and the trainers.
+    learnable=True: a trained parameter -- the kernels return d loss / d log_scale beside dq and ddocs (torch.clamp's
+    derivative: 0 outside the clamp); give `parameters()` to the optimizer along with the model's.
+    learnable=False: a fixed word that a schedule may rewrite (`log_scale.fill_(...)` under torch.no_grad()).
+    Either way the kernels read the word when they run, so a captured step (GraphedTrainStep) sees the current value at every
+    replay with no recapture."""
+
+    def __init__(self, temperature: float = 0.05, min_temperature: float = 0.01, max_temperature: float = 1.0,
+                 learnable: bool = True):
+        super().__init__()
+        t, lo, hi = float(temperature), float(min_temperature), float(max_temperature)
+        if not 0.0 < lo <= t <= hi < float("inf"):  # (NaN fails a comparison)
+            raise ValueError(f"LogitScale: want 0 < min_temperature <= temperature <= max_temperature < inf, got "
+                             f"{min_temperature!r}, {temperature!r}, {max_temperature!r}")
+        self.min_log_scale, self.max_log_scale = -math.log(hi), -math.log(lo)
+        if self.min_log_scale < -80.0 or self.max_log_scale > 80.0:
+            raise ValueError("LogitScale: temperatures outside [exp(-80), exp(80)]")
+        self.log_scale = nn.Parameter(torch.tensor([-math.log(t)], dtype=torch.float32), requires_grad=bool(learnable))
+
+    @property
+    def temperature(self) -> float:
+        """The temperature the kernels would form now (reads the device word: a host sync, for logging)."""
+        return math.exp(-min(max(float(self.log_scale.detach()[0]), self.min_log_scale), self.max_log_scale))
+
+    def extra_repr(self) -> str:
+        return (f"min_temperature={math.exp(-self.max_log_scale):g}, max_temperature={math.exp(-self.min_log_scale):g}, "
+                f"learnable={self.log_scale.requires_grad}")
+
+
+def _temperature_arg(who: str, temperature, device=None):
+    """`temperature` as a float, or the LogitScale itself (its word on `device`), or the ValueError, before any launch."""
+    if isinstance(temperature, LogitScale):
+        w = temperature.log_scale
+        if device is not None and (w.device != device or w.dtype != torch.float32 or tuple(w.shape) != (1,)):
+            raise ValueError(f"{who}: the LogitScale's log_scale must be a float32 [1] on {device}, got {w.dtype} "
+                             f"{tuple(w.shape)} on {w.device}")
+        return temperature
+    if isinstance(temperature, nn.Module) or not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
+        raise ValueError(f"{who}: temperature={temperature!r} must be finite and > 0, or a LogitScale")
+    return float(temperature)
+
+
+def scaled_workspace(B: int, M: int, H: int, device, soft: bool = False, symmetric: bool = False) -> torch.Tensor:
+    """An uninitialised workspace for tt_contrastive_loss_ls_f32 (soft: with targets) or tt_contrastive_loss_sym_ls_f32."""
+    L = _lib.lib()
+    need = L.tt_contrastive_loss_sym_ls_workspace_bytes(B, M, H) if symmetric else \
+        L.tt_contrastive_loss_ls_workspace_bytes(B, M, H, int(soft))
+    if need == 0:
+        raise ValueError(f"contrastive loss: B={B} M={M} H={H} (1 <= B <= M <= 2^25, B <= 2^24, 1 <= H <= 512)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _scaled_call(q, docs, pos_offset, scale: LogitScale, alpha, q_groups, doc_groups, targets, loss, dirs, d_log_scale, dq,
+                 ddocs, stream=None, ws=None):
+    """tt_contrastive_loss_ls_f32 (alpha None) or tt_contrastive_loss_sym_ls_f32 on contiguous tensors; the kernels read
+    scale.log_scale where it lies.  dirs, d_log_scale and the gradients may be None."""
+    L = _lib.lib()
+    (B, H), M = q.shape, docs.shape[0]
+    if ws is None:
+        ws = scaled_workspace(B, M, H, q.device, soft=targets is not None, symmetric=alpha is not None)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    word, lo, hi = scale.log_scale.data_ptr(), scale.min_log_scale, scale.max_log_scale
+    with torch.cuda.device(q.device):
+        st = _stream(q.device) if stream is None else stream
+        if alpha is None:
+            _lib.check(L.tt_contrastive_loss_ls_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), ptr(q_groups),
+                                                    ptr(doc_groups), ptr(targets), word, lo, hi, loss.data_ptr(), None,
+                                                    ptr(d_log_scale), ptr(dq), ptr(ddocs), ws.data_ptr(), ws.numel(), st))
+        else:
+            _lib.check(L.tt_contrastive_loss_sym_ls_f32(q.data_ptr(), B, docs.data_ptr(), M, H, int(pos_offset), ptr(q_groups),
+                                                        ptr(doc_groups), word, lo, hi, float(alpha), loss.data_ptr(), ptr(dirs),
+                                                        None, ptr(d_log_scale), ptr(dq), ptr(ddocs), ws.data_ptr(), ws.numel(),
+                                                        st))
+
+
+class _ScaledFn(torch.autograd.Function):
+    """The four losses at a LogitScale: the gradient of log_scale beside dq and ddocs, all scaled by the incoming g."""
+
+    @staticmethod
+    def forward(ctx, q, docs, log_scale, scale: LogitScale, pos_offset: int, alpha, q_groups=None, doc_groups=None, targets=None):
+        q, docs = q.contiguous(), docs.contiguous()
+        q_groups, doc_groups, targets = (None if t is None else t.contiguous() for t in (q_groups, doc_groups, targets))
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        dq, ddocs = torch.empty_like(q), torch.empty_like(docs)
+        dl = torch.empty(1, dtype=torch.float32, device=q.device) if ctx.needs_input_grad[2] else None
+        _scaled_call(q, docs, pos_offset, scale, alpha, q_groups, doc_groups, targets, loss, None, dl, dq, ddocs)
+        ctx.save_for_backward(dq, ddocs, *(() if dl is None else (dl,)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, ddocs, *dl = ctx.saved_tensors
+        return g * dq, g * ddocs, (g * dl[0] if dl else None), None, None, None, None, None, None
+
+
 def _symmetric_weight(who: str, symmetric) -> float:
     """`symmetric` as a float in [0, 1], or the ValueError (before any launch)."""
     if isinstance(symmetric, bool) or not isinstance(symmetric, (int, float)) or not 0.0 <= float(symmetric) <= 1.0:  # (NaN fails)
@@ -694,7 +795,7 @@ def _group_labels(who: str, name: str, t, rows: int, device) -> torch.Tensor:
 
 
 def _contrastive_args(who: str, q, docs, pos_offset, temperature, q_groups, doc_groups):
-    """The checks of the pool losses, before any launch -> (B, M, q_groups, doc_groups)."""
+    """The checks of the pool losses, before any launch -> (B, M, q_groups, doc_groups, temperature as _temperature_arg gives it)."""
     if (q_groups is None) != (doc_groups is None):
         raise ValueError(f"{who}: q_groups and doc_groups must be both given or both None")
     for t in (q, docs):
@@ -709,12 +810,11 @@ def _contrastive_args(who: str, q, docs, pos_offset, temperature, q_groups, doc_
         raise ValueError(f"{who}: M={M} documents for B={B} queries (every query needs its positive: M >= B)")
     if not 0 <= pos_offset <= M - B:
         raise ValueError(f"{who}: pos_offset={pos_offset!r} outside [0, M - B = {M - B}]")
-    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
-        raise ValueError(f"{who}: temperature={temperature!r} must be finite and > 0")
+    temperature = _temperature_arg(who, temperature, q.device)
     if q_groups is not None:
         q_groups = _group_labels(who, "q_groups", q_groups, B, q.device)
         doc_groups = _group_labels(who, "doc_groups", doc_groups, M, q.device)
-    return B, M, q_groups, doc_groups
+    return B, M, q_groups, doc_groups, temperature
 
 
 def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05,
@@ -734,14 +834,20 @@ def contrastive_softmax_loss(q: torch.Tensor, docs: torch.Tensor, pos_offset: in
     (the bidirectional InfoNCE; 0.5 is the CLIP loss).  Only the B positive rows of `docs` have a softmax of their own; every
     other row stays a negative of the query-to-document direction alone.  With labels an ignored pair leaves both softmaxes.
     0.0 is the one-directional loss above, on its own kernels; symmetric_contrastive_losses reports the two directions.
-    Soft targets (soft_contrastive_loss) do not combine with it."""
+    Soft targets (soft_contrastive_loss) do not combine with it.
+    temperature: a float (an argument of the launches), or a LogitScale: the kernels read its word on the device when they run,
+    and the loss is also differentiable in log_scale (where the module is learnable)."""
     symmetric = _symmetric_weight("contrastive_softmax_loss", symmetric)
-    B, M, q_groups, doc_groups = _contrastive_args("contrastive_softmax_loss", q, docs, pos_offset, temperature, q_groups, doc_groups)
+    B, M, q_groups, doc_groups, temperature = _contrastive_args("contrastive_softmax_loss", q, docs, pos_offset, temperature,
+                                                                q_groups, doc_groups)
+    if isinstance(temperature, LogitScale):
+        return _ScaledFn.apply(q, docs, temperature.log_scale, temperature, int(pos_offset), symmetric if symmetric > 0.0 else None,
+                               q_groups, doc_groups)
     if symmetric > 0.0:
-        return _SymmetricFn.apply(q, docs, int(pos_offset), float(temperature), symmetric, q_groups, doc_groups)
+        return _SymmetricFn.apply(q, docs, int(pos_offset), temperature, symmetric, q_groups, doc_groups)
     if q_groups is None:
-        return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature))
-    return _ContrastiveFn.apply(q, docs, int(pos_offset), float(temperature), q_groups, doc_groups)
+        return _ContrastiveFn.apply(q, docs, int(pos_offset), temperature)
+    return _ContrastiveFn.apply(q, docs, int(pos_offset), temperature, q_groups, doc_groups)
 
 
 def symmetric_contrastive_losses(q: torch.Tensor, docs: torch.Tensor, pos_offset: int = 0, temperature: float = 0.05,
@@ -749,14 +855,17 @@ def symmetric_contrastive_losses(q: torch.Tensor, docs: torch.Tensor, pos_offset
                                  doc_groups: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(L_qd, L_dq): the two directions of the symmetric contrastive_softmax_loss as 0-d tensors, for logging (one loss-only
     call; not differentiable).  Whatever weight a step trains with, its loss is (1 - symmetric) L_qd + symmetric L_dq."""
-    _, _, q_groups, doc_groups = _contrastive_args("symmetric_contrastive_losses", q, docs, pos_offset, temperature, q_groups,
-                                                   doc_groups)
+    _, _, q_groups, doc_groups, temperature = _contrastive_args("symmetric_contrastive_losses", q, docs, pos_offset, temperature,
+                                                                q_groups, doc_groups)
     q, docs = q.detach().contiguous(), docs.detach().contiguous()
     if q_groups is not None:
         q_groups, doc_groups = q_groups.contiguous(), doc_groups.contiguous()
     loss = torch.empty((), dtype=torch.float32, device=q.device)
     dirs = torch.empty(2, dtype=torch.float32, device=q.device)
-    _symmetric_call(q, docs, pos_offset, temperature, 0.0, q_groups, doc_groups, loss, dirs, None, None)
+    if isinstance(temperature, LogitScale):
+        _scaled_call(q, docs, pos_offset, temperature, 0.0, q_groups, doc_groups, None, loss, dirs, None, None, None)
+    else:
+        _symmetric_call(q, docs, pos_offset, temperature, 0.0, q_groups, doc_groups, loss, dirs, None, None)
     return dirs[0], dirs[1]
 
 
@@ -809,7 +918,7 @@ def soft_contrastive_loss(q: torch.Tensor, docs: torch.Tensor, targets: torch.Te
     gives that query no loss and no gradient.  Differentiable in q and docs, not in targets (fused forward + gradient kernels
     on the f32 matrix pipe, deterministic; [B,M] logits never reach memory).
     The symmetric loss (contrastive_softmax_loss(symmetric=)) does not combine with soft targets: they define their own rows
-    and there are no column targets."""
+    and there are no column targets.  temperature: a float or a LogitScale (contrastive_softmax_loss)."""
     for t in (q, docs):
         if not t.is_cuda:
             raise RuntimeError("soft_contrastive_loss runs only on an AMD GPU via libtt.so (no CPU fallback)")
@@ -820,10 +929,11 @@ def soft_contrastive_loss(q: torch.Tensor, docs: torch.Tensor, targets: torch.Te
         raise ValueError(f"soft_contrastive_loss: q has H={H}, docs has H={docs.shape[1]}")
     if M < B:
         raise ValueError(f"soft_contrastive_loss: M={M} documents for B={B} queries (the pool entries want M >= B)")
-    if not 0.0 < float(temperature) < float("inf"):  # (NaN fails both comparisons)
-        raise ValueError(f"soft_contrastive_loss: temperature={temperature!r} must be finite and > 0")
+    temperature = _temperature_arg("soft_contrastive_loss", temperature, q.device)
     targets = _soft_targets("soft_contrastive_loss", targets, B, M, q.device)
-    return _SoftContrastiveFn.apply(q, docs, targets.detach(), float(temperature))
+    if isinstance(temperature, LogitScale):
+        return _ScaledFn.apply(q, docs, temperature.log_scale, temperature, 0, None, None, None, targets.detach())
+    return _SoftContrastiveFn.apply(q, docs, targets.detach(), temperature)
 
 
 def distillation_targets(teacher_scores: torch.Tensor, teacher_temperature: float = 1.0,

@@ -25,9 +25,10 @@ import torch
 
 from . import _lib
 from .collective import Collective
-from .model import (RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, _soft_targets, contrastive_softmax_loss,
-                    contrastive_workspace, deferred_input_checks, in_batch_softmax_loss, in_batch_workspace, soft_contrastive_loss,
-                    soft_contrastive_workspace, symmetric_workspace, triplet_loss_cosine)
+from .model import (LogitScale, RNNEncoder, SplitRecurrenceTimeout, TwoTowerModel, _group_labels, _raise_status, _scaled_call,
+                    _soft_targets, contrastive_softmax_loss, contrastive_workspace, deferred_input_checks,
+                    in_batch_softmax_loss, in_batch_workspace, scaled_workspace, soft_contrastive_loss, soft_contrastive_workspace,
+                    symmetric_workspace, triplet_loss_cosine)
 
 __all__ = ["FusedClipAdam", "train_step", "DataParallelTrainer", "GraphedTrainStep"]
 
@@ -319,7 +320,9 @@ class _StepSpec(_StepSpecFields):
     once at the public entries -- train_step, DataParallelTrainer, GraphedTrainStep --; everything below them takes the record.
     The six tuple fields are what the record has always been (callers and tests compare and unpack it as that 6-tuple);
     `symmetric`, the weight of the document-to-query direction of the "in_batch" loss (0.0: the one-directional loss), is the
-    seventh constructor argument and a read-only attribute beside them.  Two records are equal when fields and weight are."""
+    seventh constructor argument and a read-only attribute beside them.  Two records are equal when fields and weight are.
+    `temperature` is a float or a model.LogitScale: the module itself, compared and hashed by identity -- a record (and a graph
+    cache) keys on "the temperature lives in this module", never on the value its word holds."""
 
     def __new__(cls, margin, negatives, temperature, gather_negatives, concurrent_towers, direct, symmetric=0.0):
         self = super().__new__(cls, margin, negatives, temperature, gather_negatives, concurrent_towers, direct)
@@ -354,6 +357,9 @@ class _StepSpec(_StepSpecFields):
         if self.gather_negatives and graphs:
             raise ValueError("gather_negatives=True is not available with graphs=True (the exchange of the passages sits between "
                              "the captured forward and backward)")
+        if isinstance(self.temperature, LogitScale) and self.negatives != "in_batch":
+            raise ValueError(f'temperature=LogitScale needs negatives="in_batch", got negatives={self.negatives!r} (the triplet '
+                             "loss has no temperature)")
         sym = self.symmetric
         if isinstance(sym, bool) or not isinstance(sym, (int, float)) or not 0.0 <= float(sym) <= 1.0:  # (NaN fails)
             raise ValueError(f"symmetric={sym!r} must be a number in [0, 1]")
@@ -406,6 +412,23 @@ def _batch_targets(who: str, spec: _StepSpec, optimizer, batch, targets, groups=
         raise ValueError(f"{who}: targets need as many negatives as positives as queries")
     world = getattr(getattr(optimizer, "_coll", None), "world", 1) if spec.gather_negatives else 1
     return _soft_targets(who, targets, B, world * 2 * B, queries.device)
+
+
+def _scale_grad_view(who: str, spec: _StepSpec, optimizer) -> Optional[torch.Tensor]:
+    """Where the step's loss writes d loss / d log_scale: the optimizer's gradient view [1] of a learnable LogitScale's word.
+    None: the temperature is a float, or a module that is not learnable (a fixed word, no gradient).  A learnable module whose
+    word the optimizer does not own raises ValueError before anything is launched: its gradient would go nowhere."""
+    scale = spec.temperature
+    if not isinstance(scale, LogitScale) or not scale.log_scale.requires_grad:
+        return None
+    for p, gv in zip(getattr(optimizer, "params", ()), getattr(optimizer, "_views", ())):
+        if p is scale.log_scale:
+            return gv
+    if isinstance(optimizer, _FlatClipAdam) or not any(p is scale.log_scale for g in getattr(optimizer, "param_groups", ())
+                                                       for p in g["params"]):
+        raise ValueError(f"{who}: the optimizer does not own the LogitScale's log_scale; build it over "
+                         "list(model.parameters()) + list(scale.parameters())")
+    return None
 
 
 _TOWER_STREAMS = {}
@@ -662,7 +685,7 @@ def _direct_grad_views(model, optimizer, batch, spec, capture):
     """Does the direct step apply -- and if so, into which of the optimizer's gradient views the towers' backwards write: [the
     document tower's, the query tower's], one view per _flat_params() entry.  None: it does not (the step was asked not to, a
     batch of another shape, another optimizer, a trainable embedding table, a tower in eval mode, parameters without the
-    optimizer's gradient views or views no tower call would write, an exchange of passages inside a capture or without a
+    optimizer's gradient views or views no call of the step would write, an exchange of passages inside a capture or without a
     Collective): the caller takes the autograd path, which computes the same numbers.  Looks, touches nothing."""
     if not isinstance(optimizer, _FlatClipAdam) or not torch.is_grad_enabled():
         return None
@@ -677,7 +700,13 @@ def _direct_grad_views(model, optimizer, batch, spec, capture):
         return None
     views = {id(p): gv for p, gv in zip(optimizer.params, optimizer._views)}
     params = [enc._flat_params() for enc in encs]
-    if any(id(p) not in views for ps in params for p in ps) or len({id(p) for ps in params for p in ps}) != len(optimizer.params):
+    # the optimizer's parameters are exactly the towers', but for one: a learnable LogitScale's word, BEHIND them all (the query
+    # tower's gradients stay the bucket's prefix: reduce_prefix), which the loss launch writes itself (_direct_loss)
+    own = len(optimizer.params)
+    scale = spec.temperature
+    if isinstance(scale, LogitScale) and scale.log_scale.requires_grad and optimizer.params[-1] is scale.log_scale:
+        own -= 1
+    if any(id(p) not in views for ps in params for p in ps) or len({id(p) for ps in params for p in ps}) != own:
         return None
     return [[views[id(p)] for p in ps] for ps in params]
 
@@ -726,8 +755,15 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
     entry's bits for one-hot targets); gathered, on the pool with this rank's rows [B, world * 2B] -- the targets are rank-local,
     so no collective is added and their order stays gather, reduce.
     spec.symmetric > 0 ("in_batch" only, never gathered, never with targets): the symmetric entry on pn as it lies (M = 2B,
-    pos_offset = 0), with the labels when there are any."""
+    pos_offset = 0), with the labels when there are any.
+    spec.temperature a LogitScale: every kind above goes to the two *_ls entries instead, on the pool or on pn as it lies (plain
+    "in_batch" as the pool form, M = 2B: the two-pointer entry's bits), which read the module's word where it lies -- inside the
+    optimizer's flat_params when it is learnable -- and write d loss / d log_scale straight into that parameter's gradient view.
+    Gathered, that is this rank's queries' sum; it rides the bucket's all-reduce and 1 / world like every gradient: no collective
+    is added."""
     (B, H), dev = q.shape, q.device
+    scale = spec.temperature if isinstance(spec.temperature, LogitScale) else None
+    d_scale = _scale_grad_view("train step", spec, optimizer)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     dq = torch.empty_like(q)
     pool_labels = labels
@@ -736,12 +772,17 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
         pool = torch.empty((coll.world * 2 * B, H), dtype=torch.float32, device=dev)
         d_pool = torch.empty_like(pool)
         dpn = d_pool[coll.rank * 2 * B:(coll.rank + 1) * 2 * B]
-        rows = (soft_contrastive_workspace if targets is not None else contrastive_workspace)(B, pool.shape[0], H, dev)
+        if scale is not None:
+            rows = scaled_workspace(B, pool.shape[0], H, dev, soft=targets is not None)
+        else:
+            rows = (soft_contrastive_workspace if targets is not None else contrastive_workspace)(B, pool.shape[0], H, dev)
         if labels is not None:
             pool_labels = torch.empty(coll.world * 2 * B, dtype=torch.int64, device=dev)
     else:
         dpn = torch.empty_like(pn)
-        if targets is not None:
+        if scale is not None:
+            rows = scaled_workspace(B, 2 * B, H, dev, soft=targets is not None, symmetric=spec.symmetric > 0)
+        elif targets is not None:
             rows = soft_contrastive_workspace(B, 2 * B, H, dev)
         elif spec.symmetric > 0:
             rows = symmetric_workspace(B, 2 * B, H, dev)
@@ -753,7 +794,18 @@ def _direct_loss(spec: _StepSpec, optimizer, q, pn, s_main, labels=None, targets
         t.record_stream(s_main)
     L, p, n = _lib.lib(), pn[:B], pn[B:]
     with torch.cuda.device(dev):
-        if spec.gather_negatives:
+        if scale is not None:
+            docs, d_docs, pos = (pool, d_pool, coll.rank * 2 * B) if spec.gather_negatives else (pn, dpn, 0)
+            if spec.gather_negatives:
+                coll.all_gather_blocks(pn, pool)
+                if labels is not None:
+                    coll.all_gather_blocks(labels, pool_labels)
+            # (the queries' labels are the first B of this rank's passages': the positives')
+            _scaled_call(q, docs, pos, scale, spec.symmetric if spec.symmetric > 0 else None, labels, pool_labels, targets, loss,
+                         None, d_scale, dq, d_docs, stream=s_main.cuda_stream, ws=rows)
+            if spec.gather_negatives:
+                coll.all_reduce_sum(d_pool.view(-1))
+        elif spec.gather_negatives:
             coll.all_gather_blocks(pn, pool)
             if targets is not None:
                 _lib.check(L.tt_contrastive_loss_soft_f32(q.data_ptr(), B, pool.data_ptr(), pool.shape[0], H, targets.data_ptr(),
@@ -1107,8 +1159,16 @@ def train_step(model: TwoTowerModel, optimizer: FusedClipAdam, queries: torch.Te
     CLIP loss; 0.0 (default) is the one-directional step, launch for launch.  Combines with groups / neg_groups (an ignored
     pair leaves both softmaxes), not with targets (soft targets define their own rows; there are no column targets) and not
     with gather_negatives=True (the column softmax would run over the queries of all ranks: a gather of the queries and a
-    reduction of their gradients, a second exchange in the step's collective order).  The negatives are rank-local."""
+    reduction of their gradients, a second exchange in the step's collective order).  The negatives are rank-local.
+
+    temperature (negatives="in_batch" only when it is a module): a float, or a model.LogitScale -- a temperature that lives on
+    the device.  Learnable, the optimizer must own its word (ValueError otherwise): FusedClipAdam(list(model.parameters()) +
+    list(scale.parameters())), the scale's behind the model's; the loss kernels return d loss / d log_scale (every kind: plain,
+    grouped, soft, symmetric, gathered) and Adam updates the word with the weights.  Its gradient lies in the optimizer's flat
+    buffer, so it is part of the global clip norm.  Multi-rank it is averaged over the ranks like every gradient.  Not learnable
+    (LogitScale(learnable=False)), the word is a fixed temperature that a schedule may rewrite between steps."""
     spec = _StepSpec(margin, negatives, temperature, gather_negatives, concurrent_towers, direct, symmetric).checked(graphs=False)
+    _scale_grad_view("train_step", spec, optimizer)
     batch = (queries, pos_docs, neg_docs)
     targets = _batch_targets("train_step", spec, optimizer, batch, targets, groups, neg_groups)
     return _step(model, optimizer, batch, spec, defer_check, _batch_labels("train_step", spec, batch, groups, neg_groups), targets)
@@ -1127,18 +1187,24 @@ class DataParallelTrainer:
     passages of all ranks are gathered and every query sees world * 2B - 1 negatives (every rank must bring the same B; two
     more collectives per step, same order on every rank).  Not with graphs=True.
     symmetric: see train_step (the symmetric "in_batch" loss on each rank's own batch: rank-local negatives, the gradients
-    averaged over the ranks as always; not with gather_negatives=True, not with targets)."""
+    averaged over the ranks as always; not with gather_negatives=True, not with targets).
+    temperature: a float or a model.LogitScale (train_step).  The trainer's optimizer takes a learnable module's word behind the
+    model's parameters (part of the clip norm, broadcast with them by broadcast_parameters, its gradient -- each rank's own
+    queries' sum -- averaged by the bucket's all-reduce; gathered or not, no collective is added); graphs key on the module, not
+    on its value."""
 
     def __init__(self, model: TwoTowerModel, lr: float = 1e-4, margin: float = 0.2, max_norm: float = 1.0, group=None,
                  graphs: bool = False, width_step: int = 32, max_graphs: int = 4, defer_check: bool = False,
                  negatives: str = "paired", temperature: float = 0.05, gather_negatives: bool = False, symmetric: float = 0.0):
         self.graphs, self.width_step, self.max_graphs, self.defer_check = bool(graphs), int(width_step), int(max_graphs), bool(defer_check)
         self.margin = margin
-        self.negatives, self.temperature, self.gather_negatives = negatives, float(temperature), bool(gather_negatives)
+        self.negatives, self.gather_negatives = negatives, bool(gather_negatives)
+        self.temperature = temperature if isinstance(temperature, LogitScale) else float(temperature)
         self.symmetric = symmetric
         self._spec()
         self.model = model
-        self.optimizer = FusedClipAdam(model.parameters(), lr=lr, max_norm=max_norm, group=group)
+        scale_params = list(self.temperature.parameters()) if isinstance(self.temperature, LogitScale) else []
+        self.optimizer = FusedClipAdam(list(model.parameters()) + scale_params, lr=lr, max_norm=max_norm, group=group)
         self.optimizer.watch(model)  # (a hand-written loop over self.model / self.optimizer fails collectively too)
         self._graphs: "dict" = {}
 
@@ -1150,7 +1216,9 @@ class DataParallelTrainer:
     def broadcast_parameters(self, src: int = 0) -> None:
         import torch.distributed as dist
         if dist.is_initialized() and dist.get_world_size(self.optimizer.group) > 1:
-            dist.broadcast(self.optimizer.flat_params, src=src, group=self.optimizer.group)
+            dist.broadcast(self.optimizer.flat_params, src=src, group=self.optimizer.group)   # (a learnable scale's word included)
+            if isinstance(self.temperature, LogitScale) and not self.temperature.log_scale.requires_grad:
+                dist.broadcast(self.temperature.log_scale.data, src=src, group=self.optimizer.group)
         self.optimizer.mark_params_changed()  # (the broadcast wrote the flat buffer, not the parameter tensors)
 
     def _graph_for(self, batch, spec: _StepSpec, grouped: bool = False, soft: bool = False) -> Optional["GraphedTrainStep"]:
@@ -1166,6 +1234,8 @@ class DataParallelTrainer:
             key += ("soft",)      # (and so is a step with soft targets: the soft entry's)
         if spec.symmetric > 0:
             key += (("symmetric", float(spec.symmetric)),)   # (the weight is an argument of the captured symmetric entry)
+        if isinstance(spec.temperature, LogitScale):
+            key += (("scale", id(spec.temperature)),)        # (the module, not its value: the captured launches read its word)
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= self.max_graphs:           # least recently used first
@@ -1186,6 +1256,7 @@ class DataParallelTrainer:
         float32 [B, 2B], with gather_negatives=True [B, world * 2B] in pool order)."""
         self.model.train()
         batch, spec = (queries, pos_docs, neg_docs), self._spec()
+        _scale_grad_view("DataParallelTrainer.step", spec, self.optimizer)
         targets = _batch_targets("DataParallelTrainer.step", spec, self.optimizer, batch, targets, groups, neg_groups)
         labels = _batch_labels("DataParallelTrainer.step", spec, batch, groups, neg_groups)
         if self.graphs:
@@ -1250,13 +1321,21 @@ class GraphedTrainStep:
     (train_step: targets) are a static float32 input [B, 2B], refilled in front of every replay.  A call without targets fills
     the one-hot (1 at column i: the bits of the plain "in_batch" step).
     symmetric (negatives="in_batch" only; train_step: symmetric): a captured argument like temperature; > 0 captures the
-    symmetric entry as the loss.  Combines with grouped=True; with soft=True it raises ValueError."""
+    symmetric entry as the loss.  Combines with grouped=True; with soft=True it raises ValueError.
+    temperature a model.LogitScale (negatives="in_batch" only; train_step: temperature): the captured loss launches read the
+    module's word on the device when they run, so nothing about the temperature is frozen into the graph.  Learnable, the word
+    lies in the optimizer's flat_params (build the optimizer first: that address is what is captured) and the captured Adam
+    updates it: the next replay sees the update with nothing staged.  Not learnable, rewrite the word between calls
+    (scale.log_scale.fill_(...) under torch.no_grad()) and replay: a temperature schedule with no recapture."""
 
     def __init__(self, model: TwoTowerModel, optimizer: FusedClipAdam, batch: int, q_width: int, doc_width: int, margin: float = 0.2,
                  defer_check: bool = False, negatives: str = "paired", temperature: float = 0.05, grouped: bool = False,
                  soft: bool = False, symmetric: float = 0.0):
-        # (margin, negatives, temperature and symmetric are arguments of the captured loss launches)
-        self._spec = _StepSpec(float(margin), negatives, float(temperature), False, True, True, symmetric).checked(graphs=True)
+        # (margin, negatives, a float temperature and symmetric are arguments of the captured loss launches; a LogitScale's word is
+        #  read by them on the device)
+        temperature = temperature if isinstance(temperature, LogitScale) else float(temperature)
+        self._spec = _StepSpec(float(margin), negatives, temperature, False, True, True, symmetric).checked(graphs=True)
+        _scale_grad_view("GraphedTrainStep", self._spec, optimizer)
         if grouped and negatives != "in_batch":
             raise ValueError(f'GraphedTrainStep: grouped=True needs negatives="in_batch", got negatives={negatives!r}')
         if soft and negatives != "in_batch":
@@ -1272,7 +1351,7 @@ class GraphedTrainStep:
         if not all(e.check_inputs for e in encs):
             raise ValueError("GraphedTrainStep: input checking must be on (the gate is what keeps a bad batch from being applied)")
         self.model, self.optimizer, self.margin = model, optimizer, float(margin)
-        self.negatives, self.temperature, self.symmetric = negatives, float(temperature), float(symmetric)
+        self.negatives, self.temperature, self.symmetric = negatives, temperature, float(symmetric)
         self.B, self.q_width, self.doc_width = int(batch), int(q_width), int(doc_width)
         self.defer_check = bool(defer_check)
         dev = optimizer.flat_params.device
