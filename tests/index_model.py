@@ -10,8 +10,19 @@ keep is ANDed with the removals, a NaN threshold counts nothing.
 PipelineModel is ShardedIndex.submit() / PendingSearch.result(): what each submitted step must return (its answer under the
 removals of the moment it was submitted) and until when it may be collected (two more submits of the same (B, k', k)).
 sequence() draws the random call sequences of tests/test_index_sequences_gpu.py; it never emits a call the model cannot
-judge."""
+judge.
+
+The search flavours -- tagged, biased, cursor (search_after / pages / deep_search), diverse, collapsed search and mining --
+are methods of IndexModel over its state tags / bias / groups.  Where a *_ref module states a piece (eligibility, ceiling,
+greedy selection, the collapse walk) the model calls it; what the model adds is the composition with removals, the call
+keep and exclusion lists.  tests/test_index_model_cpu.py holds every method to an independent statement.  The fixtures and
+the generators flavour_sequence() / with_flavours() at the end are those of tests/test_index_flavour_sequences_gpu.py."""
 import numpy as np
+
+import collapse_ref
+import cursor_ref
+import mmr_ref
+import tagged_ref
 
 
 # ---- the pieces tests/test_exclude_gpu.py states its expectations with ---------------------------------------------------------
@@ -70,11 +81,14 @@ def _best(s, allowed, k):
 
 
 class IndexModel:
+    WALK_PREFIX = 1024   # the first prefix of a sorted row collapsed_search walks
+
     def __init__(self, rows_f32, idx_offset=0, score_all=None):
         self.rows = np.ascontiguousarray(rows_f32, dtype=np.float32)
         self.N = self.rows.shape[0]
         self.idx_offset = int(idx_offset)
         self.removed = np.zeros(self.N, dtype=bool)
+        self.tags = self.bias = self.groups = None   # uint32 [N] / float32 [N] / int64 [N] once set
         self._score_all = score_all
         self._scores = {}
 
@@ -144,6 +158,116 @@ class IndexModel:
         with np.errstate(invalid="ignore"):
             cut = ~(v >= thr[:, None])
         return self.count(S, thr, keep), np.where(cut, np.float32(-np.inf), v), np.where(cut, -1, i)
+
+    # ---- the search flavours: tags, bias and groups are state of the index, as set_tags / set_bias / set_groups keep it ----
+
+    def set_tags(self, tags):
+        """One 32-bit word per document, read as unsigned; tags are only ever replaced."""
+        assert tags is not None and len(tags) == self.N
+        self.tags = tagged_ref.as_u32(np.asarray(tags)).copy()
+
+    def set_bias(self, bias):
+        """One float32 per document; None clears it (biased_search must then raise)."""
+        self.bias = None if bias is None else np.array(bias, dtype=np.float32)
+        assert self.bias is None or (self.bias.shape == (self.N,) and np.isfinite(self.bias).all())
+
+    def set_groups(self, groups):
+        """One int64 group id per document, negative = ungrouped; None clears it (collapsed_search must then raise)."""
+        self.groups = None if groups is None else np.array(groups, dtype=np.int64)
+        assert self.groups is None or self.groups.shape == (self.N,)
+
+    def _allowed(self, b, base, exclude):
+        """Row b of the eligibility `base` ([N], or [B,N]) without the documents exclude[b] names."""
+        allowed = base if base.ndim == 1 else base[b]
+        if exclude is not None:
+            loc, ok = self.local(exclude[b])
+            allowed = allowed.copy()
+            allowed[loc[ok]] = False
+        return allowed
+
+    def _select(self, S, base, k, exclude=None):
+        """(vals, idx) [B,k]: _best of every score row over its eligible documents, tail (-inf, -1)."""
+        B = S.shape[0]
+        ov = np.full((B, k), -np.inf, dtype=np.float32)
+        oi = np.full((B, k), -1, dtype=np.int64)
+        for b in range(B):
+            top = _best(S[b], self._allowed(b, base, exclude), k)
+            ov[b, :len(top)], oi[b, :len(top)] = S[b, top], top + self.idx_offset
+        return ov, oi
+
+    def tagged_search(self, S, k, match_mask, match_value, keep=None):
+        """Document n is eligible for query b iff it is live, kept and (tags[n] & match_mask[b]) == match_value[b]
+        (tagged_ref.eligibility; the masks are ints for every query, or one word per query)."""
+        assert self.tags is not None, "no tags: tagged_search must raise"
+        return self._select(S, tagged_ref.eligibility(self.tags, match_mask, match_value, self.live(keep), B=S.shape[0]), k)
+
+    def biased_scores(self, S):
+        """fl32(S + bias): one float32 add behind the finished score, as biased_ref states it."""
+        assert self.bias is not None, "no bias: biased_search must raise"
+        return (S + self.bias[None, :]).astype(np.float32)
+
+    def biased_search(self, S, k, keep=None, exclude=None):
+        """The selection over the biased scores; the values are the biased scores.  With exclude= it is the route the
+        docstring promises: the biased search for k + E, then filter_ref."""
+        Sb = self.biased_scores(S)
+        if exclude is None:
+            return self._select(Sb, self.live(keep), k)
+        wide = self._select(Sb, self.live(keep), k + exclude.shape[1])
+        return filter_ref(wide[0], wide[1], exclude, k)
+
+    def search_after(self, S, k, after=None, keep=None, exclude=None):
+        """The first k documents strictly after the cursor after = (scores, global ids) -- numbers, or one per query; None is
+        the open cursor (+inf, -1) -- among the live, kept and not excluded ones (cursor_ref.eligibility)."""
+        av, ai = (np.float32(np.inf), -1) if after is None else after
+        return self._select(S, cursor_ref.eligibility(S, av, ai, self.idx_offset, self.live(keep)), k, exclude)
+
+    def pages(self, S, k, n_pages, keep=None):
+        """n_pages consecutive pages of k: each page's cursor is the previous page's last column (the tail included)."""
+        after, out = None, []
+        for _ in range(n_pages):
+            v, i = self.search_after(S, k, after, keep)
+            out.append((v, i))
+            after = (v[:, -1].copy(), i[:, -1].copy())
+        return out
+
+    def deep_search(self, S, k_total, keep=None):
+        """ceil(k_total / 64) pages of 64, concatenated and cut."""
+        got = self.pages(S, 64, (k_total + 63) // 64, keep)
+        return np.concatenate([v for v, _ in got], 1)[:, :k_total], np.concatenate([i for _, i in got], 1)[:, :k_total]
+
+    def diverse_search(self, S, k, lam, fetch_k=None, keep=None, exclude=None, oracle=None):
+        """The model's own search for fetch_k (default min(128, 4 k)), then the greedy selection of mmr_ref over the model's
+        rows; (vals, idx) in selection order."""
+        fk = min(128, 4 * k) if fetch_k is None else fetch_k
+        v, i = self.search(S, fk, keep, exclude)
+        return mmr_ref.select(oracle, v, i, self.rows, k, lam, self.idx_offset)[:2]
+
+    def collapsed_search(self, S, k, m, keep=None, exclude=None):
+        """(vals, idx, gids) [B,k]: the walk of collapse_ref over ALL eligible documents of each query in (score desc, id asc)
+        order -- the exact answer, whatever rounds the product took.  The walk of a prefix of the sorted row is a prefix of
+        the walk, so the row is walked in growing prefixes until k are kept (collapse_ref.search walks all of it;
+        tests/test_index_model_cpu.py holds the two against each other)."""
+        assert self.groups is not None, "no groups: collapsed_search must raise"
+        live, out = self.live(keep), []
+        for b in range(S.shape[0]):
+            v, i = collapse_ref.sorted_row(S[b], self._allowed(b, live, exclude), self.idx_offset)
+            P = self.WALK_PREFIX
+            while True:
+                row = collapse_ref.collapse_row(v[:P], i[:P], self.groups[i[:P] - self.idx_offset], k, m)
+                if row[3][0] == k or P >= len(i):
+                    break
+                P *= 4
+            out.append(row[:3])
+        return tuple(np.stack([o[j] for o in out]) for j in range(3))
+
+    def mine(self, S, pos_ids, k, margin=0.0, ratio=None, keep=None):
+        """mine_hard_negatives: the positives' scores are the model's own score_ids (a removed or unkept positive is
+        invalid), the ceiling cursor_ref.ceiling, then the cursor search from (ceiling, -1) without the positives.  A query
+        without a valid positive has the ceiling +inf: the plain top-k without its listed ids."""
+        if pos_ids.shape[1] == 0:
+            return self.search_after(S, k, None, keep)
+        c = cursor_ref.ceiling(self.score_ids(S, pos_ids, keep), pos_ids, margin, ratio)
+        return self.search_after(S, k, (c, -1), keep, pos_ids)
 
 
 # ---- the pipeline of ShardedIndex ----------------------------------------------------------------------------------------------
@@ -272,3 +396,113 @@ def random_candidates(rs, B, C, N, idx_offset):
     c = np.where(r < 0.1, -1 - rs.randint(0, 5, size=(B, C)), c)
     c = np.where((r >= 0.1) & (r < 0.15), idx_offset + N + rs.randint(0, 1000, size=(B, C)), c)
     return np.where((r >= 0.15) & (r < 0.2), rs.randint(0, max(idx_offset, 1), size=(B, C)), c).astype(np.int64)
+
+
+# ---- the search flavours: fixtures and call sequences of tests/test_index_flavour_sequences_gpu.py ----------------------------
+
+FLAVOURS = ("tagged", "biased", "after", "pages", "diverse", "collapsed", "mine")
+SETTERS = ("set_tags", "set_bias", "set_groups")
+BIAS_CYCLE = ("random", "absorbing", "spikes")    # biased_ref.bias_patterns, taken in turn by every set_bias
+N_TIES = 20            # the first 20 pool queries ARE one of a pair of identical rows
+SMALL_TENANT = 7       # the tenant whose six rows the first removal withdraws
+BIG_GROUP = 5          # the group that owns the head of the first tie queries' lists
+HEAD = 2300            # ... this many places of each: under a keep of one half, about 1150 of the eligible best are its rows,
+                       # more than the 1024 a batched round of collapsed_search fetches, so the masked rounds must run
+FILTERS = ("tenant", "field", "all", "none")
+
+
+def twin_pairs(S):
+    """[N_TIES, 2] local numbers: the two best documents of every tie query of the pool scores S -- a pair of identical rows,
+    so every query scores the two alike."""
+    pairs = np.stack([np.lexsort((np.arange(S.shape[1]), -S[j]))[:2] for j in range(N_TIES)])
+    assert (S[np.arange(N_TIES), pairs[:, 0]] == S[np.arange(N_TIES), pairs[:, 1]]).all()
+    assert (S[:, pairs[:, 0]] == S[:, pairs[:, 1]]).all(), "twins tie for every query"
+    return pairs
+
+
+def n_heads(N):
+    """How many tie queries' heads the big group holds: as many as leave three quarters of the corpus to the other groups."""
+    return max(1, min(N_TIES, N // (4 * HEAD)))
+
+
+def tag_fixture(N, pairs, seed):
+    """uint32 [N]: a tenant in bits 0-2 and a field in bits 8-9.  Tenants 0..6 at random; tenant 7 is the twins of the first
+    three tie queries alone (the first removal of a sequence empties it); the two rows of every other twin pair live in
+    DIFFERENT tenants."""
+    rs = np.random.RandomState(seed)
+    tenant = rs.randint(0, SMALL_TENANT, size=N)
+    tenant[pairs[3:, 1]] = (tenant[pairs[3:, 0]] + 1) % SMALL_TENANT
+    tenant[pairs[:3].ravel()] = SMALL_TENANT
+    return (tenant | (rs.randint(0, 4, size=N) << 8)).astype(np.uint32)
+
+
+def draw_filters(rs, B):
+    """(match_mask, match_value) uint32 [B], per query one of FILTERS: tenant equality, the field alone, everything
+    (mask 0 / value 0), nothing (a value bit outside the mask)."""
+    kinds = rs.randint(len(FILTERS), size=B)
+    kinds[:len(FILTERS)] = rs.permutation(len(FILTERS))[:B]         # a batch of four or more holds every kind
+    tenant, field = rs.randint(0, 8, size=B), rs.randint(0, 4, size=B)
+    mm = np.choose(kinds, [np.full(B, 0x7), np.full(B, 0x300), np.zeros(B, int), np.full(B, 0x7)])
+    mv = np.choose(kinds, [tenant, field << 8, np.zeros(B, int), np.full(B, 0x8)])
+    return mm.astype(np.uint32), mv.astype(np.uint32)
+
+
+def group_fixture(S, pairs, seed):
+    """int64 [N]: runs of 1 to 40 rows of a random permutation share a group id, about 10 % of the rows are ungrouped
+    (negative ids, several of them); the twins of an even tie query share a group of their own, those of an odd one sit in
+    two groups; then BIG_GROUP takes the HEAD best places of the first n_heads(N) tie queries."""
+    N = S.shape[1]
+    rs = np.random.RandomState(seed)
+    g = np.empty(N, dtype=np.int64)
+    perm, at, gid = rs.permutation(N), 0, 10
+    while at < N:
+        size = rs.randint(1, 41)
+        g[perm[at:at + size]] = gid
+        at, gid = at + size, gid + 1
+    loose = rs.rand(N) < 0.1
+    g[loose] = -1 - rs.randint(0, 3, size=int(loose.sum()))
+    for j in range(N_TIES):
+        g[pairs[j, 1]] = 1_000_000 + j
+        g[pairs[j, 0]] = 1_000_000 + j if j % 2 == 0 else 2_000_000 + j
+    for j in range(n_heads(N)):
+        g[np.lexsort((np.arange(N), -S[j]))[:HEAD]] = BIG_GROUP
+    return g
+
+
+def flavour_sequence(seed, n_ops=24):
+    """(kind, draw) calls on one index: every flavour twice, two removals, one replacement of each of tags, bias and groups,
+    the identities and the call that must run masked collapse rounds, then random flavours and removals up to n_ops, shuffled.
+    The identities and the masked-rounds call go to the end when the shuffle put them in front of the first removal: they
+    are to run with removals in force.  `draw` seeds the call's own draws, so a call does not depend on its predecessors'."""
+    rs = np.random.RandomState(seed)
+    must = list(FLAVOURS) * 2 + ["remove", "remove", *SETTERS, "identities", "masked_rounds"]
+    body = must + list(rs.choice(FLAVOURS + ("remove",), size=max(n_ops - len(must), 0)))
+    rs.shuffle(body)
+    first = body.index("remove")
+    late = [x for x in body[:first] if x in ("identities", "masked_rounds")]
+    body = [x for x in body[:first] if x not in late] + body[first:] + late
+    return [(str(kind), int(rs.randint(1 << 30))) for kind in body]
+
+
+PIPE_FLAVOURS = ("tagged", "biased", "after")
+
+
+def with_flavours(ops, seed, batches):
+    """The pipelined sequence `ops` with flavour calls mixed in: (kind, B, start, draw) of PIPE_FLAVOURS behind about every
+    third call, B out of `batches` (the submitted steps' own), and at the end whatever kind came up less than twice.  They
+    are no submits: the steps' numbers, and the history that says which step may be collected, stay as they were."""
+    rs = np.random.RandomState(seed)
+    out, n = [], {kind: 0 for kind in PIPE_FLAVOURS}
+
+    def one(kind):
+        n[kind] += 1
+        return (kind, int(batches[rs.randint(len(batches))]), int(rs.randint(POOL)), int(rs.randint(1 << 30)))
+
+    for op in ops:
+        out.append(op)
+        if rs.rand() < 0.3:
+            out.append(one(PIPE_FLAVOURS[rs.randint(len(PIPE_FLAVOURS))]))
+    for kind in PIPE_FLAVOURS:
+        while n[kind] < 2:
+            out.append(one(kind))
+    return out

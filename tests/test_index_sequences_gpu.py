@@ -52,15 +52,24 @@ def same(got, want, what=""):
 
 # ---- corpora, made once --------------------------------------------------------------------------------------------------------
 
+# corpus name -> the pool's score matrix, kept for the process: the modules that import `corpora` make the same corpora again.
+# The name alone is the key: `corpora` makes every named corpus from fixed seeds, so one name is one matrix.
+_POOL_SCORES = {}
+
+
 class Corpus:
     """Rows (as the index takes them), their fp32 widening on the host, the query pool and its score matrix."""
 
-    def __init__(self, oracle, rows, pool, screen=False, screen_masked=False, streamed=False):
+    def __init__(self, oracle, rows, pool, screen=False, screen_masked=False, streamed=False, name=None):
         self.rows, self.screen, self.screen_masked, self.streamed = rows, screen, screen_masked, streamed
         self.wide = rows.float().cpu().numpy()
         self.N, self.d = self.wide.shape
         self.pool, self.Qd = pool, dev(pool)
-        self.S = im.IndexModel(self.wide, OFF, lambda Q, D: par_rows(lambda q: oracle.score_all(q, D), Q)).scores(pool)
+        if name is None or name not in _POOL_SCORES:
+            S = im.IndexModel(self.wide, OFF, lambda Q, D: par_rows(lambda q: oracle.score_all(q, D), Q)).scores(pool)
+            if name is not None:
+                _POOL_SCORES[name] = S
+        self.S = S if name is None else _POOL_SCORES[name]
         self.shapes = [(1, 10), (33, 10), (33, 50), (33, 100)]
         if screen:
             self.shapes.insert(3, (130, 10))
@@ -111,14 +120,14 @@ def corpora(tt, oracle):
                 D, pick = rows_with_twins(51, 3000, 64)
                 rows = torch.from_numpy(D).cuda()
                 rows = rows.to(torch.bfloat16) if base == "small_bf16" else rows
-                made[base] = Corpus(oracle, rows, pool_with_ties(52, rows.float().cpu().numpy(), pick))
+                made[base] = Corpus(oracle, rows, pool_with_ties(52, rows.float().cpu().numpy(), pick), name=base)
             elif base == "screened":
                 D, pick = rows_with_twins(53, 65536, 256)
-                made[base] = Corpus(oracle, torch.from_numpy(D).cuda(), pool_with_ties(54, D, pick), screen=True)
+                made[base] = Corpus(oracle, torch.from_numpy(D).cuda(), pool_with_ties(54, D, pick), screen=True, name=base)
             else:
                 D, pick = rows_with_twins(55, 3 * 1024 - 5, 64)
                 rows = torch.from_numpy(D).to(torch.bfloat16)               # stays on the host: three blocks, the last ragged
-                made[base] = Corpus(oracle, rows, pool_with_ties(56, rows.float().numpy(), pick), streamed=True)
+                made[base] = Corpus(oracle, rows, pool_with_ties(56, rows.float().numpy(), pick), streamed=True, name=base)
         c = made[base]
         if name == "screened_masked":                                       # the same rows and scores, the other index
             if name not in made:

@@ -2281,9 +2281,14 @@ class StreamedIndex(_CursorSearch):
         """The same corpus widened once into HBM (N*d*4 bytes fp32 + N*d*2 bytes fp16 shadow): configs[4]'s shard
         of 12.5M passages is 19.2 GB of a 288 GB GPU, after which it is searched at the resident rates.
         dtype=torch.bfloat16: the rows are copied to HBM as they are (N*d*2 bytes, 6.4 GB for that shard) and searched by
-        the exact bf16 kernel (same results)."""
+        the exact bf16 kernel (same results).
+        The new index starts from this index's state: it is handed COPIES of the keep-bitmask of remove_ids and of the tags,
+        biases and group ids (set_tags / set_bias / set_groups), so what was removed stays removed and every flavour of search
+        answers as it does here.  From then on the two are independent: a later remove_ids or set_* on one does not show on
+        the other."""
         if dtype == torch.bfloat16:
-            return BruteForceIndex(self.host.to(self.device), idx_offset=self.idx_offset, screen_masked=self.screen_masked)
+            return self._hand_state(BruteForceIndex(self.host.to(self.device), idx_offset=self.idx_offset,
+                                                    screen_masked=self.screen_masked))
         if dtype != torch.float32:
             raise ValueError(f"resident() keeps float32 or bfloat16 rows, not {dtype}")
         d32 = torch.empty((self.N, self.d), dtype=torch.float32, device=self.device)
@@ -2295,7 +2300,14 @@ class StreamedIndex(_CursorSearch):
                 d16[lo:lo + n].copy_(self._d16[s][:n])
 
         self._walk(visit)
-        return BruteForceIndex._from_buffers(d32, d16, self.dmax_norm, self.idx_offset, self.screen_masked)
+        return self._hand_state(BruteForceIndex._from_buffers(d32, d16, self.dmax_norm, self.idx_offset, self.screen_masked))
+
+    def _hand_state(self, index: "BruteForceIndex") -> "BruteForceIndex":
+        """resident(): copies of the keep-bitmask, tags, biases and group ids, in the layouts the two classes share."""
+        for name in ("_keep", "_tags", "_bias", "_groups"):
+            t = getattr(self, name)
+            setattr(index, name, None if t is None else t.clone())
+        return index
 
     @property
     def ntotal(self) -> int:
