@@ -105,7 +105,9 @@ def test_score_all_bit_exact(env, names):
 
 
 def test_score_all_drops_a_query_column_outside_F_through_the_c_abi(env):
-    """A column >= F (or negative) in the QUERY's list: the Python layer rejects it, the kernel must tolerate it."""
+    """A column >= F (or negative) in the QUERY's list: the kernel must tolerate it, and the Python layer names it when
+    asked (check_query_columns: a host read).  A search does not ask -- it stays asynchronous to the host
+    (tests/test_streams_index_gpu.py) -- and returns what the kernel computes without those columns."""
     m = env.main
     q_cols = np.array([3, F, 50, F + 1000, -7, 2 ** 31 - 1], dtype=np.int32)
     q_vals = np.array([0.5, 9.0, 0.25, 9.0, 9.0, 9.0], dtype=np.float32)
@@ -117,10 +119,15 @@ def test_score_all_drops_a_query_column_outside_F_through_the_c_abi(env):
     torch.cuda.synchronize()
     want = m.scores32(np.array([3, 50]), np.array([0.5, 0.25], dtype=np.float32))
     assert np.array_equal(_bits(S.cpu().numpy()[0]), _bits(want))
-    idx = env.tt.LexicalIndex  # the Python layer refuses the same query
-    ix = idx((_dev(np.array([0, 1], dtype=np.int64)), _dev(np.array([0], dtype=np.int32)), _dev(np.array([1.0], dtype=np.float32)), F))
-    with pytest.raises(ValueError, match="column outside"):
-        ix.search((qi, qc, qv), 1)
+    from twotowermlretrieval_amd.lexical import check_query_columns
+    with pytest.raises(ValueError, match="column outside"):  # the Python layer refuses the same query, where it looks
+        check_query_columns((qi, qc, qv), F)
+    check_query_columns(_q([(np.array([3, 50]), np.array([0.5, 0.25], dtype=np.float32))]), F)
+    small = Corpus(*ref.random_corpus(5, 300, F), F)  # (a valid matrix: LexicalIndex validates, `main` repeats columns)
+    gv, gi = env.tt.LexicalIndex((*small.t, F)).search((qi, qc, qv), 10)  # ... and a search ranks without those columns
+    torch.cuda.synchronize()
+    want = small.scores32(np.array([3, 50]), np.array([0.5, 0.25], dtype=np.float32))
+    _assert_rows(gv.cpu().numpy(), gi.cpu().numpy(), [ref.ref_topk(want, 10)], "columns outside F")
 
 
 def test_score_all_at_fmax_with_long_sorted_rows(env):

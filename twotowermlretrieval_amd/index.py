@@ -14,6 +14,8 @@ PyTorch/CPU fallback: inputs must be CUDA(ROCm) tensors.
 """
 from __future__ import annotations
 
+import contextlib
+import threading
 from functools import lru_cache
 from typing import Callable, NamedTuple, Optional, Tuple
 
@@ -1196,6 +1198,14 @@ class BruteForceIndex(_CursorSearch):
     masked exact kernel's bit for bit, and fallback_flags / search_stats() report the screen's own values.  It is opt-in:
     without it nothing changes.  k > 64 runs the exact route either way, and a masked document is still streamed and
     multiplied: a selective mask pays the full scan.
+
+    Callers, streams and threads: every search of one index may be in flight on any number of streams and host threads at
+    once; each call takes its workspace, flags and outputs per call (the caching allocator's blocks of the caller's stream)
+    and orders nothing against another call.  All of them are asynchronous to the host except collapsed_search(exact=True),
+    which reads its `complete` flags once per round.  fallback_flags, collapse_rounds and keep_stats / search_stats() name
+    "the most recent call": diagnostics of one caller at a time, not to be read while another thread searches.  remove_ids
+    and set_tags / set_bias / set_groups are the one mutating caller's: launches on its stream, ordered against searches
+    by that caller.
     """
 
     def __init__(self, doc_embeddings: torch.Tensor, idx_offset: int = 0, screen: bool = False, screen_masked: bool = False):
@@ -1529,7 +1539,12 @@ class GraphedSearch:
     (valid until the next call).
     Removals: a graph captured while the index has a persistent keep-bitmask reads that buffer at every replay, so later
     remove_ids are honoured (on a screen_masked=True index the replayed launches are the masked screened search's).  A graph captured BEFORE the index had one holds the unmasked launches: calling it after a
-    remove_ids raises RuntimeError (capture a new GraphedSearch) rather than return removed documents."""
+    remove_ids raises RuntimeError (capture a new GraphedSearch) rather than return removed documents.
+
+    Callers, streams and threads: ONE caller at a time per object -- the query, exclusion and result buffers and the graph's
+    workspaces are static, so a second replay of the same object may start only after the first one's results have been
+    read.  Different GraphedSearch objects over one index share nothing but its rows and may replay on different streams
+    at once; a replay is asynchronous to the host."""
 
     def __init__(self, index: "BruteForceIndex", batch: int, k: int = 10, exclude_width: int = 0):
         self.index, self.B, self.k = index, int(batch), int(k)
@@ -1750,7 +1765,15 @@ class ShardedIndex(_CursorSearch):
 
     Whether the seed exchange happens at all is agreed ONCE, in the constructor (a collective): every rank has an fp16 shadow
     copy and at least SCREEN_MIN_DOCS rows, or no rank exchanges seeds -- a rank-local decision (shard sizes straddling the
-    minimum, one shard outside the fp16 range) would leave some ranks in an all-gather the others never enter."""
+    minimum, one shard outside the fp16 range) would leave some ranks in an all-gather the others never enter.
+
+    Callers, streams and threads: ONE issuing host thread per object (every search is a collective: the ranks must issue the
+    same calls in the same order), on any streams.  Calls that share a slot (search / tagged_search / search_after of one
+    shape; biased_search has its own) are ordered by the slot's `merged` event, which a call waits for on entry and records
+    after its last read of the slot, so a call on another stream never overwrites rows that are still being copied out;
+    submit()'s two slots per shape are ordered the same way and search() never touches them.  Asynchronous to the host,
+    except where the shard's own index synchronises (a streamed shard's score_ids / candidates= / diverse_search) and
+    collapsed_search(exact=True)."""
 
     def __init__(self, local_docs, row_offset: int, group=None, shard_k: int = 50, screen: bool = False,
                  comm=None, block_docs: int = 1 << 20, device=None, screen_masked: bool = False):
@@ -1981,8 +2004,9 @@ class ShardedIndex(_CursorSearch):
             res = topk_exclude(sl.out_v, sl.out_i, exclude, k_out)  # (reads the slot: before it is handed on)
             sl.merged.record(cur)
             return res
+        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
         sl.merged.record(cur)
-        return sl.out_v.clone(), sl.out_i.clone()
+        return res
 
     @property
     def tags(self) -> Optional[torch.Tensor]:
@@ -2013,8 +2037,9 @@ class ShardedIndex(_CursorSearch):
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
         self._index.tagged_search(q, kp, match_mask, match_value, keep=keep, out=(sl.send_v, sl.send_i))
         self._exchange_merge(sl, q.shape[0], kp, k)
+        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
         sl.merged.record(cur)
-        return sl.out_v.clone(), sl.out_i.clone()
+        return res
 
     @property
     def bias(self) -> Optional[torch.Tensor]:
@@ -2044,8 +2069,9 @@ class ShardedIndex(_CursorSearch):
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
         self._index.biased_search(q, kp, keep=keep, out=(sl.send_v, sl.send_i))
         self._exchange_merge(sl, q.shape[0], kp, k)
+        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
         sl.merged.record(cur)
-        return sl.out_v.clone(), sl.out_i.clone()
+        return res
 
     def _cursor_device(self) -> torch.device:
         return self._dev
@@ -2065,12 +2091,13 @@ class ShardedIndex(_CursorSearch):
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
         self._index._search_after(q, kp, av, ai, keep, (sl.send_v, sl.send_i))
         self._exchange_merge(sl, q.shape[0], kp, k)
-        sl.merged.record(cur)
         if out is not None:
             out[0].copy_(sl.out_v)
             out[1].copy_(sl.out_i)
-            return out
-        return sl.out_v.clone(), sl.out_i.clone()
+        else:
+            out = sl.out_v.clone(), sl.out_i.clone()
+        sl.merged.record(cur)  # (after the copies that read the slot: the next caller may write it from here on)
+        return out
 
     def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """float32 [B,C] ([C] for a single query), identical on every rank: the exact dense score of every id of ids int64
@@ -2220,6 +2247,17 @@ class StreamedIndex(_CursorSearch):
     with the merge kernel.  Two staging buffers; events order the two streams.  The result is the exact
     top-k over the bf16 corpus (bf16 -> fp32 is exact), with the usual (score desc, index asc) order.
     PCIe-bound by design: ~55-60 GB/s on Gen5 x16, i.e. ~110 ms per pass over a 6.4 GB shard.
+
+    Callers, streams and threads: RE-ENTRANT.  Any interleaving of the searches of one object from any streams and from
+    several host threads returns what each call returns alone.  The staging buffers, the widened blocks, the copy stream and
+    the pinned gather buffers are the object's, so passes over them are ORDERED, not concurrent: a host lock covers the part
+    of a call that enqueues a pass (a walk, or score_ids' gather), and an event recorded on the caller's stream at the end of
+    each pass is waited for by the next pass's stream and by the copy stream -- passes run on the device one after another in
+    the order they were issued, whatever streams they came from (a pass is PCIe-bound: two at once would share the link).
+    No memory is added per caller.  A walk stays asynchronous to the host; score_ids, search(candidates=) and
+    diverse_search synchronise with the host as their docstrings say, and a thread that issues a pass meanwhile waits for
+    that call's lock.  remove_ids / set_tags / set_bias / set_groups are the one mutating caller's: not while searches are
+    being issued.  collapse_rounds describes the most recent call.
     """
 
     def __init__(self, host_docs: torch.Tensor, block_docs: int = 1 << 20, device=None, idx_offset: int = 0,
@@ -2240,6 +2278,8 @@ class StreamedIndex(_CursorSearch):
         self._copy = torch.cuda.Stream(device=dev)
         self._ready = [torch.cuda.Event() for _ in range(2)]
         self._free = [torch.cuda.Event() for _ in range(2)]
+        self._lock = threading.Lock()    # held while a pass over the staging buffers is being enqueued (_ordered)
+        self._done = torch.cuda.Event()  # caller's stream: the most recent pass has read the last of the shared buffers
         # one streaming pass at build time: the corpus-wide largest row norm bounds the screen's error term
         stats = torch.zeros(2, dtype=torch.float32, device=dev)
         self._walk(lambda s, lo, n: None, stats=stats)
@@ -2254,28 +2294,43 @@ class StreamedIndex(_CursorSearch):
         self._groups: Optional[torch.Tensor] = None  # one int64 group id per row, resident on the device (set_groups)
         self.collapse_rounds = (0, 0)  # (batched, masked) rounds of the most recent collapsed_search
 
+    @contextlib.contextmanager
+    def _ordered(self):
+        """One pass over the shared buffers (staging, widened blocks, pinned gather) at a time, in issue order: yields the
+        caller's stream once it and the copy stream are behind the previous pass -- whichever stream that ran on --, under
+        the object's lock; on the way out the pass's end is recorded on that stream for the next one.  Nothing here waits on
+        the host."""
+        with self._lock:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(self._done)         # the previous pass's kernels have read _d32 / _d16 / _stage
+            self._copy.wait_event(self._done)  # ... before this pass's first copy lands in _stage
+            try:
+                yield cur
+            finally:
+                self._done.record(cur)
+
     def _walk(self, visit, stats=None):
         L = _lib.lib()
-        cur = torch.cuda.current_stream(self.device)
-        for s in range(2):
-            self._free[s].record(cur)
         nblk = (self.N + self.block - 1) // self.block
-        for i in range(nblk):
-            s = i % 2
-            lo = i * self.block
-            n = min(self.block, self.N - lo)
-            with torch.cuda.stream(self._copy):
-                self._copy.wait_event(self._free[s])          # the staging buffer has been consumed
-                self._stage[s][:n].copy_(self.host[lo:lo + n], non_blocking=True)
-                self._ready[s].record(self._copy)
-            cur.wait_event(self._ready[s])
-            with torch.cuda.device(self.device):
-                _lib.check(L.tt_index_build_from_bf16(
-                    self._stage[s].data_ptr(), n, self.d, self._d32[s].data_ptr(),
-                    self._d16[s].data_ptr() if self._d16[s] is not None else None,
-                    stats.data_ptr() if stats is not None else None, 0, cur.cuda_stream))
-            self._free[s].record(cur)
-            visit(s, lo, n)
+        with self._ordered() as cur:
+            for s in range(2):
+                self._free[s].record(cur)
+            for i in range(nblk):
+                s = i % 2
+                lo = i * self.block
+                n = min(self.block, self.N - lo)
+                with torch.cuda.stream(self._copy):
+                    self._copy.wait_event(self._free[s])          # the staging buffer has been consumed
+                    self._stage[s][:n].copy_(self.host[lo:lo + n], non_blocking=True)
+                    self._ready[s].record(self._copy)
+                cur.wait_event(self._ready[s])
+                with torch.cuda.device(self.device):
+                    _lib.check(L.tt_index_build_from_bf16(
+                        self._stage[s].data_ptr(), n, self.d, self._d32[s].data_ptr(),
+                        self._d16[s].data_ptr() if self._d16[s] is not None else None,
+                        stats.data_ptr() if stats is not None else None, 0, cur.cuda_stream))
+                self._free[s].record(cur)
+                visit(s, lo, n)
 
     def resident(self, dtype: torch.dtype = torch.float32) -> "BruteForceIndex":
         """The same corpus widened once into HBM (N*d*4 bytes fp32 + N*d*2 bytes fp16 shadow): configs[4]'s shard
@@ -2345,29 +2400,29 @@ class StreamedIndex(_CursorSearch):
         U = rows.numel()
         need = min(self.block, U)  # rows per pinned buffer: grown on demand, never beyond a staging buffer
         bufs = 1 if U <= self.block else 2
-        if self._gather is None or self._gather[0].shape[0] < need or len(self._gather) < bufs:
-            self._gather = [torch.empty((need, self.d), dtype=torch.bfloat16).pin_memory() for _ in range(bufs)]
-        cur = torch.cuda.current_stream(dev)
-        for s in range(2):
-            self._free[s].record(cur)
-        for j, p0 in enumerate(range(0, U, self.block)):
-            s = j % 2
-            m = min(self.block, U - p0)
-            if j >= 2:
-                self._ready[s].synchronize()  # the copy out of this pinned buffer two pieces ago has finished
-            torch.index_select(self.host, 0, rows[p0:p0 + m], out=self._gather[s][:m])
-            with torch.cuda.stream(self._copy):
-                self._copy.wait_event(self._free[s])
-                self._stage[s][:m].copy_(self._gather[s][:m], non_blocking=True)
-                self._ready[s].record(self._copy)
-            cur.wait_event(self._ready[s])
-            piece = vals if U <= self.block else torch.empty_like(vals)  # (a single piece writes the result itself)
-            _score_ids_into(q, self._stage[s][:m], pos, p0, None, piece, None)  # positions outside the piece: padding
-            self._free[s].record(cur)
-            if piece is not vals:
-                vals = torch.maximum(vals, piece)
-        if U:
-            self._ready[(U - 1) // self.block % 2].synchronize()  # (the pinned buffers are reusable when this returns)
+        with self._ordered() as cur:  # (the pinned buffers are the object's too: the lock is held until their copies are out)
+            if self._gather is None or self._gather[0].shape[0] < need or len(self._gather) < bufs:
+                self._gather = [torch.empty((need, self.d), dtype=torch.bfloat16).pin_memory() for _ in range(bufs)]
+            for s in range(2):
+                self._free[s].record(cur)
+            for j, p0 in enumerate(range(0, U, self.block)):
+                s = j % 2
+                m = min(self.block, U - p0)
+                if j >= 2:
+                    self._ready[s].synchronize()  # the copy out of this pinned buffer two pieces ago has finished
+                torch.index_select(self.host, 0, rows[p0:p0 + m], out=self._gather[s][:m])
+                with torch.cuda.stream(self._copy):
+                    self._copy.wait_event(self._free[s])
+                    self._stage[s][:m].copy_(self._gather[s][:m], non_blocking=True)
+                    self._ready[s].record(self._copy)
+                cur.wait_event(self._ready[s])
+                piece = vals if U <= self.block else torch.empty_like(vals)  # (a single piece writes the result itself)
+                _score_ids_into(q, self._stage[s][:m], pos, p0, None, piece, None)  # positions outside the piece: padding
+                self._free[s].record(cur)
+                if piece is not vals:
+                    vals = torch.maximum(vals, piece)
+            if U:
+                self._ready[(U - 1) // self.block % 2].synchronize()  # (the pinned buffers are reusable when this returns)
         return vals, torch.where(ok, ids, torch.full_like(ids, -1))
 
     def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:

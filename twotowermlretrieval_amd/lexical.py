@@ -82,18 +82,26 @@ def _csr_tensors(t, what: str):
     return indptr.contiguous(), cols.contiguous(), vals.contiguous()
 
 
+def check_query_columns(q, n_features: int) -> None:
+    """ValueError if a (q_indptr, q_cols, q_vals) device triple holds a column outside [0, n_features).  It reads the
+    columns' extremes on the host: a SYNCHRONISATION with the stream that produced them, which is why no search makes this
+    check by itself (the kernels drop such a column).  For callers who build their own device queries and want to know."""
+    _, qc, _ = _csr_tensors(q, "q")
+    if qc.numel():
+        lo, hi = int(qc.min()), int(qc.max())
+        if lo < 0 or hi >= n_features:
+            raise ValueError(f"q: column outside [0, {n_features})")
+
+
 def _query_tensors(q, n_features: int, device):
     """The queries of a search as device CSR: a scipy sparse [B, n_features] matrix (converted like the corpus: duplicates
-    summed, a wrong width refused), or a (q_indptr, q_cols, q_vals) device triple, whose columns are checked against
-    n_features with one device read unless the stream is being captured (the kernel drops such a column either way)."""
+    summed, a wrong width refused), or a (q_indptr, q_cols, q_vals) device triple, taken as it is: its dtypes, shapes and
+    device are checked, its contents are not read -- a search stays asynchronous to the host, and the kernel drops a column
+    outside [0, n_features) (check_query_columns looks, at the price of a synchronisation)."""
     if isinstance(q, (tuple, list)):
         qi, qc, qv = _csr_tensors(q, "q")
         if qi.device != device:
             raise ValueError(f"queries on {qi.device} but the index lives on {device}")
-        if qc.numel() and not torch.cuda.is_current_stream_capturing():
-            lo, hi = int(qc.min()), int(qc.max())
-            if lo < 0 or hi >= n_features:
-                raise ValueError(f"q: column outside [0, {n_features})")
         return qi, qc, qv
     indptr, cols, vals, f = csr_arrays(q)
     if f != n_features:
@@ -168,7 +176,12 @@ class LexicalIndex:
     summed (csr_arrays); either form is validated on the host once: indptr monotone from 0, 0 <= col < F, columns ascending
     within a row.  Stored as float32 values, int32 columns, int64 indptr (8 bytes per entry + 8 per row).  F <= 20480.
     Row i is document idx_offset + i in what search() returns.  remove_ids / keep_mask / search(keep=) work as on
-    BruteForceIndex, with the same packed words (pack_keep_mask)."""
+    BruteForceIndex, with the same packed words (pack_keep_mask).
+
+    Callers, streams and threads: searches of one index may be in flight on any number of streams and host threads at once
+    (workspace and outputs are per call; nothing is ordered against another call).  With a device CSR query a search is
+    asynchronous to the host: the triple's contents are not read (check_query_columns does, and synchronises); a scipy
+    query is converted on the host and copied.  remove_ids is the one mutating caller's."""
 
     def __init__(self, matrix, device=None, idx_offset: int = 0):
         from_tensors = isinstance(matrix, (tuple, list))
