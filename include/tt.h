@@ -518,6 +518,42 @@ int tt_topk_collapse_gids(const float *in_val, const int64_t *in_idx, const int6
                           int32_t *out_info /*[B][2]*/, tt_stream_t stream);
 
 /*
+ * Fused lists (rank fusion: reciprocal rank fusion, Borda counts, weighted score sums): the best k ids of the union of L
+ * ranked lists per query.  Replaces the last step of the reference's hybrid search,
+ *   final = alpha * dense + (1 - alpha) * tfidf ; sort ; top n      frontend/main.py:102-210 (hybrid.py's docstring, step 4)
+ * where the two score scales are not comparable, where a document may be in one list only, or where there are more than two
+ * lists -- and the copy to the host and the Python dict over ids that a caller needs otherwise.
+ * The rule.  Row b of in_idx (and in_val) [B][L][M] holds L lists of M entries as the searches and merges write them: padding
+ * (-inf, idx < 0) at the tail; a shorter list is padded to M.  Entry (l, m) is LIVE if idx >= 0 and no entry (l, m' < m) of the
+ * same list carries its id: the first occurrence in a list counts.  pos_l(id) = the column of id's live entry in list l; without
+ * one, id is absent from list l.  The fused score of an id is acc = +0.0f, then for l = 0 .. L-1 in that order
+ *   acc = fl32(acc + t_l),   t_l = rank_weight[l][pos_l]                   (_rank_)   when id is present in list l,
+ *                            t_l = fl32(weight[l] * in_val[b][l][pos_l])   (_score_)  when id is present in list l,
+ *                            t_l = missing[l]                                          when it is absent,
+ * the multiply and every add rounded separately (no FMA).  The kernel divides nothing and does no other arithmetic: RRF
+ * (w_l / (c + m + 1)), Borda counts and every other rank weighting are a TABLE [L][M] that the host forms in float64 and
+ * rounds once, which is what makes the result bit-defined.
+ * out_val / out_idx [B][k]: the k ids of the row's union with the best (fused desc, id asc), then (-inf, -1).
+ * out_pos [B][k][L] (int32, may be NULL): pos_l of result r, -1 where it is absent, -1 everywhere in tail rows -- with it a
+ * caller gathers every result's component scores.
+ * Contract on inputs: tables, weights and missing are finite; in the score form the values of entries with idx >= 0 are
+ * finite.  Otherwise the order of the affected row is unspecified; the call still writes only inside its outputs and reads
+ * only inside its inputs.
+ * All pointers are device pointers.  1 <= L <= 8, M >= 1, L * M <= TT_TOPK_LARGE_KMAX (L > 8 or L * M above it:
+ * TT_ERR_UNSUPPORTED), 1 <= k <= L * M (else TT_ERR_BAD_SHAPE, like negative sizes, null or misaligned pointers -- 4 bytes for
+ * f32 / int32, 8 for int64 -- and an output that overlaps an input); B = 0 does nothing.  One launch, one 256-thread workgroup
+ * per row: ids and terms sit in LDS (about 17 KB), every entry finds its id's first occurrence in every list with broadcast
+ * 128-bit reads, the first live entry of an id sums the terms, and ranks itself among the others: O((L M)^2) compares per
+ * row.  Asynchronous, capturable: no workspace, no host synchronisation, no atomics; the result depends only on the inputs.
+ */
+int tt_topk_fuse_rank_f32(const int64_t *in_idx /*[B][L][M]*/, int B, int L, int M, const float *rank_weight /*[L][M]*/,
+                          const float *missing /*[L]*/, int k, float *out_val /*[B][k]*/, int64_t *out_idx /*[B][k]*/,
+                          int32_t *out_pos /*[B][k][L], nullable*/, tt_stream_t stream);
+int tt_topk_fuse_score_f32(const float *in_val /*[B][L][M]*/, const int64_t *in_idx /*[B][L][M]*/, int B, int L, int M,
+                           const float *weight /*[L]*/, const float *missing /*[L]*/, int k, float *out_val, int64_t *out_idx,
+                           int32_t *out_pos, tt_stream_t stream);
+
+/*
  * Threshold search (FAISS users: range_search): how many documents score at least min_score[b] for query b, and the best k
  * of them.  Replaces
  *   s = torch.matmul(q, D.t()) ; (s >= t).sum(1) ; torch.topk(s, k) with the entries below t masked

@@ -7,6 +7,8 @@ from .index import (BruteForceIndex, GraphedSearch, PendingSearch, ShardedIndex,
 from .mining import mine_hard_negatives
 from .lexical import LexicalIndex, lexical_score_all, lexical_score_topk
 from .hybrid import HybridSearcher, SimpleHybridRetriever
+from . import fusion
+from .fusion import HybridIndex, fuse_topk, fused_search, rrf_weights
 from .model import (LogitScale, RNNEncoder, TwoTowerModel, contrastive_softmax_loss, distillation_targets, in_batch_softmax_loss, multi_positive_targets,
                     soft_contrastive_loss, symmetric_contrastive_losses, triplet_loss_cosine)
 from .query_inferencer import QueryInferencer
@@ -15,6 +17,7 @@ from .trainer import DataParallelTrainer, FusedClipAdam, GraphedTrainStep, train
 
 __all__ = ["BruteForceIndex", "GraphedSearch", "ShardedIndex", "PendingSearch", "StreamedIndex", "score_topk", "topk_merge", "topk_exclude", "topk_collapse", "score_rank", "score_all", "score_ids", "mmr_select", "shard_bounds", "pack_keep_mask", "score_count", "topk_cut_below", "score_topk_tagged", "score_topk_biased", "l2_bias", "l2_distances", "score_topk_after", "mine_hard_negatives", "mining",
            "LexicalIndex", "lexical_score_topk", "lexical_score_all", "lexical",
+           "HybridIndex", "fuse_topk", "fused_search", "rrf_weights", "fusion",
            "RNNEncoder", "TwoTowerModel", "triplet_loss_cosine", "in_batch_softmax_loss", "contrastive_softmax_loss", "soft_contrastive_loss", "symmetric_contrastive_losses", "LogitScale", "distillation_targets", "multi_positive_targets", "QueryInferencer", "PretrainedTokenizer", "HybridSearcher", "SimpleHybridRetriever",
            "FusedClipAdam", "DataParallelTrainer", "train_step", "GraphedTrainStep", "model", "trainer", "tokenizer", "query_inferencer",
            "evaluators", "hybrid", "collective"]

@@ -92,6 +92,8 @@ SIGNATURES = {
     "tt_topk_exclude_ids": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "tt_topk_collapse_table": (_i, [_vp, _vp, _i, _i, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "tt_topk_collapse_gids": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "tt_topk_fuse_rank_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "tt_topk_fuse_score_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "tt_score_count_workspace_bytes": (_sz, [_i, _i64, _i, _i]),
     "tt_score_count_f32": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "tt_score_count_bf16": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _sz, _vp]),

@@ -19,6 +19,12 @@ lexical_candidates, SimpleHybridRetriever's blend over every document -- are one
 of sklearn's cosine_similarity + argsort on the host.  The GPU lexical score is the fp32 dot product of the f32-ROUNDED
 TF-IDF rows; sklearn renormalises in float64, so the two agree within (m + 3) * 2^-24 for a query of m terms and are not
 bit-identical: near-ties may swap, which is why the default, lexical="sklearn", stays the code it always was.
+
+Rank fusion (opt-in, fusion="rrf", needs lexical="gpu").  Step 4's blend adds a cosine to a TF-IDF score and sees the dense
+candidates only.  fusion="rrf" replaces steps 3 and 4 by reciprocal rank fusion (fusion.py) of the dense top-`n_candidates` and
+the lexical top-`n_candidates` of the WHOLE corpus: score = alpha / (60 + dense rank) + (1 - alpha) / (60 + lexical rank), ranks
+from 1, a list that lacks the document adding 0 -- one launch on the device.  The default, fusion="blend", is the reference's
+step 4, untouched.
 """
 from __future__ import annotations
 
@@ -43,7 +49,7 @@ def _lexical_mode(lexical: str) -> str:
 class HybridSearcher:
     def __init__(self, inferencer, documents: Sequence[str], doc_embeddings: torch.Tensor = None, tfidf_vectorizer=None,
                  doc_tfidf_matrix=None, n_candidates: int = 50, dense_score: str = "cosine", index: BruteForceIndex = None,
-                 lexical_candidates: int = 0, lexical: str = "sklearn"):
+                 lexical_candidates: int = 0, lexical: str = "sklearn", fusion: str = "blend"):
         """documents: documents.pkl's list (row i of the embeddings <-> documents[i]); any object with __len__ and __getitem__
         is used as it is (a corpus too large for a Python list: an mmap-backed or generated sequence), other iterables are
         listed.  index: an existing BruteForceIndex over the embedding matrix instead of doc_embeddings (one is built otherwise).
@@ -51,7 +57,15 @@ class HybridSearcher:
         lexical match is lost when it ranks below them by cosine.  n > 0 adds the query's n best TF-IDF matches over the
         whole corpus (similarity > 1e-5) to the candidates; their dense scores come from index.score_ids.
         lexical: "sklearn" (the default) computes the whole-corpus TF-IDF steps on the host as the reference does; "gpu"
-        uploads doc_tfidf_matrix once as a LexicalIndex and answers them with one search each (module docstring)."""
+        uploads doc_tfidf_matrix once as a LexicalIndex and answers them with one search each (module docstring).
+        fusion: "blend" (the default) is the reference's alpha * dense + (1 - alpha) * tfidf over the candidates; "rrf" (needs
+        lexical="gpu") ranks the union of the dense and the lexical top-`n_candidates` by reciprocal rank fusion with the
+        weights (alpha, 1 - alpha) (module docstring)."""
+        if fusion not in ("blend", "rrf"):
+            raise ValueError("fusion must be 'blend' or 'rrf'")
+        if fusion == "rrf" and lexical != "gpu":
+            raise ValueError("fusion='rrf' fuses the two lists on the device: it needs lexical='gpu'")
+        self.fusion = fusion
         if dense_score not in ("cosine", "chroma_l2"):
             raise ValueError("dense_score must be 'cosine' or 'chroma_l2'")
         self.lexical = _lexical_mode(lexical)
@@ -89,8 +103,34 @@ class HybridSearcher:
         live = idx >= 0
         return idx[live] - self.index.idx_offset, vals[live]
 
+    def _search_rrf(self, query: str, alpha: float, n_results: int) -> List[Dict]:
+        """fusion="rrf": the dense and the lexical top-n_candidates, one fuse launch, the reference's dict per result with the
+        fused score as `score`; a component a list lacks reads 0.0."""
+        from .fusion import fuse_topk
+        n = min(self.n_candidates, self.index.ntotal)
+        if n <= 0 or n_results <= 0:
+            return []
+        q = torch.from_numpy(self.inferencer.get_query_embedding(query)).to(self.index.docs.device)
+        dv, di = self.index.search(q, n)
+        lv, li = self.lexical_index.search(self.tfidf.transform([query]), n, min_score=LEXICAL_MIN_SCORE, keep=self.index.keep_mask)
+        fv, fi, pos = fuse_topk(((dv, di), (lv[0], li[0])), min(int(n_results), 2 * n), method="rrf",
+                                weights=(float(alpha), 1.0 - float(alpha)), return_positions=True)
+        fv, fi, pos, dv, lv = fv.cpu().numpy(), fi.cpu().numpy(), pos.cpu().numpy(), dv.cpu().numpy(), lv[0].cpu().numpy()
+        out = []
+        for s, i, (pd, pl) in zip(fv, fi, pos):
+            if i < 0:
+                break
+            cos = float(dv[pd]) if pd >= 0 else 0.0
+            row = int(i) - self.index.idx_offset
+            out.append({"doc": self.documents[row], "index": row, "score": float(s),
+                        "dense_score": cos if self.dense_score == "cosine" or pd < 0 else 2.0 * cos - 1.0,
+                        "tfidf_score": float(lv[pl]) if pl >= 0 else 0.0})
+        return out
+
     def search(self, query: str, alpha: float = 0.5, n_results: int = 10) -> List[Dict]:
         from sklearn.metrics.pairwise import cosine_similarity
+        if self.fusion == "rrf":
+            return self._search_rrf(query, alpha, n_results)
         if alpha == 0.0 and self.lexical == "gpu":
             rows, sims = self._lexical_top(self.tfidf.transform([query]), n_results)
             return [{"doc": self.documents[int(i)], "index": int(i), "score": float(s), "dense_score": 0.0,
