@@ -108,6 +108,26 @@ def _out_pair(B: int, k: int, device, out=None) -> Tuple[torch.Tensor, torch.Ten
     return (torch.empty((B, k), dtype=torch.float32, device=device), torch.empty((B, k), dtype=torch.int64, device=device))
 
 
+def _pad_pair(vals: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(vals, idx) filled with the padding of a search that found nothing: (-inf, -1)."""
+    vals.fill_(float("-inf"))
+    idx.fill_(-1)
+    return vals, idx
+
+
+def _copied(out, vals: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A finished (vals, idx) as the caller gets it: copied into `out` when that is given."""
+    if out is None:
+        return vals, idx
+    out[0].copy_(vals)
+    out[1].copy_(idx)
+    return out
+
+
+def _cloned(vals: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return vals.clone(), idx.clone()
+
+
 def _squeezed(search: Callable, q: torch.Tensor, *args) -> Tuple[torch.Tensor, torch.Tensor]:
     """A single query vector [d]: the same search as the [1,d] batch, squeezed result."""
     vals, idx = search(q.unsqueeze(0), *args)
@@ -122,8 +142,10 @@ def _keep_words(n: int) -> int:
 _KEEP_DTYPES = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
 
 
-def _check_keep(keep: torch.Tensor, n: int, device) -> torch.Tensor:
-    """A packed keep-bitmask over n documents on `device`, as the masked kernels read it (int32 view)."""
+def _check_keep(keep: Optional[torch.Tensor], n: int, device) -> Optional[torch.Tensor]:
+    """A packed keep-bitmask over n documents on `device`, as the masked kernels read it (int32 view); None stays None."""
+    if keep is None:
+        return None
     if keep.dtype not in _KEEP_DTYPES:
         raise TypeError(f"keep must be a packed int32 / uint32 bitmask (pack_keep_mask), got {keep.dtype}")
     if keep.device != device:
@@ -166,10 +188,25 @@ def _clear_ids(keep: Optional[torch.Tensor], n: int, device, ids, idx_offset: in
 def _and_keep(persistent: Optional[torch.Tensor], keep: Optional[torch.Tensor], n: int, device) -> Optional[torch.Tensor]:
     """The mask a search runs under: the index's persistent mask, the caller's per-call one, or their AND (one torch op on
     n/32 words); None = unmasked."""
+    keep = _check_keep(keep, n, device)
     if keep is None:
         return persistent
-    keep = _check_keep(keep, n, device)
     return keep if persistent is None else keep & persistent
+
+
+def _keep_slice(keep: Optional[torch.Tensor], lo: int, n: int) -> Optional[torch.Tensor]:
+    """The words of a checked keep-bitmask that cover rows [lo, lo + n), lo a multiple of 32 (a StreamedIndex block's)."""
+    return None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)]
+
+
+def _front(q: torch.Tensor, docs: torch.Tensor, docs_c: Callable = _docs_c) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What every module-level scoring function checks first of q [B,d] and docs [N,d]: both on the GPU, q float32 and docs
+    as the kernels read them (docs_c: _docs_c, or _f32c where no bf16 kernel exists), contiguous, of one width."""
+    _need_cuda(q, docs)
+    q, docs = _f32c(q), docs_c(docs)
+    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
+        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    return q, docs
 
 
 def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
@@ -181,14 +218,10 @@ def score_topk(q: torch.Tensor, docs: torch.Tensor, k: int, idx_offset: int = 0,
     fewer than k are kept.  A masked document is still read and scored: a selective mask pays the full scan."""
     if q.dim() == 1:
         return _squeezed(score_topk, q, docs, k, idx_offset, workspace, keep)
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
+    q, docs = _front(q, docs)
     B, d = q.shape
     N = docs.shape[0]
-    if docs.dim() != 2 or docs.shape[1] != d:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
-    if keep is not None:
-        keep = _check_keep(keep, N, docs.device)
+    keep = _check_keep(keep, N, docs.device)
     vals, idx = _out_pair(B, k, q.device)
     with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
         route = _exact_route(docs.dtype, k, keep is not None)
@@ -244,30 +277,66 @@ def _match_words(x, B: int, device, what: str) -> torch.Tensor:
 
 
 TAGGED_KMAX = SMALL_KMAX  # tagged search keeps the k <= 64 lists only (tt_score_topk_tagged_*)
+BIASED_KMAX = SMALL_KMAX  # biased search keeps the k <= 64 lists only (tt_score_topk_biased_*)
+AFTER_KMAX = SMALL_KMAX   # one cursor call answers k <= 64 (tt_score_topk_after_*): a larger page is two consecutive calls
 
 
-def _tagged_into(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, mm: torch.Tensor, mv: torch.Tensor,
-                 keep: Optional[torch.Tensor], k: int, idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """tt_score_topk_tagged_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, tags padded int32, mm / mv
-    int32 [B], keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
-    if not 1 <= k <= TAGGED_KMAX:
-        raise ValueError(f"tagged search answers 1 <= k <= {TAGGED_KMAX}, got k = {k}")
+class _Mode(NamedTuple):
+    """One k <= 64 mode of the exact kernel: its entry points, its bound on k and the words of its refusals.  The entry
+    points take (q, B, d, docs, N, *the mode's own tensors, keep, k, idx_offset, vals, idx, workspace, its bytes, stream)."""
+    ws_fn: str
+    fn_f32: str
+    fn_bf16: str
+    kmax: int
+    subject: str    # "... answers 1 <= k <= kmax"
+    per: str = ""   # behind the bound of one call
+    hint: str = ""  # behind the refusal of one call, where a deeper search exists
+
+    def check_k(self, k: int, hint: bool = True) -> None:
+        if not 1 <= k <= self.kmax:
+            raise ValueError(f"{self.subject} answers 1 <= k <= {self.kmax}{self.per}, got k = {k}{self.hint if hint else ''}")
+
+    def shard_k(self, k: int, shard_k: int) -> int:
+        """max(k, shard_k), the length of a shard's list (ShardedIndex), which the mode must answer."""
+        kp = max(k, shard_k)
+        if not 1 <= k or kp > self.kmax:
+            raise ValueError(f"{self.subject} answers 1 <= max(k, shard_k) <= {self.kmax}, got k = {k}, shard_k = {shard_k}")
+        return kp
+
+
+def _mode(stem: str, kmax: int, subject: str, per: str = "", hint: str = "") -> _Mode:
+    return _Mode(f"tt_score_topk_{stem}_workspace_bytes", f"tt_score_topk_{stem}_f32", f"tt_score_topk_{stem}_bf16", kmax,
+                 subject, per, hint)
+
+
+# The one place that names the modes' entry points; their own tensors are (tags, match_mask, match_value), (bias,), (av, ai).
+_TAGGED = _mode("tagged", TAGGED_KMAX, "tagged search")
+_BIASED = _mode("biased", BIASED_KMAX, "biased search")
+_AFTER = _mode("after", AFTER_KMAX, "a cursor search", " per call", " (pages() / deep_search() go deeper)")
+
+
+def _mode_into(mode: _Mode, q: torch.Tensor, docs: torch.Tensor, own: tuple, keep: Optional[torch.Tensor], k: int,
+               idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A mode's entry point over checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, `own` the mode's tensors as its
+    kernel reads them (padded tags and int32 [B] match words; a padded bias whose storage is 16-byte aligned; a checked
+    cursor, _cursor), keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
+    mode.check_k(k)
     B, d = q.shape
     N = docs.shape[0]
     bf16 = docs.dtype == torch.bfloat16
-    vals, idx = _out_pair(B, k, q.device, out)
+    pair = _out_pair(B, k, q.device, out)
     if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
-        vals.fill_(float("-inf"))
-        idx.fill_(-1)
-        return (vals, idx) if out is None else out
+        _pad_pair(*pair)
+        return pair
+    vals, idx = pair
     with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
         L = _lib.lib()
-        ws = torch.empty(max(L.tt_score_topk_tagged_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
-        fn = L.tt_score_topk_tagged_bf16 if bf16 else L.tt_score_topk_tagged_f32
-        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, tags.data_ptr(), mm.data_ptr(), mv.data_ptr(),
+        ws = torch.empty(max(getattr(L, mode.ws_fn)(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
+        fn = getattr(L, mode.fn_bf16 if bf16 else mode.fn_f32)
+        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, *[t.data_ptr() for t in own],
                       None if keep is None else keep.data_ptr(), k, idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(),
                       ws.numel(), _stream(q)))
-    return (vals, idx) if out is None else out
+    return pair
 
 
 def score_topk_tagged(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, match_mask, match_value, k: int,
@@ -282,18 +351,12 @@ def score_topk_tagged(q: torch.Tensor, docs: torch.Tensor, tags: torch.Tensor, m
     and scored: the batch pays one full scan, whatever its filters."""
     if q.dim() == 1:
         return _squeezed(score_topk_tagged, q, docs, tags, match_mask, match_value, k, idx_offset, keep)
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
-    B, d = q.shape
-    N = docs.shape[0]
-    if docs.dim() != 2 or docs.shape[1] != d:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    q, docs = _front(q, docs)
+    B, N = q.shape[0], docs.shape[0]
     tags = _check_tags(tags, N, docs.device)
     mm = _match_words(match_mask, B, docs.device, "match_mask")
     mv = _match_words(match_value, B, docs.device, "match_value")
-    if keep is not None:
-        keep = _check_keep(keep, N, docs.device)
-    return _tagged_into(q, docs, tags, mm, mv, keep, k, int(idx_offset))
+    return _mode_into(_TAGGED, q, docs, (tags, mm, mv), _check_keep(keep, N, docs.device), k, int(idx_offset))
 
 
 def _check_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
@@ -312,36 +375,15 @@ def _check_bias(bias: torch.Tensor, n: int, device) -> torch.Tensor:
     return bias if bias.is_contiguous() else bias.contiguous()
 
 
-def _finite_bias(bias: torch.Tensor, n: int) -> None:
-    """set_bias of the indexes: the one finiteness check of the first n values (a host synchronisation on a device tensor)."""
+def _set_bias(bias: Optional[torch.Tensor], n: int, device) -> Optional[torch.Tensor]:
+    """set_bias of the indexes: the checked, padded biases of n rows on `device` (None clears them), with the one finiteness
+    check of the first n values (a host synchronisation on a device tensor)."""
+    if bias is None:
+        return None
+    bias = _check_bias(bias, n, device)
     if not bool(torch.isfinite(bias[:n]).all()):
         raise ValueError("set_bias: every bias must be finite (NaN or +-inf found)")
-
-
-BIASED_KMAX = SMALL_KMAX  # biased search keeps the k <= 64 lists only (tt_score_topk_biased_*)
-
-
-def _biased_into(q: torch.Tensor, docs: torch.Tensor, bias: torch.Tensor, keep: Optional[torch.Tensor], k: int,
-                 idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """tt_score_topk_biased_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, bias padded f32 whose
-    storage is 16-byte aligned, keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
-    if not 1 <= k <= BIASED_KMAX:
-        raise ValueError(f"biased search answers 1 <= k <= {BIASED_KMAX}, got k = {k}")
-    B, d = q.shape
-    N = docs.shape[0]
-    bf16 = docs.dtype == torch.bfloat16
-    vals, idx = _out_pair(B, k, q.device, out)
-    if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
-        vals.fill_(float("-inf"))
-        idx.fill_(-1)
-        return (vals, idx) if out is None else out
-    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
-        L = _lib.lib()
-        ws = torch.empty(max(L.tt_score_topk_biased_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
-        fn = L.tt_score_topk_biased_bf16 if bf16 else L.tt_score_topk_biased_f32
-        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, bias.data_ptr(), None if keep is None else keep.data_ptr(), k,
-                      idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
-    return (vals, idx) if out is None else out
+    return bias
 
 
 def score_topk_biased(q: torch.Tensor, docs: torch.Tensor, bias: torch.Tensor, k: int, idx_offset: int = 0,
@@ -355,16 +397,10 @@ def score_topk_biased(q: torch.Tensor, docs: torch.Tensor, bias: torch.Tensor, k
     function does NOT check it, a check would need a host synchronisation (the indexes' set_bias checks once)."""
     if q.dim() == 1:
         return _squeezed(score_topk_biased, q, docs, bias, k, idx_offset, keep)
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
-    B, d = q.shape
+    q, docs = _front(q, docs)
     N = docs.shape[0]
-    if docs.dim() != 2 or docs.shape[1] != d:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
     bias = _check_bias(bias, N, docs.device)
-    if keep is not None:
-        keep = _check_keep(keep, N, docs.device)
-    return _biased_into(q, docs, bias, keep, k, int(idx_offset))
+    return _mode_into(_BIASED, q, docs, (bias,), _check_keep(keep, N, docs.device), k, int(idx_offset))
 
 
 def l2_bias(docs: torch.Tensor) -> torch.Tensor:
@@ -386,9 +422,6 @@ def l2_distances(q: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
     returned -> |q|^2 - 2 vals, clamped at 0, with the (-inf) tail mapped to +inf.  float32, ascending along k."""
     qn = (q.to(torch.float32) ** 2).sum(dim=-1, keepdim=True)
     return (qn - 2.0 * vals).clamp_(min=0.0)
-
-
-AFTER_KMAX = SMALL_KMAX  # one cursor call answers k <= 64 (tt_score_topk_after_*): a larger page is two consecutive calls
 
 
 def _cursor(after, B: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -415,29 +448,6 @@ def _cursor(after, B: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
     return parts[0], parts[1]
 
 
-def _after_into(q: torch.Tensor, docs: torch.Tensor, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], k: int,
-                idx_offset: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """tt_score_topk_after_f32 / _bf16 of checked arguments: q [B,d] f32, docs [N,d] f32 or bf16, (av, ai) a checked cursor
-    (_cursor), keep a checked keep-bitmask or None -> (vals, idx), `out` when given."""
-    if not 1 <= k <= AFTER_KMAX:
-        raise ValueError(f"a cursor search answers 1 <= k <= {AFTER_KMAX} per call, got k = {k} (pages() / deep_search() go deeper)")
-    B, d = q.shape
-    N = docs.shape[0]
-    bf16 = docs.dtype == torch.bfloat16
-    vals, idx = _out_pair(B, k, q.device, out)
-    if N == 0 or B == 0:  # (an empty torch tensor has no address to hand to the call)
-        vals.fill_(float("-inf"))
-        idx.fill_(-1)
-        return (vals, idx) if out is None else out
-    with torch.cuda.device(q.device):  # workspace sizing depends on the device's CU count
-        L = _lib.lib()
-        ws = torch.empty(max(L.tt_score_topk_after_workspace_bytes(B, N, d, k, int(bf16)), 16), dtype=torch.uint8, device=q.device)
-        fn = L.tt_score_topk_after_bf16 if bf16 else L.tt_score_topk_after_f32
-        _lib.check(fn(q.data_ptr(), B, d, docs.data_ptr(), N, av.data_ptr(), ai.data_ptr(), None if keep is None else keep.data_ptr(),
-                      k, idx_offset, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(q)))
-    return (vals, idx) if out is None else out
-
-
 def score_topk_after(q: torch.Tensor, docs: torch.Tensor, after_val, after_idx, k: int, idx_offset: int = 0,
                      keep: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The next k results after a cursor, in one pass over docs: document n (global id g = n + idx_offset) with score s --
@@ -450,16 +460,9 @@ def score_topk_after(q: torch.Tensor, docs: torch.Tensor, after_val, after_idx, 
     (tt_score_topk_after_f32 / _bf16; k <= 64 per call)."""
     if q.dim() == 1:
         return _squeezed(score_topk_after, q, docs, after_val, after_idx, k, idx_offset, keep)
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
-    B, d = q.shape
-    N = docs.shape[0]
-    if docs.dim() != 2 or docs.shape[1] != d:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
-    av, ai = _cursor((after_val, after_idx), B, docs.device)
-    if keep is not None:
-        keep = _check_keep(keep, N, docs.device)
-    return _after_into(q, docs, av, ai, keep, k, int(idx_offset))
+    q, docs = _front(q, docs)
+    cursor = _cursor((after_val, after_idx), q.shape[0], docs.device)
+    return _mode_into(_AFTER, q, docs, cursor, _check_keep(keep, docs.shape[0], docs.device), k, int(idx_offset))
 
 
 class _CursorSearch:
@@ -620,13 +623,9 @@ def score_count(q: torch.Tensor, docs: torch.Tensor, min_score, keep: Optional[t
     pass of the exact kernel over docs in its counting mode (tt_score_count_f32 / _bf16): the cost of an exact search."""
     if q.dim() == 1:
         return score_count(q.unsqueeze(0), docs, min_score, keep)[0]
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
-    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    q, docs = _front(q, docs)
     thr = _min_score(min_score, q.shape[0], q.device)
-    if keep is not None:
-        keep = _check_keep(keep, docs.shape[0], docs.device)
+    keep = _check_keep(keep, docs.shape[0], docs.device)
     count = torch.empty(q.shape[0], dtype=torch.int64, device=q.device)
     _count_into(q, docs, thr, keep, count, False)
     return count
@@ -689,10 +688,7 @@ def score_all(q: torch.Tensor, docs: torch.Tensor) -> torch.Tensor:
     squeeze = q.dim() == 1
     if squeeze:
         q = q.unsqueeze(0)
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _f32c(docs)
-    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    q, docs = _front(q, docs, _f32c)
     out = torch.empty((q.shape[0], docs.shape[0]), dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
         _lib.check(_lib.lib().tt_score_all_f32(q.data_ptr(), q.shape[0], q.shape[1], docs.data_ptr(), docs.shape[0],
@@ -743,13 +739,9 @@ def score_ids(q: torch.Tensor, docs: torch.Tensor, ids: torch.Tensor, idx_offset
     id is scored at each of its positions."""
     if q.dim() == 1:
         return score_ids(q.unsqueeze(0), docs, _ids_row(ids), idx_offset, keep)[0]
-    _need_cuda(q, docs)
-    q, docs = _f32c(q), _docs_c(docs)
-    if docs.dim() != 2 or docs.shape[1] != q.shape[1]:
-        raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(docs.shape)}")
+    q, docs = _front(q, docs)
     ids = _check_ids(ids, q.shape[0], docs.device)
-    if keep is not None:
-        keep = _check_keep(keep, docs.shape[0], docs.device)
+    keep = _check_keep(keep, docs.shape[0], docs.device)
     out = torch.empty(ids.shape, dtype=torch.float32, device=q.device)
     _score_ids_into(q, docs, ids, int(idx_offset), keep, out, None)
     return out
@@ -772,9 +764,7 @@ def _merge_candidates(vals: torch.Tensor, idx: torch.Tensor, k: int, out=None) -
     B, C = vals.shape
     ov, oi = _out_pair(B, k, vals.device, out)
     if C == 0 or B == 0:
-        ov.fill_(float("-inf"))
-        oi.fill_(-1)
-        return ov, oi
+        return _pad_pair(ov, oi)
     if k > SMALL_KMAX:
         vals, idx = _unique_pairs(vals, idx)
     with torch.cuda.device(vals.device):
@@ -1270,6 +1260,25 @@ class BruteForceIndex(_CursorSearch):
             off = _lib.lib().tt_score_topk_screened_stats_offset(B, self.docs.shape[0], 256, k)
         return ws[off:off + 8 * B].view(torch.int32).view(B, 2).clone()
 
+    def _check_q(self, q: torch.Tensor, width: bool = True) -> None:
+        """The queries of every search of this index: on the GPU, on the rows' device, of their width (width=False: the
+        caller's own pass checks it, behind the dtype)."""
+        _need_cuda(q)
+        if q.device != self.docs.device:
+            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
+        if width and q.shape[-1] != self.docs.shape[1]:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+
+    def _mask(self, keep: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The mask a call runs under: the persistent one ANDed with the call's checked `keep`, or None."""
+        return _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+
+    def _exact_took_over(self, B: int) -> None:
+        """fallback_flags after a search of B queries that ran the exact kernel whatever the layout: on a screened index
+        every 32-query tile reads "the exact kernel took over"."""
+        if self._screen is not None:
+            self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+
     def search(self, q: torch.Tensor, k: int = 10, _prof_events=None, out=None, _seed_union=None,
                _k_seed: int = 0, _k_list: int = 0, keep: Optional[torch.Tensor] = None,
                exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1297,28 +1306,19 @@ class BruteForceIndex(_CursorSearch):
         if q.dim() == 1:  # single query (QueryInferencer / hybrid rerank)
             return _squeezed(self.search, q, k, _prof_events, None, None, 0, 0, keep, _exclude_row(exclude),
                              _ids_row(candidates, "candidates"))
-        _need_cuda(q)
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != self.docs.shape[1]:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        self._check_q(q)
         if exclude is not None:
             exclude, kk = _check_exclude(exclude, q.shape[0], k, self.docs.device)
             v, i = self.search(q, kk, _prof_events, None, _seed_union, _k_seed, _k_list, keep, None, candidates)
             return topk_exclude(v, i, exclude, k, out)
-        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
+        keep = self._mask(keep)
         if candidates is not None:
             return _merge_candidates(*self._score_ids(q, candidates, keep, True, "candidates"), k, out)
         if self._screens(q.shape[0], k, keep is not None):
             return self._search_screened(q, k, _prof_events, out, _seed_union, _k_seed, _k_list, keep)
-        if keep is not None and self._screen is not None:  # (the exact kernel took over every tile of a screened index)
-            self.fallback_flags = torch.ones((q.shape[0] + 31) // 32, dtype=torch.int32, device=self.docs.device)
-        v, i = score_topk(q, self.docs, k, self.idx_offset, keep=keep)
-        if out is not None:
-            out[0].copy_(v)
-            out[1].copy_(i)
-            return out
-        return v, i
+        if keep is not None:
+            self._exact_took_over(q.shape[0])
+        return _copied(out, *score_topk(q, self.docs, k, self.idx_offset, keep=keep))
 
     @property
     def tags(self) -> Optional[torch.Tensor]:
@@ -1342,19 +1342,11 @@ class BruteForceIndex(_CursorSearch):
             raise ValueError("tagged_search: this index has no tags (set_tags)")
         if q.dim() == 1:
             return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
-        _need_cuda(q)
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != self.docs.shape[1]:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
+        self._check_q(q)
         B = q.shape[0]
         mm = _match_words(match_mask, B, self.docs.device, "match_mask")
         mv = _match_words(match_value, B, self.docs.device, "match_value")
-        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
-        res = _tagged_into(_f32c(q), self.docs, self._tags, mm, mv, keep, k, self.idx_offset, out)
-        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
-            self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
-        return res
+        return self._mode_search(_TAGGED, q, (self._tags, mm, mv), keep, k, out)
 
     @property
     def bias(self) -> Optional[torch.Tensor]:
@@ -1366,12 +1358,7 @@ class BruteForceIndex(_CursorSearch):
         or a demotion added to every score by biased_search; l2_bias(docs) for Euclidean neighbours.  Kept padded (4 bytes per
         row).  Checked once here: a NaN or an infinity among the N values raises ValueError (a host synchronisation).
         None clears it."""
-        if bias is None:
-            self._bias = None
-            return
-        bias = _check_bias(bias, self.docs.shape[0], self.docs.device)
-        _finite_bias(bias, self.docs.shape[0])
-        self._bias = bias
+        self._bias = _set_bias(bias, self.docs.shape[0], self.docs.device)
 
     def biased_search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
                       exclude: Optional[torch.Tensor] = None, out=None, candidates=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1387,22 +1374,20 @@ class BruteForceIndex(_CursorSearch):
             raise ValueError("biased_search takes no candidates=: the candidate scores (score_ids) carry no bias")
         if q.dim() == 1:
             return _squeezed(self.biased_search, q, k, keep, _exclude_row(exclude))
-        _need_cuda(q)
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != self.docs.shape[1]:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        B = q.shape[0]
+        self._check_q(q)
         if exclude is not None:
-            exclude, kk = _check_exclude(exclude, B, k, self.docs.device)
+            exclude, kk = _check_exclude(exclude, q.shape[0], k, self.docs.device)
             if kk > BIASED_KMAX:
                 raise ValueError(f"a biased search with an exclusion list runs for k + E = {kk} > {BIASED_KMAX}")
             v, i = self.biased_search(q, kk, keep)
             return topk_exclude(v, i, exclude, k, out)
-        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
-        res = _biased_into(_f32c(q), self.docs, self._bias, keep, k, self.idx_offset, out)
-        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
-            self.fallback_flags = torch.ones((B + 31) // 32, dtype=torch.int32, device=self.docs.device)
+        return self._mode_search(_BIASED, q, (self._bias,), keep, k, out)
+
+    def _mode_search(self, mode: _Mode, q: torch.Tensor, own: tuple, keep: Optional[torch.Tensor], k: int, out):
+        """A checked q [B,d] through one mode of the exact kernel (_mode_into) over the rows, under the ANDed mask."""
+        keep = self._mask(keep)
+        res = _mode_into(mode, _f32c(q), self.docs, own, keep, k, self.idx_offset, out)
+        self._exact_took_over(q.shape[0])
         return res
 
     def _cursor_device(self) -> torch.device:
@@ -1410,15 +1395,8 @@ class BruteForceIndex(_CursorSearch):
 
     def _search_after(self, q: torch.Tensor, k: int, av: torch.Tensor, ai: torch.Tensor, keep: Optional[torch.Tensor], out=None):
         """search_after (_CursorSearch) of q [B,d] under a checked cursor: the exact kernel in its cursor mode over the rows."""
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != self.docs.shape[1]:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        keep = _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device)
-        res = _after_into(_f32c(q), self.docs, av, ai, keep, k, self.idx_offset, out)
-        if self._screen is not None:  # (the exact kernel took over every tile of a screened index)
-            self.fallback_flags = torch.ones((q.shape[0] + 31) // 32, dtype=torch.int32, device=self.docs.device)
-        return res
+        self._check_q(q)
+        return self._mode_search(_AFTER, q, (av, ai), keep, k, out)
 
     def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], want_idx: bool, what: str = "ids"):
         """tt_score_ids_* of q [B,d] over this index's rows under the ANDed mask `keep` (checked) or None: (scores f32 [B,C],
@@ -1436,12 +1414,8 @@ class BruteForceIndex(_CursorSearch):
         negative, not this index's, removed (remove_ids) or not kept by `keep`.  One launch that gathers B*C rows."""
         if q.dim() == 1:
             return self.score_ids(q.unsqueeze(0), _ids_row(ids), keep)[0]
-        _need_cuda(q)
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        if q.shape[-1] != self.docs.shape[1]:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {tuple(self.docs.shape)}")
-        return self._score_ids(q, ids, _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device), False)[0]
+        self._check_q(q)
+        return self._score_ids(q, ids, self._mask(keep), False)[0]
 
     def diverse_search(self, q: torch.Tensor, k: int = 10, lambda_: float = 0.5, fetch_k: Optional[int] = None,
                        keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1481,10 +1455,8 @@ class BruteForceIndex(_CursorSearch):
         `keep` when given -- score at least min_score (a float, or a float32 [B] device tensor) for each query.  The scores
         are the ones search() returns, bit for bit, so a returned entry at the threshold is always counted.  One exact pass
         over the rows (score_count), also on a screen=True index."""
-        _need_cuda(q)
-        if q.device != self.docs.device:
-            raise ValueError(f"queries on {q.device} but the index lives on {self.docs.device}")
-        return score_count(q, self.docs, min_score, _and_keep(self._keep, keep, self.docs.shape[0], self.docs.device))
+        self._check_q(q, width=False)  # (score_count checks the width, behind the dtype as it always has: the order stays)
+        return score_count(q, self.docs, min_score, self._mask(keep))
 
     def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
         return _range_search(self, q, min_score, k, keep)
@@ -1994,17 +1966,24 @@ class ShardedIndex(_CursorSearch):
         if candidates is not None:
             candidates = _check_ids(candidates, q.shape[0], self._dev, "candidates")
         kp = max(k, self.shard_k)
-        sl = self._slot(q.shape[0], kp, k, 2)
+        return self._exchange_step(2, q.shape[0], kp, k,
+                                   lambda sl: self._local_search(q, kp, k, sl, keep=keep, candidates=candidates),
+                                   _cloned if exclude is None else lambda v, i: topk_exclude(v, i, exclude, k_out))
+
+    def _exchange_step(self, which: int, B: int, kp: int, k: int, local: Callable, read: Callable):
+        """One search of this class on the caller's stream, through slot `which` (_slot) of the shape: local(slot) writes this
+        shard's [B,kp] list into the slot's send block (slot.send_v, slot.send_i), the ranks' lists are gathered and merged
+        to k, and read(out_v, out_i) takes the result out of the slot -- copies, clones or the exclusion filter: whatever
+        read returns is the caller's own.  The rule that orders callers on different streams: `merged` is waited for before
+        anything writes the slot and recorded AFTER THE LAST READ of it, so the next caller, on whatever stream, never
+        overwrites rows that are still being copied out."""
+        sl = self._slot(B, kp, k, which)
         cur = torch.cuda.current_stream(sl.send.device)
-        cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
+        cur.wait_event(sl.merged)  # (a call on another stream may still own the slot)
         self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._local_search(q, kp, k, sl, keep=keep, candidates=candidates)
-        self._exchange_merge(sl, q.shape[0], kp, k)
-        if exclude is not None:
-            res = topk_exclude(sl.out_v, sl.out_i, exclude, k_out)  # (reads the slot: before it is handed on)
-            sl.merged.record(cur)
-            return res
-        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
+        local(sl)
+        self._exchange_merge(sl, B, kp, k)
+        res = read(sl.out_v, sl.out_i)
         sl.merged.record(cur)
         return res
 
@@ -2028,18 +2007,9 @@ class ShardedIndex(_CursorSearch):
             raise ValueError("tagged_search: this index has no tags (set_tags)")
         if q.dim() == 1:
             return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
-        kp = max(k, self.shard_k)
-        if not 1 <= k or kp > TAGGED_KMAX:
-            raise ValueError(f"tagged search answers 1 <= max(k, shard_k) <= {TAGGED_KMAX}, got k = {k}, shard_k = {self.shard_k}")
-        sl = self._slot(q.shape[0], kp, k, 2)
-        cur = torch.cuda.current_stream(sl.send.device)
-        cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
-        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._index.tagged_search(q, kp, match_mask, match_value, keep=keep, out=(sl.send_v, sl.send_i))
-        self._exchange_merge(sl, q.shape[0], kp, k)
-        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
-        sl.merged.record(cur)
-        return res
+        kp = _TAGGED.shard_k(k, self.shard_k)
+        return self._exchange_step(2, q.shape[0], kp, k, lambda sl: self._index.tagged_search(
+            q, kp, match_mask, match_value, keep=keep, out=(sl.send_v, sl.send_i)), _cloned)
 
     @property
     def bias(self) -> Optional[torch.Tensor]:
@@ -2060,18 +2030,9 @@ class ShardedIndex(_CursorSearch):
             raise ValueError("biased_search: this index has no bias (set_bias)")
         if q.dim() == 1:
             return _squeezed(self.biased_search, q, k, keep)
-        kp = max(k, self.shard_k)
-        if not 1 <= k or kp > BIASED_KMAX:
-            raise ValueError(f"biased search answers 1 <= max(k, shard_k) <= {BIASED_KMAX}, got k = {k}, shard_k = {self.shard_k}")
-        sl = self._slot(q.shape[0], kp, k, 3)
-        cur = torch.cuda.current_stream(sl.send.device)
-        cur.wait_event(sl.merged)  # (a biased_search() on another stream may still own the slot)
-        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._index.biased_search(q, kp, keep=keep, out=(sl.send_v, sl.send_i))
-        self._exchange_merge(sl, q.shape[0], kp, k)
-        res = sl.out_v.clone(), sl.out_i.clone()  # (reads the slot: before it is handed on)
-        sl.merged.record(cur)
-        return res
+        kp = _BIASED.shard_k(k, self.shard_k)
+        return self._exchange_step(3, q.shape[0], kp, k, lambda sl: self._index.biased_search(
+            q, kp, keep=keep, out=(sl.send_v, sl.send_i)), _cloned)
 
     def _cursor_device(self) -> torch.device:
         return self._dev
@@ -2082,22 +2043,23 @@ class ShardedIndex(_CursorSearch):
         max(k, shard_k) (<= 64: ValueError above), then the usual all-gather and merge on the caller's stream; no seed exchange
         is involved.  A COLLECTIVE like every search of this class, and so are pages(), deep_search() and
         mine_hard_negatives over it.  keep: as in search()."""
-        kp = max(k, self.shard_k)
-        if not 1 <= k or kp > AFTER_KMAX:
-            raise ValueError(f"a cursor search answers 1 <= max(k, shard_k) <= {AFTER_KMAX}, got k = {k}, shard_k = {self.shard_k}")
-        sl = self._slot(q.shape[0], kp, k, 2)
-        cur = torch.cuda.current_stream(sl.send.device)
-        cur.wait_event(sl.merged)  # (a search() on another stream may still own the slot)
-        self._flush()              # (a submitted step's exchange goes out first: one issue order on every rank)
-        self._index._search_after(q, kp, av, ai, keep, (sl.send_v, sl.send_i))
-        self._exchange_merge(sl, q.shape[0], kp, k)
-        if out is not None:
-            out[0].copy_(sl.out_v)
-            out[1].copy_(sl.out_i)
-        else:
-            out = sl.out_v.clone(), sl.out_i.clone()
-        sl.merged.record(cur)  # (after the copies that read the slot: the next caller may write it from here on)
-        return out
+        kp = _AFTER.shard_k(k, self.shard_k)
+        return self._exchange_step(2, q.shape[0], kp, k, lambda sl: self._index._search_after(
+            q, kp, av, ai, keep, (sl.send_v, sl.send_i)), _cloned if out is None else lambda v, i: _copied(out, v, i))
+
+    def _all_reduce(self, t: torch.Tensor, op: str) -> torch.Tensor:
+        """t reduced elementwise over the ranks, op "SUM" or "MAX": torch.distributed's all_reduce on the index's group, in
+        place; with a communicator of the library's own and no torch.distributed, the ranks' blocks gathered and reduced
+        here.  One rank: t as it is."""
+        if self._coll.world == 1:
+            return t
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(t, op=getattr(dist.ReduceOp, op), group=self.group)
+            return t
+        recv = torch.empty((self._coll.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+        self._coll.all_gather_blocks(t.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
+        return recv.sum(0) if op == "SUM" else recv.amax(0)
 
     def score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         """float32 [B,C] ([C] for a single query), identical on every rank: the exact dense score of every id of ids int64
@@ -2106,16 +2068,7 @@ class ShardedIndex(_CursorSearch):
         shards' ids are padding (-inf); exactly one rank holds a real value, so the result is the elementwise MAX over the
         ranks: one all_reduce(MAX) of the [B,C] floats on the index's group.  A COLLECTIVE: every rank calls it at the same
         point."""
-        scores = self._index.score_ids(q, ids, keep=keep)
-        if self._coll.world > 1:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                dist.all_reduce(scores, op=dist.ReduceOp.MAX, group=self.group)
-            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' scores and take the maximum)
-                recv = torch.empty((self._coll.world,) + tuple(scores.shape), dtype=torch.float32, device=scores.device)
-                self._coll.all_gather_blocks(scores.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
-                scores = recv.amax(0)
-        return scores
+        return self._all_reduce(self._index.score_ids(q, ids, keep=keep), "MAX")
 
     def diverse_search(self, q: torch.Tensor, k: int = 10, lambda_: float = 0.5, fetch_k: Optional[int] = None,
                        keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2123,16 +2076,7 @@ class ShardedIndex(_CursorSearch):
             return _squeezed(self.diverse_search, q, k, lambda_, fetch_k, keep, _exclude_row(exclude))
         fk, lam = _mmr_fetch_k(k, fetch_k), _check_lambda(lambda_)
         v, i = self.search(q, fk, keep=keep, exclude=exclude)
-        rows = self._index._candidate_rows(i)
-        if self._coll.world > 1:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=self.group)
-            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' blocks and add)
-                recv = torch.empty((self._coll.world,) + tuple(rows.shape), dtype=torch.float32, device=rows.device)
-                self._coll.all_gather_blocks(rows.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
-                rows = recv.sum(0)
-        return mmr_select(v, i, None, k, lam, rows=rows)
+        return mmr_select(v, i, None, k, lam, rows=self._all_reduce(self._index._candidate_rows(i), "SUM"))
 
     diverse_search.__doc__ = _DIVERSE_DOC + """
         Sharded, a COLLECTIVE like every search of this class: the sharded search for fetch_k, identical on every rank; then
@@ -2154,16 +2098,7 @@ class ShardedIndex(_CursorSearch):
     def _gather_gids(self, ids: torch.Tensor) -> torch.Tensor:
         """The group ids of merged result ids on every rank: each rank fills in the ids it owns (zeros elsewhere), one
         all_reduce(SUM) of the int64 block on the index's group."""
-        g = _owned_gids(self._index.groups, ids, self.row_offset)
-        if self._coll.world > 1:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group)
-            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' blocks and add)
-                recv = torch.empty((self._coll.world,) + tuple(g.shape), dtype=torch.int64, device=g.device)
-                self._coll.all_gather_blocks(g.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
-                g = recv.sum(0)
-        return g
+        return self._all_reduce(_owned_gids(self._index.groups, ids, self.row_offset), "SUM")
 
     def collapsed_search(self, q: torch.Tensor, k: int = 10, max_per_group: int = 1, fetch_k: Optional[int] = None,
                          keep: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, exact: bool = True):
@@ -2182,16 +2117,7 @@ class ShardedIndex(_CursorSearch):
         """The count of the whole corpus, identical on every rank: this rank's count over its shard under its mask (keep: over
         THIS RANK'S rows, on all ranks or on none, as in search()), then one all_reduce(SUM) of the int64 [B] on the index's
         group.  A COLLECTIVE: every rank calls it at the same point."""
-        counts = self._index.count(q, min_score, keep=keep)
-        if self._coll.world > 1:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
-            else:  # (a communicator of the library's own, no torch.distributed: gather the ranks' counts and add)
-                recv = torch.empty((self._coll.world,) + tuple(counts.shape), dtype=torch.int64, device=counts.device)
-                self._coll.all_gather_blocks(counts.reshape(-1).view(torch.uint8), recv.view(-1).view(torch.uint8))
-                counts = recv.sum(0)
-        return counts
+        return self._all_reduce(self._index.count(q, min_score, keep=keep), "SUM")
 
     def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
         return _range_search(self, q, min_score, k, keep)
@@ -2309,9 +2235,31 @@ class StreamedIndex(_CursorSearch):
             finally:
                 self._done.record(cur)
 
+    def _staged(self, s: int, rows: torch.Tensor, cur, consume: Callable) -> None:
+        """The staging handshake, for both kinds of pass: `rows` (pinned host memory) -> staging buffer s on the copy stream
+        once that buffer has been consumed (_free[s]); the caller's stream `cur` waits for the copy (_ready[s]);
+        consume(staged rows, s) enqueues on `cur` what reads the buffer; then _free[s] is recorded on `cur`.  (A plain call,
+        not a context manager: it runs once per block of every walk.)"""
+        staged = self._stage[s][:rows.shape[0]]
+        with torch.cuda.stream(self._copy):
+            self._copy.wait_event(self._free[s])
+            staged.copy_(rows, non_blocking=True)
+            self._ready[s].record(self._copy)
+        cur.wait_event(self._ready[s])
+        consume(staged, s)
+        self._free[s].record(cur)
+
     def _walk(self, visit, stats=None):
         L = _lib.lib()
         nblk = (self.N + self.block - 1) // self.block
+
+        def widen(staged, s):  # bf16 block -> fp32 rows (+ fp16 shadow, + the build pass's statistics)
+            with torch.cuda.device(self.device):
+                _lib.check(L.tt_index_build_from_bf16(
+                    self._stage[s].data_ptr(), staged.shape[0], self.d, self._d32[s].data_ptr(),
+                    self._d16[s].data_ptr() if self._d16[s] is not None else None,
+                    stats.data_ptr() if stats is not None else None, 0, cur.cuda_stream))
+
         with self._ordered() as cur:
             for s in range(2):
                 self._free[s].record(cur)
@@ -2319,17 +2267,7 @@ class StreamedIndex(_CursorSearch):
                 s = i % 2
                 lo = i * self.block
                 n = min(self.block, self.N - lo)
-                with torch.cuda.stream(self._copy):
-                    self._copy.wait_event(self._free[s])          # the staging buffer has been consumed
-                    self._stage[s][:n].copy_(self.host[lo:lo + n], non_blocking=True)
-                    self._ready[s].record(self._copy)
-                cur.wait_event(self._ready[s])
-                with torch.cuda.device(self.device):
-                    _lib.check(L.tt_index_build_from_bf16(
-                        self._stage[s].data_ptr(), n, self.d, self._d32[s].data_ptr(),
-                        self._d16[s].data_ptr() if self._d16[s] is not None else None,
-                        stats.data_ptr() if stats is not None else None, 0, cur.cuda_stream))
-                self._free[s].record(cur)
+                self._staged(s, self.host[lo:lo + n], cur, widen)
                 visit(s, lo, n)
 
     def resident(self, dtype: torch.dtype = torch.float32) -> "BruteForceIndex":
@@ -2377,6 +2315,38 @@ class StreamedIndex(_CursorSearch):
         """Withdraw documents by global id (with idx_offset); other ids are ignored.  The mask stays on the device."""
         self._keep = _clear_ids(self._keep, self.N, self.device, ids, self.idx_offset)
 
+    def _check_q(self, q: torch.Tensor) -> None:
+        """The queries [B,d] of every pass of this index: on its device, of the rows' width."""
+        if q.device != self.device:
+            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
+        if q.shape[1] != self.d:
+            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+
+    def _mask(self, keep: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The mask a call runs under, over the whole corpus: the persistent one ANDed with the call's checked `keep`, or None."""
+        return _and_keep(self._keep, keep, self.N, self.device)
+
+    def _need_word_blocks(self, what: str, needed: bool = True) -> None:
+        """A pass that hands every block its slice of per-row words (keep-bitmask, tags) needs blocks that start on
+        32-row boundaries, unless there is one block only."""
+        if needed and self.block % 32 and self.N > self.block:
+            raise ValueError(f"a {what} needs block_docs to be a multiple of 32, got {self.block}")
+
+    def _walk_topk(self, q: torch.Tensor, k: int, out, keep: Optional[torch.Tensor], block_topk: Callable):
+        """The one top-k walk: block_topk(s, lo, n, keep_slice) -> (vals [B,k], idx [B,k]) is the search of the n widened rows
+        from lo in buffer s under the block's words of the ANDed mask `keep`; the blocks' lists are folded into a running
+        top-k with the merge kernel, an empty corpus gives padding only, and the result goes into `out` when given."""
+        run = []  # the running top-k: (values, indices)
+
+        def visit(s, lo, n):
+            v, i = block_topk(s, lo, n, _keep_slice(keep, lo, n))
+            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+
+        self._walk(visit)
+        if not run:
+            run = _pad_pair(*_out_pair(q.shape[0], k, q.device))
+        return _copied(out, run[0], run[1])
+
     def _score_ids(self, q: torch.Tensor, ids: torch.Tensor, keep: Optional[torch.Tensor], what: str = "ids"):
         """(scores f32 [B,C], global ids int64 [B,C], -1 where the entry yields nothing) of checked q [B,d] under the ANDed
         mask `keep` or None.  The rows are in host memory, so the gather happens there: the distinct present ids of the
@@ -2411,14 +2381,9 @@ class StreamedIndex(_CursorSearch):
                 if j >= 2:
                     self._ready[s].synchronize()  # the copy out of this pinned buffer two pieces ago has finished
                 torch.index_select(self.host, 0, rows[p0:p0 + m], out=self._gather[s][:m])
-                with torch.cuda.stream(self._copy):
-                    self._copy.wait_event(self._free[s])
-                    self._stage[s][:m].copy_(self._gather[s][:m], non_blocking=True)
-                    self._ready[s].record(self._copy)
-                cur.wait_event(self._ready[s])
                 piece = vals if U <= self.block else torch.empty_like(vals)  # (a single piece writes the result itself)
-                _score_ids_into(q, self._stage[s][:m], pos, p0, None, piece, None)  # positions outside the piece: padding
-                self._free[s].record(cur)
+                self._staged(s, self._gather[s][:m], cur,  # (positions outside the piece: padding)
+                             lambda staged, _: _score_ids_into(q, staged, pos, p0, None, piece, None))
                 if piece is not vals:
                     vals = torch.maximum(vals, piece)
             if U:
@@ -2434,11 +2399,8 @@ class StreamedIndex(_CursorSearch):
         _need_cuda(q)
         if q.dim() == 1:
             return self.score_ids(q.unsqueeze(0), _ids_row(ids), keep)[0]
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
-        return self._score_ids(_f32c(q), ids, _and_keep(self._keep, keep, self.N, self.device))[0]
+        self._check_q(q)
+        return self._score_ids(_f32c(q), ids, self._mask(keep))[0]
 
     def search(self, q: torch.Tensor, k: int = 10, out=None, keep: Optional[torch.Tensor] = None,
                exclude: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2455,38 +2417,23 @@ class StreamedIndex(_CursorSearch):
         _need_cuda(q)
         if q.dim() == 1:
             return _squeezed(self.search, q, k, None, keep, _exclude_row(exclude), _ids_row(candidates, "candidates"))
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        self._check_q(q)
         if exclude is not None:
             exclude, kk = _check_exclude(exclude, q.shape[0], k, self.device)
             v, i = self.search(q, kk, None, keep, None, candidates)
             return topk_exclude(v, i, exclude, k, out)
         q = _f32c(q)
-        keep = _and_keep(self._keep, keep, self.N, self.device)
+        keep = self._mask(keep)
         if candidates is not None:
             return _merge_candidates(*self._score_ids(q, candidates, keep, "candidates"), k, out)
-        if keep is not None and self.block % 32 and self.N > self.block:
-            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
-        run = []  # the running top-k: (values, indices)
+        self._need_word_blocks("masked StreamedIndex search", keep is not None)
 
-        def visit(s, lo, n):
+        def block_topk(s, lo, n, keep_words):  # the block as a resident index of its own: it screens where it can
             blk = BruteForceIndex._from_buffers(self._d32[s][:n], self._d16[s][:n] if self._d16[s] is not None else None,
                                                 self.dmax_norm, self.idx_offset + lo, self.screen_masked)
-            v, i = blk.search(q, k, keep=None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)])
-            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+            return blk.search(q, k, keep=keep_words)
 
-        self._walk(visit)
-        if not run:
-            run = _out_pair(q.shape[0], k, q.device)  # an empty corpus: padding only
-            run[0].fill_(float("-inf"))
-            run[1].fill_(-1)
-        if out is not None:
-            out[0].copy_(run[0])
-            out[1].copy_(run[1])
-            return out
-        return run[0], run[1]
+        return self._walk_topk(q, k, out, keep, block_topk)
 
     @property
     def tags(self) -> Optional[torch.Tensor]:
@@ -2510,38 +2457,22 @@ class StreamedIndex(_CursorSearch):
         if q.dim() == 1:
             return _squeezed(self.tagged_search, q, k, match_mask, match_value, keep)
         _need_cuda(q)
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
-        if not 1 <= k <= TAGGED_KMAX:
-            raise ValueError(f"tagged search answers 1 <= k <= {TAGGED_KMAX}, got k = {k}")
+        self._check_q(q)
+        _TAGGED.check_k(k)
         q = _f32c(q)
         B = q.shape[0]
         mm = _match_words(match_mask, B, self.device, "match_mask")
         mv = _match_words(match_value, B, self.device, "match_value")
-        keep = _and_keep(self._keep, keep, self.N, self.device)
-        if self.block % 32 and self.N > self.block:
-            raise ValueError(f"a tagged StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
-        run = []  # the running top-k: (values, indices)
+        keep = self._mask(keep)
+        self._need_word_blocks("tagged StreamedIndex search")
 
-        def visit(s, lo, n):
+        def block_topk(s, lo, n, keep_words):
             if lo % 32:
                 raise ValueError(f"block at row {lo}: the tags of a 32-document tile belong to one block")
-            v, i = _tagged_into(q, self._d32[s][:n], self._tags[lo:lo + _tag_words(n)], mm, mv,
-                                None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k, self.idx_offset + lo)
-            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+            return _mode_into(_TAGGED, q, self._d32[s][:n], (self._tags[lo:lo + _tag_words(n)], mm, mv), keep_words, k,
+                              self.idx_offset + lo)
 
-        self._walk(visit)
-        if not run:
-            run = _out_pair(B, k, q.device)  # an empty corpus: padding only
-            run[0].fill_(float("-inf"))
-            run[1].fill_(-1)
-        if out is not None:
-            out[0].copy_(run[0])
-            out[1].copy_(run[1])
-            return out
-        return run[0], run[1]
+        return self._walk_topk(q, k, out, keep, block_topk)
 
     @property
     def bias(self) -> Optional[torch.Tensor]:
@@ -2552,12 +2483,7 @@ class StreamedIndex(_CursorSearch):
         """One float32 bias per row of the whole corpus (float32 [N] or padded to [32*ceil(N/32)]), on the index's DEVICE: the
         rows stream from the host, the biases stay resident at 4 bytes per row.  Checked for NaN and infinities once, here
         (ValueError; a host synchronisation).  None clears it."""
-        if bias is None:
-            self._bias = None
-            return
-        bias = _check_bias(bias, self.N, self.device)
-        _finite_bias(bias, self.N)
-        self._bias = bias
+        self._bias = _set_bias(bias, self.N, self.device)
 
     def biased_search(self, q: torch.Tensor, k: int = 10, keep: Optional[torch.Tensor] = None,
                       out=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2571,39 +2497,21 @@ class StreamedIndex(_CursorSearch):
         if q.dim() == 1:
             return _squeezed(self.biased_search, q, k, keep)
         _need_cuda(q)
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
-        if not 1 <= k <= BIASED_KMAX:
-            raise ValueError(f"biased search answers 1 <= k <= {BIASED_KMAX}, got k = {k}")
+        self._check_q(q)
+        _BIASED.check_k(k)
         q = _f32c(q)
-        B = q.shape[0]
-        keep = _and_keep(self._keep, keep, self.N, self.device)
-        if keep is not None and self.block % 32 and self.N > self.block:
-            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
-        run = []  # the running top-k: (values, indices)
+        keep = self._mask(keep)
+        self._need_word_blocks("masked StreamedIndex search", keep is not None)
 
-        def visit(s, lo, n):
+        def block_topk(s, lo, n, keep_words):
             if lo % 32 == 0:  # whole tiles from a 128-byte aligned start: read in place
                 b = self._bias[lo:lo + _tag_words(n)]
             else:
                 b = torch.zeros(_tag_words(n), dtype=torch.float32, device=self.device)
                 b[:n] = self._bias[lo:lo + n]
-            v, i = _biased_into(q, self._d32[s][:n], b, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k,
-                                self.idx_offset + lo)
-            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
+            return _mode_into(_BIASED, q, self._d32[s][:n], (b,), keep_words, k, self.idx_offset + lo)
 
-        self._walk(visit)
-        if not run:
-            run = _out_pair(B, k, q.device)  # an empty corpus: padding only
-            run[0].fill_(float("-inf"))
-            run[1].fill_(-1)
-        if out is not None:
-            out[0].copy_(run[0])
-            out[1].copy_(run[1])
-            return out
-        return run[0], run[1]
+        return self._walk_topk(q, k, out, keep, block_topk)
 
     def _cursor_device(self) -> torch.device:
         return self.device
@@ -2612,33 +2520,13 @@ class StreamedIndex(_CursorSearch):
         """search_after (_CursorSearch) over the streamed rows: every block runs the exact kernel in its cursor mode under
         the same global cursor (and its slice of the ANDed keep-bitmask, if any), and the blocks' lists are merged as in
         search().  A keep-bitmask needs whole words per block, as in search()."""
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
-        if not 1 <= k <= AFTER_KMAX:
-            raise ValueError(f"a cursor search answers 1 <= k <= {AFTER_KMAX} per call, got k = {k}")
+        self._check_q(q)
+        _AFTER.check_k(k, hint=False)  # (this class's refusal has always read without the pages() hint: the words stay)
         q = _f32c(q)
-        keep = _and_keep(self._keep, keep, self.N, self.device)
-        if keep is not None and self.block % 32 and self.N > self.block:
-            raise ValueError(f"a masked StreamedIndex search needs block_docs to be a multiple of 32, got {self.block}")
-        run = []  # the running top-k: (values, indices)
-
-        def visit(s, lo, n):
-            v, i = _after_into(q, self._d32[s][:n], av, ai, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], k,
-                               self.idx_offset + lo)
-            run[:] = (v, i) if not run else topk_merge(torch.cat([run[0], v], 1), torch.cat([run[1], i], 1), k)
-
-        self._walk(visit)
-        if not run:
-            run = _out_pair(q.shape[0], k, q.device)  # an empty corpus: padding only
-            run[0].fill_(float("-inf"))
-            run[1].fill_(-1)
-        if out is not None:
-            out[0].copy_(run[0])
-            out[1].copy_(run[1])
-            return out
-        return run[0], run[1]
+        keep = self._mask(keep)
+        self._need_word_blocks("masked StreamedIndex search", keep is not None)
+        return self._walk_topk(q, k, out, keep, lambda s, lo, n, keep_words: _mode_into(
+            _AFTER, q, self._d32[s][:n], (av, ai), keep_words, k, self.idx_offset + lo))
 
     def _candidate_rows(self, ids: torch.Tensor) -> torch.Tensor:
         """float32 [B,C,d]: the rows of the global ids this index owns (bf16 widened exactly), zeros elsewhere.  The rows are
@@ -2694,21 +2582,13 @@ class StreamedIndex(_CursorSearch):
         _need_cuda(q)
         if q.dim() == 1:
             return self.count(q.unsqueeze(0), min_score, keep)[0]
-        if q.device != self.device:
-            raise ValueError(f"queries on {q.device} but the index streams through {self.device}")
-        if q.shape[1] != self.d:
-            raise ValueError(f"shape mismatch: q {tuple(q.shape)} vs docs {(self.N, self.d)}")
+        self._check_q(q)
         q = _f32c(q)
         thr = _min_score(min_score, q.shape[0], self.device)
-        keep = _and_keep(self._keep, keep, self.N, self.device)
-        if keep is not None and self.block % 32 and self.N > self.block:
-            raise ValueError(f"a masked StreamedIndex count needs block_docs to be a multiple of 32, got {self.block}")
+        keep = self._mask(keep)
+        self._need_word_blocks("masked StreamedIndex count", keep is not None)
         counts = torch.zeros(q.shape[0], dtype=torch.int64, device=self.device)
-
-        def visit(s, lo, n):
-            _count_into(q, self._d32[s][:n], thr, None if keep is None else keep[lo // 32:lo // 32 + _keep_words(n)], counts, True)
-
-        self._walk(visit)
+        self._walk(lambda s, lo, n: _count_into(q, self._d32[s][:n], thr, _keep_slice(keep, lo, n), counts, True))
         return counts
 
     def range_search(self, q: torch.Tensor, min_score, k: int = 10, keep: Optional[torch.Tensor] = None):
